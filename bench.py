@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the QPSK receive hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, roofline).  --full adds
+everything else the line used to carry: the oracle parity gate, the CPU baseline, the sustained figures and, at N = 1 on
+config 2's shape, the side measurements (config3, hist, awgn, shard_8192, gather, config5, streams; each has its --no-* switch).
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32/float64, at most 64 MB).
 
 One "step" = one pass of the fused RRC-FIR + Costas + slicer kernel (qpsk_rx_batch, fixed timing
 offset) over one batch of synthetic frames that is already resident in HBM.
@@ -35,6 +40,26 @@ FRAMES_1GPU = 4096                         # BASELINE configs[1]
 FRAMES_PER_GPU_SHARDED = 8192              # BASELINE configs[3]: 65536 frames over 8 GPUs
 HBM_PEAK_GBS = 8000.0                      # MI355X HBM3E peak (MI355X_MICROARCH.md)
 BYTES_PER_SAMPLE = 8                       # one complex float read per input sample
+DUMP_BUDGET = 64 * 10 ** 6                 # --dump-outputs: bytes of all .npy files of the job together
+
+
+def dump_outputs(dirname, sym, freq, phase, prefix="", budget=DUMP_BUDGET):
+    """What a caller of the timed path receives, as float32 .npy files: <prefix>sym (F, nsym), <prefix>freq (F,), <prefix>phase (F,).
+    Where the symbols do not fit the budget, a fixed seeded sample of whole frames is written instead, with the frames' indices
+    (ascending) in <prefix>sym_frames.npy (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    F, nsym = sym.shape
+    out = {"freq": freq.cpu().numpy().astype(np.float32), "phase": phase.cpu().numpy().astype(np.float32)}
+    sym_h = sym.cpu().numpy()
+    room = budget - 8 * F - 4 * 1024                      # freq, phase and the .npy headers
+    if sym_h.size * 4 <= room:
+        out["sym"] = sym_h.astype(np.float32)
+    else:
+        keep = np.sort(np.random.default_rng(0).choice(F, room // (nsym * 4 + 8), replace=False))
+        out["sym"] = sym_h[keep].astype(np.float32)
+        out["sym_frames"] = keep.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, prefix + name + ".npy"), a)
 
 
 def synth_frames_gpu(torch, dev, nframes, taps, seed, offset_hz=50.0):
@@ -225,8 +250,14 @@ def main():
                     help="tx: frames from the library's own transmit chain (qpsk_tx_symbols, N2); synth: torch conv1d (rounds 1-3)")
     ap.add_argument("--settle", type=float, default=0.25, help="seconds of untimed launches before the warmup steps (GPU clocks)")
     ap.add_argument("--frame-size", type=int, default=L, help="complex samples per frame (config 2: 16384)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity gate, the CPU baseline, the sustained figures and the side measurements (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the symbols, freq and phase of the last timed step as DIR/<name>.npy (float32; rank r > 0: rank<r>_<name>.npy)")
     args = ap.parse_args()
     L = args.frame_size
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus is None:
@@ -382,16 +413,19 @@ def main():
     sym, freq, phase = outs
     note("frames ready")
     dt, kernel_ms = timed_region(m, x, F, outs, args.steps, args.warmup, args.settle)
+    if args.dump_outputs:       # the buffers hold the last timed step's results (timed_region synchronised)
+        dump_outputs(args.dump_outputs, sym, freq, phase, prefix="rank%d_" % rank if rank else "", budget=DUMP_BUDGET // world)
     elapsed = max_over_ranks(dt, dist)
     joined = int(round(sum_over_ranks(1, dist)))      # ranks that really took part
     kernel_name = m.last_kernel()                     # reported by the library, not inferred from the shape
-    hz_n, hz_bad, hz_mean = hz_check(freq)
-    hz_bad_all = int(round(sum_over_ranks(hz_bad, dist)))
-    hz_n_all = int(round(sum_over_ranks(hz_n, dist)))
+    if args.full:
+        hz_n, hz_bad, hz_mean = hz_check(freq)
+        hz_bad_all = int(round(sum_over_ranks(hz_bad, dist)))
+        hz_n_all = int(round(sum_over_ranks(hz_n, dist)))
 
     # (round 5's "kernel_ms_event_pair_per_launch" -- one event pair per launch -- read 24 % above the span figure: it measured the
     # events' own cost, not the kernel; dropped.  The steady-state step below is the figure worth having beside the timed region.)
-    sustained = sustained_region(m, x, F, outs) if world == 1 and not args.no_sustained else None
+    sustained = sustained_region(m, x, F, outs) if args.full and world == 1 and not args.no_sustained else None
 
     if rank != 0:
         if dist:
@@ -466,8 +500,8 @@ def main():
                     "sha256": lib_sha256,
                     "override_QPSK_HIP_LIB": bool(os.environ.get("QPSK_HIP_LIB")), "version": qpsk_amd.version()},
     }
-    parity = {"hz_frames_checked": hz_n_all, "hz_out_of_range": hz_bad_all, "mean_freq_hz": hz_mean}
-    if not args.no_parity:       # parity gate of the same run (rank 0's shard): bits against the oracle
+    parity = {"hz_frames_checked": hz_n_all, "hz_out_of_range": hz_bad_all, "mean_freq_hz": hz_mean} if args.full else None
+    if args.full and not args.no_parity:       # parity gate of the same run (rank 0's shard): bits against the oracle
         from oracle.pyoracle import Oracle, TIMING_FIXED
         # EVERY frame of the timed batch (round 4 checked 256 of 4096): the oracle's fixed-offset path is the decimating filter + the
         # loop, 56 Msamples/s on one core -- 16 threads take config 2's 67 M samples in a fraction of a second
@@ -483,13 +517,14 @@ def main():
         parity.update({"frames_checked": npar, "symbol_mismatches": int(np.sum(gs != want["sym"])),
                        "freq_bit_mismatches": int(np.sum(gf.view(np.uint32) != want["freq"].view(np.uint32))),
                        "phase_bit_mismatches": int(np.sum(gp.view(np.uint32) != want["phase"].view(np.uint32)))})
-    res["parity"] = parity
-    if world == 1:          # the CPU baseline is reported at N = 1 only
+    if args.full:
+        res["parity"] = parity
+    if args.full and world == 1:          # the CPU baseline is reported at N = 1 only
         ncpu = min(args.cpu_frames, F)
         if ncpu > 0:
             xh = x[:ncpu].cpu().numpy()
             res["cpu_baseline"] = cpu_baseline(xh, m.taps)
-    if world == 1 and (F, L) == (FRAMES_1GPU, 16384) and not args.no_timing_modes:
+    if args.full and world == 1 and (F, L) == (FRAMES_1GPU, 16384) and not args.no_timing_modes:
         # The same resident batch with a timing ESTIMATE in front of the receive kernel, by the same timed-region code, after
         # config 2's region: key config3 = BASELINE configs[2] (the FFT timing estimate: timing_fft_kernel + receive kernel per
         # step), key hist = the reference's own histogram estimate (qpsk.c:127-180: timing_scan_kernel + receive kernel).  A step
@@ -556,7 +591,7 @@ def main():
             res[key] = ent
             mt.close()
             del outs_t, idx_t
-    if world == 1 and (F, L) == (FRAMES_1GPU, 16384) and not args.no_timing_modes:
+    if args.full and world == 1 and (F, L) == (FRAMES_1GPU, 16384) and not args.no_timing_modes:
         # SURVEY 8(d)'s optional AWGN variant, reported separately (the reference has no channel model: qpsk.c:314-334): config 2's
         # batch plus complex white noise at Es/N0 = 12 dB after the matched filter (sigma per component from the measured mean sample
         # power), same kernel, same fixed offset.  The time is data-independent except through the loop's 2 pi wraps.
@@ -585,7 +620,7 @@ def main():
             aw["freq_bit_mismatches"] = int(np.sum(outs_n[1][:32].cpu().numpy().view(np.uint32) != want_n["freq"].view(np.uint32)))
         res["awgn"] = aw
         del xn, outs_n
-    if world == 1 and (F, L) == (FRAMES_1GPU, 16384) and not args.no_shard:
+    if args.full and world == 1 and (F, L) == (FRAMES_1GPU, 16384) and not args.no_shard:
         # BASELINE configs[3]'s per-GPU share (8192 x 16384: the shape of every rank of an N > 1 run, and the one where
         # the filter, not the recurrence, is the limit) measured in the same run, after config 2's region and by the
         # same timed-region code.  `value`, `config` and `roofline` above stay config 2's.
@@ -674,7 +709,7 @@ def main():
                                      "overlapped_direct_packed with the symbols four to a byte (qpsk_multi_set_packed)"}
             mj.close()
         res["shard_8192"] = sh
-    if world == 1 and (args.frames, L) == (FRAMES_1GPU, 16384) and not args.no_config5:
+    if args.full and world == 1 and (args.frames, L) == (FRAMES_1GPU, 16384) and not args.no_config5:
         # BASELINE configs[4]: "1200-baud / 8x oversample long-frame variant, 1M samples/frame, Costas loop-BW sweep TAU/100-TAU/200" --
         # FS 9600 / RS 1200, 1,048,576 samples per frame, 11 loop bandwidths TAU/100, TAU/110, ... TAU/200 as independent Costas
         # chains over ONE filter pass (README.md:12; qpsk_rx_batch_bw).  384 frames (384 x 11 = 4224 chains >= 4096, 3 GiB
@@ -718,7 +753,7 @@ def main():
         m5.close()
         del x5, out5
         torch.cuda.empty_cache()
-    if world == 1 and (args.frames, L) == (FRAMES_1GPU, 16384) and not args.no_streams:
+    if args.full and world == 1 and (args.frames, L) == (FRAMES_1GPU, 16384) and not args.no_streams:
         # SURVEY 8(f) N1, the reference's real input and call pattern (qpsk.c:88, 344-354), measured beside the headline and NOT part of it:
         #  (a) 4096 running streams, one 16384-sample int16 PCM block each per call (PCM from the library's own transmit chain at +50 Hz):
         #      mix + rrc_fir() + histogram timing in one kernel, then the loop kernel; ms per block = median of blocks 2..7, an event pair

@@ -29,7 +29,7 @@ def test_bench_defaults_are_the_contract_defaults():
 
 @pytest.mark.gpu
 def test_bench_json_line():
-    d = run_bench("--steps", "5", "--warmup", "2", "--frames", "256", "--cpu-frames", "8")
+    d = run_bench("--full", "--steps", "5", "--warmup", "2", "--frames", "256", "--cpu-frames", "8")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "parity", "ranks", "gpu_shared",
               "devices", "library", "control_plane"):
@@ -72,6 +72,59 @@ def test_bench_json_line():
     assert p["hz_frames_checked"] == 256 and p["hz_out_of_range"] == 0       # EVERY frame locked on the +50 Hz carrier
 
 
+@pytest.mark.gpu
+def test_bench_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """without --full the line carries the headline only (no parity gate, CPU baseline or side measurement); --dump-outputs writes
+    the last timed step's results as float32 .npy, the same from run to run with the same arguments"""
+    args = ("--steps", "4", "--warmup", "1", "--frames", "256")
+    d = run_bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "config"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    for k in ("parity", "cpu_baseline", "sustained", "sustained_ms_per_step", "config3", "hist", "awgn", "shard_8192", "gather",
+              "config5", "streams"):
+        assert k not in d, k
+    run_bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    import numpy as np
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["freq.npy", "phase.npy", "sym.npy"] and sorted(os.listdir(tmp_path / "b")) == names
+    a = {n[:-len(".npy")]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["sym"].shape == (256, 16384 // 8) and a["freq"].shape == (256,) and a["phase"].shape == (256,)
+    assert set(np.unique(a["sym"]).tolist()) <= {0.0, 1.0, 2.0, 3.0}
+    assert np.all(np.abs(a["freq"].astype(np.float64) * 2400.0 / (2 * np.pi) - 50.0) < 2.0)     # every frame locked on +50 Hz
+    for k, v in a.items():
+        assert np.load(tmp_path / "b" / (k + ".npy")).tobytes() == v.tobytes(), k
+
+
+def test_dump_outputs_samples_whole_frames_within_the_budget(tmp_path):
+    """a batch whose symbols exceed the budget is written as a fixed seeded sample of whole frames, with their indices"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    F, nsym = 8192, 2048
+    rng = np.random.default_rng(3)
+    sym = torch.from_numpy(rng.integers(0, 4, size=(F, nsym), dtype=np.uint8))
+    freq = torch.from_numpy(rng.standard_normal(F).astype(np.float32))
+    phase = torch.from_numpy(rng.standard_normal(F).astype(np.float32))
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), sym, freq, phase)
+    total = sum(os.path.getsize(tmp_path / "a" / n) for n in os.listdir(tmp_path / "a"))
+    assert total <= bench.DUMP_BUDGET == 64 * 10 ** 6
+    keep = np.load(tmp_path / "a" / "sym_frames.npy")
+    got = np.load(tmp_path / "a" / "sym.npy")
+    assert keep.dtype == np.float64 and got.dtype == np.float32 and np.all(np.diff(keep) > 0)
+    assert got.shape == (keep.size, nsym) and keep.size > F // 2
+    assert np.array_equal(got, sym.numpy()[keep.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "freq.npy"), freq.numpy())
+    assert np.array_equal(np.load(tmp_path / "b" / "sym_frames.npy"), keep)       # the same sample every time
+    # a batch that fits is written whole, without an index file
+    bench.dump_outputs(str(tmp_path / "c"), sym[:256], freq[:256], phase[:256])
+    assert sorted(os.listdir(tmp_path / "c")) == ["freq.npy", "phase.npy", "sym.npy"]
+    assert np.array_equal(np.load(tmp_path / "c" / "sym.npy"), sym[:256].numpy().astype(np.float32))
+
+
 def test_bench_shard_key_is_wired_to_config_2():
     """the 8192-frame per-GPU share rides along in the N = 1 line as `shard_8192` (its own timed region, the same
     code), without touching `value` / `config` / `roofline`"""
@@ -82,6 +135,11 @@ def test_bench_shard_key_is_wired_to_config_2():
     assert '"sustained_ms_per_step"' in src and 'sh["sustained_ms_per_step"]' in src and 'res["gather"]' in src and "kernel_ms_event_pair_per_launch\"]" not in src
     # BASELINE configs[2] (FFT timing estimate in front) and the reference's histogram mode ride along the same way
     assert 'res[key] = ent' in src and '("config3", qpsk_amd.TIMING_FFT' in src and '("hist", qpsk_amd.TIMING_HIST' in src
+    # all of them only under --full: a plain run is the headline alone
+    assert "args.full and world == 1 and (F, L) == (FRAMES_1GPU, 16384) and not args.no_shard" in src
+    assert src.count("if args.full and world == 1 and (F, L) == (FRAMES_1GPU, 16384) and not args.no_timing_modes:") == 2
+    assert "if args.full and world == 1 and (args.frames, L) == (FRAMES_1GPU, 16384) and not args.no_config5:" in src
+    assert "if args.full and world == 1 and (args.frames, L) == (FRAMES_1GPU, 16384) and not args.no_streams:" in src
 
 
 def test_control_plane_is_gloo_only():

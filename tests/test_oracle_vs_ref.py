@@ -1,14 +1,22 @@
-"""The oracle against the reference ITSELF (oracle/_ref = /root/reference compiled untouched, see
-oracle/Makefile).  Only possible in the build container; skipped where oracle/_ref is absent (GPU box),
-where tests/test_oracle_golden.py pins the same functions through the committed fixtures instead."""
+"""The oracle against the reference ITSELF (oracle/_ref = the reference compiled untouched, see oracle/Makefile).  Where
+oracle/_ref is built the reference answers, and its answers must also equal the record under tests/golden/vs_ref/; elsewhere
+the record answers the same questions (tests/refrecord.py), so these tests run wherever the repository does."""
 import numpy as np
 import pytest
 
-from oracle.pyoracle import TAU, TIMING_HIST, Reference, ref_available
+from oracle.pyoracle import TAU, TIMING_HIST
+from refrecord import Recorder
 from sigutil import bits_equal, make_frames, random_frames
 
-pytestmark = pytest.mark.skipif(not ref_available("c1small"), reason="oracle/_ref not built (no /root/reference here)")
 BW = np.float32(TAU / 100.0)
+
+
+@pytest.fixture
+def reference(request):
+    """reference(name) stands for Reference(name): the reference itself where oracle/_ref is built, else its record"""
+    rec = Recorder(request.node.name)
+    yield rec.reference
+    rec.finish()
 
 
 def rrc_grid():
@@ -22,7 +30,7 @@ def rrc_grid():
     return out
 
 
-def test_rrc_make_matches_reference(oracle):
+def test_rrc_make_matches_reference(oracle, reference):
     """rrc_make() (rrc_fir.c:32-76): oracle == reference == the product's host routine, bit for bit, on every set -- round 4's
     oracle answered NaN taps where the reference's cosf/sinf arguments reach 120 (FS/RS <= 2.2 at alpha .35)."""
     import ctypes as C
@@ -30,7 +38,7 @@ def test_rrc_make_matches_reference(oracle):
     hip = C.CDLL(qpsk_amd.lib_path())          # host symbol only: no GPU call
     hip.qpsk_host_rrc_taps.argtypes = [C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float)]
     hip.qpsk_host_rrc_taps.restype = None
-    ref = Reference("shipped")
+    ref = reference("shipped")
     large = 0
     for fs, rs, alpha in rrc_grid():
         want = ref.taps(fs, rs, alpha)
@@ -45,8 +53,8 @@ def test_rrc_make_matches_reference(oracle):
 
 
 @pytest.mark.parametrize("name", ["shipped", "c1small", "c5small"])
-def test_streaming_pcm_matches_reference(oracle, name):
-    ref = Reference(name)
+def test_streaming_pcm_matches_reference(oracle, reference, name):
+    ref = reference(name)
     ref.reset(BW, -1.0, 1.0, .35, 1550.0, 1500.0)
     rng = np.random.default_rng(100)
     L, N = ref.frame_size, ref.nsym
@@ -76,8 +84,8 @@ def test_streaming_pcm_matches_reference(oracle, name):
 
 
 @pytest.mark.parametrize("name,kind", [("c1small", "modem"), ("c1small", "noise"), ("c5small", "modem"), ("c1", "modem")])
-def test_independent_frames_match_reference(oracle, name, kind):
-    ref = Reference(name)
+def test_independent_frames_match_reference(oracle, reference, name, kind):
+    ref = reference(name)
     ref.reset()
     L = ref.frame_size
     F = 2 if name == "c1" else 6
@@ -101,13 +109,13 @@ def _same_with_nans(a, b):
 
 
 @pytest.mark.parametrize("where", [0, 700, 2047])
-def test_nan_input_matches_reference(oracle, where):
+def test_nan_input_matches_reference(oracle, reference, where):
     """A NaN sample: the reference's complex products go through __mulsc3 (qpsk.c:197, 114-118), whose
     recovery branch only acts on INFINITE operands, so for NaN inputs the oracle's component-wise arithmetic gives the
     reference's values: the same symbols, the same finite values before the NaN reaches the loop, NaN in the same places
     after.  (An infinite sample is not compared: the reference's phase_wrap() never returns from an infinite phase,
     costas_loop.c:61-67 -- the library fences both, tests/test_gpu_parity.py::test_nonfinite_input_is_an_error.)"""
-    ref = Reference("c1small")
+    ref = reference("c1small")
     ref.reset()
     L = ref.frame_size
     x, _ = make_frames(3, L, ref.cycles, ref.taps(), ref.fs, offset_hz=40.0, base_seed=11, noise=0.05)
@@ -122,8 +130,8 @@ def test_nan_input_matches_reference(oracle, where):
     assert (np.isnan(o["phase"][1]) or where >= L - 1) and not np.isnan(o["phase"][0]) and not np.isnan(o["phase"][2])
 
 
-def test_loop_bandwidth_sweep_matches_reference(oracle):
-    ref = Reference("c5small")
+def test_loop_bandwidth_sweep_matches_reference(oracle, reference):
+    ref = reference("c5small")
     ref.reset()
     x, _ = make_frames(2, ref.frame_size, ref.cycles, ref.taps(), ref.fs, offset_hz=20.0, base_seed=5)
     bws = [np.float32(TAU / d) for d in (100.0, 150.0, 200.0)]
@@ -134,10 +142,10 @@ def test_loop_bandwidth_sweep_matches_reference(oracle):
             assert bits_equal(r["sym"], o["sym"][f, b]) and r["phase"] == o["phase"][f, b] and r["freq"] == o["freq"][f, b]
 
 
-def test_costas_scalar_api_matches_reference(oracle):
+def test_costas_scalar_api_matches_reference(oracle, reference):
     from oracle.pyoracle import Costas
     import ctypes as C
-    ref = Reference("shipped")
+    ref = reference("shipped")
     ref.reset()
     rng = np.random.default_rng(8)
     for bw, lo, hi in [(BW, -1.0, 1.0), (np.float32(TAU / 200), -0.2, 0.3), (np.float32(0.5), -5.0, 5.0)]:
@@ -160,8 +168,8 @@ def test_costas_scalar_api_matches_reference(oracle):
             assert bits_equal(ref.costas_state, mine), name
 
 
-def test_fft_matches_reference(oracle):
-    ref = Reference("shipped")
+def test_fft_matches_reference(oracle, reference):
+    ref = reference("shipped")
     rng = np.random.default_rng(4)
     for n in (1, 2, 4, 16, 512, 1024):
         x = rng.standard_normal(n) + 1j * rng.standard_normal(n)
@@ -169,8 +177,8 @@ def test_fft_matches_reference(oracle):
         assert bits_equal(ref.ifftn(x), oracle.ifftn(x)), n
 
 
-def test_bit_stages_match_reference(oracle):
-    ref = Reference("shipped")
+def test_bit_stages_match_reference(oracle, reference):
+    ref = reference("shipped")
     rng = np.random.default_rng(6)
     for n in (1, 2, 8, 22, 40, 43):
         d = rng.integers(0, 256, size=n).astype(np.uint8)
@@ -182,7 +190,7 @@ def test_bit_stages_match_reference(oracle):
 
 
 @pytest.mark.parametrize("name", ["shipped", "c1small"])
-def test_zero_symbols_and_signed_zero_states_match_reference(oracle, name):
+def test_zero_symbols_and_signed_zero_states_match_reference(oracle, reference, name):
     """Exactly-zero symbols (the first block after start-up, silent PCM) meeting loop states where the sign of a zero decides
     (costas_loop.c:44-59: sgn(0) = -1, x + -0): the oracle against the reference itself, state loaded through the reference's own
     set_phase() / set_frequency().  The HIP path's handling of such stretches (costas_asm.h `ign`, costas_step_t's exact-zero branch) is
@@ -193,7 +201,7 @@ def test_zero_symbols_and_signed_zero_states_match_reference(oracle, name):
               (nz, -1e-42)]
     rng = np.random.default_rng(5)
     for ph, fr in states:
-        ref = Reference(name)
+        ref = reference(name)
         ref.reset(BW, -1.0, 1.0, .35, 1550.0, 1500.0)
         ref.lib.set_phase(float(ph))
         ref.lib.set_frequency(float(fr))

@@ -97,7 +97,7 @@ def test_bench_gpus_2_starts_two_ranks():
     a 1-GPU box both ranks share the GPU (`gpu_shared`: a rehearsal of the launch path, not a scaling number).  The
     control plane is the one an 8-GPU run executes (gloo, host scalars)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
                         "--frames", "64", "--frame-size", "2048"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -126,7 +126,7 @@ def test_two_rank_clock_excludes_the_rendezvous():
     outside the other's event span -- a granularity of the rehearsal that eight GPUs do not have (measured: 0.7-2.8 %,
     profiles/r05_bench_gpus2_shared_20steps.json, ..._gpus6_...); the rendezvous round 4 timed was 7.5 % of this region."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "5"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])

@@ -9,11 +9,11 @@ txt() { name=$1; shift; rm -f $O/$name.failed; timeout -k 10 400 "$@" > $O/$name
 prof() { d=$1; shift; rm -rf $O/$d $O/$d.failed; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$d -- "$@" > $O/$d.log 2>&1 || echo FAILED > $O/$d.failed; }
 pmcrun() { d=$1; c=$2; shift 2; rm -rf $O/$d $O/$d.failed; timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $O/$d -- "$@" > $O/$d.log 2>&1 || echo FAILED > $O/$d.failed; }
 if [[ $part == *a* ]]; then
-run bench python3 bench.py
-run bench20 python3 bench.py --steps 20 --warmup 5
-run bench8192 python3 bench.py --frames 8192 --cpu-frames 0 --no-shard
-prof prof_bench python3 bench.py --cpu-frames 0                    # config 2, config 3, histogram mode, the 8192-frame shard: the default command, CPU leg off
-prof prof_bench20 python3 bench.py --steps 20 --warmup 5 --cpu-frames 0 --no-shard --no-timing-modes   # the driver's command
+run bench python3 bench.py --full
+run bench20 python3 bench.py --full --steps 20 --warmup 5
+run bench8192 python3 bench.py --full --frames 8192 --cpu-frames 0 --no-shard
+prof prof_bench python3 bench.py --full --cpu-frames 0                    # config 2, config 3, histogram mode, the 8192-frame shard: the default command, CPU leg off
+prof prof_bench20 python3 bench.py --full --steps 20 --warmup 5 --cpu-frames 0 --no-shard --no-timing-modes   # the driver's command
 prof prof_config3 python3 tools/loop_kernel.py config3 2
 prof prof_fft_sep python3 tools/loop_kernel.py fft_est 2
 prof prof_streams python3 tools/bench_streams.py
@@ -40,13 +40,13 @@ txt streams_host_1 python3 tools/bench_streams_host.py 1 3000
 txt streams_host_8 python3 tools/bench_streams_host.py 8 2000
 txt streams_host_64 python3 tools/bench_streams_host.py 64 1000
 txt config5 python3 tools/bench_config5.py
-run bench_gpus2_shared python3 bench.py --gpus 2 --cpu-frames 0
-run bench_gpus6_shared python3 bench.py --gpus 6 --frames 1024 --cpu-frames 0        # six ranks on this box's one GPU (the pool allows six GPU processes): the launch path, not a scaling number
-run bench_torchrun2_shared python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --cpu-frames 0
+run bench_gpus2_shared python3 bench.py --full --gpus 2 --cpu-frames 0
+run bench_gpus6_shared python3 bench.py --full --gpus 6 --frames 1024 --cpu-frames 0        # six ranks on this box's one GPU (the pool allows six GPU processes): the launch path, not a scaling number
+run bench_torchrun2_shared python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --cpu-frames 0
 fi
 if [[ $part == *c* ]]; then
 # (the elastic agent of torch.distributed.run holds the GPU open too: six ranks under it exceed the pool's limit of six GPU processes)
-run bench_torchrun4_shared python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 4 --frames 1024 --cpu-frames 0
+run bench_torchrun4_shared python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29512 bench.py --full --gpus 4 --frames 1024 --cpu-frames 0
 make -C qpsk_amd/csrc VARIANT=sbprof EXTRA=-DQPSK_SBLK_PROF > $O/sbprof_build.log 2>&1 && QPSK_HIP_LIB=qpsk_amd/libqpsk_hip_sbprof.so txt stream_block_profile python3 tools/bench_streams_host.py 1 60
 fi
 if [[ $part == *d* ]]; then      # the streams composition alone (after streamscan.hip)
@@ -57,19 +57,19 @@ txt streams_2560 python3 tools/bench_streams.py --streams 2560
 QPSK_STREAM_SCAN=0 txt streams_2560_apart python3 tools/bench_streams.py --streams 2560
 fi
 if [[ $part == *e* ]]; then      # final refresh: the bench lines (with the streams key) and the streams path's counters and power
-run bench python3 bench.py
-run bench20 python3 bench.py --steps 20 --warmup 5
-prof prof_bench python3 bench.py --cpu-frames 0
+run bench python3 bench.py --full
+run bench20 python3 bench.py --full --steps 20 --warmup 5
+prof prof_bench python3 bench.py --full --cpu-frames 0
 pmcrun pmc_fetch_streams FETCH_SIZE python3 tools/loop_kernel.py streams 0 4096 8
 pmcrun pmc_write_streams WRITE_SIZE python3 tools/loop_kernel.py streams 0 4096 8
 txt power_streams python3 tools/power_probe.py --cmd "python3 tools/loop_kernel.py streams 6"
 fi
 if [[ $part == *f* ]]; then      # after the streams' one carrier (carrier.h) and the zero-symbol stretches: bench lines, streams, drop-in
-run bench python3 bench.py
-run bench20 python3 bench.py --steps 20 --warmup 5
-run bench8192 python3 bench.py --frames 8192 --cpu-frames 0 --no-shard
-prof prof_bench python3 bench.py --cpu-frames 0
-prof prof_bench20 python3 bench.py --steps 20 --warmup 5 --cpu-frames 0 --no-shard --no-timing-modes
+run bench python3 bench.py --full
+run bench20 python3 bench.py --full --steps 20 --warmup 5
+run bench8192 python3 bench.py --full --frames 8192 --cpu-frames 0 --no-shard
+prof prof_bench python3 bench.py --full --cpu-frames 0
+prof prof_bench20 python3 bench.py --full --steps 20 --warmup 5 --cpu-frames 0 --no-shard --no-timing-modes
 prof prof_streams python3 tools/bench_streams.py
 txt streams python3 tools/bench_streams.py
 QPSK_STREAM_CARRIER=0 txt streams_own_carrier python3 tools/bench_streams.py
