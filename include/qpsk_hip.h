@@ -56,7 +56,8 @@ extern "C" {
 typedef enum {
     QPSK_OK = 0,
     QPSK_ERR_NO_DEVICE = -1, /* no HIP device / device index out of range */
-    QPSK_ERR_ARG = -2,       /* null pointer, non-positive size, frame_size % cycles != 0, ... */
+    QPSK_ERR_ARG = -2,       /* null pointer, non-positive size, frame_size % cycles != 0, ...; also, from the next synchronising
+                                call, an external timing offset (qpsk_rx_batch_ext d_index_in) outside 0..7 */
     QPSK_ERR_HIP = -3,       /* a HIP runtime call or a kernel launch failed */
     QPSK_ERR_ALLOC = -4,
     QPSK_ERR_STATE = -5,     /* call sequence error (e.g. stream call on a context made for 0 streams) */
@@ -174,6 +175,34 @@ int qpsk_rx_batch_pitched(qpsk_ctx *ctx, const float *d_in, long long frame_pitc
  * bandwidth sweep, README.md:12).  Outputs are [nframes][nbw][...]. */
 int qpsk_rx_batch_bw(qpsk_ctx *ctx, const float *d_in, int nframes, const float *h_loop_bw, int nbw,
                      uint8_t *d_sym, float *d_freq, float *d_phase, int32_t *d_index);
+
+/* -------------------------------------------------------------------------
+ * The same batch with the acquisition supplied from OUTSIDE ("ext"): the caller's own timing offsets and / or a coarse carrier
+ * estimate per loop, on the same kernels (qpsk_ctx_last_kernel() names them as for qpsk_rx_batch).  Per frame this is, bit for bit,
+ * the reference with a fresh process:
+ *       rx_frame(frame)            with index = d_index_in[f] at qpsk.c:190
+ *       set_phase(seed[f][0]); set_frequency(seed[f][1]);      (costas_loop.c:117-132: phase_wrap, then the [min_freq, max_freq] clamp)
+ *       rx_frame(zeros)
+ * results taken after the second call as qpsk_rx_batch() takes them.
+ *
+ *   frame_pitch  samples between frames as qpsk_rx_batch_pitched() (0 = frame_size)
+ *   d_index_in   [nframes] int32 decimation offsets 0..7 (the range fixed_index accepts; with CYCLES = 4, offsets 4..7 pick past the
+ *                block, read as 0 as the fixed mode does) -- every timing estimate is skipped, the in-launch FFT estimate included.
+ *                NULL = the context's timing mode, exactly as qpsk_rx_batch_pitched() computes it.  An offset outside 0..7 is not read
+ *                as an address (the frame is demodulated at 0) and the context's NEXT SYNCHRONISING call returns QPSK_ERR_ARG
+ *   d_seed       [nframes][2] float (phase, freq) the loop starts from; NULL = (0, 0).  A non-finite seed or a phase beyond the
+ *                bounded 2 pi wrap fails like a non-finite input: QPSK_ERR_RANGE at the next synchronisation
+ *   outputs      as qpsk_rx_batch(); d_index receives the offsets used (d_index may be d_index_in)
+ * Both NULL: the results of qpsk_rx_batch_pitched().  Ext calls neither read nor update the histogram mode's one-pass guess (with
+ * d_index_in NULL in QPSK_TIMING_HIST the batch takes the two-launch route).  A caller that estimates offsets once
+ * (qpsk_timing_fft_batch, qpsk_timing_scan_batch, or its own estimator) and reuses them for later batches pays for no estimate there.
+ * ------------------------------------------------------------------------- */
+int qpsk_rx_batch_ext(qpsk_ctx *ctx, const float *d_in, long long frame_pitch, int nframes, const int32_t *d_index_in,
+                      const float *d_seed, uint8_t *d_sym, float *d_freq, float *d_phase, float *d_costas, int32_t *d_index,
+                      float *d_hz);
+/* qpsk_rx_batch_bw() the same way: d_seed [nframes][nbw][2] (one seed per loop) or NULL; d_index_in [nframes] or NULL */
+int qpsk_rx_batch_bw_ext(qpsk_ctx *ctx, const float *d_in, int nframes, const float *h_loop_bw, int nbw, const int32_t *d_index_in,
+                         const float *d_seed, uint8_t *d_sym, float *d_freq, float *d_phase, int32_t *d_index);
 
 /* -------------------------------------------------------------------------
  * The stages on their own (each is what the corresponding reference function
@@ -358,6 +387,11 @@ int qpsk_pack_symbols(qpsk_ctx *ctx, const uint8_t *d_sym, long long nrows, int 
 int qpsk_unpack_symbols_host(const uint8_t *h_packed, long long nrows, int nsym, uint8_t *h_sym);
 int qpsk_host_alloc(void **h_ptr, size_t bytes);      /* page-locked host memory, usable from every device */
 int qpsk_host_free(void *h_ptr);
+/* The job's acquisition from outside: every later rx_begin runs qpsk_rx_batch_ext on each shard's slice of h_index [total_frames]
+ * int32 and h_seed [total_frames][2] float (phase, freq) -- either may be NULL; both NULL = back to the context's timing.  The slices
+ * are uploaded once, here (no slot may be in flight).  A call that fails on any shard leaves every shard with its previous setting;
+ * a later qpsk_multi_load clears it. */
+int qpsk_multi_set_acquisition(qpsk_multi *mj, const int32_t *h_index, const float *h_seed);
 int qpsk_multi_rx_begin(qpsk_multi *mj, int slot);
 int qpsk_multi_rx_end(qpsk_multi *mj, int slot, uint8_t *h_sym, float *h_freq, float *h_phase);
 

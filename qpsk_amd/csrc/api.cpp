@@ -202,6 +202,9 @@ static int check_status(qpsk_ctx *c)
     if (st == STATUS_PHASE_RANGE)
         return fail(QPSK_ERR_RANGE, "Costas loop phase beyond the bounded 2 pi wrap (input amplitude far outside the modem's range; "
                                     "the reference's phase_wrap() would spin or hang, costas_loop.c:61-67); results of the calls since the last synchronisation are invalid");
+    if (st == STATUS_BAD_INDEX)
+        return fail(QPSK_ERR_ARG, "an external timing offset (qpsk_rx_batch_ext d_index_in) lies outside 0..%d: the kernel demodulated that frame "
+                                  "at offset 0; results of the calls since the last synchronisation are invalid", MAX_INDEX);
     if (st == STATUS_NONFINITE)
         return fail(QPSK_ERR_RANGE, "a Costas loop ended on a NaN / Inf state: the input held a non-finite sample (the reference hangs in phase_wrap() "
                                     "on an infinite phase, costas_loop.c:61-67); results of the calls since the last synchronisation are invalid");
@@ -643,8 +646,16 @@ static int timing_indices(qpsk_ctx *c, const float *d_in, size_t pitch, int nfra
     return QPSK_OK;
 }
 
+/* acquisition supplied from outside (qpsk_rx_batch_ext): per-frame decimation offsets in place of the context's timing estimate,
+ * per-loop (phase, freq) seeds in place of (0, 0); either may be NULL */
+struct ExtAcq {
+    const int32_t *index;
+    const float *seed;
+};
+
 static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch, int nframes, int nbw, uint8_t *d_sym,
-                           float *d_freq, float *d_phase, float *d_costas, int32_t *d_index, float *d_hz)
+                           float *d_freq, float *d_phase, float *d_costas, int32_t *d_index, float *d_hz,
+                           const ExtAcq *ext = nullptr)
 {
     if (!c || !d_in || !d_sym) return fail(QPSK_ERR_ARG, "qpsk_rx_batch: null context, input or symbol buffer");
     if (nframes <= 0) return fail(QPSK_ERR_ARG, "qpsk_rx_batch: nframes = %d", nframes);
@@ -683,6 +694,12 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
     a.costas = reinterpret_cast<float2 *>(d_costas);
     a.hz = d_hz;
     a.status = c->d_status;
+    /* an ext call's seeds: the serial waves apply set_phase() / set_frequency() at the load (kernels.h, seed_setters) */
+    const bool ext_index = ext && ext->index;
+    if (ext && ext->seed) {
+        a.state_in = ext->seed;
+        a.seed_setters = 1;
+    }
 
     /* ---- which kernel takes the batch: decided ONCE, here, as a plan; the timing estimate's placement (below) reads the plan and
      * the launches execute it -- nothing restates the choice (round 4 restated it for the in-launch FFT estimate and missed a
@@ -805,7 +822,8 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
      * the next guess.  No guess yet, a shape the kernel does not serve, or a last batch that missed more than an eighth of its frames
      * (a batch of mixed indices: the fall-back pass would carry it): the two-launch route below. */
     const bool hist_mode = c->prm.timing_mode == QPSK_TIMING_HIST;
-    if (hist_mode && pipe_ok && c->taps_symmetric && scan_fused_ok(c, d_in) && c->tune.pipe_v < 0) {      /* (QPSK_PIPE_V asks for one of the receive kernels by name) */
+    /* (an ext call neither reads nor updates the guess: with its own offsets it needs no estimate, without them it takes the two-launch route) */
+    if (hist_mode && !ext && pipe_ok && c->taps_symmetric && scan_fused_ok(c, d_in) && c->tune.pipe_v < 0) {      /* (QPSK_PIPE_V asks for one of the receive kernels by name) */
         if (!c->d_hint) {
             HIP_TRY(hipMalloc((void **)&c->d_hint, 2 * sizeof(int32_t)));
             HIP_TRY(hipMemset(c->d_hint, 0, 2 * sizeof(int32_t)));
@@ -850,7 +868,7 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
      * from a launch in front (timing_fft_kernel / timing_scan_kernel / ...). */
     bool fused_fft = false;
     double *est_tw = nullptr, *est_cs = nullptr;
-    if (c->prm.timing_mode == QPSK_TIMING_FFT && rem_pl.nframes == 0 && nbw == 1 && tuned(c->tune.fft_fused, 1) != 0 &&
+    if (c->prm.timing_mode == QPSK_TIMING_FFT && !ext_index && rem_pl.nframes == 0 && nbw == 1 && tuned(c->tune.fft_fused, 1) != 0 &&
         c->prm.frame_size >= timing_fft_first() + timing_fft_nfft() &&
         ((main_pl.kind == K_FUSED_PIPE && main_pl.nf == pipe_max_nf() && !(tuned(c->tune.pipe_variant, 0) & (128 | 4))) ||
          (main_pl.kind == K_LEAN && lean_est_ok(a, main_pl.G, main_pl.layout)))) {
@@ -859,8 +877,12 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
         fused_fft = true;
     }
     const int32_t *idx = nullptr;
-    int rc = timing_indices(c, d_in, (size_t)frame_pitch, nframes, &idx, fused_fft);
-    if (rc) return rc;
+    if (ext_index) {
+        idx = ext->index;      /* every timing estimate skipped; the kernels check each value where they read it (STATUS_BAD_INDEX) */
+    } else {
+        int rc = timing_indices(c, d_in, (size_t)frame_pitch, nframes, &idx, fused_fft);
+        if (rc) return rc;
+    }
     a.index = idx;
     if (fused_fft) {
         a.est_tw = reinterpret_cast<const double2 *>(est_tw);
@@ -904,6 +926,7 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
             ar.nframes = rem_pl.nframes;
             ar.x += o * a.frame_pitch;
             if (ar.index) ar.index += o;
+            if (ar.state_in) ar.state_in += 2 * o * (size_t)nbw;
             ar.sym += o * (size_t)a.nsym;
             if (ar.freq) ar.freq += o;
             if (ar.phase) ar.phase += o;
@@ -914,7 +937,7 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
             c->last_kernel = lk;
         }
     }
-    if (hist_mode && c->d_hint && idx && tuned(c->tune.hist_onepass, -1) != 0) {
+    if (hist_mode && !ext && c->d_hint && idx && tuned(c->tune.hist_onepass, -1) != 0) {
         /* the batch's majority index as the next histogram-mode call's guess (one workgroup, in stream order) */
         KERNEL_TRY(launch_index_majority(idx, nframes, c->d_hint, c->d_hint + 1, c->d_hist_stats, c->stream));
         c->hint_valid = true;
@@ -927,7 +950,9 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
                                (size_t)c->nsym, hipMemcpyDeviceToDevice, c->stream));
     }
     if (d_index) {
-        if (idx)
+        if (idx == d_index) {
+            /* the caller's own offsets, in place */
+        } else if (idx)
             HIP_TRY(hipMemcpyAsync(d_index, idx, sizeof(int32_t) * (size_t)nframes, hipMemcpyDeviceToDevice, c->stream));
         else
             KERNEL_TRY(launch_fill_i32(d_index, nframes, c->prm.fixed_index, c->stream));
@@ -956,8 +981,8 @@ int qpsk_rx_batch_pitched(qpsk_ctx *c, const float *d_in, long long frame_pitch,
     return rx_batch_common(c, d_in, frame_pitch, nframes, 1, d_sym, d_freq, d_phase, d_costas, d_index, d_hz);
 }
 
-int qpsk_rx_batch_bw(qpsk_ctx *c, const float *d_in, int nframes, const float *h_loop_bw, int nbw, uint8_t *d_sym,
-                     float *d_freq, float *d_phase, int32_t *d_index)
+static int rx_batch_bw_impl(qpsk_ctx *c, const float *d_in, int nframes, const float *h_loop_bw, int nbw, uint8_t *d_sym,
+                            float *d_freq, float *d_phase, int32_t *d_index, const ExtAcq *ext)
 {
     if (!c || !h_loop_bw) return fail(QPSK_ERR_ARG, "qpsk_rx_batch_bw: null argument");
     if (nbw < 1 || nbw > MAX_BW) return fail(QPSK_ERR_ARG, "nbw = %d outside 1..%d", nbw, MAX_BW);
@@ -970,7 +995,32 @@ int qpsk_rx_batch_bw(qpsk_ctx *c, const float *d_in, int nframes, const float *h
         c->h_gains = g;
         HIP_TRY(hipMemcpyAsync(c->d_gains, c->h_gains.data(), sizeof(float) * g.size(), hipMemcpyHostToDevice, c->stream));
     }
-    return rx_batch_common(c, d_in, 0, nframes, nbw, d_sym, d_freq, d_phase, nullptr, d_index, nullptr);
+    return rx_batch_common(c, d_in, 0, nframes, nbw, d_sym, d_freq, d_phase, nullptr, d_index, nullptr, ext);
+}
+
+int qpsk_rx_batch_bw(qpsk_ctx *c, const float *d_in, int nframes, const float *h_loop_bw, int nbw, uint8_t *d_sym,
+                     float *d_freq, float *d_phase, int32_t *d_index)
+{
+    return rx_batch_bw_impl(c, d_in, nframes, h_loop_bw, nbw, d_sym, d_freq, d_phase, d_index, nullptr);
+}
+
+int qpsk_rx_batch_ext(qpsk_ctx *c, const float *d_in, long long frame_pitch, int nframes, const int32_t *d_index_in, const float *d_seed,
+                      uint8_t *d_sym, float *d_freq, float *d_phase, float *d_costas, int32_t *d_index, float *d_hz)
+{
+    if (c) {
+        if (bind(c)) return QPSK_ERR_HIP;
+        if (int rg = use_context_gains(c)) return rg;
+    }
+    if (frame_pitch < 0) return fail(QPSK_ERR_ARG, "qpsk_rx_batch_ext: frame_pitch = %lld", frame_pitch);
+    const ExtAcq ext = {d_index_in, d_seed};
+    return rx_batch_common(c, d_in, frame_pitch, nframes, 1, d_sym, d_freq, d_phase, d_costas, d_index, d_hz, &ext);
+}
+
+int qpsk_rx_batch_bw_ext(qpsk_ctx *c, const float *d_in, int nframes, const float *h_loop_bw, int nbw, const int32_t *d_index_in,
+                         const float *d_seed, uint8_t *d_sym, float *d_freq, float *d_phase, int32_t *d_index)
+{
+    const ExtAcq ext = {d_index_in, d_seed};
+    return rx_batch_bw_impl(c, d_in, nframes, h_loop_bw, nbw, d_sym, d_freq, d_phase, d_index, &ext);
 }
 
 /* Costas + slicer over decimated symbols already in device memory (qpsk.c:196-212): the pipeline kernel with

@@ -16,6 +16,8 @@ constexpr int MAX_INDEX = 7;
 constexpr int STATUS_PIPE_TIMEOUT = 1;   /* the in-LDS producer/consumer pipeline exhausted its bounded spins */
 constexpr int STATUS_PHASE_RANGE = 2;    /* a loop phase beyond the bounded 2 pi wrap (qpsk_device.h, phase_wrap) */
 constexpr int STATUS_NONFINITE = 3;      /* a loop ended on a NaN / Inf phase or frequency: the input held a non-finite sample */
+constexpr int STATUS_BAD_INDEX = 4;      /* a per-frame decimation offset outside 0..MAX_INDEX (caller-supplied: qpsk_rx_batch_ext); the kernel
+                                            addressed with 0 instead */
 
 struct FusedArgs {
     const float2 *x;        /* [nframes] frames of frame_size samples, frame_pitch samples apart */
@@ -64,6 +66,9 @@ struct FusedArgs {
     float min_freq, max_freq;
     double rs;
     const float *state_in;  /* [nframes][nbw][2] phase, freq or NULL */
+    int seed_setters;       /* state_in is a caller's seed (qpsk_rx_batch_ext): the serial wave applies set_phase() / set_frequency()
+                               (costas_loop.c:117-132) at the load -- phase_wrap, then the [min_freq, max_freq] clamp.  0 = loaded raw
+                               (qpsk_costas_batch, the streams' carried state) */
     float *state_out;       /* same or NULL */
     uint8_t *sym;           /* [nframes][nbw][nsym] */
     uint8_t *sym_pad;       /* rx_lean_kernel on a batch whose last workgroup is not full: [G][nsym] bytes for the pad frames' symbols (and for

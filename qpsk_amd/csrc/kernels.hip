@@ -67,7 +67,7 @@ rx_fused_kernel(FusedArgs a)
     if (tid < G) {
         const int fr = tid < gcount ? (a.frame_list ? a.frame_list[f0 + tid] : f0 + tid) : 0;
         fid[tid] = fr;
-        idx[tid] = (tid < gcount) ? (a.index ? a.index[fr] : a.fixed_index) : 0;
+        idx[tid] = (tid < gcount) ? checked_index(a.index ? a.index[fr] : a.fixed_index, a.status) : 0;
     }
 
     /* Costas lane state (wave 0 only) */
@@ -83,6 +83,7 @@ rx_fused_kernel(FusedArgs a)
         if (a.state_in) {
             st.phase = a.state_in[2 * ((size_t)fid[lane_g] * nbw + lane_b)];
             st.freq = a.state_in[2 * ((size_t)fid[lane_g] * nbw + lane_b) + 1];
+            if (a.seed_setters) seed_setters(st.phase, st.freq, a.min_freq, a.max_freq, over);
         }
     }
 

@@ -37,6 +37,10 @@ struct Shard {
     hipStream_t compute = nullptr, copy = nullptr;
     float *d_in = nullptr;            /* [count][frame_size][2]; owned unless `borrowed` */
     bool borrowed = false;
+    /* qpsk_multi_set_acquisition: this shard's slice of the caller's offsets [count] and seeds [count][2] (NULL: not given); acq = run the ext call */
+    int32_t *d_acq_index = nullptr;
+    float *d_acq_seed = nullptr;
+    bool acq = false;
     uint8_t *d_sym[2] = {nullptr, nullptr};
     uint8_t *d_pack[2] = {nullptr, nullptr};      /* packed mode: four symbols per byte, what is copied back instead of d_sym */
     float *d_fp[2] = {nullptr, nullptr};          /* freq [count] then phase [count] */
@@ -92,8 +96,10 @@ int shard_begin(qpsk_multi *mj, Shard *s, int slot)
     }
     /* the kernel may overwrite the slot only once its previous copy-back has left it */
     M_HIP(s, hipStreamWaitEvent(s->compute, s->copied[slot], 0));
-    const int rc = qpsk_rx_batch(s->ctx, s->d_in, (int)s->count, s->d_sym[slot], s->d_fp[slot], s->d_fp[slot] + s->count, nullptr,
-                                 nullptr, nullptr);
+    const int rc = s->acq ? qpsk_rx_batch_ext(s->ctx, s->d_in, 0, (int)s->count, s->d_acq_index, s->d_acq_seed, s->d_sym[slot], s->d_fp[slot],
+                                              s->d_fp[slot] + s->count, nullptr, nullptr, nullptr)
+                          : qpsk_rx_batch(s->ctx, s->d_in, (int)s->count, s->d_sym[slot], s->d_fp[slot], s->d_fp[slot] + s->count, nullptr,
+                                          nullptr, nullptr);
     if (rc) {
         snprintf(s->err, sizeof(s->err), "device %d: %s", s->device, qpsk_last_error());
         return rc;
@@ -204,6 +210,11 @@ void free_shard_buffers(Shard *s)
     if (s->d_in && !s->borrowed) hipFree(s->d_in);
     s->d_in = nullptr;
     s->borrowed = false;
+    if (s->d_acq_index) hipFree(s->d_acq_index);
+    if (s->d_acq_seed) hipFree(s->d_acq_seed);
+    s->d_acq_index = nullptr;
+    s->d_acq_seed = nullptr;
+    s->acq = false;
     for (int k = 0; k < 2; k++) {
         if (s->d_sym[k]) hipFree(s->d_sym[k]);
         if (s->d_pack[k]) hipFree(s->d_pack[k]);
@@ -376,6 +387,49 @@ int qpsk_host_alloc(void **h_ptr, size_t bytes)
 int qpsk_host_free(void *h_ptr)
 {
     return hipHostFree(h_ptr) == hipSuccess ? QPSK_OK : qpsk_set_error(QPSK_ERR_HIP, "qpsk_host_free: hipHostFree failed");
+}
+
+int qpsk_multi_set_acquisition(qpsk_multi *mj, const int32_t *h_index, const float *h_seed)
+{
+    if (!mj || mj->total <= 0) return qpsk_set_error(QPSK_ERR_ARG, "qpsk_multi_set_acquisition: null job or no frames loaded");
+    for (Shard *s : mj->shards)
+        if (s->in_flight[0] || s->in_flight[1]) return qpsk_set_error(QPSK_ERR_STATE, "qpsk_multi_set_acquisition: a slot is in flight");
+    /* every shard's new slices first; only when all stand do they replace the old ones (a failure leaves every shard as it was) */
+    const size_t ns = mj->shards.size();
+    std::vector<int32_t *> ni(ns, nullptr);
+    std::vector<float *> nsd(ns, nullptr);
+    bool ok = true;
+    for (size_t r = 0; r < ns && ok; r++) {
+        Shard *s = mj->shards[r];
+        if (s->count == 0) continue;
+        const size_t n = (size_t)s->count;
+        ok = hipSetDevice(s->device) == hipSuccess;
+        if (ok && h_index)
+            ok = hipMalloc((void **)&ni[r], sizeof(int32_t) * n) == hipSuccess &&
+                 hipMemcpy(ni[r], h_index + s->first, sizeof(int32_t) * n, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok && h_seed)
+            ok = hipMalloc((void **)&nsd[r], sizeof(float) * 2 * n) == hipSuccess &&
+                 hipMemcpy(nsd[r], h_seed + 2 * (size_t)s->first, sizeof(float) * 2 * n, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    if (!ok) {
+        for (size_t r = 0; r < ns; r++) {
+            hipSetDevice(mj->shards[r]->device);
+            if (ni[r]) hipFree(ni[r]);
+            if (nsd[r]) hipFree(nsd[r]);
+        }
+        return qpsk_set_error(QPSK_ERR_ALLOC, "qpsk_multi_set_acquisition: allocation or upload of a shard's slice failed; no shard changed");
+    }
+    for (size_t r = 0; r < ns; r++) {
+        Shard *s = mj->shards[r];
+        hipSetDevice(s->device);
+        if (s->compute) hipStreamSynchronize(s->compute);      /* the last step that read the old slices */
+        if (s->d_acq_index) hipFree(s->d_acq_index);
+        if (s->d_acq_seed) hipFree(s->d_acq_seed);
+        s->d_acq_index = ni[r];
+        s->d_acq_seed = nsd[r];
+        s->acq = h_index || h_seed;
+    }
+    return QPSK_OK;
 }
 
 int qpsk_multi_rx_begin(qpsk_multi *mj, int slot)

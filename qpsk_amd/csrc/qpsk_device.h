@@ -86,6 +86,27 @@ __device__ __forceinline__ float phase_wrap(float p, bool &over)
     return p;
 }
 
+/* set_phase() + set_frequency() (costas_loop.c:117-132) on a loop state loaded as a caller's seed: the phase wrapped as phase_wrap()
+ * wraps it (bounded: `over` as there), the frequency clamped as frequency_limit() clamps it (-0 stays -0).  A NaN / Inf seed raises
+ * `over` here, at the load: the call fails with QPSK_ERR_RANGE whatever the serial stream then makes of the state */
+__device__ __forceinline__ void seed_setters(float &phase, float &freq, float min_freq, float max_freq, bool &over)
+{
+    if (!(fabsf(phase) <= 3.402823466e+38f) || !(fabsf(freq) <= 3.402823466e+38f)) over = true;
+    phase = phase_wrap(phase, over);
+    freq = freq > max_freq ? max_freq : (freq < min_freq ? min_freq : freq);
+}
+
+/* a per-frame decimation offset as the kernels read it: a value outside 0..MAX_INDEX (only a caller's array can hold one) is reported
+ * through the context's status word (STATUS_BAD_INDEX -> QPSK_ERR_ARG at the next synchronisation) and replaced by 0, so that no
+ * address is ever formed from it */
+__device__ __forceinline__ int checked_index(int ix, int *status)
+{
+    const bool bad = (unsigned)ix > (unsigned)MAX_INDEX;
+    if (__builtin_expect(bad, 0) && status)
+        __hip_atomic_store(status, STATUS_BAD_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return bad ? 0 : ix;
+}
+
 /* qpsk.c:74-79 with the natural symbol index (bits[1]<<1)|bits[0], qpsk.c:270 */
 __device__ __forceinline__ int slicer(float2 z)
 {

@@ -226,12 +226,16 @@ __device__ __forceinline__ void costas_wave(const FusedArgs &a, SM *sm, const fl
     const bool active = inwg && f0 + g < a.nframes;
     Loop st = {0.0f, 0.0f};
     LoopGains lg = {0.0f, 0.0f, a.min_freq, a.max_freq};
+    bool over = false;   /* a phase beyond the bounded 2 pi wrap (qpsk_device.h, phase_wrap) */
     if (active) {
         lg.alpha = a.gains[2 * b];
         lg.beta = a.gains[2 * b + 1];
         if (a.state_in) {
             st.phase = a.state_in[2 * ((size_t)(f0 + g) * nbw + b)];
             st.freq = a.state_in[2 * ((size_t)(f0 + g) * nbw + b) + 1];
+            /* a caller's seed (qpsk_rx_batch_ext): set_phase() / set_frequency() here, in the prologue, so that the first record -- the
+             * phase the first step starts from -- is the wrapped seed, and the -0 tests below see the state the steps will see */
+            if (a.seed_setters) seed_setters(st.phase, st.freq, a.min_freq, a.max_freq, over);
         }
     }
     /* the FIR wave that feeds this lane: 4 frames each; in the mixed workgroup frames 12..15 come two per wave */
@@ -242,7 +246,6 @@ __device__ __forceinline__ void costas_wave(const FusedArgs &a, SM *sm, const fl
     /* one median-of-3 instead of two compare/select pairs when the clamp is the usual min < 0 < max */
     const bool fast_clamp = a.min_freq < 0.0f && a.max_freq > 0.0f;
     float ph = st.phase, fr = st.freq;
-    bool over = false;   /* a phase beyond the bounded 2 pi wrap (qpsk_device.h, phase_wrap) */
     /* Symbols that are exactly (+0, +0) -- a stream's first block, a squelched input, an all-zero frame -- trip the instruction
      * stream's exact-zero test in every group although its step is the reference's for them (costas_asm.h, `ign`).  When a group
      * is abandoned, the lanes that tripped the test look at the symbols they have ahead in the chunk: nothing but +0.0 there and no
@@ -622,7 +625,7 @@ costas_pipe_kernel(FusedArgs a, int *status)
              * the slots this lane has just emptied, off the hand-over path */
             const float2 *blk = a.refill + (size_t)frame * a.frame_size;
             float2 *row = a.refill_dst + (size_t)frame * a.dstride;
-            const int ix = a.index ? a.index[frame] : a.fixed_index;
+            const int ix = checked_index(a.index ? a.index[frame] : a.fixed_index, a.status);
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 const int i = c * S + R * q + r, s = i * a.cycles + ix;
@@ -791,7 +794,7 @@ rx_fused_pipe_kernel(FusedArgs a, int *status)
             const int fr = f0 + gbase + ff;
             cx.fv[ff] = fr < a.nframes;
             const int ix = a.est_tw ? (cx.fv[ff] ? sm->est_index[gbase + ff] : 0)
-                                    : a.index ? (cx.fv[ff] ? a.index[fr] : 0) : a.fixed_index;   /* decimation offset, < C */
+                                    : checked_index(a.index ? (cx.fv[ff] ? a.index[fr] : 0) : a.fixed_index, a.status);   /* decimation offset, < C */
             const int p0 = 2 * lane + 126 - ix;               /* window position of sample 2*lane of the chunk */
             cx.wr0[ff] = (gbase + ff) * WSLOTS + p0 + PADS * (p0 / PAD);
             cx.wr1[ff] = (gbase + ff) * WSLOTS + (p0 + 1) + PADS * ((p0 + 1) / PAD);
@@ -1151,7 +1154,7 @@ __device__ __forceinline__ void fir_wave2(const FusedArgs &a, Smem *sm, float2 *
         for (int ff = 0; ff < UF; ff++) {
             const int fr = f0 + UF * U.u + ff;
             U.fv[ff] = UF * U.u + ff < G && fr < a.nframes;      /* an odd G leaves the last unit one frame */
-            const int ix = a.index ? (U.fv[ff] ? a.index[fr] : 0) : a.fixed_index;   /* decimation offset, < C */
+            const int ix = checked_index(a.index ? (U.fv[ff] ? a.index[fr] : 0) : a.fixed_index, a.status);   /* decimation offset, < C */
             U.ix[ff] = __builtin_amdgcn_readfirstlane(ix);
             U.src[ff] = reinterpret_cast<const float4 *>(a.x + (size_t)(U.fv[ff] ? fr : 0) * a.frame_pitch);
             U.hist[ff] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);       /* a fresh delay line (qpsk.c:37) */
@@ -1561,7 +1564,7 @@ __device__ __forceinline__ void fir_wave_lean(const FusedArgs &a, lean::Ctl *sm,
         for (int ff = 0; ff < UF; ff++) {
             const int fr = f0 + UF * (u0 + ui) + ff;
             /* decimation offset, < C: the estimate made inside this launch (est[], in LDS), the caller's array, or the fixed one */
-            const int ix = __builtin_amdgcn_readfirstlane(est ? est[UF * (u0 + ui) + ff] : a.index ? a.index[min(fr, a.nframes - 1)] : a.fixed_index) & 7;
+            const int ix = checked_index(__builtin_amdgcn_readfirstlane(est ? est[UF * (u0 + ui) + ff] : a.index ? a.index[min(fr, a.nframes - 1)] : a.fixed_index), status);
             ixpack |= (unsigned)ix << (4 * (2 * ui + ff));
         }
     /* which stream this wave runs (wave-uniform): LDS-DMA staging needs even offsets (16-byte pairs); a two-unit wave that stages by
@@ -1846,8 +1849,8 @@ unsigned long long lean_default_layout(int NU)
 
 /* what rx_lean_kernel serves (see its header); the caller has checked CYCLES = 8, the alignment and the filter's symmetry */
 bool lean_shape_ok(const FusedArgs &a, int G)
-{
-    return a.nbw == 1 && !a.costas && !a.state_in && !a.state_out && a.nsym % pipe2::S == 0 && a.nsym >= 2 * pipe2::S &&
+{   /* a loop state to start from only as a caller's seed (qpsk_rx_batch_ext: costas_wave applies the setters in its prologue) */
+    return a.nbw == 1 && !a.costas && (!a.state_in || a.seed_setters) && !a.state_out && a.nsym % pipe2::S == 0 && a.nsym >= 2 * pipe2::S &&
            a.frame_size == a.nsym * C && G >= 2 && G % 2 == 0 && G <= pipe2::UF * pipe2::MAX_UNITS && a.nframes >= 1 &&
            (a.nframes % G == 0 || a.sym_pad) && !(a.dbg & (8 | 16));
 }

@@ -55,6 +55,7 @@ API_SYMBOLS = [
     "qpsk_multi_create", "qpsk_multi_destroy", "qpsk_multi_shards", "qpsk_multi_load", "qpsk_multi_shard", "qpsk_multi_use_device_input",
     "qpsk_multi_rx_begin", "qpsk_multi_rx_end", "qpsk_multi_set_direct_output", "qpsk_host_alloc", "qpsk_host_free",
     "qpsk_multi_set_packed", "qpsk_pack_symbols", "qpsk_unpack_symbols_host",
+    "qpsk_rx_batch_ext", "qpsk_rx_batch_bw_ext", "qpsk_multi_set_acquisition",
 ]
 # every symbol include/qpsk_dropin.h declares
 DROPIN_SYMBOLS = [
@@ -106,6 +107,9 @@ def load():
     L.qpsk_rx_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.qpsk_rx_batch_pitched.argtypes = [vp, vp, C.c_longlong, i32, vp, vp, vp, vp, vp, vp]
     L.qpsk_rx_batch_bw.argtypes = [vp, vp, i32, C.POINTER(f32), i32, vp, vp, vp, vp]
+    L.qpsk_rx_batch_ext.argtypes = [vp, vp, C.c_longlong, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.qpsk_rx_batch_bw_ext.argtypes = [vp, vp, i32, C.POINTER(f32), i32, vp, vp, vp, vp, vp, vp]
+    L.qpsk_multi_set_acquisition.argtypes = [vp, vp, vp]
     L.qpsk_rrc_fir_batch.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_rrc_fir_batch_fast.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_timing_hist_batch.argtypes = [vp, vp, i32, vp, vp]
@@ -283,6 +287,44 @@ class Modem:
                  phase=self.empty((F, B), t.float32), index=self.empty((F,), t.int32))
         self._check(self.L.qpsk_rx_batch_bw(self.h, _ptr(x), F, bws, B, _ptr(o["sym"]), _ptr(o["freq"]),
                                             _ptr(o["phase"]), _ptr(o["index"])))
+        return o
+
+    def rx_batch_ext(self, frames, index=None, seed=None, want_costas=False, pitch=0):
+        """rx_batch with the acquisition from outside (qpsk_rx_batch_ext): index (F,) int32 decimation offsets 0..7 in place of the
+        context's timing estimate, seed (F, 2) float32 (phase, freq) each loop starts from (set_phase / set_frequency); None = the
+        context's timing / (0, 0).  pitch: frames are (F, pitch, 2) with the first frame_size samples of each row used (0 = packed).
+        An offset outside 0..7 or a bad seed is reported by the next synchronising call (sync())."""
+        t = self.torch
+        x = self._dev(frames, t.float32)
+        F = x.shape[0]
+        assert x.shape[1] == (pitch or self.frame_size) and x.shape[2] == 2
+        ix = None if index is None else self._dev(index, t.int32)
+        sd = None if seed is None else self._dev(seed, t.float32)
+        assert ix is None or tuple(ix.shape) == (F,)
+        assert sd is None or tuple(sd.shape) == (F, 2)
+        o = dict(sym=self.empty((F, self.nsym), t.uint8), freq=self.empty((F,), t.float32),
+                 phase=self.empty((F,), t.float32), index=self.empty((F,), t.int32), hz=self.empty((F,), t.float32),
+                 costas=self.empty((F, self.nsym, 2), t.float32) if want_costas else None)
+        self._check(self.L.qpsk_rx_batch_ext(self.h, _ptr(x), int(pitch), F, _ptr(ix), _ptr(sd), _ptr(o["sym"]), _ptr(o["freq"]),
+                                             _ptr(o["phase"]), _ptr(o["costas"]), _ptr(o["index"]), _ptr(o["hz"])))
+        o["_keep"] = (x, ix, sd)      # the inputs stay alive until the caller is done with the outputs (stream order)
+        return o
+
+    def rx_batch_bw_ext(self, frames, loop_bws, index=None, seed=None):
+        """rx_batch_bw with the acquisition from outside (qpsk_rx_batch_bw_ext): index (F,) int32 or None, seed (F, nbw, 2) or None"""
+        t = self.torch
+        x = self._dev(frames, t.float32)
+        F, B = x.shape[0], len(loop_bws)
+        bws = (C.c_float * B)(*[float(b) for b in loop_bws])
+        ix = None if index is None else self._dev(index, t.int32)
+        sd = None if seed is None else self._dev(seed, t.float32)
+        assert ix is None or tuple(ix.shape) == (F,)
+        assert sd is None or tuple(sd.shape) == (F, B, 2)
+        o = dict(sym=self.empty((F, B, self.nsym), t.uint8), freq=self.empty((F, B), t.float32),
+                 phase=self.empty((F, B), t.float32), index=self.empty((F,), t.int32))
+        self._check(self.L.qpsk_rx_batch_bw_ext(self.h, _ptr(x), F, bws, B, _ptr(ix), _ptr(sd), _ptr(o["sym"]), _ptr(o["freq"]),
+                                                _ptr(o["phase"]), _ptr(o["index"])))
+        o["_keep"] = (x, ix, sd)
         return o
 
     # ---- stages
@@ -476,6 +518,16 @@ class MultiJob:
     def end(self, slot, sym=None, freq=None, phase=None):
         p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)      # noqa: E731
         self._check(self.L.qpsk_multi_rx_end(self.h, slot, p(sym), p(freq), p(phase)))
+
+    def set_acquisition(self, index=None, seed=None):
+        """qpsk_multi_set_acquisition: index (total,) int32 and / or seed (total, 2) float32 host arrays for every later begin(); both
+        None = back to the contexts' timing.  A later load() clears it."""
+        ix = None if index is None else np.ascontiguousarray(index, np.int32)
+        sd = None if seed is None else np.ascontiguousarray(seed, np.float32)
+        assert ix is None or ix.shape == (self.total,)
+        assert sd is None or sd.shape == (self.total, 2)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        self._check(self.L.qpsk_multi_set_acquisition(self.h, p(ix), p(sd)))
 
     def set_packed(self, on):
         self._check(self.L.qpsk_multi_set_packed(self.h, int(bool(on))))
