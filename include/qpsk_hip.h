@@ -205,6 +205,31 @@ int qpsk_rx_batch_bw_ext(qpsk_ctx *ctx, const float *d_in, int nframes, const fl
                          const float *d_seed, uint8_t *d_sym, float *d_freq, float *d_phase, int32_t *d_index);
 
 /* -------------------------------------------------------------------------
+ * A coarse carrier estimate per frame, in the form the ext calls take as a seed: the Costas loop (costas_loop.c) matched bit for bit
+ * only pulls in small offsets within a frame; a Doppler offset beyond its pull-in range is acquired by seeding the loop's frequency.
+ * Per frame x, with the context's taps, CYCLES = C and loop clamp [min_freq, max_freq] (qpsk_ctx_set_loop):
+ *   y  = rrc_fir() of x[0 .. start+n-1] with a fresh delay line          (bit for bit qpsk_rrc_fir_batch)
+ *   z[m] = y[start+m]^4 in fp64, m < n: with a = y.re, b = y.im: s = (a*a - b*b, 2.0*(a*b)), z = (s.re*s.re - s.im*s.im, 2.0*(s.re*s.im))
+ *   X  = fftn(z, n)                                                       (fft.c:110-120; bit for bit qpsk_fft_batch)
+ *   S  = { integer k : |k| < n / (2 C), min_freq <= w(k) <= max_freq },  w(k) = (float)(TAU * (double)(k*C) / (double)(4*n)) rad/symbol
+ *   k* = the k in S with the largest X.re*X.re + X.im*X.im of X[k mod n] (fp64); ties: the smallest |k|, then the smaller k
+ * A signal rotating as e^{+j 2 pi df t} gives w(k*) ~ +2 pi df / RS (the sign of get_frequency()).  RANGE: |df| < RS / 8 (+-300 Hz at
+ * 2400 baud): S is limited to |w| < pi / 4 because y^4 also carries symbol-rate sidebands at 4 df +- RS, which an offset inside the range
+ * never puts into S.  RESOLUTION: one bin = 2 pi C / (4 n) rad/symbol (0.0123 at C = 8, n = 1024).  No phase estimate: the seed's
+ * phase is 0.  The definition has no counterpart in the reference beyond the filter and the transform (parity unpinned).
+ *
+ *   frame_pitch  as qpsk_rx_batch_ext (0 = frame_size; otherwise even and >= frame_size)
+ *   start, n     the window: start >= 0, n a power of two in 64..8192, start + n <= frame_size
+ *   d_seed       [nframes][2] float (0, w(k*)): pass it unchanged to qpsk_rx_batch_ext as d_seed
+ *   d_freq       [nframes] float w(k*);  d_bin [nframes] int32 k*;  d_line [nframes][2] double X[k*]
+ * Each output may be NULL, not all.  QPSK_ERR_ARG at the call for a bad argument or an empty S; a NaN / Inf sample the estimate reads
+ * (x[max(0, start-126) .. start+n-1]) gives QPSK_ERR_RANGE at the next synchronisation.  Stream-ordered; qpsk_ctx_last_kernel() names
+ * the kernel; the histogram mode's one-pass guess is neither read nor updated.  Usage: INTEGRATION.md 2.0.
+ * ------------------------------------------------------------------------- */
+int qpsk_carrier_est_batch(qpsk_ctx *ctx, const float *d_in, long long frame_pitch, int nframes, int start, int n,
+                           float *d_seed, float *d_freq, int32_t *d_bin, double *d_line);
+
+/* -------------------------------------------------------------------------
  * The stages on their own (each is what the corresponding reference function
  * computes, batched).
  * ------------------------------------------------------------------------- */

@@ -205,6 +205,9 @@ static int check_status(qpsk_ctx *c)
     if (st == STATUS_BAD_INDEX)
         return fail(QPSK_ERR_ARG, "an external timing offset (qpsk_rx_batch_ext d_index_in) lies outside 0..%d: the kernel demodulated that frame "
                                   "at offset 0; results of the calls since the last synchronisation are invalid", MAX_INDEX);
+    if (st == STATUS_EST_NONFINITE)
+        return fail(QPSK_ERR_RANGE, "qpsk_carrier_est_batch: a NaN / Inf sample inside the window the estimate reads; results of the calls since "
+                                    "the last synchronisation are invalid");
     if (st == STATUS_NONFINITE)
         return fail(QPSK_ERR_RANGE, "a Costas loop ended on a NaN / Inf state: the input held a non-finite sample (the reference hangs in phase_wrap() "
                                     "on an infinite phase, costas_loop.c:61-67); results of the calls since the last synchronisation are invalid");
@@ -326,6 +329,7 @@ int qpsk_ctx_create(qpsk_ctx **out, int device, const qpsk_params *p, void *stre
     KERNEL_TRY(prepare_timing_scan());
     KERNEL_TRY(prepare_stream_block());
     KERNEL_TRY(prepare_stream_scan());
+    KERNEL_TRY(prepare_carrier_est());
     qpsk_ctx *c = new qpsk_ctx();
     c->device = device;
     for (const auto &k : TUNING_KEYS) {   /* the only place the environment is read */
@@ -1155,6 +1159,50 @@ int qpsk_timing_fft_bin_batch(qpsk_ctx *c, const float *d_in, int nframes, int32
     if (nframes <= 0) return fail(QPSK_ERR_ARG, "nframes = %d", nframes);
     if (bind(c)) return QPSK_ERR_HIP;
     return fft_timing_indices(c, d_in, nframes, d_index, d_filtered, nullptr, 0, d_bin);
+}
+
+/* the fourth-power carrier estimate (carrier_est.hip; definition in include/qpsk_hip.h).  S = { k : |k| < n / (2 CYCLES), min_freq <=
+ * w(k) <= max_freq } is a contiguous range of k (w(k) is monotone in k): found here, once per call, with the kernel's own formula */
+static float carrier_est_omega(int k, int C, int n)
+{
+    const double tau = 2.0 * 3.14159265358979323846;      /* qpsk.h:29, as the kernel's TAU */
+    return (float)(tau * (double)(k * C) / (double)(4 * n));
+}
+
+int qpsk_carrier_est_batch(qpsk_ctx *c, const float *d_in, long long frame_pitch, int nframes, int start, int n, float *d_seed,
+                           float *d_freq, int32_t *d_bin, double *d_line)
+{
+    if (!c || !d_in) return fail(QPSK_ERR_ARG, "qpsk_carrier_est_batch: null context or input");
+    if (!d_seed && !d_freq && !d_bin && !d_line) return fail(QPSK_ERR_ARG, "qpsk_carrier_est_batch: every output is NULL");
+    if (nframes <= 0) return fail(QPSK_ERR_ARG, "qpsk_carrier_est_batch: nframes = %d", nframes);
+    if (n < 64 || n > 8192 || (n & (n - 1)))
+        return fail(QPSK_ERR_ARG, "qpsk_carrier_est_batch: n = %d must be a power of two in 64..8192", n);
+    const int fs = c->prm.frame_size;
+    if (start < 0 || (long long)start + n > fs)
+        return fail(QPSK_ERR_ARG, "qpsk_carrier_est_batch: start %d + n %d outside the frame (%d samples)", start, n, fs);
+    if (frame_pitch == 0) frame_pitch = fs;
+    if (frame_pitch < fs || (frame_pitch % 2) != 0)
+        return fail(QPSK_ERR_ARG, "qpsk_carrier_est_batch: frame_pitch = %lld (0, or even and >= frame_size %d)", frame_pitch, fs);
+    const int C = c->cycles;
+    int klo = 1, khi = 0;
+    for (int k = -(n / (2 * C)); k <= n / (2 * C); k++) {
+        if ((long long)(k < 0 ? -k : k) * 2 * C >= n) continue;
+        const float w = carrier_est_omega(k, C, n);
+        if (!(w >= c->min_freq && w <= c->max_freq)) continue;
+        if (klo > khi) klo = k;
+        khi = k;
+    }
+    if (klo > khi)
+        return fail(QPSK_ERR_ARG, "qpsk_carrier_est_batch: no bin |k| < n / (2 CYCLES) = %d / %d lies in the loop clamp [%g, %g]", n, 2 * C,
+                    (double)c->min_freq, (double)c->max_freq);
+    const int kdef = klo <= 0 && khi >= 0 ? 0 : (khi < 0 ? khi : klo);
+    if (bind(c)) return QPSK_ERR_HIP;
+    double *tw = nullptr;
+    if (int rt = get_twiddles(c, n, &tw)) return rt;
+    KERNEL_TRY(launch_carrier_est(d_in, (size_t)frame_pitch, nframes, start, n, C, klo, khi, kdef, c->d_taps, tw, d_seed, d_freq, d_bin,
+                                  d_line, c->d_status, c->taps_symmetric && tuned(c->tune.fir_generic, 0) == 0, c->stream));
+    c->last_kernel = "carrier_est_kernel";
+    return QPSK_OK;
 }
 
 int qpsk_costas_batch(qpsk_ctx *c, const float *d_symbols_in, int nframes, int nsym, float *d_state, uint8_t *d_sym,

@@ -18,6 +18,7 @@ constexpr int STATUS_PHASE_RANGE = 2;    /* a loop phase beyond the bounded 2 pi
 constexpr int STATUS_NONFINITE = 3;      /* a loop ended on a NaN / Inf phase or frequency: the input held a non-finite sample */
 constexpr int STATUS_BAD_INDEX = 4;      /* a per-frame decimation offset outside 0..MAX_INDEX (caller-supplied: qpsk_rx_batch_ext); the kernel
                                             addressed with 0 instead */
+constexpr int STATUS_EST_NONFINITE = 5;  /* qpsk_carrier_est_batch: a NaN / Inf sample inside the window the estimate reads */
 
 struct FusedArgs {
     const float2 *x;        /* [nframes] frames of frame_size samples, frame_pitch samples apart */
@@ -153,6 +154,12 @@ int launch_timing_fft(const float *x, int nframes, int frame_size, int cycles, c
                       pruned one), Xk [nframes][2] the symbol-rate bin as the pruned transform delivers it */
 int timing_fft_nfft(void);
 int timing_fft_first(void);
+/* carrier_est.hip: the fourth-power carrier estimate (qpsk_carrier_est_batch) over S = [klo, khi] (kdef: the member of S with the
+ * smallest |k|); tw: the size-n twiddle table; pitch in samples; each output may be NULL */
+int prepare_carrier_est(void);
+int launch_carrier_est(const float *x, size_t pitch, int nframes, int start, int n, int cycles, int klo, int khi, int kdef,
+                       const float *taps, const double *tw, float *seed, float *freq, int32_t *bin, double *line, int *status,
+                       bool symmetric, hipStream_t s);
 /* streamblock.hip: one launch per rx_frame() block and stream (few, short streams: the reference's call pattern) */
 struct StreamBlockArgs {
     const int16_t *pcm;     /* [n][frame_size] PCM (device memory or mapped pinned host memory), or NULL: */

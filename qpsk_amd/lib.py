@@ -55,7 +55,7 @@ API_SYMBOLS = [
     "qpsk_multi_create", "qpsk_multi_destroy", "qpsk_multi_shards", "qpsk_multi_load", "qpsk_multi_shard", "qpsk_multi_use_device_input",
     "qpsk_multi_rx_begin", "qpsk_multi_rx_end", "qpsk_multi_set_direct_output", "qpsk_host_alloc", "qpsk_host_free",
     "qpsk_multi_set_packed", "qpsk_pack_symbols", "qpsk_unpack_symbols_host",
-    "qpsk_rx_batch_ext", "qpsk_rx_batch_bw_ext", "qpsk_multi_set_acquisition",
+    "qpsk_rx_batch_ext", "qpsk_rx_batch_bw_ext", "qpsk_multi_set_acquisition", "qpsk_carrier_est_batch",
 ]
 # every symbol include/qpsk_dropin.h declares
 DROPIN_SYMBOLS = [
@@ -110,6 +110,7 @@ def load():
     L.qpsk_rx_batch_ext.argtypes = [vp, vp, C.c_longlong, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.qpsk_rx_batch_bw_ext.argtypes = [vp, vp, i32, C.POINTER(f32), i32, vp, vp, vp, vp, vp, vp]
     L.qpsk_multi_set_acquisition.argtypes = [vp, vp, vp]
+    L.qpsk_carrier_est_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, vp, vp, vp, vp]
     L.qpsk_rrc_fir_batch.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_rrc_fir_batch_fast.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_timing_hist_batch.argtypes = [vp, vp, i32, vp, vp]
@@ -325,6 +326,23 @@ class Modem:
         self._check(self.L.qpsk_rx_batch_bw_ext(self.h, _ptr(x), F, bws, B, _ptr(ix), _ptr(sd), _ptr(o["sym"]), _ptr(o["freq"]),
                                                 _ptr(o["phase"]), _ptr(o["index"])))
         o["_keep"] = (x, ix, sd)
+        return o
+
+    def carrier_est(self, frames, n=1024, start=128, pitch=0, want_line=False):
+        """Coarse carrier estimate from the fourth-power line (qpsk_carrier_est_batch) over samples start .. start + n - 1 of each frame:
+        dict of torch tensors seed (F, 2) float32 = (0, freq), ready for rx_batch_ext(seed=...); freq (F,) float32 in rad/symbol; bin (F,)
+        int32; with want_line also line (F, 2) float64, the spectral line X[bin].  pitch as rx_batch_ext.  A NaN / Inf sample inside the
+        window is reported by the next synchronising call (sync())."""
+        t = self.torch
+        x = self._dev(frames, t.float32)
+        F = x.shape[0]
+        assert x.shape[1] == (pitch or self.frame_size) and x.shape[2] == 2
+        o = dict(seed=self.empty((F, 2), t.float32), freq=self.empty((F,), t.float32), bin=self.empty((F,), t.int32))
+        if want_line:
+            o["line"] = self.empty((F, 2), t.float64)
+        self._check(self.L.qpsk_carrier_est_batch(self.h, _ptr(x), int(pitch), F, int(start), int(n), _ptr(o["seed"]), _ptr(o["freq"]),
+                                                  _ptr(o["bin"]), _ptr(o.get("line"))))
+        o["_keep"] = (x,)      # the input stays alive until the caller is done with the outputs (stream order)
         return o
 
     # ---- stages
