@@ -200,6 +200,47 @@ int qpsk_rx_batch_bw(qpsk_ctx *ctx, const float *d_in, int nframes, const float 
 int qpsk_rx_batch_ext(qpsk_ctx *ctx, const float *d_in, long long frame_pitch, int nframes, const int32_t *d_index_in,
                       const float *d_seed, uint8_t *d_sym, float *d_freq, float *d_phase, float *d_costas, int32_t *d_index,
                       float *d_hz);
+/* -------------------------------------------------------------------------
+ * DATA: the same batch with the transmitter's dibits as an output.  d_sym is the reference's slicer bit for bit, and the reference's
+ * loop parks the constellation on the diagonals, which qpsk_demod() turns another 45 degrees onto its own decision boundaries: d_sym
+ * is half noise by construction.  d_data takes the decision the loop's constellation supports.  Per symbol i, with
+ * z = costas_frame[i] exactly as qpsk.c:197 forms it:
+ *       bits[0] = z.re < 0.0f;  bits[1] = z.im < 0.0f;  d_data = (bits[1] << 1) | bits[0]
+ * i.e. qpsk_demod() WITHOUT its ROT45 step.  At the loop's rotation 0 this is the dibit qpsk_tx_symbols() sent (qpsk.c:58-63:
+ * 1 -> 0, j -> 1, -j -> 2, -1 -> 3); the loop may settle on any of four quarter turns, which qpsk_sync_batch() resolves.  The "< 0.0f"
+ * test does not see the sign of a zero, so every kernel route gives the same bits.
+ *
+ *   every argument it shares with qpsk_rx_batch_ext: the same meaning, the same error contract (the histogram mode's guess left alone)
+ *   d_data   [nframes][nsym] uint8, required
+ *   d_sym    [nframes][nsym] uint8 or NULL: the slicer's decisions as well
+ * Every output other than d_data is bit for bit what qpsk_rx_batch_ext() returns for the same arguments.  With d_sym NULL the batch runs
+ * on rx_lean_kernel wherever qpsk_rx_batch_ext() would (qpsk_ctx_last_kernel() says so), at the same speed; other shapes, and d_sym
+ * requested as well, dump costas_frame[] into a context buffer (8 bytes per symbol) and take the rule from it.
+ * ------------------------------------------------------------------------- */
+int qpsk_rx_batch_data(qpsk_ctx *ctx, const float *d_in, long long frame_pitch, int nframes, const int32_t *d_index_in,
+                       const float *d_seed, uint8_t *d_data, uint8_t *d_sym, float *d_freq, float *d_phase, int32_t *d_index,
+                       float *d_hz);
+
+/* -------------------------------------------------------------------------
+ * SYNC: a caller's sync word places the payload in each row of data decisions and resolves the loop's quarter-turn ambiguity.
+ * ring = {0, 1, 3, 2} is a dibit's place on the circle in quarter turns (its own inverse); only the low two bits of d_data are read.
+ * For every lag L in [lag_min, lag_max] and rotation r in 0..3:
+ *       score(L, r) = #{ i < nsync : ring[(ring[data[L+i]] - r) & 3] == sync[i] }
+ * (L*, r*) has the largest score; ties go to the smallest L, then the smallest r.  Per frame f:
+ *       d_out[f][i] = ring[(ring[data[L*+nsync+i]] - r*) & 3], i < nout      (the payload de-rotated into the transmitter's dibits)
+ *       d_lag[f] = L*,  d_rot[f] = r*,  d_score[f] = score(L*, r*)
+ *
+ *   d_data       [nframes][nsym] uint8 (qpsk_rx_batch_data's d_data; nsym is the row length)
+ *   h_sync       [nsync] dibits 0..3 on the host, 1 <= nsync <= 128: it travels in the kernel arguments, so it may be freed on return
+ *   lag window   0 <= lag_min <= lag_max, lag_max + nsync + nout <= nsym (a window as large as the whole row works)
+ *   outputs      d_out [nframes][nout] uint8 (must not overlap d_data), d_lag, d_rot, d_score [nframes] int32; each may be NULL, not all
+ * QPSK_ERR_ARG at the call for a bad argument.  A sync word equal to one of its own rotations -- as a rotated, shifted copy of itself,
+ * e.g. a periodic word -- cannot resolve the ambiguity: the tie rule then picks the smallest lag and rotation.  The call does not check
+ * for this; choose a word whose rotations match it poorly at every shift.  Stream-ordered.
+ * ------------------------------------------------------------------------- */
+int qpsk_sync_batch(qpsk_ctx *ctx, const uint8_t *d_data, int nframes, int nsym, const uint8_t *h_sync, int nsync, int lag_min,
+                    int lag_max, int nout, uint8_t *d_out, int32_t *d_lag, int32_t *d_rot, int32_t *d_score);
+
 /* qpsk_rx_batch_bw() the same way: d_seed [nframes][nbw][2] (one seed per loop) or NULL; d_index_in [nframes] or NULL */
 int qpsk_rx_batch_bw_ext(qpsk_ctx *ctx, const float *d_in, int nframes, const float *h_loop_bw, int nbw, const int32_t *d_index_in,
                          const float *d_seed, uint8_t *d_sym, float *d_freq, float *d_phase, int32_t *d_index);
@@ -417,6 +458,9 @@ int qpsk_host_free(void *h_ptr);
  * are uploaded once, here (no slot may be in flight).  A call that fails on any shard leaves every shard with its previous setting;
  * a later qpsk_multi_load clears it. */
 int qpsk_multi_set_acquisition(qpsk_multi *mj, const int32_t *h_index, const float *h_seed);
+/* Data mode: while on, every rx_begin runs qpsk_rx_batch_data (with the acquisition above, if set) and the rows it gathers (h_sym of
+ * rx_end, direct or packed as before) hold the data rule's decisions instead of the slicer's.  No slot may be in flight (QPSK_ERR_STATE). */
+int qpsk_multi_set_data(qpsk_multi *mj, int on);
 int qpsk_multi_rx_begin(qpsk_multi *mj, int slot);
 int qpsk_multi_rx_end(qpsk_multi *mj, int slot, uint8_t *h_sym, float *h_freq, float *h_phase);
 

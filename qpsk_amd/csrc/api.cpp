@@ -125,6 +125,7 @@ struct qpsk_ctx {
     int *d_status = nullptr;     /* device view of the same word */
     std::vector<float> h_gains;
     DevBuf index, filtered, mixed, keystream, sympad, mislist;
+    DevBuf datacostas;            /* qpsk_rx_batch_data off rx_lean_kernel: the costas_frame[] the data rule is taken from */
     /* the one-pass histogram route (rx_hist_kernel): d_hint[0] = the guessed decimation offset = the majority index of the context's last
      * histogram-mode batch (left there by index_majority_kernel, in stream order: no synchronisation), d_hint[1] = the frames the guess
      * missed in the running call; h_hist_stats (pinned, written by that kernel) = {majority, frames, missed} of the last batch whose
@@ -659,9 +660,9 @@ struct ExtAcq {
 
 static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch, int nframes, int nbw, uint8_t *d_sym,
                            float *d_freq, float *d_phase, float *d_costas, int32_t *d_index, float *d_hz,
-                           const ExtAcq *ext = nullptr)
+                           const ExtAcq *ext = nullptr, uint8_t *d_data = nullptr)
 {
-    if (!c || !d_in || !d_sym) return fail(QPSK_ERR_ARG, "qpsk_rx_batch: null context, input or symbol buffer");
+    if (!c || !d_in || !(d_sym || d_data)) return fail(QPSK_ERR_ARG, "qpsk_rx_batch: null context, input or symbol buffer");
     if (nframes <= 0) return fail(QPSK_ERR_ARG, "qpsk_rx_batch: nframes = %d", nframes);
     if (frame_pitch == 0) frame_pitch = c->prm.frame_size;
     if (frame_pitch < c->prm.frame_size)
@@ -692,7 +693,14 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
     a.min_freq = c->min_freq;
     a.max_freq = c->max_freq;
     a.rs = c->prm.rs;
-    a.sym = d_sym;
+    /* qpsk_rx_batch_data: with d_sym NULL, rx_lean_kernel writes the data rule's decisions where the slicer's go (FusedArgs::data_rule);
+     * every other route dumps costas_frame[] and takes the data rule from it behind the launch (below) */
+    a.sym = d_sym ? d_sym : d_data;
+    a.data_rule = d_data && !d_sym;
+    if (d_data && d_sym && !d_costas) {
+        if (int rd = ensure(c, c->datacostas, sizeof(float2) * (size_t)nframes * (size_t)c->nsym)) return rd;
+        d_costas = (float *)c->datacostas.p;
+    }
     a.freq = d_freq;
     a.phase = d_phase;
     a.costas = reinterpret_cast<float2 *>(d_costas);
@@ -818,6 +826,11 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
     if (!lean) {
         int rp = plan_general(nframes, pipe_v == 3 ? (nframes > 16 * c->ncu ? 2 : 1) : pipe_v, &main_pl);
         if (rp) return rp;
+        if (d_data && !a.costas) {
+            if (int rd = ensure(c, c->datacostas, sizeof(float2) * (size_t)nframes * (size_t)c->nsym)) return rd;
+            a.costas = (float2 *)c->datacostas.p;
+        }
+        a.data_rule = 0;
     }
 
     /* ---- histogram timing in ONE pass (round 6; rx_fused.hip, rx_hist_kernel): where the context has a guess -- the majority index of
@@ -900,6 +913,8 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
         /* only rx_fused_pipe_kernel's full workgroups and rx_lean_kernel look at est_tw; any other kernel would demodulate with fixed_index */
         if (fa.est_tw && !(pl.kind == K_FUSED_PIPE && pl.nf == pipe_max_nf()) && pl.kind != K_LEAN)
             return fail(QPSK_ERR_STATE, "internal: in-launch FFT timing estimate planned for a kernel that has none");
+        if (fa.data_rule && pl.kind != K_LEAN)
+            return fail(QPSK_ERR_STATE, "internal: data rule planned for a kernel that has none");
         switch (pl.kind) {
         case K_LEAN:
             KERNEL_TRY(launch_rx_lean(fa, pl.G, pl.layout, c->d_status, c->stream));
@@ -950,9 +965,11 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
         /* the last frame of an odd batch shares its two-frame unit with a pad frame: the unit's rows are pad rows (rx_fused.hip,
          * lean_unit_rows); its own row goes to its place behind the launch */
         const size_t last0 = (size_t)((nframes - 1) / main_pl.G) * (size_t)main_pl.G;      /* the last workgroup's first frame */
-        HIP_TRY(hipMemcpyAsync(d_sym + (size_t)(nframes - 1) * (size_t)c->nsym, (const uint8_t *)c->sympad.p + ((size_t)(nframes - 1) - last0) * (size_t)c->nsym,
+        HIP_TRY(hipMemcpyAsync(a.sym + (size_t)(nframes - 1) * (size_t)c->nsym, (const uint8_t *)c->sympad.p + ((size_t)(nframes - 1) - last0) * (size_t)c->nsym,
                                (size_t)c->nsym, hipMemcpyDeviceToDevice, c->stream));
     }
+    if (d_data && !a.data_rule)      /* qpsk_rx_batch_data off rx_lean_kernel: the data rule over the costas_frame[] just written */
+        KERNEL_TRY(launch_data_from_costas(a.costas, d_data, (size_t)nframes * (size_t)c->nsym, c->stream));
     if (d_index) {
         if (idx == d_index) {
             /* the caller's own offsets, in place */
@@ -1018,6 +1035,42 @@ int qpsk_rx_batch_ext(qpsk_ctx *c, const float *d_in, long long frame_pitch, int
     if (frame_pitch < 0) return fail(QPSK_ERR_ARG, "qpsk_rx_batch_ext: frame_pitch = %lld", frame_pitch);
     const ExtAcq ext = {d_index_in, d_seed};
     return rx_batch_common(c, d_in, frame_pitch, nframes, 1, d_sym, d_freq, d_phase, d_costas, d_index, d_hz, &ext);
+}
+
+int qpsk_rx_batch_data(qpsk_ctx *c, const float *d_in, long long frame_pitch, int nframes, const int32_t *d_index_in, const float *d_seed,
+                       uint8_t *d_data, uint8_t *d_sym, float *d_freq, float *d_phase, int32_t *d_index, float *d_hz)
+{
+    if (c) {
+        if (bind(c)) return QPSK_ERR_HIP;
+        if (int rg = use_context_gains(c)) return rg;
+    }
+    if (frame_pitch < 0) return fail(QPSK_ERR_ARG, "qpsk_rx_batch_data: frame_pitch = %lld", frame_pitch);
+    if (!d_data) return fail(QPSK_ERR_ARG, "qpsk_rx_batch_data: d_data is NULL");
+    const ExtAcq ext = {d_index_in, d_seed};
+    return rx_batch_common(c, d_in, frame_pitch, nframes, 1, d_sym, d_freq, d_phase, nullptr, d_index, d_hz, &ext, d_data);
+}
+
+int qpsk_sync_batch(qpsk_ctx *c, const uint8_t *d_data, int nframes, int nsym, const uint8_t *h_sync, int nsync, int lag_min, int lag_max,
+                    int nout, uint8_t *d_out, int32_t *d_lag, int32_t *d_rot, int32_t *d_score)
+{
+    if (!c || !d_data || !h_sync) return fail(QPSK_ERR_ARG, "qpsk_sync_batch: null context, data or sync word");
+    if (nframes <= 0 || nsym <= 0) return fail(QPSK_ERR_ARG, "qpsk_sync_batch: nframes = %d, nsym = %d", nframes, nsym);
+    if (nsync < 1 || nsync > SYNC_MAX_WORD) return fail(QPSK_ERR_ARG, "qpsk_sync_batch: nsync = %d outside 1..%d", nsync, SYNC_MAX_WORD);
+    if (nout < 0 || lag_min < 0 || lag_max < lag_min || (long long)lag_max + nsync + nout > nsym)
+        return fail(QPSK_ERR_ARG, "qpsk_sync_batch: lags %d..%d, nsync %d, nout %d do not fit a row of %d", lag_min, lag_max, nsync, nout, nsym);
+    if (!d_out && !d_lag && !d_rot && !d_score) return fail(QPSK_ERR_ARG, "qpsk_sync_batch: every output is NULL");
+    for (int i = 0; i < nsync; i++)
+        if (h_sync[i] > 3) return fail(QPSK_ERR_ARG, "qpsk_sync_batch: sync[%d] = %d is not a dibit", i, (int)h_sync[i]);
+    if (d_out && nout > 0) {
+        const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)nframes * (size_t)nout;
+        const uintptr_t d0 = (uintptr_t)d_data, d1 = d0 + (size_t)nframes * (size_t)nsym;
+        if (o0 < d1 && d0 < o1) return fail(QPSK_ERR_ARG, "qpsk_sync_batch: d_out overlaps d_data");
+    }
+    if (bind(c)) return QPSK_ERR_HIP;
+    KERNEL_TRY(launch_sync_search(d_data, nframes, nsym, h_sync, nsync, lag_min, lag_max, nout, nout > 0 ? d_out : nullptr, d_lag, d_rot,
+                                  d_score, c->stream));
+    c->last_kernel = "sync_search_kernel";
+    return QPSK_OK;
 }
 
 int qpsk_rx_batch_bw_ext(qpsk_ctx *c, const float *d_in, int nframes, const float *h_loop_bw, int nbw, const int32_t *d_index_in,

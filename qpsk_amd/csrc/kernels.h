@@ -84,6 +84,8 @@ struct FusedArgs {
     float *carrier_state;
     float2 *carrier_tab;
     int carrier_frame;      /* samples per block of that table */
+    int data_rule;          /* rx_lean_kernel only (qpsk_rx_batch_data): sym / sym_pad receive the data rule's decisions (qpsk_device.h,
+                               data_rule) instead of the slicer's.  0 = the slicer */
 };
 
 size_t fused_lds_bytes(int G, int S, int cycles, int nbw);
@@ -218,6 +220,12 @@ int launch_crc16(const uint8_t *data, int npackets, int nbytes, uint16_t *crc, h
 int launch_interleave(uint8_t *data, int npackets, int nbytes, unsigned b, int dir, hipStream_t s);
 int launch_scramble(uint8_t *sym, const uint8_t *keystream, int npackets, int nsym, hipStream_t s);
 int launch_pack_dibits(const uint8_t *sym, uint8_t *packed, size_t nrows, int nsym, hipStream_t s);      /* sym 16-byte aligned when nsym % 16 == 0 */
+/* sync.hip: the sync-word search of qpsk_sync_batch (h_sync: nsync <= SYNC_MAX_WORD dibits on the host, passed in the kernel arguments; the
+ * caller has checked every bound), and the data rule over a costas_frame[] dump (qpsk_rx_batch_data off rx_lean_kernel) */
+constexpr int SYNC_MAX_WORD = 128;
+int launch_sync_search(const uint8_t *data, int nframes, int nsym, const uint8_t *h_sync, int nsync, int lag_min, int lag_max, int nout,
+                       uint8_t *out, int32_t *lag, int32_t *rot, int32_t *score, hipStream_t s);
+int launch_data_from_costas(const float2 *costas, uint8_t *data, size_t n, hipStream_t s);
 /* txchain.hip */
 int tx_history_symbols(void);          /* symbols of state per transmitter (uint8 each, 4 = none yet) */
 int launch_tx_shape(const uint8_t *sym, uint8_t *hist, const float *taps, float *sig, int nstreams, int nsym,

@@ -70,6 +70,7 @@ struct qpsk_multi {
     qpsk_params prm{};
     int nsym = 0;
     bool packed = false;      /* h_sym rows are ceil(nsym / 4) bytes (qpsk_multi_set_packed) */
+    bool data = false;        /* rows are qpsk_rx_batch_data's decisions (qpsk_multi_set_data) */
     size_t row_bytes() const { return packed ? (size_t)(nsym + 3) / 4 : (size_t)nsym; }
     long long total = 0;
     std::vector<Shard *> shards;
@@ -96,7 +97,9 @@ int shard_begin(qpsk_multi *mj, Shard *s, int slot)
     }
     /* the kernel may overwrite the slot only once its previous copy-back has left it */
     M_HIP(s, hipStreamWaitEvent(s->compute, s->copied[slot], 0));
-    const int rc = s->acq ? qpsk_rx_batch_ext(s->ctx, s->d_in, 0, (int)s->count, s->d_acq_index, s->d_acq_seed, s->d_sym[slot], s->d_fp[slot],
+    const int rc = mj->data ? qpsk_rx_batch_data(s->ctx, s->d_in, 0, (int)s->count, s->d_acq_index, s->d_acq_seed, s->d_sym[slot], nullptr,
+                                                 s->d_fp[slot], s->d_fp[slot] + s->count, nullptr, nullptr)
+                 : s->acq ? qpsk_rx_batch_ext(s->ctx, s->d_in, 0, (int)s->count, s->d_acq_index, s->d_acq_seed, s->d_sym[slot], s->d_fp[slot],
                                               s->d_fp[slot] + s->count, nullptr, nullptr, nullptr)
                           : qpsk_rx_batch(s->ctx, s->d_in, (int)s->count, s->d_sym[slot], s->d_fp[slot], s->d_fp[slot] + s->count, nullptr,
                                           nullptr, nullptr);
@@ -374,6 +377,15 @@ int qpsk_multi_set_packed(qpsk_multi *mj, int on)
     for (Shard *s : mj->shards)
         if (s->in_flight[0] || s->in_flight[1]) return qpsk_set_error(QPSK_ERR_STATE, "qpsk_multi_set_packed: a slot is in flight");
     mj->packed = on != 0;
+    return QPSK_OK;
+}
+
+int qpsk_multi_set_data(qpsk_multi *mj, int on)
+{
+    if (!mj) return qpsk_set_error(QPSK_ERR_ARG, "qpsk_multi_set_data: null job");
+    for (Shard *s : mj->shards)
+        if (s->in_flight[0] || s->in_flight[1]) return qpsk_set_error(QPSK_ERR_STATE, "qpsk_multi_set_data: a slot is in flight");
+    mj->data = on != 0;
     return QPSK_OK;
 }
 

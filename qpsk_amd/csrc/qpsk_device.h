@@ -115,6 +115,13 @@ __device__ __forceinline__ int slicer(float2 z)
     return ((ri < 0.0f) ? 2 : 0) | ((rr < 0.0f) ? 1 : 0);
 }
 
+/* the data rule of qpsk_rx_batch_data: qpsk_demod() on costas_frame[i] WITHOUT its ROT45 step -- at the loop's rotation 0 the dibit
+ * qpsk_tx_symbols sent (qpsk.c:58-63).  "< 0.0f" does not see the sign of a zero */
+__device__ __forceinline__ int data_rule(float2 z)
+{
+    return ((z.y < 0.0f) ? 2 : 0) | ((z.x < 0.0f) ? 1 : 0);
+}
+
 /* one iteration of qpsk.c:196-212: returns the de-rotated symbol, advances the loop.
  * EXACT_ZERO = true uses the sin/cos form that also reproduces sin(-0) = -0; the faster form is
  * identical for every other argument and a -0 phase can only be LOADED, never produced by the loop

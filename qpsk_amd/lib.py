@@ -56,6 +56,7 @@ API_SYMBOLS = [
     "qpsk_multi_rx_begin", "qpsk_multi_rx_end", "qpsk_multi_set_direct_output", "qpsk_host_alloc", "qpsk_host_free",
     "qpsk_multi_set_packed", "qpsk_pack_symbols", "qpsk_unpack_symbols_host",
     "qpsk_rx_batch_ext", "qpsk_rx_batch_bw_ext", "qpsk_multi_set_acquisition", "qpsk_carrier_est_batch",
+    "qpsk_rx_batch_data", "qpsk_sync_batch", "qpsk_multi_set_data",
 ]
 # every symbol include/qpsk_dropin.h declares
 DROPIN_SYMBOLS = [
@@ -111,6 +112,9 @@ def load():
     L.qpsk_rx_batch_bw_ext.argtypes = [vp, vp, i32, C.POINTER(f32), i32, vp, vp, vp, vp, vp, vp]
     L.qpsk_multi_set_acquisition.argtypes = [vp, vp, vp]
     L.qpsk_carrier_est_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, vp, vp, vp, vp]
+    L.qpsk_rx_batch_data.argtypes = [vp, vp, C.c_longlong, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.qpsk_sync_batch.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.qpsk_multi_set_data.argtypes = [vp, i32]
     L.qpsk_rrc_fir_batch.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_rrc_fir_batch_fast.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_timing_hist_batch.argtypes = [vp, vp, i32, vp, vp]
@@ -204,8 +208,13 @@ class Modem:
         except Exception:
             pass
 
-    def sync(self):
-        self._check(self.L.qpsk_ctx_sync(self.h))
+    def sync(self, data=None, sync=None, lag_min=0, lag_max=0, nout=0):
+        """No arguments: wait for the context's work (qpsk_ctx_sync) and report a kernel's verdict.  With data and a sync word: the
+        sync-word search of qpsk_sync_batch (see _sync_search)."""
+        if data is None:
+            self._check(self.L.qpsk_ctx_sync(self.h))
+            return None
+        return self._sync_search(data, sync, lag_min, lag_max, nout)
 
     def last_kernel(self):
         """Name of the receive kernel the last rx_batch*() call launched (which geometry served that shape)."""
@@ -309,6 +318,41 @@ class Modem:
         self._check(self.L.qpsk_rx_batch_ext(self.h, _ptr(x), int(pitch), F, _ptr(ix), _ptr(sd), _ptr(o["sym"]), _ptr(o["freq"]),
                                              _ptr(o["phase"]), _ptr(o["costas"]), _ptr(o["index"]), _ptr(o["hz"])))
         o["_keep"] = (x, ix, sd)      # the inputs stay alive until the caller is done with the outputs (stream order)
+        return o
+
+    def rx_batch_data(self, frames, index=None, seed=None, want_sym=False, pitch=0):
+        """rx_batch_ext with the data rule's decisions (qpsk_rx_batch_data): dict of torch tensors data (F, nsym) uint8 -- (z.im < 0) << 1 |
+        (z.re < 0) of costas_frame[], the transmitter's dibits up to the loop's quarter-turn rotation -- and freq, phase, index, hz as
+        rx_batch_ext; with want_sym also sym, the slicer's decisions.  index, seed, pitch as rx_batch_ext."""
+        t = self.torch
+        x = self._dev(frames, t.float32)
+        F = x.shape[0]
+        assert x.shape[1] == (pitch or self.frame_size) and x.shape[2] == 2
+        ix = None if index is None else self._dev(index, t.int32)
+        sd = None if seed is None else self._dev(seed, t.float32)
+        assert ix is None or tuple(ix.shape) == (F,)
+        assert sd is None or tuple(sd.shape) == (F, 2)
+        o = dict(data=self.empty((F, self.nsym), t.uint8), sym=self.empty((F, self.nsym), t.uint8) if want_sym else None,
+                 freq=self.empty((F,), t.float32), phase=self.empty((F,), t.float32), index=self.empty((F,), t.int32),
+                 hz=self.empty((F,), t.float32))
+        self._check(self.L.qpsk_rx_batch_data(self.h, _ptr(x), int(pitch), F, _ptr(ix), _ptr(sd), _ptr(o["data"]), _ptr(o["sym"]),
+                                              _ptr(o["freq"]), _ptr(o["phase"]), _ptr(o["index"]), _ptr(o["hz"])))
+        o["_keep"] = (x, ix, sd)
+        return o
+
+    def _sync_search(self, data, sync, lag_min, lag_max, nout):
+        """Sync-word search (qpsk_sync_batch) over data (F, nsym) uint8 decisions: sync is a sequence of dibits (1..128 of them), lags
+        lag_min..lag_max.  Dict of torch tensors out (F, nout) uint8 -- the payload behind the word, de-rotated into the transmitter's
+        dibits -- lag, rot, score (F,) int32."""
+        t = self.torch
+        d = self._dev(data, t.uint8)
+        F, N = d.shape
+        sw = np.ascontiguousarray(np.asarray(sync, dtype=np.uint8))
+        o = dict(out=self.empty((F, nout), t.uint8), lag=self.empty((F,), t.int32), rot=self.empty((F,), t.int32),
+                 score=self.empty((F,), t.int32))
+        self._check(self.L.qpsk_sync_batch(self.h, _ptr(d), F, N, sw.ctypes.data_as(C.c_void_p), len(sw), int(lag_min), int(lag_max),
+                                           int(nout), _ptr(o["out"]), _ptr(o["lag"]), _ptr(o["rot"]), _ptr(o["score"])))
+        o["_keep"] = (d,)
         return o
 
     def rx_batch_bw_ext(self, frames, loop_bws, index=None, seed=None):
@@ -550,6 +594,11 @@ class MultiJob:
     def set_packed(self, on):
         self._check(self.L.qpsk_multi_set_packed(self.h, int(bool(on))))
         self.packed = bool(on)
+
+    def set_data(self, on):
+        """qpsk_multi_set_data: while on, the gathered rows are qpsk_rx_batch_data's decisions instead of the slicer's"""
+        self._check(self.L.qpsk_multi_set_data(self.h, int(bool(on))))
+        self.data = bool(on)
 
     def unpack(self, packed):
         out = np.empty((packed.shape[0], self.nsym), np.uint8)

@@ -4,6 +4,7 @@ one gfx950 instruction stream per wave shape (1 or 2 two-frame units per wave).
 
     python tools/gen_lean_asm.py > qpsk_amd/csrc/fir_lean_asm.h
     python tools/gen_lean_asm.py --profile > qpsk_amd/csrc/build/fir_lean_prof_asm.h   (measurement build only: `make profile` does this)
+    python tools/gen_lean_asm.py --data > qpsk_amd/csrc/build/fir_lean_data_asm.h      (qpsk_rx_batch_data's streams: every `make` does this)
 
 What one iteration of the loop does for one unit (2 frames x 64 symbols of chunk c; reference rrc_fir.c:17-30 evaluated at
 the samples qpsk.c:190 keeps, then the slicer of qpsk.c:74-79 on the loop's de-rotated symbols, qpsk.c:197):
@@ -20,7 +21,8 @@ the samples qpsk.c:190 keeps, then the slicer of qpsk.c:74-79 on the loop's de-r
   flush     of chunk c - 2, once the loop has consumed it: sin/cos of the recorded phase again (the library's
             polynomials, Horner form), T = d x conj(C + jS) exactly as the loop formed it, (T.x, T.y) * ROT45, sum and
             difference, then the quadrant of the phase selects and signs them (bits[0] = Re < 0, bits[1] = Im < 0 of
-            qpsk.c:77-78 on the rotated symbol -- exact, including the zeros); one 2-byte store per lane;
+            qpsk.c:77-78 on the rotated symbol -- exact, including the zeros); one 2-byte store per lane.  The _data streams
+            (qpsk_rx_batch_data) skip the rotation and the sum / difference: the quadrant selects and signs (T.x, T.y) itself;
   hand-over the unit's 128 new symbols -> the symbol ring, then ready[unit] = c + 1 (LDS executes a wave's operations in
             order: no fence, and in particular no wait for the global stores and loads in flight).
 Synchronisation with the serial wave: `consumed` (and the workgroup's abort flag beside it) polled with bounded spins.
@@ -75,6 +77,7 @@ PROFILE = False
 #            the register path (one load, one ds_write_b128, the history registers).  Even decimation offsets only (16-byte DMA
 #            granules).  [measured, profiles/r05_energy_ledger.txt] bit-exact, 1.7 % less energy per launch at 8192 frames.
 ABLATE = None
+DATA = False         # the flush takes the data rule of qpsk_rx_batch_data instead of the slicer (--data: fir_lean_loop*_data, built by make)
 DMA = False          # the stream with LDS-DMA window staging (fir_lean_loop*_dma), see "dma" above: product code since round 5
 TWOWIN = False       # DMA stream of a two-unit wave that has a window PER UNIT (fir_lean_loop2_dma2w; workgroups of up to 16 frames leave the
                      # LDS for it): unit 1's window lies WOFF bytes above unit 0's, so the next unit's DMAs are issued a whole unit ahead again
@@ -439,23 +442,27 @@ def flush(e, ui):
     for k in range(2):
         B = b[k]
         e("v_pk_add_f32 %s, %s, %s neg_hi:[0,1]", vp(B + 18), vp(B + 14), vp(B + 16))
-    for k in range(2):
-        B = b[k]
-        # (T.x, T.y) * ROT45 (qpsk.c:75: both components of the rotation are the same float)
-        e("v_pk_mul_f32 %s, %s, %s op_sel_hi:[1,0]", vp(B + 14), vp(B + 18), vp(TMP))
-    for k in range(2):
-        B = b[k]
-        e("v_sub_f32_e32 v%d, v%d, v%d", B + 16, B + 14, B + 15)      # D = a - b
-        e("v_add_f32_e32 v%d, v%d, v%d", B + 17, B + 14, B + 15)      # S = a + b
-    # quadrant q = n & 3 of the phase: z = T (-j)^q, so with (rr, ri) = (zx - zy, zx + zy) R:
-    #   q: 0 (D, S)   1 (S, -D)   2 (-D, -S)   3 (-S, D)        bits[0] = rr < 0, bits[1] = ri < 0
+    # DATA (qpsk_rx_batch_data): the signs of z = costas_frame[i] itself, no ROT45 and no sum / difference -- with z = T (-j)^q:
+    #   q: 0 (Tx, Ty)   1 (Ty, -Tx)   2 (-Tx, -Ty)   3 (-Ty, Tx)     bits[0] = z.re < 0, bits[1] = z.im < 0
+    if not DATA:
+        for k in range(2):
+            B = b[k]
+            # (T.x, T.y) * ROT45 (qpsk.c:75: both components of the rotation are the same float)
+            e("v_pk_mul_f32 %s, %s, %s op_sel_hi:[1,0]", vp(B + 14), vp(B + 18), vp(TMP))
+        for k in range(2):
+            B = b[k]
+            e("v_sub_f32_e32 v%d, v%d, v%d", B + 16, B + 14, B + 15)      # D = a - b
+            e("v_add_f32_e32 v%d, v%d, v%d", B + 17, B + 14, B + 15)      # S = a + b
+        # quadrant q = n & 3 of the phase: z = T (-j)^q, so with (rr, ri) = (zx - zy, zx + zy) R:
+        #   q: 0 (D, S)   1 (S, -D)   2 (-D, -S)   3 (-S, D)        bits[0] = rr < 0, bits[1] = ri < 0
     for k in range(2):
         B = b[k]
         n = B + 2
+        P, Q = (B + 18, B + 19) if DATA else (B + 16, B + 17)            # (D, S), or (Tx, Ty) for the data rule
         e("v_and_b32_e32 v%d, 1, v%d", B + 4, n)
         e("v_cmp_eq_u32_e32 vcc, 1, v%d", B + 4)
-        e("v_cndmask_b32_e32 v%d, v%d, v%d, vcc", B + 5, B + 16, B + 17)     # rr magnitude: q odd ? S : D
-        e("v_cndmask_b32_e32 v%d, v%d, v%d, vcc", B + 6, B + 17, B + 16)     # ri magnitude: q odd ? D : S
+        e("v_cndmask_b32_e32 v%d, v%d, v%d, vcc", B + 5, P, Q)     # rr magnitude: q odd ? S : D
+        e("v_cndmask_b32_e32 v%d, v%d, v%d, vcc", B + 6, Q, P)     # ri magnitude: q odd ? D : S
         e("v_and_b32_e32 v%d, 2, v%d", B + 4, n)
         e("v_lshl_add_u32 v%d, v%d, 30, v%d", B + 5, B + 4, B + 5)           # rr negated in quadrants 2, 3
         e("v_add_u32_e32 v%d, 1, v%d", B + 4, n)
@@ -695,7 +702,8 @@ __device__ __forceinline__ int fir_lean_loop%(nuw)d%(sfx)s(%(args)s, const LeanL
 }
 ''' % dict(nuw=nuw, n=len([ln for ln in lines if not ln.endswith(":")]), nvalu=nvalu, args=", ".join(args), body=body,
            ops=",\n          ".join(ops), clob=", ".join(clob), outs=",\n          ".join(outs),
-           sfx=("" if packed else "u") + ("_dma" if DMA else "") + ("2w" if TWOWIN else "") + ("_a" + ABLATE if ABLATE else "_prof" if PROFILE else ""),
+           sfx=("" if packed else "u") + ("_dma" if DMA else "") + ("2w" if TWOWIN else "") + ("_data" if DATA else "") +
+               ("_a" + ABLATE if ABLATE else "_prof" if PROFILE else ""),
            how="" if packed else ", the filter in single-float instructions (the wave beside the serial wave)", parg=", unsigned (&prof)[%d]" % NPROF if stamped else "")
 
 
@@ -728,6 +736,8 @@ def main():
     if "--profile" in sys.argv:
         PROFILE = True
         return main_profile()
+    if "--data" in sys.argv:
+        return main_data()
     print('''/*
  * fir_lean_asm.h -- GENERATED by tools/gen_lean_asm.py; do not edit.
  *
@@ -790,6 +800,31 @@ struct LeanLaneAddr {
     TWOWIN = False
     DMA = False
     print("constexpr unsigned FIR_LEAN_WOFF = %d;" % WOFF)
+    print("} // namespace qpsk\n#endif")
+
+
+def main_data():
+    global DATA, DMA, TWOWIN
+    DATA = True
+    print('''/*
+ * fir_lean_data_asm.h -- GENERATED at build time by tools/gen_lean_asm.py --data (the Makefile writes it into the build directory; it
+ * is not committed).  fir_lean_asm.h's five loops with the data rule of qpsk_rx_batch_data in the flush: bits[0] = z.re < 0,
+ * bits[1] = z.im < 0 of z = costas_frame[i] itself -- the slicer without its ROT45 step, so the rotation multiply and the sum /
+ * difference drop out and the quadrant of the phase selects and signs (T.x, T.y) directly.  Same registers, same contract, same
+ * stores (the symbol store bases receive the decisions).
+ */
+#ifndef QPSK_FIR_LEAN_DATA_ASM_H
+#define QPSK_FIR_LEAN_DATA_ASM_H
+#include "fir_lean_asm.h"
+
+namespace qpsk {''')
+    print(emit_function(1))
+    print(emit_function(2))
+    DMA = True
+    print(emit_function(1))
+    print(emit_function(2))
+    TWOWIN = True
+    print(emit_function(2))
     print("} // namespace qpsk\n#endif")
 
 
