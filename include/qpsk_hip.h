@@ -241,6 +241,38 @@ int qpsk_rx_batch_data(qpsk_ctx *ctx, const float *d_in, long long frame_pitch, 
 int qpsk_sync_batch(qpsk_ctx *ctx, const uint8_t *d_data, int nframes, int nsym, const uint8_t *h_sync, int nsync, int lag_min,
                     int lag_max, int nout, uint8_t *d_out, int32_t *d_lag, int32_t *d_rot, int32_t *d_score);
 
+/* -------------------------------------------------------------------------
+ * DEFRAMER: packets out of continuous streams of data decisions -- the stream calls' costas_frame[] block after block, or any rows
+ * of dibits.  One state per stream, independent of the receive streams' state.  For one stream let D be the concatenation of every
+ * row pushed since the reset, d[i] = ring[D[i] & 3] (ring as in SYNC), n = nsync and N = 4 (nbytes + 2).  Then, from h = 0:
+ *       score(p, r) = #{ i < n : (d[p+i] - ring[sync[i]]) & 3 == r }                 (qpsk_sync_batch's score)
+ *       p* = the smallest p >= h with p + n <= len(D) and max_r score(p, r) >= min_score;  r* = the smallest r attaining the max
+ *       the packet is complete once p* + n + N <= len(D), and reported by the push during which that happens:
+ *       u[i] = ring[(d[p*+n+i] - r*) & 3] ^ keystream[i], i < N    (de-rotated, then descrambled as qpsk_scramble_batch: SEED reloaded at
+ *                                                                   the payload's first dibit)
+ *       b[k] = u[4k] | u[4k+1] << 2 | u[4k+2] << 4 | u[4k+3] << 6  (qpsk_pack_symbols' packing)
+ *       crc_ok = crc16(b[0 .. nbytes-1]) == b[nbytes] << 8 | b[nbytes+1]
+ *       h = p* + n + N                                             (hunting resumes behind the packet, CRC pass or fail)
+ * The result depends only on D, not on how it is cut into pushes (apart from which push reports a packet).
+ *
+ * qpsk_deframer_reset: 1 <= nsync <= 128 dibits h_sync on the host (copied: it may be freed on return), 1 <= min_score <= nsync,
+ *   1 <= nbytes <= 1024, 1 <= max_packets <= 64.  Allocates and zeroes every stream's state; a second reset replaces everything.
+ * qpsk_deframer_push: exactly one input -- d_costas [nstreams][nsym][2] float (the stream calls' d_costas; qpsk_rx_batch_data's data
+ *   rule is applied on load) or d_data [nstreams][nsym] uint8 (only the low two bits are read); 1 <= nsym <= 2^21, any size per push.
+ *   Per stream s, the packets completed in this push:
+ *       d_count  [nstreams] int32             how many (the true number, also beyond max_packets)    -- required
+ *       d_bytes  [nstreams][max_packets][nbytes + 2] uint8   the payload and the received CRC        -- each of these may be NULL;
+ *       d_pos    [nstreams][max_packets] int64               p*, counted from the reset                 only the first min(count,
+ *       d_rot, d_score [nstreams][max_packets] int32          r*, score(p*, r*)                          max_packets) rows of a stream
+ *       d_crc_ok [nstreams][max_packets] uint8                                                           are written
+ * QPSK_ERR_ARG at the call for a bad argument (no input or both, an input overlapping an output); QPSK_ERR_STATE for a push before a
+ * reset.  Stream-ordered on the context's stream; touches neither the receive streams nor the batch paths.  A push that fails after
+ * it enqueued work leaves the deframer's state undefined: later pushes return QPSK_ERR_STATE until a reset has succeeded.
+ * ------------------------------------------------------------------------- */
+int qpsk_deframer_reset(qpsk_ctx *ctx, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets);
+int qpsk_deframer_push(qpsk_ctx *ctx, const float *d_costas, const uint8_t *d_data, int nsym, int32_t *d_count, uint8_t *d_bytes,
+                       long long *d_pos, int32_t *d_rot, int32_t *d_score, uint8_t *d_crc_ok);
+
 /* qpsk_rx_batch_bw() the same way: d_seed [nframes][nbw][2] (one seed per loop) or NULL; d_index_in [nframes] or NULL */
 int qpsk_rx_batch_bw_ext(qpsk_ctx *ctx, const float *d_in, int nframes, const float *h_loop_bw, int nbw, const int32_t *d_index_in,
                          const float *d_seed, uint8_t *d_sym, float *d_freq, float *d_phase, int32_t *d_index);

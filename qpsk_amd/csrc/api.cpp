@@ -160,6 +160,13 @@ struct qpsk_ctx {
     uint8_t *t_hist = nullptr;    /* [ntx][tx_history_symbols()]: the symbols still inside tx_filter */
     float *t_mixer = nullptr;     /* [ntx][4]: carrier phase and step */
     DevBuf tx_b;                  /* shaped baseband when the caller does not want it */
+    /* deframer (qpsk_deframer_*): per-stream state (kernels.h, DeframeHeader) and the tables (packed keystream, then the lanes' CRC
+     * advance factors at DF_ADV_OFFSET) */
+    uint8_t *df_state = nullptr, *df_tables = nullptr;
+    size_t df_stride = 0;
+    int df_nstreams = 0, df_nsync = 0, df_min_score = 0, df_nbytes = 0, df_max_packets = 0;
+    unsigned long long df_sync_lo[2] = {0, 0}, df_sync_hi[2] = {0, 0};
+    bool df_ready = false;        /* a reset has completed and no push has failed since */
 };
 
 static const int MAX_BW = 64;
@@ -384,6 +391,14 @@ static void free_streams(qpsk_ctx *c)
     c->nstreams = 0;
 }
 
+static void free_deframer(qpsk_ctx *c)
+{
+    hipFree(c->df_state); hipFree(c->df_tables);
+    c->df_state = c->df_tables = nullptr;
+    c->df_ready = false;
+    c->df_nstreams = 0;
+}
+
 static void free_transmitters(qpsk_ctx *c)
 {
     hipFree(c->t_hist); hipFree(c->t_mixer); hipFree(c->tx_b.p);
@@ -414,6 +429,7 @@ void qpsk_ctx_destroy(qpsk_ctx *c)
     hipFree(c->d_fast);
     free_streams(c);
     free_transmitters(c);
+    free_deframer(c);
     delete c;
 }
 
@@ -1854,6 +1870,120 @@ int qpsk_scramble_batch(qpsk_ctx *c, uint8_t *d_sym, int npackets, int nsym)
         c->keystream_len = nsym;
     }
     KERNEL_TRY(launch_scramble(d_sym, (const uint8_t *)c->keystream.p, npackets, nsym, c->stream));
+    return QPSK_OK;
+}
+
+/* ---------------------------------------------------------------- deframer */
+static const int DF_ADV_OFFSET = 1040;      /* the tables: keystream bytes [0, nbytes + 2), then 64 uint16 */
+
+/* x^(8 k) mod the CRC-16 polynomial 0x1021: k zero bytes through crc16()'s register, starting from 1 */
+static uint16_t crc_advance(int k)
+{
+    unsigned r = 1;
+    for (int i = 0; i < 8 * k; i++) r = ((r << 1) ^ ((r & 0x8000u) ? 0x1021u : 0u)) & 0xFFFFu;
+    return (uint16_t)r;
+}
+
+int qpsk_deframer_reset(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets)
+{
+    if (!c || !h_sync) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: null context or sync word");
+    if (nstreams <= 0) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: nstreams = %d", nstreams);
+    if (nsync < 1 || nsync > SYNC_MAX_WORD) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: nsync = %d outside 1..%d", nsync, SYNC_MAX_WORD);
+    if (min_score < 1 || min_score > nsync) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: min_score = %d outside 1..%d", min_score, nsync);
+    if (nbytes < 1 || nbytes > DEFRAME_MAX_BYTES) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: nbytes = %d outside 1..%d", nbytes, DEFRAME_MAX_BYTES);
+    if (max_packets < 1 || max_packets > DEFRAME_MAX_PACKETS)
+        return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: max_packets = %d outside 1..%d", max_packets, DEFRAME_MAX_PACKETS);
+    for (int i = 0; i < nsync; i++)
+        if (h_sync[i] > 3) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: sync[%d] = %d is not a dibit", i, (int)h_sync[i]);
+    if (bind(c)) return QPSK_ERR_HIP;
+    /* refused until this call has completed */
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    free_deframer(c);
+    const int nb = nbytes + 2, N = 4 * nb;
+    const size_t stride = (size_t)DEFRAME_PEND_OFFSET + (((size_t)N + 15) & ~(size_t)15);
+    if (hipMalloc(&c->df_state, stride * (size_t)nstreams) != hipSuccess || hipMalloc(&c->df_tables, DF_ADV_OFFSET + 128) != hipSuccess) {
+        free_deframer(c);
+        (void)hipGetLastError();
+        return fail(QPSK_ERR_ALLOC, "qpsk_deframer_reset: %d streams of %zu bytes of state", nstreams, stride);
+    }
+    std::vector<unsigned char> ks((size_t)N);
+    qpsk_host_scramble_keystream(ks.data(), N);
+    std::vector<uint8_t> tab(DF_ADV_OFFSET + 128, 0);
+    for (int k = 0; k < nb; k++) tab[k] = (uint8_t)(ks[4 * k] | ks[4 * k + 1] << 2 | ks[4 * k + 2] << 4 | ks[4 * k + 3] << 6);
+    const int per = (nb + 63) / 64;
+    for (int l = 0; l < 64; l++) {
+        const int end = (l + 1) * per < nbytes ? (l + 1) * per : nbytes;
+        const uint16_t v = crc_advance(nbytes - end);
+        memcpy(&tab[DF_ADV_OFFSET + 2 * l], &v, 2);
+    }
+    c->df_sync_lo[0] = c->df_sync_lo[1] = c->df_sync_hi[0] = c->df_sync_hi[1] = 0;
+    for (int i = 0; i < nsync; i++) {
+        const unsigned r = h_sync[i] ^ (h_sync[i] >> 1);
+        if (r & 1u) c->df_sync_lo[i >> 6] |= 1ull << (i & 63);
+        if (r & 2u) c->df_sync_hi[i >> 6] |= 1ull << (i & 63);
+    }
+    HIP_TRY(hipMemsetAsync(c->df_state, 0, stride * (size_t)nstreams, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->df_tables, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->df_stride = stride;
+    c->df_nstreams = nstreams;
+    c->df_nsync = nsync;
+    c->df_min_score = min_score;
+    c->df_nbytes = nbytes;
+    c->df_max_packets = max_packets;
+    c->df_ready = true;
+    return QPSK_OK;
+}
+
+int qpsk_deframer_push(qpsk_ctx *c, const float *d_costas, const uint8_t *d_data, int nsym, int32_t *d_count, uint8_t *d_bytes,
+                       long long *d_pos, int32_t *d_rot, int32_t *d_score, uint8_t *d_crc_ok)
+{
+    if (!c) return fail(QPSK_ERR_ARG, "qpsk_deframer_push: null context");
+    if ((d_costas != nullptr) == (d_data != nullptr)) return fail(QPSK_ERR_ARG, "qpsk_deframer_push: give exactly one of d_costas, d_data");
+    if (!d_count) return fail(QPSK_ERR_ARG, "qpsk_deframer_push: d_count is required");
+    if (nsym < 1 || nsym > DEFRAME_MAX_NSYM) return fail(QPSK_ERR_ARG, "qpsk_deframer_push: nsym = %d outside 1..%d", nsym, DEFRAME_MAX_NSYM);
+    if (!c->df_state) return fail(QPSK_ERR_STATE, "qpsk_deframer_push: no qpsk_deframer_reset yet");
+    if (!c->df_ready) return fail(QPSK_ERR_STATE, "qpsk_deframer_push: the deframer's state is undefined after a failed push; reset it");
+    const size_t S = (size_t)c->df_nstreams, M = (size_t)c->df_max_packets;
+    const uintptr_t i0 = d_costas ? (uintptr_t)d_costas : (uintptr_t)d_data;
+    const uintptr_t i1 = i0 + S * (size_t)nsym * (d_costas ? 2 * sizeof(float) : 1);
+    const struct { const void *p; size_t bytes; const char *name; } outs[] = {
+        {d_count, S * 4, "d_count"}, {d_bytes, S * M * (size_t)(c->df_nbytes + 2), "d_bytes"}, {d_pos, S * M * 8, "d_pos"},
+        {d_rot, S * M * 4, "d_rot"}, {d_score, S * M * 4, "d_score"}, {d_crc_ok, S * M, "d_crc_ok"}};
+    for (const auto &o : outs) {
+        if (!o.p) continue;
+        const uintptr_t o0 = (uintptr_t)o.p, o1 = o0 + o.bytes;
+        if (o0 < i1 && i0 < o1) return fail(QPSK_ERR_ARG, "qpsk_deframer_push: %s overlaps the input", o.name);
+    }
+    if (bind(c)) return QPSK_ERR_HIP;
+    DeframeArgs a{};
+    a.data = d_data;
+    a.costas = reinterpret_cast<const float2 *>(d_costas);
+    a.nstreams = c->df_nstreams;
+    a.nsym = nsym;
+    a.nsync = c->df_nsync;
+    a.min_score = c->df_min_score;
+    a.nbytes = c->df_nbytes;
+    a.max_packets = c->df_max_packets;
+    a.bytes_per_lane = (c->df_nbytes + 2 + 63) / 64;
+    a.state = c->df_state;
+    a.state_stride = c->df_stride;
+    a.keystream = c->df_tables;
+    a.crc_adv = reinterpret_cast<const uint16_t *>(c->df_tables + DF_ADV_OFFSET);
+    for (int i = 0; i < 2; i++) { a.sync_lo[i] = c->df_sync_lo[i]; a.sync_hi[i] = c->df_sync_hi[i]; }
+    a.count = d_count;
+    a.bytes = d_bytes;
+    a.pos = d_pos;
+    a.rot = d_rot;
+    a.score = d_score;
+    a.crc_ok = d_crc_ok;
+    (void)hipGetLastError();
+    const int e = launch_deframe(a, c->stream);
+    if (e != 0) {
+        c->df_ready = false;
+        return fail(QPSK_ERR_HIP, "deframe_kernel launch: %s", hipGetErrorString((hipError_t)e));
+    }
+    c->last_kernel = "deframe_kernel";
     return QPSK_OK;
 }
 

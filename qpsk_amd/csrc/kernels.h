@@ -226,6 +226,34 @@ constexpr int SYNC_MAX_WORD = 128;
 int launch_sync_search(const uint8_t *data, int nframes, int nsym, const uint8_t *h_sync, int nsync, int lag_min, int lag_max, int nout,
                        uint8_t *out, int32_t *lag, int32_t *rot, int32_t *score, hipStream_t s);
 int launch_data_from_costas(const float2 *costas, uint8_t *data, size_t n, hipStream_t s);
+/* deframe.hip: qpsk_deframer_push.  Per stream, state_stride bytes of state: the header, the carried tail (the ring values of the last
+ * min(len, nsync-1) dibits) at DEFRAME_TAIL_OFFSET, the pending packet's received payload (ring values) at DEFRAME_PEND_OFFSET */
+struct DeframeHeader {
+    long long len;          /* dibits pushed since the reset */
+    long long h;            /* the hunt resumes at this position */
+    long long ppos;         /* the pending packet: its sync word's position, rotation, score, payload dibits received */
+    int pending, have, prot, pscore;
+};
+constexpr int DEFRAME_TAIL_OFFSET = 64, DEFRAME_PEND_OFFSET = 192;
+constexpr int DEFRAME_MAX_BYTES = 1024, DEFRAME_MAX_PACKETS = 64, DEFRAME_MAX_NSYM = 1 << 21;
+struct DeframeArgs {
+    const uint8_t *data;          /* exactly one of data [nstreams][nsym] / costas [nstreams][nsym] */
+    const float2 *costas;
+    int nstreams, nsym;
+    int nsync, min_score, nbytes, max_packets;
+    int bytes_per_lane;           /* ceil((nbytes + 2) / 64): the packet bytes one lane builds */
+    uint8_t *state;
+    size_t state_stride;
+    const uint8_t *keystream;     /* [nbytes + 2]: the scrambler's keystream packed four dibits to the byte */
+    const uint16_t *crc_adv;      /* [64]: x^(8 k) mod the CRC-16 polynomial, k = the data bytes behind lane l's chunk */
+    unsigned long long sync_lo[2], sync_hi[2];   /* bit i % 64 of word i / 64: bit 0 / bit 1 of ring(sync[i]) */
+    int32_t *count;
+    uint8_t *bytes;
+    long long *pos;
+    int32_t *rot, *score;
+    uint8_t *crc_ok;
+};
+int launch_deframe(const DeframeArgs &a, hipStream_t s);
 /* txchain.hip */
 int tx_history_symbols(void);          /* symbols of state per transmitter (uint8 each, 4 = none yet) */
 int launch_tx_shape(const uint8_t *sym, uint8_t *hist, const float *taps, float *sig, int nstreams, int nsym,

@@ -115,6 +115,11 @@ __device__ __forceinline__ int slicer(float2 z)
     return ((ri < 0.0f) ? 2 : 0) | ((rr < 0.0f) ? 1 : 0);
 }
 
+/* ring(x) = {0, 1, 3, 2}[x] = x ^ (x >> 1): a dibit's place on the circle in quarter turns (qpsk.c:58-63), its own inverse.  The sync
+ * search (sync.hip) and the deframer (deframe.hip) compare words in this form: a sync dibit s matches a received dibit x under rotation r
+ * exactly when r = (ring(x) - ring(s)) & 3 */
+__host__ __device__ __forceinline__ unsigned ring_of(unsigned x) { return x ^ (x >> 1); }
+
 /* the data rule of qpsk_rx_batch_data: qpsk_demod() on costas_frame[i] WITHOUT its ROT45 step -- at the loop's rotation 0 the dibit
  * qpsk_tx_symbols sent (qpsk.c:58-63).  "< 0.0f" does not see the sign of a zero */
 __device__ __forceinline__ int data_rule(float2 z)

@@ -23,8 +23,6 @@ namespace {
 
 constexpr int SYNC_WAVES = 4;     /* frames per workgroup: one wave each */
 
-__host__ __device__ __forceinline__ unsigned ring_of(unsigned x) { return x ^ (x >> 1); }
-
 struct SyncWord {
     uint8_t ring[SYNC_MAX_WORD];  /* ring(sync[i]), i < nsync */
 };

@@ -56,7 +56,7 @@ API_SYMBOLS = [
     "qpsk_multi_rx_begin", "qpsk_multi_rx_end", "qpsk_multi_set_direct_output", "qpsk_host_alloc", "qpsk_host_free",
     "qpsk_multi_set_packed", "qpsk_pack_symbols", "qpsk_unpack_symbols_host",
     "qpsk_rx_batch_ext", "qpsk_rx_batch_bw_ext", "qpsk_multi_set_acquisition", "qpsk_carrier_est_batch",
-    "qpsk_rx_batch_data", "qpsk_sync_batch", "qpsk_multi_set_data",
+    "qpsk_rx_batch_data", "qpsk_sync_batch", "qpsk_multi_set_data", "qpsk_deframer_reset", "qpsk_deframer_push",
 ]
 # every symbol include/qpsk_dropin.h declares
 DROPIN_SYMBOLS = [
@@ -115,6 +115,8 @@ def load():
     L.qpsk_rx_batch_data.argtypes = [vp, vp, C.c_longlong, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.qpsk_sync_batch.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.qpsk_multi_set_data.argtypes = [vp, i32]
+    L.qpsk_deframer_reset.argtypes = [vp, i32, vp, i32, i32, i32, i32]
+    L.qpsk_deframer_push.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.qpsk_rrc_fir_batch.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_rrc_fir_batch_fast.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_timing_hist_batch.argtypes = [vp, vp, i32, vp, vp]
@@ -481,6 +483,38 @@ class Modem:
         o = self._stream_out(want_costas)
         self._check(self.L.qpsk_streams_rx_pcm(self.h, _ptr(x), _ptr(o["sym"]), _ptr(o["freq"]), _ptr(o["phase"]),
                                                _ptr(o["costas"]), _ptr(o["index"])))
+        return o
+
+    # ---- packets from continuous streams (qpsk_deframer_*)
+    def deframer_reset(self, nstreams, sync, nbytes, min_score, max_packets=8):
+        """One deframer state per stream (independent of the receive streams): sync is a sequence of 1..128 dibits, a packet is nbytes
+        of payload and its CRC-16; a position whose best rotation matches min_score or more of the word's dibits starts a packet."""
+        sw = np.ascontiguousarray(np.asarray(sync, dtype=np.uint8))
+        self._check(self.L.qpsk_deframer_reset(self.h, int(nstreams), sw.ctypes.data_as(C.c_void_p), len(sw), int(min_score), int(nbytes),
+                                               int(max_packets)))
+        self.df_shape = (int(nstreams), int(nbytes), int(max_packets))
+
+    def deframe(self, costas=None, data=None):
+        """Push one row per stream: costas (nstreams, nsym, 2) float32 -- e.g. the dict streams_rx_pcm(..., want_costas=True) returns --
+        or data (nstreams, nsym) uint8 dibits.  Dict of torch tensors for the packets completed by this push: count (nstreams,) int32
+        (the true number; only the first max_packets rows are written), bytes (nstreams, max_packets, nbytes + 2) uint8, pos
+        (nstreams, max_packets) int64, rot, score int32, crc_ok uint8."""
+        t = self.torch
+        if isinstance(costas, dict):
+            costas = costas["costas"]
+        if (costas is None) == (data is None):
+            raise ValueError("deframe() takes exactly one of costas, data")
+        x = self._dev(costas, t.float32) if costas is not None else self._dev(data, t.uint8)
+        S, nb, M = self.df_shape
+        if x.shape[0] != S or (costas is not None and (x.dim() != 3 or x.shape[2] != 2)) or (data is not None and x.dim() != 2):
+            raise ValueError("deframe() input must be (%d, nsym, 2) float32 or (%d, nsym) uint8" % (S, S))
+        o = dict(count=self.empty((S,), t.int32), bytes=self.torch.zeros((S, M, nb + 2), dtype=t.uint8, device=self.dev),
+                 pos=t.zeros((S, M), dtype=t.int64, device=self.dev), rot=t.zeros((S, M), dtype=t.int32, device=self.dev),
+                 score=t.zeros((S, M), dtype=t.int32, device=self.dev), crc_ok=t.zeros((S, M), dtype=t.uint8, device=self.dev))
+        self._check(self.L.qpsk_deframer_push(self.h, _ptr(x) if costas is not None else None, _ptr(x) if data is not None else None,
+                                              x.shape[1], _ptr(o["count"]), _ptr(o["bytes"]), _ptr(o["pos"]), _ptr(o["rot"]),
+                                              _ptr(o["score"]), _ptr(o["crc_ok"])))
+        o["_keep"] = (x,)
         return o
 
     def streams_loop_state(self):
