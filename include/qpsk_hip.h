@@ -303,6 +303,58 @@ int qpsk_carrier_est_batch(qpsk_ctx *ctx, const float *d_in, long long frame_pit
                            float *d_seed, float *d_freq, int32_t *d_bin, double *d_line);
 
 /* -------------------------------------------------------------------------
+ * SOFT DECISIONS AND SIGNAL QUALITY per row of costas_frame[] (what qpsk_rx_batch* with d_costas, qpsk_streams_rx_* and
+ * qpsk_costas_batch write).  The reference has no counterpart: this is the library's own definition (parity unpinned),
+ * restated in numpy by tests/test_soft_cpu.py.  Per symbol z = (a, b) of a row.
+ *
+ * SUMS.  IEEE fp64 on the float inputs widened to double, nothing fused, over the symbols skip <= i < nsym; k = i - skip, m = nsym - skip:
+ *       p = a*a + b*b;   s = (a*a - b*b, 2.0*(a*b))                                  (qpsk_carrier_est_batch's squaring)
+ *       t1 = |a| + |b|;  t2 = p;  t4 = p*p;  tq = s.re*s.re - s.im*s.im              ( = Re z^4 )
+ * The ORDER of summation is part of the definition.  There are 256 partial sums P[l], l = k mod 256; each starts from +0.0 and takes
+ * its terms in increasing k.  They are folded: for h = 128, 64, ..., 1: P[l] += P[l+h] for every l < h.  S1, S2, S4, SQ are the four P[0].
+ *
+ * QUALITY, d_quality [nrows][4] float, each figure computed in fp64 and rounded once:
+ *       M2 = S2/m;  M4 = S4/m;  D = 2*M2*M2 - M4;  Ps = D > 0 ? sqrt(D) : 0;  Pn = M2 - Ps
+ *                                                     (the M2M4 estimator: a constant-modulus signal in Gaussian noise)
+ *       [0] amp  = S1 / (2m)                 mean |component|: where the loop parks the constellation on each axis
+ *       [1] snr  = Pn > 0 ? Ps / Pn : 0      Es/N0 as a ratio (dB is left to the caller: a device log10 would not be bit-exact)
+ *       [2] lock = S4 > 0 ? -SQ / S4 : 0     +1: locked on the diagonals (z^4 = -|z|^4); ~0: noise, or a carrier the loop does not follow
+ *       [3] nvar = max(Pn, 0) / 2            noise variance per component
+ * d_sums [nrows][4] double receives S1, S2, S4, SQ, for callers that average over rows or blocks themselves.
+ *
+ * SOFT DECISIONS, d_soft [nrows][nout][2] int8.  The gain g is one float per row, always finite; amp_d is the fp64 S1 / (2m):
+ *       QPSK_SOFT_UNIT   g = amp_d > 0 ? (float)min((double)scale / amp_d, FLT_MAX) : 0
+ *                        the constellation lands at +-scale whatever the input level (scale = 64 leaves headroom)
+ *       QPSK_SOFT_LLR    g = Pn > 0 ? (float)min(2.0*sqrt(Ps/2) / (Pn/2) / (double)scale, FLT_MAX) : the UNIT rule with 127 for scale
+ *                        the output is the bit's log-likelihood ratio in steps of scale
+ *       d_gain_in [nrows] float, when not NULL, replaces both: the caller's own gain (e.g. one held over several blocks of a stream)
+ * The payload is placed per row by lag[row] + first: d_lag and d_rot are qpsk_sync_batch's outputs, first is its nsync; d_lag NULL
+ * means 0 and d_rot NULL means 0.  For i < nout, with z = row[lag + first + i] and r = rot & 3:
+ *       (u, v) = z * (-j)^r:   r=0 (a, b)   r=1 (b, -a)   r=2 (-a, -b)   r=3 (-b, a)          (swaps and sign flips: exact)
+ *       q(x)   = (int8) min(127, max(-127, rintf(x * g)))                                      (fp32 multiply, round half to even)
+ *       d_soft[row][i][0] = q(u)  (bit 0 of the dibit)     d_soft[row][i][1] = q(v)  (bit 1)     positive <=> the bit is 0
+ * Wherever q != 0, (q < 0) is the corresponding bit of qpsk_sync_batch's de-rotated d_out; at an exact zero component q is 0.
+ *
+ *   d_costas     [nrows][nsym] complex float, rows row_pitch symbols apart (0 = nsym; otherwise >= nsym), 8-byte aligned;
+ *                1 <= nsym <= 2^21; what lies between the rows is never read
+ *   skip         0 .. nsym-1: leaves the loop's acquisition transient out of the sums
+ *   mode, scale  QPSK_SOFT_UNIT / QPSK_SOFT_LLR; scale finite and > 0 (checked also where d_gain_in makes them unused)
+ *   first, nout  first >= 0, nout >= 0, first + nout <= nsym; ignored when d_soft is NULL
+ *   outputs      d_soft (2-byte aligned, must not overlap the input), d_quality, d_sums: each may be NULL, not all.  With d_gain_in and
+ *                neither d_quality nor d_sums nothing is summed and only the payload is read
+ * QPSK_ERR_ARG at the call for a bad argument.  A device-side lag with lag < 0 or lag + first + nout > nsym is never used as an address:
+ * that row's soft output is zeros and the context's next synchronising call returns QPSK_ERR_ARG.  A NaN / Inf sample among those a
+ * row's sums (skip <= i < nsym, when anything is summed) or soft output (the payload) use, or a NaN / Inf entry of d_gain_in, gives
+ * QPSK_ERR_RANGE at the next synchronisation.  Stream-ordered on the context's stream; neither reads nor updates the histogram mode's
+ * guess, the receive streams or the deframer; qpsk_ctx_last_kernel() names the kernel: rows of up to 4096 symbols are read once
+ * (soft_onepass_kernel), longer ones twice (sums, then soft).  Usage: INTEGRATION.md 2.0.
+ * ------------------------------------------------------------------------- */
+enum { QPSK_SOFT_UNIT = 0, QPSK_SOFT_LLR = 1 };
+int qpsk_soft_batch(qpsk_ctx *ctx, const float *d_costas, long long row_pitch, int nrows, int nsym, int skip, int mode, float scale,
+                    const float *d_gain_in, const int32_t *d_lag, const int32_t *d_rot, int first, int nout, int8_t *d_soft,
+                    float *d_quality, double *d_sums);
+
+/* -------------------------------------------------------------------------
  * The stages on their own (each is what the corresponding reference function
  * computes, batched).
  * ------------------------------------------------------------------------- */

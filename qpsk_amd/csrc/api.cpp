@@ -126,6 +126,7 @@ struct qpsk_ctx {
     std::vector<float> h_gains;
     DevBuf index, filtered, mixed, keystream, sympad, mislist;
     DevBuf datacostas;            /* qpsk_rx_batch_data off rx_lean_kernel: the costas_frame[] the data rule is taken from */
+    DevBuf softgain;              /* qpsk_soft_batch on rows beyond the one-pass bound: the gain per row, between the two passes */
     /* the one-pass histogram route (rx_hist_kernel): d_hint[0] = the guessed decimation offset = the majority index of the context's last
      * histogram-mode batch (left there by index_majority_kernel, in stream order: no synchronisation), d_hint[1] = the frames the guess
      * missed in the running call; h_hist_stats (pinned, written by that kernel) = {majority, frames, missed} of the last batch whose
@@ -216,6 +217,12 @@ static int check_status(qpsk_ctx *c)
     if (st == STATUS_EST_NONFINITE)
         return fail(QPSK_ERR_RANGE, "qpsk_carrier_est_batch: a NaN / Inf sample inside the window the estimate reads; results of the calls since "
                                     "the last synchronisation are invalid");
+    if (st == STATUS_SOFT_NONFINITE)
+        return fail(QPSK_ERR_RANGE, "qpsk_soft_batch: a NaN / Inf sample among those a row's sums or soft output use, or a NaN / Inf gain in d_gain_in; "
+                                    "results of the calls since the last synchronisation are invalid");
+    if (st == STATUS_SOFT_BAD_LAG)
+        return fail(QPSK_ERR_ARG, "qpsk_soft_batch: a lag in d_lag is negative or puts the payload beyond the row (that row's soft output is zeros); "
+                                  "results of the calls since the last synchronisation are invalid");
     if (st == STATUS_NONFINITE)
         return fail(QPSK_ERR_RANGE, "a Costas loop ended on a NaN / Inf state: the input held a non-finite sample (the reference hangs in phase_wrap() "
                                     "on an infinite phase, costas_loop.c:61-67); results of the calls since the last synchronisation are invalid");
@@ -423,6 +430,7 @@ void qpsk_ctx_destroy(qpsk_ctx *c)
     hipFree(c->keystream.p);
     hipFree(c->sympad.p);
     hipFree(c->mislist.p);
+    hipFree(c->softgain.p);
     if (c->d_hint) hipFree(c->d_hint);
     if (c->h_hist_stats) hipHostFree(c->h_hist_stats);
     for (auto &kv : c->twiddles) hipFree(kv.second);
@@ -1271,6 +1279,58 @@ int qpsk_carrier_est_batch(qpsk_ctx *c, const float *d_in, long long frame_pitch
     KERNEL_TRY(launch_carrier_est(d_in, (size_t)frame_pitch, nframes, start, n, C, klo, khi, kdef, c->d_taps, tw, d_seed, d_freq, d_bin,
                                   d_line, c->d_status, c->taps_symmetric && tuned(c->tune.fir_generic, 0) == 0, c->stream));
     c->last_kernel = "carrier_est_kernel";
+    return QPSK_OK;
+}
+
+/* soft decisions and signal quality per row of costas_frame[] (soft.hip; definition in include/qpsk_hip.h).  Rows up to SOFT_ONE_PASS_MAX
+ * symbols that need both the sums and the soft output are read once (soft_onepass_kernel); longer rows take sums, then soft */
+int qpsk_soft_batch(qpsk_ctx *c, const float *d_costas, long long row_pitch, int nrows, int nsym, int skip, int mode, float scale,
+                    const float *d_gain_in, const int32_t *d_lag, const int32_t *d_rot, int first, int nout, int8_t *d_soft,
+                    float *d_quality, double *d_sums)
+{
+    if (!c || !d_costas) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: null context or input");
+    if (!d_soft && !d_quality && !d_sums) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: every output is NULL");
+    if (nrows <= 0 || nsym <= 0 || nsym > SOFT_MAX_NSYM)
+        return fail(QPSK_ERR_ARG, "qpsk_soft_batch: nrows = %d, nsym = %d (1..%d)", nrows, nsym, SOFT_MAX_NSYM);
+    if (skip < 0 || skip >= nsym) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: skip = %d outside 0..%d", skip, nsym - 1);
+    if (mode != QPSK_SOFT_UNIT && mode != QPSK_SOFT_LLR) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: unknown mode %d", mode);
+    if (!(scale > 0.0f && scale <= 3.402823466e+38f)) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: scale = %g is not finite and > 0", (double)scale);
+    if (row_pitch == 0) row_pitch = nsym;
+    if (row_pitch < nsym) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: row_pitch = %lld (0, or >= nsym %d)", row_pitch, nsym);
+    if ((uintptr_t)d_costas % 8) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: d_costas is not 8-byte aligned");
+    if (d_soft) {
+        if (nout < 0 || first < 0 || (long long)first + nout > nsym)
+            return fail(QPSK_ERR_ARG, "qpsk_soft_batch: first %d, nout %d do not fit a row of %d", first, nout, nsym);
+        if ((uintptr_t)d_soft % 2) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: d_soft is not 2-byte aligned");
+        const uintptr_t o0 = (uintptr_t)d_soft, o1 = o0 + 2 * (size_t)nrows * (size_t)nout;
+        const uintptr_t i0 = (uintptr_t)d_costas, i1 = i0 + 8 * ((size_t)(nrows - 1) * (size_t)row_pitch + (size_t)nsym);
+        if (o0 < i1 && i0 < o1) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: d_soft overlaps d_costas");
+    }
+    static_assert(QPSK_SOFT_UNIT == SOFT_MODE_UNIT && QPSK_SOFT_LLR == SOFT_MODE_LLR, "the kernels take the header's mode values");
+    if (bind(c)) return QPSK_ERR_HIP;
+    const size_t pitch = (size_t)row_pitch;
+    const bool need_sums = d_quality || d_sums || !d_gain_in;
+    if (!d_soft) {
+        KERNEL_TRY(launch_soft_sums(d_costas, pitch, nrows, nsym, skip, mode, scale, nullptr, d_quality, d_sums, c->d_status, c->stream));
+        c->last_kernel = "soft_sums_kernel";
+    } else if (!need_sums) {
+        KERNEL_TRY(launch_soft_apply(d_costas, pitch, nrows, nsym, d_gain_in, true, d_lag, d_rot, first, nout, d_soft, c->d_status, c->stream));
+        c->last_kernel = "soft_apply_kernel";
+    } else if (nsym <= SOFT_ONE_PASS_MAX) {
+        KERNEL_TRY(launch_soft_onepass(d_costas, pitch, nrows, nsym, skip, mode, scale, d_gain_in, d_lag, d_rot, first, nout, d_soft, d_quality,
+                                       d_sums, c->d_status, c->stream));
+        c->last_kernel = "soft_onepass_kernel";
+    } else {
+        float *gain = nullptr;
+        if (!d_gain_in) {
+            if (int rg = ensure(c, c->softgain, sizeof(float) * (size_t)nrows)) return rg;
+            gain = (float *)c->softgain.p;
+        }
+        KERNEL_TRY(launch_soft_sums(d_costas, pitch, nrows, nsym, skip, mode, scale, gain, d_quality, d_sums, c->d_status, c->stream));
+        KERNEL_TRY(launch_soft_apply(d_costas, pitch, nrows, nsym, d_gain_in ? d_gain_in : gain, d_gain_in != nullptr, d_lag, d_rot, first, nout,
+                                     d_soft, c->d_status, c->stream));
+        c->last_kernel = "soft_sums_kernel + soft_apply_kernel";
+    }
     return QPSK_OK;
 }
 

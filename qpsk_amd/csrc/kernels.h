@@ -19,6 +19,8 @@ constexpr int STATUS_NONFINITE = 3;      /* a loop ended on a NaN / Inf phase or
 constexpr int STATUS_BAD_INDEX = 4;      /* a per-frame decimation offset outside 0..MAX_INDEX (caller-supplied: qpsk_rx_batch_ext); the kernel
                                             addressed with 0 instead */
 constexpr int STATUS_EST_NONFINITE = 5;  /* qpsk_carrier_est_batch: a NaN / Inf sample inside the window the estimate reads */
+constexpr int STATUS_SOFT_NONFINITE = 6; /* qpsk_soft_batch: a NaN / Inf sample among those a row's sums or soft output use, or a NaN / Inf gain in d_gain_in */
+constexpr int STATUS_SOFT_BAD_LAG = 7;   /* qpsk_soft_batch: a per-row lag that would leave the row; that row's soft output is zeros */
 
 struct FusedArgs {
     const float2 *x;        /* [nframes] frames of frame_size samples, frame_pitch samples apart */
@@ -226,6 +228,20 @@ constexpr int SYNC_MAX_WORD = 128;
 int launch_sync_search(const uint8_t *data, int nframes, int nsym, const uint8_t *h_sync, int nsync, int lag_min, int lag_max, int nout,
                        uint8_t *out, int32_t *lag, int32_t *rot, int32_t *score, hipStream_t s);
 int launch_data_from_costas(const float2 *costas, uint8_t *data, size_t n, hipStream_t s);
+/* soft.hip: qpsk_soft_batch (the definition: include/qpsk_hip.h).  One workgroup per row; pitch in symbols; mode = SOFT_MODE_*.
+ * onepass: nsym <= SOFT_ONE_PASS_MAX, the row staged in LDS and read once (gain_in != NULL replaces the row's own gain);
+ * sums: quality / sums / the gain per row into gain_out (each may be NULL); apply: soft output from gain [nrows] (check_gain: flag a
+ * NaN / Inf entry).  lag, rot may be NULL (0) */
+constexpr int SOFT_ONE_PASS_MAX = 4096;
+constexpr int SOFT_MAX_NSYM = 1 << 21;
+constexpr int SOFT_MODE_UNIT = 0, SOFT_MODE_LLR = 1;
+int launch_soft_onepass(const float *x, size_t pitch, int nrows, int nsym, int skip, int mode, float scale, const float *gain_in,
+                        const int32_t *lag, const int32_t *rot, int first, int nout, int8_t *soft, float *quality, double *sums, int *status,
+                        hipStream_t s);
+int launch_soft_sums(const float *x, size_t pitch, int nrows, int nsym, int skip, int mode, float scale, float *gain_out, float *quality,
+                     double *sums, int *status, hipStream_t s);
+int launch_soft_apply(const float *x, size_t pitch, int nrows, int nsym, const float *gain, bool check_gain, const int32_t *lag,
+                      const int32_t *rot, int first, int nout, int8_t *soft, int *status, hipStream_t s);
 /* deframe.hip: qpsk_deframer_push.  Per stream, state_stride bytes of state: the header, the carried tail (the ring values of the last
  * min(len, nsync-1) dibits) at DEFRAME_TAIL_OFFSET, the pending packet's received payload (ring values) at DEFRAME_PEND_OFFSET */
 struct DeframeHeader {

@@ -57,6 +57,7 @@ API_SYMBOLS = [
     "qpsk_multi_set_packed", "qpsk_pack_symbols", "qpsk_unpack_symbols_host",
     "qpsk_rx_batch_ext", "qpsk_rx_batch_bw_ext", "qpsk_multi_set_acquisition", "qpsk_carrier_est_batch",
     "qpsk_rx_batch_data", "qpsk_sync_batch", "qpsk_multi_set_data", "qpsk_deframer_reset", "qpsk_deframer_push",
+    "qpsk_soft_batch",
 ]
 # every symbol include/qpsk_dropin.h declares
 DROPIN_SYMBOLS = [
@@ -117,6 +118,7 @@ def load():
     L.qpsk_multi_set_data.argtypes = [vp, i32]
     L.qpsk_deframer_reset.argtypes = [vp, i32, vp, i32, i32, i32, i32]
     L.qpsk_deframer_push.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.qpsk_soft_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, i32, f32, vp, vp, vp, i32, i32, vp, vp, vp]
     L.qpsk_rrc_fir_batch.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_rrc_fir_batch_fast.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_timing_hist_batch.argtypes = [vp, vp, i32, vp, vp]
@@ -389,6 +391,47 @@ class Modem:
         self._check(self.L.qpsk_carrier_est_batch(self.h, _ptr(x), int(pitch), F, int(start), int(n), _ptr(o["seed"]), _ptr(o["freq"]),
                                                   _ptr(o["bin"]), _ptr(o.get("line"))))
         o["_keep"] = (x,)      # the input stays alive until the caller is done with the outputs (stream order)
+        return o
+
+    SOFT_MODES = {"unit": 0, "llr": 1}      # QPSK_SOFT_UNIT, QPSK_SOFT_LLR
+
+    def soft(self, costas, skip=0, mode="unit", scale=64.0, gain=None, lag=None, rot=None, first=0, nout=None, want_sums=False):
+        """Soft decisions and signal quality (qpsk_soft_batch) from rows of costas_frame[]: costas (R, nsym, 2) float32, or the dict that
+        rx_batch_ext(want_costas=True) or streams_rx_pcm() returns.  Dict of torch tensors soft (R, nout, 2) int8 -- one value per bit of
+        each dibit, positive <=> the bit is 0 -- quality (R, 4) float32 = (amp, snr, lock, nvar) and, with want_sums, sums (R, 4) float64.
+        skip leaves the first symbols out of the sums; mode "unit" puts the constellation at +-scale, "llr" gives log-likelihood ratios
+        in steps of scale; gain (R,) float32 replaces the row's own gain; lag, rot (R,) int32 and first, nout place and de-rotate the
+        payload as sync() found it (lag, rot: its outputs; first: its word's length); nout None = the rest of the row.  A lag that leaves
+        the row, or a NaN / Inf sample, is reported by the next synchronising call (sync())."""
+        return self._soft(costas, skip, mode, scale, gain, lag, rot, first, nout, want_sums, True)
+
+    def quality(self, costas, skip=0):
+        """soft() without the soft output: dict with quality (R, 4) float32 = (amp, snr, lock, nvar) per row"""
+        return self._soft(costas, skip, "unit", 64.0, None, None, None, 0, 0, False, False)
+
+    def _soft(self, costas, skip, mode, scale, gain, lag, rot, first, nout, want_sums, want_soft):
+        t = self.torch
+        if isinstance(costas, dict):
+            costas = costas["costas"]
+        z = self._dev(costas, t.float32)
+        if z.dim() != 3 or z.shape[2] != 2:
+            raise ValueError("soft() input must be (rows, nsym, 2) float32")
+        R, N = z.shape[0], z.shape[1]
+        g = None if gain is None else self._dev(gain, t.float32)
+        lg = None if lag is None else self._dev(lag, t.int32)
+        rt = None if rot is None else self._dev(rot, t.int32)
+        for a in (g, lg, rt):
+            assert a is None or tuple(a.shape) == (R,)
+        if nout is None:
+            nout = N - first
+        o = dict(quality=self.empty((R, 4), t.float32))
+        if want_soft:
+            o["soft"] = self.empty((R, nout, 2), t.int8)
+        if want_sums:
+            o["sums"] = self.empty((R, 4), t.float64)
+        self._check(self.L.qpsk_soft_batch(self.h, _ptr(z), 0, R, N, int(skip), self.SOFT_MODES[mode], float(scale), _ptr(g), _ptr(lg),
+                                           _ptr(rt), int(first), int(nout), _ptr(o.get("soft")), _ptr(o["quality"]), _ptr(o.get("sums"))))
+        o["_keep"] = (z, g, lg, rt)      # the inputs stay alive until the caller is done with the outputs (stream order)
         return o
 
     # ---- stages
