@@ -122,7 +122,9 @@ int qpsk_ctx_set_stream(qpsk_ctx *ctx, void *stream);
  * unset: that route only while every frame of the context's last histogram-mode batch sat on that batch's majority index -- a missed
  * frame costs more than the route saves), "QPSK_EST_WAVES" (hardware waves that share the
  * in-launch FFT timing estimate), "QPSK_LEAN_PAIR" (rx_lean_kernel's serial wave: 0 = one lane per Costas loop, 1 = two lanes per
- * loop -- they share the step's sine / cosine polynomial chains -- in workgroups of up to 16 frames, 2 = up to 32; the library's own choice is up to 24); value < 0 = back to
+ * loop -- they share the step's sine / cosine polynomial chains -- in workgroups of up to 16 frames, 2 = up to 32; the library's own choice is up to 24),
+ * "QPSK_VITERBI_LDS" (qpsk_viterbi_batch: 0 = the decision words always wait in the context's scratch buffer, 1 = in LDS whenever a row's
+ * fit -- up to 8192 steps; the library's own choice is LDS where every row of the call is resident at once); value < 0 = back to
  * the library's own choice.
  * Environment variables of the same names are read once, by qpsk_ctx_create(), as the context's initial values;
  * no other call reads the environment, and none of them can change a result. */
@@ -353,6 +355,52 @@ enum { QPSK_SOFT_UNIT = 0, QPSK_SOFT_LLR = 1 };
 int qpsk_soft_batch(qpsk_ctx *ctx, const float *d_costas, long long row_pitch, int nrows, int nsym, int skip, int mode, float scale,
                     const float *d_gain_in, const int32_t *d_lag, const int32_t *d_rot, int first, int nout, int8_t *d_soft,
                     float *d_quality, double *d_sums);
+
+/* -------------------------------------------------------------------------
+ * CONVOLUTIONAL CODE AND VITERBI DECODER: constraint length 7, rate 1/2, generators 171 / 133 octal, on the int8 soft decisions
+ * qpsk_soft_batch writes.  One QPSK symbol carries the two coded bits of one trellis step, so d_soft[row][t][0..1] is step t's input as
+ * it lies in memory.  The reference has no FEC: this is the library's own definition (parity unpinned), restated in
+ * numpy by tests/test_viterbi_cpu.py.  Everything is integer arithmetic; there is no tolerance anywhere.
+ *
+ * CODE.  Register r of 7 bits, r = ((r << 1) | bit) & 127 (newest bit in bit 0), starting from 0.  Per input bit the coded pair is
+ *       c0 = parity(r & 0x79)   c1 = parity(r & 0x5B)          (171, 133 octal; neither output inverted)
+ * sent as the dibit c0 | c1 << 1: c0 rides on bit 0 of the dibit (the real axis, d_soft[..][0]), c1 on bit 1.  The state is r & 63.
+ * QPSK_CONV_TAIL appends six zero bits: nsteps = nbits + 6; without it nsteps = nbits.
+ *
+ * DECODER.  Input per step t: (s0, s1) = d_soft[row][t][0..1], int8, positive <=> the bit is 0; 0 is an erasure and needs no special
+ * case.  A -128 is taken as -127 before anything else.  If d_flip is given ([nsteps] uint8, one array for all rows), bit j of d_flip[t]
+ * negates s_j first: this undoes an additive scrambler (qpsk_scramble_batch's keystream dibits) on soft values.
+ *   branch metric of a transition into register value r:   bm(r) = (c0(r) ? -s0 : s0) + (c1(r) ? -s1 : s1)      (the decoder maximises)
+ *   path metrics pm[64], int32.  Start: pm[0] = 0, every other state NEG = -2^30; with QPSK_VITERBI_OPEN_START all 64 start at 0
+ *   step, for every new state ns (input bit ns & 1):  p0 = ns >> 1,  p1 = p0 | 32,
+ *       m0 = pm[p0] + bm(ns);  m1 = pm[p1] + bm(ns | 64);  d[t][ns] = (m1 > m0)  (A TIE KEEPS p0);  pm'[ns] = d ? m1 : m0
+ *       No normalisation: with nsteps <= 131072, |metric| <= 254 * 131072 < 2^26, and NEG plus that stays below every reachable metric
+ *   end: state 0; with QPSK_VITERBI_OPEN_END the state of the largest pm, TIES TO THE LOWEST STATE NUMBER
+ *   trace-back over the WHOLE row (no truncation window): from the end state st, for t = nsteps-1 .. 0:
+ *       bit[t] = st & 1;   st = (st >> 1) | (d[t][st] << 5)
+ *   d_bits [nrows][ceil(nsteps/8)] uint8: bit t in byte t >> 3 at position t & 7 (low bits first, the packing of qpsk_pack_symbols;
+ *       tail bits included, padding bits 0)
+ *   d_info [nrows][4] int32 = { the end state's path metric, the end state, the state the trace-back arrives at (0 unless open start),
+ *       the number of non-zero soft values whose sign disagrees with the re-encoded path: a channel bit-error count for free }
+ * Decisions of states that no path from the start reaches do not influence any output.  (Every state is reachable from every state in
+ * six steps, hence max(pm) - min(pm) over reachable states <= 12 * 254 = 3048 at every step, and any finite start penalty > 3048 gives
+ * the same outputs as NEG.)
+ *
+ *   qpsk_conv_encode_batch   d_bits [nrows][ceil(nbits/8)] packed as above -> d_dibits [nrows][nsteps] uint8, ready for
+ *                qpsk_scramble_batch and qpsk_tx_symbols; nrows >= 1, 1 <= nbits, nsteps <= 131072; flags 0 or QPSK_CONV_TAIL
+ *   qpsk_viterbi_batch       d_soft rows row_pitch steps apart (0 = nsteps; otherwise >= nsteps; what lies between rows is never read),
+ *                2-byte aligned; 1 <= nsteps <= 131072; nrows >= 1; d_flip may be NULL; d_bits or d_info may be NULL, not both
+ * QPSK_ERR_ARG at the call for a bad argument, nothing launched.  Stream-ordered on the context's stream like qpsk_soft_batch; neither
+ * reads nor updates the histogram mode's guess, the receive streams or the deframer.  qpsk_ctx_last_kernel() names the kernel: the
+ * decision words of a row (8 bytes per step) wait for the trace-back in LDS (viterbi_lds_kernel: rows of up to 8192 steps, where every
+ * row of the call is resident at once) or in a per-context scratch buffer that grows on demand (viterbi_kernel; a failed allocation
+ * returns QPSK_ERR_ALLOC and leaves the context usable).  Usage: INTEGRATION.md 2.0.
+ * ------------------------------------------------------------------------- */
+enum { QPSK_CONV_TAIL = 1 };
+enum { QPSK_VITERBI_OPEN_START = 1, QPSK_VITERBI_OPEN_END = 2 };
+int qpsk_conv_encode_batch(qpsk_ctx *ctx, const uint8_t *d_bits, int nrows, int nbits, int flags, uint8_t *d_dibits);
+int qpsk_viterbi_batch(qpsk_ctx *ctx, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const uint8_t *d_flip,
+                       int flags, uint8_t *d_bits, int32_t *d_info);
 
 /* -------------------------------------------------------------------------
  * The stages on their own (each is what the corresponding reference function

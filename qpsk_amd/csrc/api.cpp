@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <algorithm>
 #include <map>
 #include <vector>
 
@@ -76,6 +77,7 @@ struct Tuning {
     int hist_onepass = -1;                            /* histogram timing: 0 = never the one-pass route (rx_hist_kernel on the previous batch's majority index + a fall-back pass), 1 = whenever the shape allows and a guess exists (unset: only while every frame of the last batch sat on its majority index) */
     int est_waves = -1;                               /* rx_lean_kernel, in-launch FFT estimate: hardware waves launched for it */
     int lean_pair = -1;                               /* rx_lean_kernel: 0 = one lane per loop in the serial wave, 1 = two lanes per loop up to 16 frames per workgroup, 2 = up to 32; unset: up to 24, where it pays in steady state (profiles/r06_step_cost.txt) */
+    int viterbi_lds = -1;                             /* qpsk_viterbi_batch: 0 = decision words always through the global scratch buffer, 1 = in LDS whenever a row's fit (unset: in LDS where every row of the call is resident at once) */
     int fft_fused = -1;                               /* FFT timing estimate: 0 = always a launch of its own (1 / unset: inside rx_fused_pipe_kernel's launch for full workgroups) */
 };
 
@@ -90,6 +92,7 @@ static const struct { const char *name; int Tuning::*field; } TUNING_KEYS[] = {
     {"QPSK_STREAM_SCAN", &Tuning::stream_scan}, {"QPSK_STREAM_CARRIER", &Tuning::stream_carrier},
     {"QPSK_LEAN_DMA", &Tuning::lean_dma},     {"QPSK_LEAN_PAIR", &Tuning::lean_pair},
     {"QPSK_EST_WAVES", &Tuning::est_waves},   {"QPSK_HIST_ONEPASS", &Tuning::hist_onepass},
+    {"QPSK_VITERBI_LDS", &Tuning::viterbi_lds},
 };
 
 /* layout bits a product build honours: 4 no spare waves, 8 C++ Costas step, 64/128 lane-mapping variants.  The
@@ -126,6 +129,7 @@ struct qpsk_ctx {
     std::vector<float> h_gains;
     DevBuf index, filtered, mixed, keystream, sympad, mislist;
     DevBuf datacostas;            /* qpsk_rx_batch_data off rx_lean_kernel: the costas_frame[] the data rule is taken from */
+    DevBuf vitdec;                /* qpsk_viterbi_batch off the LDS route: the decision words between the forward pass and the trace-back */
     DevBuf softgain;              /* qpsk_soft_batch on rows beyond the one-pass bound: the gain per row, between the two passes */
     /* the one-pass histogram route (rx_hist_kernel): d_hint[0] = the guessed decimation offset = the majority index of the context's last
      * histogram-mode batch (left there by index_majority_kernel, in stream order: no synchronisation), d_hint[1] = the frames the guess
@@ -431,6 +435,7 @@ void qpsk_ctx_destroy(qpsk_ctx *c)
     hipFree(c->sympad.p);
     hipFree(c->mislist.p);
     hipFree(c->softgain.p);
+    hipFree(c->vitdec.p);
     if (c->d_hint) hipFree(c->d_hint);
     if (c->h_hist_stats) hipHostFree(c->h_hist_stats);
     for (auto &kv : c->twiddles) hipFree(kv.second);
@@ -1331,6 +1336,65 @@ int qpsk_soft_batch(qpsk_ctx *c, const float *d_costas, long long row_pitch, int
                                      d_soft, c->d_status, c->stream));
         c->last_kernel = "soft_sums_kernel + soft_apply_kernel";
     }
+    return QPSK_OK;
+}
+
+/* the K = 7, rate-1/2 convolutional code (viterbi.hip; definition in include/qpsk_hip.h) */
+int qpsk_conv_encode_batch(qpsk_ctx *c, const uint8_t *d_bits, int nrows, int nbits, int flags, uint8_t *d_dibits)
+{
+    if (!c || !d_bits || !d_dibits) return fail(QPSK_ERR_ARG, "qpsk_conv_encode_batch: null argument");
+    if (flags & ~QPSK_CONV_TAIL) return fail(QPSK_ERR_ARG, "qpsk_conv_encode_batch: unknown flags 0x%x", flags);
+    const int tail = (flags & QPSK_CONV_TAIL) ? 6 : 0;
+    if (nrows <= 0 || nbits <= 0 || nbits > VITERBI_MAX_STEPS - tail)
+        return fail(QPSK_ERR_ARG, "qpsk_conv_encode_batch: nrows = %d, nbits = %d (1..%d)", nrows, nbits, VITERBI_MAX_STEPS - tail);
+    if (bind(c)) return QPSK_ERR_HIP;
+    KERNEL_TRY(launch_conv_encode(d_bits, nrows, nbits, nbits + tail, d_dibits, c->stream));
+    c->last_kernel = "conv_encode_kernel";
+    return QPSK_OK;
+}
+
+/* Where the decision words (8 bytes per step) wait for the trace-back: in LDS when a row's fit the launch limit and -- the library's own
+ * choice -- every row of the call is resident at once (160 KB of LDS per compute unit), so that the LDS never costs a second round of
+ * workgroups; otherwise in the context's scratch buffer, rows in chunks of at most VITERBI_SCRATCH_MAX bytes of it */
+static const size_t VITERBI_SCRATCH_MAX = (size_t)1 << 30;
+
+int qpsk_viterbi_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const uint8_t *d_flip, int flags,
+                       uint8_t *d_bits, int32_t *d_info)
+{
+    if (!c || !d_soft) return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: null context or input");
+    if (!d_bits && !d_info) return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: every output is NULL");
+    if (nrows <= 0 || nsteps <= 0 || nsteps > VITERBI_MAX_STEPS)
+        return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: nrows = %d, nsteps = %d (1..%d)", nrows, nsteps, VITERBI_MAX_STEPS);
+#ifdef QPSK_VITERBI_PROFILE
+    const int known = QPSK_VITERBI_OPEN_START | QPSK_VITERBI_OPEN_END | VITERBI_PROFILE_FORWARD_ONLY | VITERBI_PROFILE_CYCLES;
+#else
+    const int known = QPSK_VITERBI_OPEN_START | QPSK_VITERBI_OPEN_END;
+#endif
+    if (flags & ~known) return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: unknown flags 0x%x", flags);
+    if (row_pitch == 0) row_pitch = nsteps;
+    if (row_pitch < nsteps) return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: row_pitch = %lld (0, or >= nsteps %d)", row_pitch, nsteps);
+    if ((uintptr_t)d_soft % 2) return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: d_soft is not 2-byte aligned");
+    if ((uintptr_t)d_info % 4) return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: d_info is not 4-byte aligned");
+    static_assert(QPSK_VITERBI_OPEN_START == VITERBI_OPEN_START && QPSK_VITERBI_OPEN_END == VITERBI_OPEN_END, "the kernel takes the header's flag values");
+    if (bind(c)) return QPSK_ERR_HIP;
+    const size_t per_row = viterbi_scratch_bytes_per_row(nsteps);
+    const bool fits = per_row <= (size_t)VITERBI_LDS_MAX_BYTES;
+    const bool resident = fits && (size_t)nrows <= (size_t)c->ncu * (((size_t)160 << 10) / per_row);
+    const bool lds = fits && tuned(c->tune.viterbi_lds, resident ? 1 : 0) != 0;
+    const size_t nbytes = ((size_t)nsteps + 7) / 8;
+    if (lds) {
+        KERNEL_TRY(launch_viterbi(d_soft, (size_t)row_pitch, nrows, nsteps, d_flip, flags, nullptr, true, d_bits, d_info, c->stream));
+        c->last_kernel = "viterbi_lds_kernel";
+        return QPSK_OK;
+    }
+    const size_t chunk_rows = std::min<size_t>((size_t)nrows, std::max<size_t>(1, VITERBI_SCRATCH_MAX / per_row));
+    if (int rg = ensure(c, c->vitdec, chunk_rows * per_row)) return rg;
+    for (size_t r0 = 0; r0 < (size_t)nrows; r0 += chunk_rows) {      /* stream order: a chunk's trace-back is over before the next one's forward pass */
+        const int n = (int)std::min<size_t>(chunk_rows, (size_t)nrows - r0);
+        KERNEL_TRY(launch_viterbi(d_soft + 2 * r0 * (size_t)row_pitch, (size_t)row_pitch, n, nsteps, d_flip, flags, (unsigned long long *)c->vitdec.p,
+                                  false, d_bits ? d_bits + r0 * nbytes : nullptr, d_info ? d_info + 4 * r0 : nullptr, c->stream));
+    }
+    c->last_kernel = "viterbi_kernel";
     return QPSK_OK;
 }
 

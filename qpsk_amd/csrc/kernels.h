@@ -242,6 +242,18 @@ int launch_soft_sums(const float *x, size_t pitch, int nrows, int nsym, int skip
                      double *sums, int *status, hipStream_t s);
 int launch_soft_apply(const float *x, size_t pitch, int nrows, int nsym, const float *gain, bool check_gain, const int32_t *lag,
                       const int32_t *rot, int first, int nout, int8_t *soft, int *status, hipStream_t s);
+/* viterbi.hip: qpsk_conv_encode_batch / qpsk_viterbi_batch (the definition: include/qpsk_hip.h).  One wave per row, lane = state; the
+ * 64-bit decision word of every step waits for the trace-back in scratch ([nrows][viterbi_scratch_bytes_per_row] bytes: viterbi_kernel)
+ * or, lds = true, in dynamic LDS (rows of up to VITERBI_LDS_MAX_BYTES: viterbi_lds_kernel).  pitch in steps; flip, and one of bits / info,
+ * may be NULL.  The PROFILE flags exist in the measurement build only (make viterbi_profile, -DQPSK_VITERBI_PROFILE): stop after the
+ * forward pass / info words 1, 2 = the shader cycles of the forward pass and of the trace-back */
+constexpr int VITERBI_MAX_STEPS = 131072;
+constexpr int VITERBI_LDS_MAX_BYTES = 65536;
+constexpr int VITERBI_OPEN_START = 1, VITERBI_OPEN_END = 2, VITERBI_PROFILE_FORWARD_ONLY = 0x100, VITERBI_PROFILE_CYCLES = 0x200;
+size_t viterbi_scratch_bytes_per_row(int nsteps);
+int launch_viterbi(const int8_t *soft, size_t pitch, int nrows, int nsteps, const uint8_t *flip, int flags, unsigned long long *scratch,
+                   bool lds, uint8_t *bits, int32_t *info, hipStream_t s);
+int launch_conv_encode(const uint8_t *bits, int nrows, int nbits, int nsteps, uint8_t *dibits, hipStream_t s);
 /* deframe.hip: qpsk_deframer_push.  Per stream, state_stride bytes of state: the header, the carried tail (the ring values of the last
  * min(len, nsync-1) dibits) at DEFRAME_TAIL_OFFSET, the pending packet's received payload (ring values) at DEFRAME_PEND_OFFSET */
 struct DeframeHeader {

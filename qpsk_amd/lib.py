@@ -57,7 +57,7 @@ API_SYMBOLS = [
     "qpsk_multi_set_packed", "qpsk_pack_symbols", "qpsk_unpack_symbols_host",
     "qpsk_rx_batch_ext", "qpsk_rx_batch_bw_ext", "qpsk_multi_set_acquisition", "qpsk_carrier_est_batch",
     "qpsk_rx_batch_data", "qpsk_sync_batch", "qpsk_multi_set_data", "qpsk_deframer_reset", "qpsk_deframer_push",
-    "qpsk_soft_batch",
+    "qpsk_soft_batch", "qpsk_conv_encode_batch", "qpsk_viterbi_batch",
 ]
 # every symbol include/qpsk_dropin.h declares
 DROPIN_SYMBOLS = [
@@ -119,6 +119,8 @@ def load():
     L.qpsk_deframer_reset.argtypes = [vp, i32, vp, i32, i32, i32, i32]
     L.qpsk_deframer_push.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.qpsk_soft_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, i32, f32, vp, vp, vp, i32, i32, vp, vp, vp]
+    L.qpsk_conv_encode_batch.argtypes = [vp, vp, i32, i32, i32, vp]
+    L.qpsk_viterbi_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, vp, i32, vp, vp]
     L.qpsk_rrc_fir_batch.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_rrc_fir_batch_fast.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_timing_hist_batch.argtypes = [vp, vp, i32, vp, vp]
@@ -432,6 +434,39 @@ class Modem:
         self._check(self.L.qpsk_soft_batch(self.h, _ptr(z), 0, R, N, int(skip), self.SOFT_MODES[mode], float(scale), _ptr(g), _ptr(lg),
                                            _ptr(rt), int(first), int(nout), _ptr(o.get("soft")), _ptr(o["quality"]), _ptr(o.get("sums"))))
         o["_keep"] = (z, g, lg, rt)      # the inputs stay alive until the caller is done with the outputs (stream order)
+        return o
+
+    # ---- the K = 7, rate-1/2 convolutional code
+    def conv_encode(self, bits_packed, nbits, tail=True):
+        """qpsk_conv_encode_batch: bits_packed (R, ceil(nbits / 8)) uint8, bit t in byte t >> 3 at position t & 7 -> (R, nsteps) uint8 coded
+        dibits, nsteps = nbits + 6 with the tail (six zero bits that bring the encoder back to state 0)"""
+        t = self.torch
+        b = self._dev(bits_packed, t.uint8)
+        if b.dim() != 2 or b.shape[1] != (int(nbits) + 7) // 8:
+            raise ValueError("conv_encode() input must be (rows, ceil(nbits / 8)) uint8")
+        out = self.empty((b.shape[0], int(nbits) + (6 if tail else 0)), t.uint8)
+        self._check(self.L.qpsk_conv_encode_batch(self.h, _ptr(b), b.shape[0], int(nbits), 1 if tail else 0, _ptr(out)))
+        return out
+
+    def viterbi(self, soft, flip=None, open_start=False, open_end=False, pitch=0, nsteps=None):
+        """qpsk_viterbi_batch on soft (R, nsteps, 2) int8 -- what soft() returns under "soft" -- or, with pitch, (R, pitch, 2) of which the
+        first nsteps steps of each row are decoded.  flip (nsteps,) uint8: the scrambler's keystream dibits, undone on the soft values.
+        Dict of torch tensors bits (R, ceil(nsteps / 8)) uint8, packed low bits first, tail bits included, and info (R, 4) int32 = (end
+        metric, end state, state the trace-back arrives at, channel bit errors against the re-encoded path)."""
+        t = self.torch
+        if isinstance(soft, dict):
+            soft = soft["soft"]
+        q = self._dev(soft, t.int8)
+        if q.dim() != 3 or q.shape[2] != 2 or (pitch and q.shape[1] != pitch):
+            raise ValueError("viterbi() input must be (rows, nsteps or pitch, 2) int8")
+        R = q.shape[0]
+        n = int(nsteps) if nsteps is not None else q.shape[1]
+        f = None if flip is None else self._dev(flip, t.uint8)
+        assert f is None or tuple(f.shape) == (n,)
+        o = dict(bits=self.empty((R, (n + 7) // 8), t.uint8), info=self.empty((R, 4), t.int32))
+        self._check(self.L.qpsk_viterbi_batch(self.h, _ptr(q), int(pitch), R, n, _ptr(f), (1 if open_start else 0) | (2 if open_end else 0),
+                                              _ptr(o["bits"]), _ptr(o["info"])))
+        o["_keep"] = (q, f)      # the inputs stay alive until the caller is done with the outputs (stream order)
         return o
 
     # ---- stages
