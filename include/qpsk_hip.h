@@ -275,6 +275,47 @@ int qpsk_deframer_reset(qpsk_ctx *ctx, int nstreams, const uint8_t *h_sync, int 
 int qpsk_deframer_push(qpsk_ctx *ctx, const float *d_costas, const uint8_t *d_data, int nsym, int32_t *d_count, uint8_t *d_bytes,
                        long long *d_pos, int32_t *d_rot, int32_t *d_score, uint8_t *d_crc_ok);
 
+/* -------------------------------------------------------------------------
+ * CODED DEFRAMER: the same hunt on streams whose packets carry the K = 7 rate-1/2 code (CONVOLUTIONAL CODE below).  On air:
+ *       [sync: n = nsync dibits, uncoded][body: Nc = 8 (nbytes + 2) + 6 dibits]
+ *       body = keystream (qpsk_scramble_batch's, SEED reloaded at the body's first dibit) xor
+ *              qpsk_conv_encode_batch(payload ++ crc16 big-endian, QPSK_CONV_TAIL)          (the bytes' bits low bit first)
+ * The library's own definition (the reference has no FEC; parity unpinned), restated in numpy by
+ * tests/test_deframe_coded_cpu.py.  A context holds ONE deframer, in one mode: either reset replaces the other's state, and a push of
+ * the other kind returns QPSK_ERR_STATE, as a push before any reset does.  Per stream, with D, d, score, p*, r* exactly as DEFRAMER
+ * defines them on the data rule of the pushed costas_frame[]:
+ *       HUNT    identical with N replaced by Nc: a packet is complete once p* + n + Nc <= len(D), reported by the push during which that
+ *               happens, and h = p* + n + Nc, CRC pass or fail.  The hunt never depends on the decoder's result.
+ *       SOFT    body symbol i is z = costas at stream position p* + n + i; g = the gain of the push during which that symbol arrived;
+ *               (u, v) = z (-j)^r* and q(x) exactly as qpsk_soft_batch defines them with that g;  s[i] = (q(u), q(v))
+ *       GAIN    one float per stream and push: d_gain [nstreams] when given (a caller's AGC, or one value held over blocks); with
+ *               d_gain NULL the gain qpsk_soft_batch defines for this push's row with skip = 0 and the reset's mode / scale (the same
+ *               sums in the same order).  With a constant d_gain the result depends only on D, not on the cuts (apart from which push
+ *               reports a packet); with per-push gains each symbol takes the gain of the push that brought it.
+ *       DECODE  qpsk_viterbi_batch's decoder on s[0 .. Nc-1] with d_flip = the keystream dibits and flags 0;  b[k] = byte k of its
+ *               d_bits, k < nbytes + 2;  crc_ok = crc16(b[0 .. nbytes-1]) == b[nbytes] << 8 | b[nbytes+1]
+ *
+ * qpsk_deframer_reset_coded: nsync, min_score, nbytes, max_packets as qpsk_deframer_reset; mode, scale as qpsk_soft_batch (checked
+ *   also where d_gain makes them unused).
+ * qpsk_deframer_push_coded: d_costas [nstreams][nsym][2] float, 8-byte aligned (soft values need amplitudes: there is no d_data form);
+ *   1 <= nsym <= 2^21; d_gain [nstreams] float or NULL.  Outputs shaped and ruled as qpsk_deframer_push's -- d_count required and the
+ *   true number, only the first min(count, max_packets) rows of a stream written, packets beyond max_packets counted and not decoded --
+ *   plus
+ *       d_info   [nstreams][max_packets][4] int32   the decoder's four info words (path metric, end state, start state, channel bit errors)
+ *   Every output other than d_count may be NULL.
+ * QPSK_ERR_ARG at the call for a bad argument, nothing launched.  A NaN / Inf among the body symbols of a decoded packet, in the summed
+ * row (d_gain NULL) or in d_gain gives QPSK_ERR_RANGE at the next synchronisation, as qpsk_soft_batch.  The staging rows and the
+ * decoder's scratch grow on demand: a failed allocation returns QPSK_ERR_ALLOC, launches nothing and leaves the context and the
+ * deframer usable.  Stream-ordered; touches neither the receive streams, the histogram mode's guess nor the batch paths.
+ * qpsk_ctx_last_kernel() names the kernels and the decoder's route (decision words in LDS or in the scratch buffer, by
+ * qpsk_viterbi_batch's rule on the rows a push can complete).  Usage: INTEGRATION.md 2.0.
+ * ------------------------------------------------------------------------- */
+int qpsk_deframer_reset_coded(qpsk_ctx *ctx, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes,
+                              int max_packets, int mode, float scale);
+int qpsk_deframer_push_coded(qpsk_ctx *ctx, const float *d_costas, int nsym, const float *d_gain, int32_t *d_count,
+                             uint8_t *d_bytes, long long *d_pos, int32_t *d_rot, int32_t *d_score, uint8_t *d_crc_ok,
+                             int32_t *d_info);
+
 /* qpsk_rx_batch_bw() the same way: d_seed [nframes][nbw][2] (one seed per loop) or NULL; d_index_in [nframes] or NULL */
 int qpsk_rx_batch_bw_ext(qpsk_ctx *ctx, const float *d_in, int nframes, const float *h_loop_bw, int nbw, const int32_t *d_index_in,
                          const float *d_seed, uint8_t *d_sym, float *d_freq, float *d_phase, int32_t *d_index);

@@ -172,6 +172,13 @@ struct qpsk_ctx {
     int df_nstreams = 0, df_nsync = 0, df_min_score = 0, df_nbytes = 0, df_max_packets = 0;
     unsigned long long df_sync_lo[2] = {0, 0}, df_sync_hi[2] = {0, 0};
     bool df_ready = false;        /* a reset has completed and no push has failed since */
+    /* the coded mode (qpsk_deframer_reset_coded): the same state with int8 soft pairs as the pending body; the tables are the keystream
+     * dibits [nsteps], then the CRC advance factors x^(8 m), m < nbytes, at DFC_ADV_OFFSET.  One deframer per context, in one mode */
+    bool df_coded = false;
+    int df_mode = 0, df_nsteps = 0;
+    float df_scale = 0.f;
+    unsigned df_crc_init = 0;
+    DevBuf dfstage;               /* the soft rows of the packets a coded push completes, between the hunt and the decode */
 };
 
 static const int MAX_BW = 64;
@@ -222,7 +229,7 @@ static int check_status(qpsk_ctx *c)
         return fail(QPSK_ERR_RANGE, "qpsk_carrier_est_batch: a NaN / Inf sample inside the window the estimate reads; results of the calls since "
                                     "the last synchronisation are invalid");
     if (st == STATUS_SOFT_NONFINITE)
-        return fail(QPSK_ERR_RANGE, "qpsk_soft_batch: a NaN / Inf sample among those a row's sums or soft output use, or a NaN / Inf gain in d_gain_in; "
+        return fail(QPSK_ERR_RANGE, "qpsk_soft_batch / qpsk_deframer_push_coded: a NaN / Inf sample among those a row's sums or soft output use, or a NaN / Inf gain; "
                                     "results of the calls since the last synchronisation are invalid");
     if (st == STATUS_SOFT_BAD_LAG)
         return fail(QPSK_ERR_ARG, "qpsk_soft_batch: a lag in d_lag is negative or puts the payload beyond the row (that row's soft output is zeros); "
@@ -407,6 +414,7 @@ static void free_deframer(qpsk_ctx *c)
     hipFree(c->df_state); hipFree(c->df_tables);
     c->df_state = c->df_tables = nullptr;
     c->df_ready = false;
+    c->df_coded = false;
     c->df_nstreams = 0;
 }
 
@@ -436,6 +444,7 @@ void qpsk_ctx_destroy(qpsk_ctx *c)
     hipFree(c->mislist.p);
     hipFree(c->softgain.p);
     hipFree(c->vitdec.p);
+    hipFree(c->dfstage.p);
     if (c->d_hint) hipFree(c->d_hint);
     if (c->h_hist_stats) hipHostFree(c->h_hist_stats);
     for (auto &kv : c->twiddles) hipFree(kv.second);
@@ -2008,37 +2017,72 @@ static uint16_t crc_advance(int k)
     return (uint16_t)r;
 }
 
+static const int DFC_ADV_OFFSET = (DEFRAME_CODED_MAX_STEPS + 15) & ~15;      /* the coded mode's tables: keystream dibits [nsteps], then nbytes uint16 */
+
+/* both resets: who = the entry point's name; coded: the body is 8 (nbytes + 2) + 6 coded dibits held as int8 pairs */
+static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes,
+                               int max_packets, bool coded, int mode, float scale);
+
 int qpsk_deframer_reset(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets)
 {
-    if (!c || !h_sync) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: null context or sync word");
-    if (nstreams <= 0) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: nstreams = %d", nstreams);
-    if (nsync < 1 || nsync > SYNC_MAX_WORD) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: nsync = %d outside 1..%d", nsync, SYNC_MAX_WORD);
-    if (min_score < 1 || min_score > nsync) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: min_score = %d outside 1..%d", min_score, nsync);
-    if (nbytes < 1 || nbytes > DEFRAME_MAX_BYTES) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: nbytes = %d outside 1..%d", nbytes, DEFRAME_MAX_BYTES);
+    return deframer_reset_impl(c, "qpsk_deframer_reset", nstreams, h_sync, nsync, min_score, nbytes, max_packets, false, 0, 1.0f);
+}
+
+int qpsk_deframer_reset_coded(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets,
+                              int mode, float scale)
+{
+    return deframer_reset_impl(c, "qpsk_deframer_reset_coded", nstreams, h_sync, nsync, min_score, nbytes, max_packets, true, mode, scale);
+}
+
+static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes,
+                               int max_packets, bool coded, int mode, float scale)
+{
+    if (!c || !h_sync) return fail(QPSK_ERR_ARG, "%s: null context or sync word", who);
+    if (nstreams <= 0) return fail(QPSK_ERR_ARG, "%s: nstreams = %d", who, nstreams);
+    if (nsync < 1 || nsync > SYNC_MAX_WORD) return fail(QPSK_ERR_ARG, "%s: nsync = %d outside 1..%d", who, nsync, SYNC_MAX_WORD);
+    if (min_score < 1 || min_score > nsync) return fail(QPSK_ERR_ARG, "%s: min_score = %d outside 1..%d", who, min_score, nsync);
+    if (nbytes < 1 || nbytes > DEFRAME_MAX_BYTES) return fail(QPSK_ERR_ARG, "%s: nbytes = %d outside 1..%d", who, nbytes, DEFRAME_MAX_BYTES);
     if (max_packets < 1 || max_packets > DEFRAME_MAX_PACKETS)
-        return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: max_packets = %d outside 1..%d", max_packets, DEFRAME_MAX_PACKETS);
+        return fail(QPSK_ERR_ARG, "%s: max_packets = %d outside 1..%d", who, max_packets, DEFRAME_MAX_PACKETS);
     for (int i = 0; i < nsync; i++)
-        if (h_sync[i] > 3) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset: sync[%d] = %d is not a dibit", i, (int)h_sync[i]);
+        if (h_sync[i] > 3) return fail(QPSK_ERR_ARG, "%s: sync[%d] = %d is not a dibit", who, i, (int)h_sync[i]);
+    if (coded && mode != QPSK_SOFT_UNIT && mode != QPSK_SOFT_LLR) return fail(QPSK_ERR_ARG, "%s: unknown mode %d", who, mode);
+    if (coded && !(scale > 0.0f && scale <= 3.402823466e+38f)) return fail(QPSK_ERR_ARG, "%s: scale = %g is not finite and > 0", who, (double)scale);
     if (bind(c)) return QPSK_ERR_HIP;
     /* refused until this call has completed */
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_deframer(c);
-    const int nb = nbytes + 2, N = 4 * nb;
-    const size_t stride = (size_t)DEFRAME_PEND_OFFSET + (((size_t)N + 15) & ~(size_t)15);
-    if (hipMalloc(&c->df_state, stride * (size_t)nstreams) != hipSuccess || hipMalloc(&c->df_tables, DF_ADV_OFFSET + 128) != hipSuccess) {
+    const int nb = nbytes + 2, N = coded ? 8 * nb + 6 : 4 * nb;      /* dibits of a body */
+    const size_t stride = (size_t)DEFRAME_PEND_OFFSET + (((size_t)N * (coded ? 2 : 1) + 15) & ~(size_t)15);
+    const size_t tab_bytes = coded ? (size_t)DFC_ADV_OFFSET + 2 * (size_t)DEFRAME_MAX_BYTES : (size_t)DF_ADV_OFFSET + 128;
+    if (hipMalloc(&c->df_state, stride * (size_t)nstreams) != hipSuccess || hipMalloc(&c->df_tables, tab_bytes) != hipSuccess) {
         free_deframer(c);
         (void)hipGetLastError();
-        return fail(QPSK_ERR_ALLOC, "qpsk_deframer_reset: %d streams of %zu bytes of state", nstreams, stride);
+        return fail(QPSK_ERR_ALLOC, "%s: %d streams of %zu bytes of state", who, nstreams, stride);
     }
     std::vector<unsigned char> ks((size_t)N);
     qpsk_host_scramble_keystream(ks.data(), N);
-    std::vector<uint8_t> tab(DF_ADV_OFFSET + 128, 0);
-    for (int k = 0; k < nb; k++) tab[k] = (uint8_t)(ks[4 * k] | ks[4 * k + 1] << 2 | ks[4 * k + 2] << 4 | ks[4 * k + 3] << 6);
-    const int per = (nb + 63) / 64;
-    for (int l = 0; l < 64; l++) {
-        const int end = (l + 1) * per < nbytes ? (l + 1) * per : nbytes;
-        const uint16_t v = crc_advance(nbytes - end);
-        memcpy(&tab[DF_ADV_OFFSET + 2 * l], &v, 2);
+    std::vector<uint8_t> tab(tab_bytes, 0);
+    if (coded) {
+        memcpy(tab.data(), ks.data(), (size_t)N);
+        unsigned adv = 1, init = 0xFFFFu;                               /* x^(8 m), and 0xFFFF x^(8 m), m = 0 .. nbytes */
+        for (int m = 0; m < nbytes; m++) {
+            const uint16_t v = (uint16_t)adv;
+            memcpy(&tab[DFC_ADV_OFFSET + 2 * m], &v, 2);
+            for (int i = 0; i < 8; i++) {
+                adv = ((adv << 1) ^ ((adv & 0x8000u) ? 0x1021u : 0u)) & 0xFFFFu;
+                init = ((init << 1) ^ ((init & 0x8000u) ? 0x1021u : 0u)) & 0xFFFFu;
+            }
+        }
+        c->df_crc_init = init;
+    } else {
+        for (int k = 0; k < nb; k++) tab[k] = (uint8_t)(ks[4 * k] | ks[4 * k + 1] << 2 | ks[4 * k + 2] << 4 | ks[4 * k + 3] << 6);
+        const int per = (nb + 63) / 64;
+        for (int l = 0; l < 64; l++) {
+            const int end = (l + 1) * per < nbytes ? (l + 1) * per : nbytes;
+            const uint16_t v = crc_advance(nbytes - end);
+            memcpy(&tab[DF_ADV_OFFSET + 2 * l], &v, 2);
+        }
     }
     c->df_sync_lo[0] = c->df_sync_lo[1] = c->df_sync_hi[0] = c->df_sync_hi[1] = 0;
     for (int i = 0; i < nsync; i++) {
@@ -2055,6 +2099,10 @@ int qpsk_deframer_reset(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int ns
     c->df_min_score = min_score;
     c->df_nbytes = nbytes;
     c->df_max_packets = max_packets;
+    c->df_coded = coded;
+    c->df_mode = mode;
+    c->df_scale = scale;
+    c->df_nsteps = coded ? N : 0;
     c->df_ready = true;
     return QPSK_OK;
 }
@@ -2067,6 +2115,7 @@ int qpsk_deframer_push(qpsk_ctx *c, const float *d_costas, const uint8_t *d_data
     if (!d_count) return fail(QPSK_ERR_ARG, "qpsk_deframer_push: d_count is required");
     if (nsym < 1 || nsym > DEFRAME_MAX_NSYM) return fail(QPSK_ERR_ARG, "qpsk_deframer_push: nsym = %d outside 1..%d", nsym, DEFRAME_MAX_NSYM);
     if (!c->df_state) return fail(QPSK_ERR_STATE, "qpsk_deframer_push: no qpsk_deframer_reset yet");
+    if (c->df_coded) return fail(QPSK_ERR_STATE, "qpsk_deframer_push: the deframer was reset in coded mode (qpsk_deframer_push_coded)");
     if (!c->df_ready) return fail(QPSK_ERR_STATE, "qpsk_deframer_push: the deframer's state is undefined after a failed push; reset it");
     const size_t S = (size_t)c->df_nstreams, M = (size_t)c->df_max_packets;
     const uintptr_t i0 = d_costas ? (uintptr_t)d_costas : (uintptr_t)d_data;
@@ -2108,6 +2157,90 @@ int qpsk_deframer_push(qpsk_ctx *c, const float *d_costas, const uint8_t *d_data
         return fail(QPSK_ERR_HIP, "deframe_kernel launch: %s", hipGetErrorString((hipError_t)e));
     }
     c->last_kernel = "deframe_kernel";
+    return QPSK_OK;
+}
+
+/* the coded mode's push (deframe_coded.hip): [the row's gain, unless the caller gives one] -> hunt + soft rows -> decode.  Everything that can
+ * fail without a launch -- arguments, the three buffers -- comes before the first launch */
+int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const float *d_gain, int32_t *d_count, uint8_t *d_bytes,
+                             long long *d_pos, int32_t *d_rot, int32_t *d_score, uint8_t *d_crc_ok, int32_t *d_info)
+{
+    if (!c) return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: null context");
+    if (!d_costas) return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: d_costas is required");
+    if (!d_count) return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: d_count is required");
+    if (nsym < 1 || nsym > DEFRAME_MAX_NSYM) return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: nsym = %d outside 1..%d", nsym, DEFRAME_MAX_NSYM);
+    if ((uintptr_t)d_costas % 8) return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: d_costas is not 8-byte aligned");
+    if ((uintptr_t)d_gain % 4 || (uintptr_t)d_count % 4 || (uintptr_t)d_rot % 4 || (uintptr_t)d_score % 4 || (uintptr_t)d_info % 4 || (uintptr_t)d_pos % 8)
+        return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: a misaligned array");
+    if (!c->df_state) return fail(QPSK_ERR_STATE, "qpsk_deframer_push_coded: no qpsk_deframer_reset_coded yet");
+    if (!c->df_coded) return fail(QPSK_ERR_STATE, "qpsk_deframer_push_coded: the deframer was reset in uncoded mode (qpsk_deframer_push)");
+    if (!c->df_ready) return fail(QPSK_ERR_STATE, "qpsk_deframer_push_coded: the deframer's state is undefined after a failed push; reset it");
+    const size_t S = (size_t)c->df_nstreams, M = (size_t)c->df_max_packets;
+    const uintptr_t i0 = (uintptr_t)d_costas, i1 = i0 + S * (size_t)nsym * 2 * sizeof(float);
+    const struct { const void *p; size_t bytes; const char *name; } outs[] = {
+        {d_count, S * 4, "d_count"}, {d_bytes, S * M * (size_t)(c->df_nbytes + 2), "d_bytes"}, {d_pos, S * M * 8, "d_pos"},
+        {d_rot, S * M * 4, "d_rot"}, {d_score, S * M * 4, "d_score"}, {d_crc_ok, S * M, "d_crc_ok"}, {d_info, S * M * 16, "d_info"}};
+    for (const auto &o : outs) {
+        if (!o.p) continue;
+        const uintptr_t o0 = (uintptr_t)o.p, o1 = o0 + o.bytes;
+        if (o0 < i1 && i0 < o1) return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: %s overlaps the input", o.name);
+    }
+    if (bind(c)) return QPSK_ERR_HIP;
+    const int Nc = c->df_nsteps;
+    const int per = std::min<long long>(c->df_max_packets, (long long)nsym / (c->df_nsync + Nc) + 1);
+    const size_t rows = S * (size_t)per;
+    const bool decode = d_bytes || d_crc_ok || d_info;
+    const size_t per_row = viterbi_scratch_bytes_per_row(Nc);
+    const bool fits = per_row <= (size_t)VITERBI_LDS_MAX_BYTES;
+    const bool resident = fits && rows <= (size_t)c->ncu * (((size_t)160 << 10) / per_row);
+    const bool lds = fits && tuned(c->tune.viterbi_lds, resident ? 1 : 0) != 0;
+    const size_t chunk_rows = std::min<size_t>(rows, std::max<size_t>(1, VITERBI_SCRATCH_MAX / per_row));
+    if (int rg = ensure(c, c->dfstage, rows * 2 * (size_t)Nc)) return rg;
+    if (!d_gain)
+        if (int rg = ensure(c, c->softgain, sizeof(float) * S)) return rg;
+    if (decode && !lds)
+        if (int rg = ensure(c, c->vitdec, chunk_rows * per_row)) return rg;
+
+    DeframeCodedArgs a{};
+    a.costas = reinterpret_cast<const float2 *>(d_costas);
+    a.gain = d_gain ? d_gain : (const float *)c->softgain.p;
+    a.check_gain = d_gain != nullptr;
+    a.nstreams = c->df_nstreams;
+    a.nsym = nsym;
+    a.nsync = c->df_nsync;
+    a.min_score = c->df_min_score;
+    a.nbytes = c->df_nbytes;
+    a.max_packets = c->df_max_packets;
+    a.nsteps = Nc;
+    a.per_stream = per;
+    a.state = c->df_state;
+    a.state_stride = c->df_stride;
+    for (int i = 0; i < 2; i++) { a.sync_lo[i] = c->df_sync_lo[i]; a.sync_hi[i] = c->df_sync_hi[i]; }
+    a.stage = (int8_t *)c->dfstage.p;
+    a.flip = c->df_tables;
+    a.crc_adv = reinterpret_cast<const uint16_t *>(c->df_tables + DFC_ADV_OFFSET);
+    a.crc_init = c->df_crc_init;
+    a.count = d_count;
+    a.bytes = d_bytes;
+    a.pos = d_pos;
+    a.rot = d_rot;
+    a.score = d_score;
+    a.crc_ok = d_crc_ok;
+    a.info = d_info;
+    a.status = c->d_status;
+    (void)hipGetLastError();
+    if (!d_gain)      /* nothing of the deframer's has run yet: a failure here leaves its state as it was */
+        KERNEL_TRY(launch_soft_sums(d_costas, (size_t)nsym, c->df_nstreams, nsym, 0, c->df_mode, c->df_scale, (float *)c->softgain.p, nullptr, nullptr,
+                                    c->d_status, c->stream));
+    int e = launch_deframe_coded_hunt(a, c->stream);
+    for (size_t r0 = 0; e == 0 && decode && r0 < rows; r0 += chunk_rows)      /* stream order: a chunk's trace-back is over before the next one's forward pass */
+        e = launch_deframe_coded_decode(a, (int)r0, (int)std::min<size_t>(chunk_rows, rows - r0), lds ? nullptr : (unsigned long long *)c->vitdec.p, lds, c->stream);
+    if (e != 0) {
+        c->df_ready = false;
+        return fail(QPSK_ERR_HIP, "qpsk_deframer_push_coded launch: %s", hipGetErrorString((hipError_t)e));
+    }
+    c->last_kernel = !decode ? "deframe_coded_hunt_kernel" : lds ? "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<lds>"
+                                                                 : "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<global>";
     return QPSK_OK;
 }
 

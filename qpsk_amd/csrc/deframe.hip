@@ -23,6 +23,7 @@
 
 #include "kernels.h"
 #include "qpsk_device.h"
+#include "deframe_bits.h"
 
 namespace qpsk {
 
@@ -31,29 +32,11 @@ namespace {
 constexpr int DF_WAVES = 4;       /* streams per workgroup: one wave each */
 constexpr int DF_CHUNK = 4;       /* steps of 64 positions per load batch (4 + 2 plane words): more spills SGPRs (103 of 106 at 4) */
 
-__device__ __forceinline__ unsigned long long funnel64(unsigned long long lo, unsigned long long hi, int l)
-{
-    return l ? (lo >> l) | (hi << (64 - l)) : lo;
-}
-
-__device__ __forceinline__ unsigned long long ballot64(bool b) { return (unsigned long long)__ballot(b); }
-
 template <bool COSTAS>
 __device__ __forceinline__ unsigned ring_at(const void *row, long long i)
 {
     if (COSTAS) return ring_of((unsigned)data_rule(reinterpret_cast<const float2 *>(row)[i]));
     return ring_of(reinterpret_cast<const uint8_t *>(row)[i] & 3u);
-}
-
-/* multiply a CRC register by m(x) modulo the CRC-16 polynomial x^16 + x^12 + x^5 + 1 */
-__device__ __forceinline__ unsigned crc_mulmod(unsigned a, unsigned m)
-{
-    unsigned r = 0;
-    for (int i = 15; i >= 0; i--) {
-        r = ((r << 1) ^ ((r & 0x8000u) ? 0x1021u : 0u)) & 0xFFFFu;
-        if ((m >> i) & 1u) r ^= a;
-    }
-    return r;
 }
 
 /*

@@ -19,7 +19,7 @@ constexpr int STATUS_NONFINITE = 3;      /* a loop ended on a NaN / Inf phase or
 constexpr int STATUS_BAD_INDEX = 4;      /* a per-frame decimation offset outside 0..MAX_INDEX (caller-supplied: qpsk_rx_batch_ext); the kernel
                                             addressed with 0 instead */
 constexpr int STATUS_EST_NONFINITE = 5;  /* qpsk_carrier_est_batch: a NaN / Inf sample inside the window the estimate reads */
-constexpr int STATUS_SOFT_NONFINITE = 6; /* qpsk_soft_batch: a NaN / Inf sample among those a row's sums or soft output use, or a NaN / Inf gain in d_gain_in */
+constexpr int STATUS_SOFT_NONFINITE = 6; /* qpsk_soft_batch, qpsk_deframer_push_coded: a NaN / Inf sample among those a row's sums or soft output use, or a NaN / Inf gain */
 constexpr int STATUS_SOFT_BAD_LAG = 7;   /* qpsk_soft_batch: a per-row lag that would leave the row; that row's soft output is zeros */
 
 struct FusedArgs {
@@ -282,6 +282,38 @@ struct DeframeArgs {
     uint8_t *crc_ok;
 };
 int launch_deframe(const DeframeArgs &a, hipStream_t s);
+/* deframe_coded.hip: qpsk_deframer_push_coded.  The same per-stream state, with the pending packet's received body as int8 soft pairs
+ * (2 nsteps bytes) at DEFRAME_PEND_OFFSET.  Two launches: the hunt, which quantises the body symbols of this push and leaves every
+ * packet it completes as a soft row in the staging buffer -- row stream * per_stream + slot, slot = the packet's output row -- and the
+ * decode, one wave per staging row (rows at or beyond the stream's count retire at once) */
+constexpr int DEFRAME_CODED_MAX_STEPS = 8 * (DEFRAME_MAX_BYTES + 2) + 6;
+struct DeframeCodedArgs {
+    const float2 *costas;         /* [nstreams][nsym] */
+    const float *gain;            /* [nstreams]: this push's gain per stream */
+    int check_gain;               /* the gains are the caller's: flag a NaN / Inf one */
+    int nstreams, nsym;
+    int nsync, min_score, nbytes, max_packets;
+    int nsteps;                   /* Nc = 8 (nbytes + 2) + 6 */
+    int per_stream;               /* staging rows per stream: min(max_packets, nsym / (nsync + nsteps) + 1), the most a push completes */
+    uint8_t *state;
+    size_t state_stride;
+    unsigned long long sync_lo[2], sync_hi[2];
+    int8_t *stage;                /* [nstreams * per_stream][nsteps][2] */
+    const uint8_t *flip;          /* [nsteps]: the scrambler's keystream dibits */
+    const uint16_t *crc_adv;      /* [nbytes]: x^(8 m) mod the CRC-16 polynomial */
+    unsigned crc_init;            /* crc16()'s register after nbytes zero bytes from 0xFFFF */
+    int32_t *count;
+    uint8_t *bytes;
+    long long *pos;
+    int32_t *rot, *score;
+    uint8_t *crc_ok;
+    int32_t *info;
+    int *status;
+};
+int launch_deframe_coded_hunt(const DeframeCodedArgs &a, hipStream_t s);
+/* rows [row0, row0 + nrows) of the staging buffer; lds: the decision words in LDS (viterbi_scratch_bytes_per_row(nsteps) <=
+ * VITERBI_LDS_MAX_BYTES), otherwise in scratch ([nrows] rows of that many bytes) */
+int launch_deframe_coded_decode(const DeframeCodedArgs &a, int row0, int nrows, unsigned long long *scratch, bool lds, hipStream_t s);
 /* txchain.hip */
 int tx_history_symbols(void);          /* symbols of state per transmitter (uint8 each, 4 = none yet) */
 int launch_tx_shape(const uint8_t *sym, uint8_t *hist, const float *taps, float *sig, int nstreams, int nsym,

@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "soft_quant.h"
 
 namespace qpsk {
 
@@ -43,7 +44,6 @@ struct Sums {
     double s1, s2, s4, sq;
 };
 
-__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= FLT_MAX; }
 __device__ __forceinline__ bool finite_d(double x) { return fabs(x) <= DBL_MAX; }
 
 /* one symbol's terms (qpsk_hip.h): t1 = |a| + |b|, t2 = p, t4 = p p, tq = Re z^4, fp64 on the widened floats, nothing fused */
@@ -139,21 +139,6 @@ __device__ __forceinline__ float finish_row(const Sums &S, int m, int mode, floa
     if (mode == SOFT_MODE_LLR && Pn > 0.0) return gain_of(2.0 * sqrt(Ps / 2.0) / (Pn / 2.0), (double)scale);
     const double target = mode == SOFT_MODE_LLR ? 127.0 : (double)scale;
     return amp > 0.0 ? gain_of(target, amp) : 0.0f;
-}
-
-__device__ __forceinline__ unsigned q8(float x, float g)
-{
-    const float v = fminf(127.0f, fmaxf(-127.0f, rintf(x * g)));
-    return (unsigned)(int)v & 255u;
-}
-
-/* z (-j)^r as the two int8 of one output symbol, bit 0's in the low byte */
-__device__ __forceinline__ unsigned soft_pair(float2 z, int r, float g, bool &bad)
-{
-    bad |= !finite_f(z.x) || !finite_f(z.y);
-    const float u = r == 0 ? z.x : r == 1 ? z.y : r == 2 ? -z.x : -z.y;
-    const float v = r == 0 ? z.y : r == 1 ? -z.x : r == 2 ? -z.y : z.x;
-    return q8(u, g) | (q8(v, g) << 8);
 }
 
 /*

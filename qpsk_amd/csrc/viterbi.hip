@@ -24,50 +24,19 @@
  * The two routes differ only in where the decision words wait between the passes: viterbi_kernel (global scratch, [row][steps padded
  * to 64] words) and viterbi_lds_kernel (dynamic LDS, 8 bytes per padded step).
  *
+ * The row's passes themselves live in viterbi_row.h, which deframe_coded.hip runs on the packets of a stream as well.
+ *
  * conv_encode_kernel: one thread per coded dibit; a plain kernel so that a loopback stays on the device.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "kernels.h"
+#include "viterbi_row.h"
 
 namespace qpsk {
 
 namespace {
-
-constexpr int NEG = -(1 << 30);      /* the start penalty of the 63 other states (qpsk_hip.h) */
-
-__device__ __forceinline__ int parity(unsigned v) { return __popc(v) & 1; }
-
-/* lane `lane`: the soft pair of step t0 + lane after the -128 rule and d_flip; (0, 0) -- an erasure -- beyond the row */
-__device__ __forceinline__ void load_soft(const int8_t *__restrict__ row, const uint8_t *__restrict__ flip, int t0, int nsteps, int lane,
-                                          int &s0, int &s1)
-{
-    const int t = t0 + lane;
-    s0 = s1 = 0;
-    if (t < nsteps) {
-        const unsigned w = *reinterpret_cast<const unsigned short *>(row + 2 * (size_t)t);
-        s0 = max((int)(int8_t)(w & 255u), -127);
-        s1 = max((int)(int8_t)(w >> 8), -127);
-        if (flip) {
-            const unsigned f = flip[t];
-            s0 = (f & 1u) ? -s0 : s0;
-            s1 = (f & 2u) ? -s1 : s1;
-        }
-    }
-}
-
-/* the channel errors of block blk, lane-parallel: cur / prev = the decoded bits of blocks blk / blk - 1 (bit j = step 64 blk + j).
- * x = bits t-6 .. t of the row with bit t - 6 lowest, so the generators apply bit-reversed: 171 -> 0x4F, 133 -> 0x6D */
-__device__ __forceinline__ int block_errors(const int8_t *__restrict__ row, const uint8_t *__restrict__ flip, int blk, int nsteps, int lane,
-                                            unsigned long long cur, unsigned long long prev)
-{
-    const unsigned long long lo = (cur << 6) | (prev >> 58), hi = cur >> 58;
-    const unsigned x = (unsigned)((lo >> lane) | ((hi << 1) << (63 - lane))) & 127u;
-    int s0, s1;
-    load_soft(row, flip, blk << 6, nsteps, lane, s0, s1);
-    return (int)(s0 != 0 && (s0 < 0) != (bool)parity(x & 0x4Fu)) + (int)(s1 != 0 && (s1 < 0) != (bool)parity(x & 0x6Du));
-}
 
 struct VitArgs {
     const int8_t *soft;
@@ -79,118 +48,19 @@ struct VitArgs {
     int32_t *info;
 };
 
-#ifdef QPSK_VITERBI_PROFILE
-#define VIT_STAMP(t) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory")
-#endif
-
+/* workgroup = wave = row blockIdx.x of the call (viterbi_row.h) */
 template <bool LDS>
-__device__ __forceinline__ void viterbi_row(const VitArgs &a)
+__device__ __forceinline__ void viterbi_batch_row(const VitArgs &a)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long ldec[];      /* LDS route: [nblk * 64] decision words */
-    const int lane = threadIdx.x, row = blockIdx.x;
-    const int nsteps = a.nsteps, nblk = (nsteps + 63) >> 6;
-    const int8_t *soft = a.soft + 2 * (size_t)row * a.pitch;
-    unsigned long long *gdec = a.scratch + (size_t)row * ((size_t)nblk << 6);
-#ifdef QPSK_VITERBI_PROFILE
-    unsigned long long stamp0, stamp1, stamp2;
-    VIT_STAMP(stamp0);
-#endif
-
-    /* ---- forward */
-    int sg0 = parity((unsigned)lane & 0x79u) ? -1 : 1, sg1 = parity((unsigned)lane & 0x5Bu) ? -1 : 1;
-    asm volatile("" : "+v"(sg0), "+v"(sg1));      /* opaque: keeps b at a 24-bit multiply and a multiply-add instead of selects on +-1 */
-    const int from0 = (lane >> 1) << 2, from1 = from0 | 128;      /* byte addresses of lanes ns >> 1 and (ns >> 1) | 32 */
-    int pm = ((a.flags & VITERBI_OPEN_START) || lane == 0) ? 0 : NEG;
-    int n0, n1;
-    load_soft(soft, a.flip, 0, nsteps, lane, n0, n1);
-    for (int blk = 0; blk < nblk; blk++) {
-        const int s0v = n0, s1v = n1;
-        if (blk + 1 < nblk) load_soft(soft, a.flip, (blk + 1) << 6, nsteps, lane, n0, n1);      /* a block ahead: no step waits on memory */
-        const int n = min(64, nsteps - (blk << 6));
-        unsigned dh[2] = {0u, 0u};
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-            const int nh = min(32, n - 32 * half);
-            unsigned acc = 0u;
-#pragma unroll 8
-            for (int j = 0; j < nh; j++) {
-                const int s0 = __builtin_amdgcn_readlane(s0v, 32 * half + j), s1 = __builtin_amdgcn_readlane(s1v, 32 * half + j);
-                const int b = __mul24(sg0, s0) + __mul24(sg1, s1);
-                const int m0 = __builtin_amdgcn_ds_bpermute(from0, pm) + b;
-                const int m1 = __builtin_amdgcn_ds_bpermute(from1, pm) - b;
-                acc |= m1 > m0 ? 1u << j : 0u;       /* a tie keeps p0 */
-                pm = max(m0, m1);
-            }
-            dh[half] = acc;
-        }
-        const unsigned dlo = dh[0], dhi = dh[1];
-        const unsigned long long w = ((unsigned long long)dhi << 32) | dlo;
-        if (LDS) ldec[(blk << 6) + lane] = w;
-        else gdec[(blk << 6) + lane] = w;
-    }
-#ifdef QPSK_VITERBI_PROFILE
-    VIT_STAMP(stamp1);
-    if (a.flags & VITERBI_PROFILE_FORWARD_ONLY) {      /* measurement: the decisions are in memory / LDS, the metrics go out so that nothing is dead */
-        if (a.info && lane < 4) a.info[4 * (size_t)row + lane] = lane == 0 ? pm : lane == 1 ? (int)(stamp1 - stamp0) : 0;
-        return;
-    }
-#endif
-
-    /* ---- the end state */
-    int st = 0;
-    if (a.flags & VITERBI_OPEN_END) {
-        int mx = pm;
-#pragma unroll
-        for (int h = 32; h >= 1; h >>= 1) mx = max(mx, __shfl_xor(mx, h, 64));
-        st = __ffsll((long long)__ballot(pm == mx)) - 1;      /* ties to the lowest state */
-    }
-    st = __builtin_amdgcn_readfirstlane(st);
-    const int end_state = st, end_metric = __builtin_amdgcn_readlane(pm, st);
-
-    /* ---- trace-back over the whole row, the error count one block behind it */
-    const size_t nbytes = ((size_t)nsteps + 7) >> 3;
-    uint8_t *bits = a.bits ? a.bits + (size_t)row * nbytes : nullptr;
-    unsigned long long later = 0;      /* the decoded bits of block blk + 1 */
-    int errs = 0;
-    for (int blk = nblk - 1; blk >= 0; blk--) {
-        const unsigned long long w = LDS ? ldec[(blk << 6) + lane] : gdec[(blk << 6) + lane];
-        const int wlo = (int)(unsigned)w, whi = (int)(unsigned)(w >> 32);
-        const int n = min(64, nsteps - (blk << 6));
-        unsigned long long word = 0;
-#pragma unroll
-        for (int half = 1; half >= 0; half--) {
-            const int nh = min(32, n - 32 * half), wv = half ? whi : wlo;
-            unsigned wh = 0u;
-#pragma unroll 8
-            for (int j = nh - 1; j >= 0; j--) {
-                const unsigned d = ((unsigned)__builtin_amdgcn_readlane(wv, st) >> j) & 1u;      /* d[t][st]: bit j of state st's word */
-                wh |= (unsigned)(st & 1) << j;
-                st = (st >> 1) | (int)(d << 5);
-            }
-            word |= (unsigned long long)wh << (32 * half);
-        }
-        if (bits && lane < ((n + 7) >> 3)) bits[(blk << 3) + lane] = (uint8_t)(word >> (lane << 3));
-        if (a.info && blk + 1 < nblk) errs += block_errors(soft, a.flip, blk + 1, nsteps, lane, later, word);
-        later = word;
-    }
-    if (a.info) {
-        /* the six bits before the row are the state the trace-back arrived at (0 unless open start): state bit k = bit -1 - k */
-        errs += block_errors(soft, a.flip, 0, nsteps, lane, later, (unsigned long long)(__brev((unsigned)st) >> 26) << 58);
-#pragma unroll
-        for (int h = 32; h >= 1; h >>= 1) errs += __shfl_xor(errs, h, 64);
-#ifdef QPSK_VITERBI_PROFILE
-        VIT_STAMP(stamp2);
-        if (a.flags & VITERBI_PROFILE_CYCLES) {      /* measurement: words 1, 2 = the cycles of the two passes */
-            if (lane < 4) a.info[4 * (size_t)row + lane] = lane == 0 ? end_metric : lane == 1 ? (int)(stamp1 - stamp0) : lane == 2 ? (int)(stamp2 - stamp1) : errs;
-            return;
-        }
-#endif
-        if (lane < 4) a.info[4 * (size_t)row + lane] = lane == 0 ? end_metric : lane == 1 ? end_state : lane == 2 ? st : errs;
-    }
+    const size_t row = blockIdx.x;
+    const size_t nblk = ((size_t)a.nsteps + 63) >> 6;
+    BitsSink sink = {a.bits ? a.bits + row * (((size_t)a.nsteps + 7) >> 3) : nullptr};
+    viterbi_row<LDS>(a.soft + 2 * row * a.pitch, a.flip, a.nsteps, a.flags, LDS ? nullptr : a.scratch + row * (nblk << 6),
+                     a.info ? a.info + 4 * row : nullptr, sink);
 }
 
-__global__ void __launch_bounds__(64) viterbi_kernel(VitArgs a) { viterbi_row<false>(a); }
-__global__ void __launch_bounds__(64) viterbi_lds_kernel(VitArgs a) { viterbi_row<true>(a); }
+__global__ void __launch_bounds__(64) viterbi_kernel(VitArgs a) { viterbi_batch_row<false>(a); }
+__global__ void __launch_bounds__(64) viterbi_lds_kernel(VitArgs a) { viterbi_batch_row<true>(a); }
 
 /* one thread per coded dibit: register r of step t = bits t-6 .. t (bit t in bit 0), zeros before the row and in the tail */
 __global__ void __launch_bounds__(256)

@@ -57,6 +57,7 @@ API_SYMBOLS = [
     "qpsk_multi_set_packed", "qpsk_pack_symbols", "qpsk_unpack_symbols_host",
     "qpsk_rx_batch_ext", "qpsk_rx_batch_bw_ext", "qpsk_multi_set_acquisition", "qpsk_carrier_est_batch",
     "qpsk_rx_batch_data", "qpsk_sync_batch", "qpsk_multi_set_data", "qpsk_deframer_reset", "qpsk_deframer_push",
+    "qpsk_deframer_reset_coded", "qpsk_deframer_push_coded",
     "qpsk_soft_batch", "qpsk_conv_encode_batch", "qpsk_viterbi_batch",
 ]
 # every symbol include/qpsk_dropin.h declares
@@ -118,6 +119,8 @@ def load():
     L.qpsk_multi_set_data.argtypes = [vp, i32]
     L.qpsk_deframer_reset.argtypes = [vp, i32, vp, i32, i32, i32, i32]
     L.qpsk_deframer_push.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.qpsk_deframer_reset_coded.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, f32]
+    L.qpsk_deframer_push_coded.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.qpsk_soft_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, i32, f32, vp, vp, vp, i32, i32, vp, vp, vp]
     L.qpsk_conv_encode_batch.argtypes = [vp, vp, i32, i32, i32, vp]
     L.qpsk_viterbi_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, vp, i32, vp, vp]
@@ -593,6 +596,37 @@ class Modem:
                                               x.shape[1], _ptr(o["count"]), _ptr(o["bytes"]), _ptr(o["pos"]), _ptr(o["rot"]),
                                               _ptr(o["score"]), _ptr(o["crc_ok"])))
         o["_keep"] = (x,)
+        return o
+
+    def deframer_reset_coded(self, nstreams, sync, nbytes, min_score, max_packets=8, mode="unit", scale=64.0):
+        """deframer_reset() for packets whose body carries the K = 7 rate-1/2 code: [sync][scrambled conv_encode(payload + CRC-16, tail)].
+        mode, scale: soft()'s, for the gain of a push that brings none of its own.  Replaces an uncoded deframer of the context."""
+        sw = np.ascontiguousarray(np.asarray(sync, dtype=np.uint8))
+        self._check(self.L.qpsk_deframer_reset_coded(self.h, int(nstreams), sw.ctypes.data_as(C.c_void_p), len(sw), int(min_score), int(nbytes),
+                                                     int(max_packets), self.SOFT_MODES[mode], float(scale)))
+        self.df_shape = (int(nstreams), int(nbytes), int(max_packets))
+
+    def deframe_coded(self, costas, gain=None):
+        """Push one row per stream: costas (nstreams, nsym, 2) float32, or the dict streams_rx_pcm(..., want_costas=True) returns; gain
+        (nstreams,) float32 = this push's soft gain per stream, None = each row's own (soft()'s rule with skip 0).  Dict of torch tensors
+        for the packets completed by this push: count, bytes, pos, rot, score, crc_ok as deframe(), and info (nstreams, max_packets, 4)
+        int32 = the decoder's (end metric, end state, start state, channel bit errors)."""
+        t = self.torch
+        if isinstance(costas, dict):
+            costas = costas["costas"]
+        x = self._dev(costas, t.float32)
+        S, nb, M = self.df_shape
+        if x.dim() != 3 or x.shape[0] != S or x.shape[2] != 2:
+            raise ValueError("deframe_coded() input must be (%d, nsym, 2) float32" % S)
+        g = None if gain is None else self._dev(gain, t.float32)
+        if g is not None and tuple(g.shape) != (S,):
+            raise ValueError("deframe_coded() gain must be (%d,) float32" % S)
+        z = lambda shape, dt: t.zeros(shape, dtype=dt, device=self.dev)      # noqa: E731
+        o = dict(count=self.empty((S,), t.int32), bytes=z((S, M, nb + 2), t.uint8), pos=z((S, M), t.int64), rot=z((S, M), t.int32),
+                 score=z((S, M), t.int32), crc_ok=z((S, M), t.uint8), info=z((S, M, 4), t.int32))
+        self._check(self.L.qpsk_deframer_push_coded(self.h, _ptr(x), x.shape[1], _ptr(g), _ptr(o["count"]), _ptr(o["bytes"]), _ptr(o["pos"]),
+                                                    _ptr(o["rot"]), _ptr(o["score"]), _ptr(o["crc_ok"]), _ptr(o["info"])))
+        o["_keep"] = (x, g)
         return o
 
     def streams_loop_state(self):
