@@ -316,6 +316,18 @@ int qpsk_deframer_push_coded(qpsk_ctx *ctx, const float *d_costas, int nsym, con
                              uint8_t *d_bytes, long long *d_pos, int32_t *d_rot, int32_t *d_score, uint8_t *d_crc_ok,
                              int32_t *d_info);
 
+/* The coded deframer behind a puncturing pattern (PUNCTURING below).  On air:
+ *       [sync: n dibits, uncoded][body: Nc = ntx(8 (nbytes + 2) + 6) dibits]
+ *       body = keystream xor qpsk_conv_encode_punct_batch(payload ++ crc16 big-endian, QPSK_CONV_TAIL, pattern)
+ * HUNT, SOFT and GAIN are exactly CODED DEFRAMER's with this Nc.  DECODE is qpsk_viterbi_punct_batch's decoder on the Nc staged dibits
+ * with nsteps = 8 (nbytes + 2) + 6, d_flip = the keystream dibits (over the transmitted dibits) and flags 0.  The pattern lives in the
+ * deframer's state: qpsk_deframer_push_coded is the push of both resets, unchanged.  qpsk_deframer_reset_coded is the pattern (1, 1, 1)
+ * and the two agree bit for bit.  Arguments and errors as qpsk_deframer_reset_coded; a bad pattern gives QPSK_ERR_ARG and resets
+ * nothing.  qpsk_ctx_last_kernel() names deframe_coded_decode_punct_kernel<lds> or <global> after a push.  Restated in numpy by
+ * tests/test_punct_cpu.py (deframe_coded_punct_ref). */
+int qpsk_deframer_reset_coded_punct(qpsk_ctx *ctx, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes,
+                                    int max_packets, int mode, float scale, int period, uint32_t keep0, uint32_t keep1);
+
 /* qpsk_rx_batch_bw() the same way: d_seed [nframes][nbw][2] (one seed per loop) or NULL; d_index_in [nframes] or NULL */
 int qpsk_rx_batch_bw_ext(qpsk_ctx *ctx, const float *d_in, int nframes, const float *h_loop_bw, int nbw, const int32_t *d_index_in,
                          const float *d_seed, uint8_t *d_sym, float *d_freq, float *d_phase, int32_t *d_index);
@@ -442,6 +454,52 @@ enum { QPSK_VITERBI_OPEN_START = 1, QPSK_VITERBI_OPEN_END = 2 };
 int qpsk_conv_encode_batch(qpsk_ctx *ctx, const uint8_t *d_bits, int nrows, int nbits, int flags, uint8_t *d_dibits);
 int qpsk_viterbi_batch(qpsk_ctx *ctx, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const uint8_t *d_flip,
                        int flags, uint8_t *d_bits, int32_t *d_info);
+
+/* -------------------------------------------------------------------------
+ * PUNCTURING: the rates 2/3, 3/4, 5/6, 7/8 (and any other pattern of period <= 32) of the code above, by not sending some of the coded
+ * bits.  The library's own definition, integers only (the reference has no FEC; parity unpinned), restated in numpy by
+ * tests/test_punct_cpu.py.
+ *
+ * PATTERN (period, keep0, keep1): 1 <= period <= 32; keep0, keep1 uint32 with no bit set at or above period and keep0 | keep1 != 0.
+ *   Coded bit j (0 is c0, 1 is c1) of trellis step t is SENT iff bit r = t mod period of keep_j is set.  K = popc(keep0) + popc(keep1).
+ *   A period position where neither bit is sent is legal.
+ * NUMBERING of the sent bits, in the order (t, j).  With low(r) = (1u << r) - 1:
+ *       idx(t, 0) = (t / period) K + popc(keep0 & low(r)) + popc(keep1 & low(r))
+ *       idx(t, 1) = idx(t, 0) + ((keep0 >> r) & 1)
+ *       nsent(nsteps) = idx(nsteps, 0)            ntx(nsteps) = ceil(nsent / 2) dibits
+ * PACKING.  Sent bit k rides on bit k & 1 of transmitted dibit k >> 1.  When nsent is odd, bit 1 of the last dibit is a pad bit: the
+ *   encoder sends 0, the receiver never reads its soft value.  This serial packing IS the definition: the mapping of the sent bits
+ *   onto I and Q that DVB-S prescribes for its punctured rates is NOT reproduced.
+ * NAMED PATTERNS, as macros that expand to the three arguments; bit r of a mask is step r of the period.  They are the usual X / Y
+ *   patterns for 171 / 133 (X 10, Y 11; X 101, Y 110; X 10101, Y 11010; X 1000101, Y 1111010).
+ * DECODER INPUT.  v(k) = flat int8 number k of the row = d_soft[row][k >> 1][k & 1], what qpsk_soft_batch writes for the transmitted
+ *   symbols.  -128 is taken as -127; then v(k) is negated iff bit k & 1 of d_flip[k >> 1] is set: d_flip is [ntx] and runs over the
+ *   TRANSMITTED dibits, because the scrambler acts on what is on air.  Step t's input is
+ *       s_j = sent(t, j) ? v(idx(t, j)) : 0
+ *   and everything after that is word for word qpsk_viterbi_batch: start, step, tie rule, end, whole-row trace-back, d_bits and the four
+ *   d_info words (the error count ignores zeros, so it counts over the sent bits).  nsteps <= 131072 and the metric bound are unchanged.
+ * Hence, and tested:  (1) the punctured call equals qpsk_viterbi_batch with d_flip NULL on the zero-filled row (s_j above, after the
+ *   -128 rule and the flip) in d_bits and all four d_info words;  (2) the pattern (1, 1, 1) equals qpsk_viterbi_batch with the same d_flip.
+ *
+ *   qpsk_punct_ntx                host only, no context: ntx(nsteps), 1 <= nsteps <= 131072, or QPSK_ERR_ARG.  May be 0 when every
+ *                step of so short a row is deleted.
+ *   qpsk_conv_encode_punct_batch  as qpsk_conv_encode_batch -> d_dibits [nrows][ntx(nsteps)] uint8
+ *   qpsk_viterbi_punct_batch      as qpsk_viterbi_batch; d_soft rows row_pitch TRANSMITTED symbols apart (0 = ntx; otherwise >= ntx; what
+ *                lies between rows, and the pad value, is never read); d_flip [ntx] or NULL
+ * Arguments and errors as the unpunctured twins; a bad pattern gives QPSK_ERR_ARG at the call with nothing launched.  Where the
+ * decision words wait (LDS or the scratch buffer) goes by nsteps, as in qpsk_viterbi_batch; qpsk_ctx_last_kernel() names
+ * viterbi_punct_lds_kernel, viterbi_punct_kernel or conv_encode_punct_kernel.  Usage: INTEGRATION.md 2.0.
+ * ------------------------------------------------------------------------- */
+#define QPSK_PUNCT_1_2 1, 0x1u, 0x1u
+#define QPSK_PUNCT_2_3 2, 0x1u, 0x3u
+#define QPSK_PUNCT_3_4 3, 0x5u, 0x3u
+#define QPSK_PUNCT_5_6 5, 0x15u, 0x0Bu
+#define QPSK_PUNCT_7_8 7, 0x51u, 0x2Fu
+int qpsk_punct_ntx(int nsteps, int period, uint32_t keep0, uint32_t keep1);
+int qpsk_conv_encode_punct_batch(qpsk_ctx *ctx, const uint8_t *d_bits, int nrows, int nbits, int flags, int period, uint32_t keep0,
+                                 uint32_t keep1, uint8_t *d_dibits);
+int qpsk_viterbi_punct_batch(qpsk_ctx *ctx, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, int period, uint32_t keep0,
+                             uint32_t keep1, const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info);
 
 /* -------------------------------------------------------------------------
  * The stages on their own (each is what the corresponding reference function

@@ -175,7 +175,10 @@ struct qpsk_ctx {
     /* the coded mode (qpsk_deframer_reset_coded): the same state with int8 soft pairs as the pending body; the tables are the keystream
      * dibits [nsteps], then the CRC advance factors x^(8 m), m < nbytes, at DFC_ADV_OFFSET.  One deframer per context, in one mode */
     bool df_coded = false;
-    int df_mode = 0, df_nsteps = 0;
+    int df_mode = 0, df_nsteps = 0;      /* df_nsteps: the trellis steps of a packet, 8 (nbytes + 2) + 6 */
+    int df_nbody = 0;             /* Nc: a body's dibits on air (df_nsteps; ntx(df_nsteps) after qpsk_deframer_reset_coded_punct) */
+    bool df_punct = false;        /* reset by qpsk_deframer_reset_coded_punct: the decode takes the punctured kernels, whatever the pattern */
+    Puncture df_pattern = {1, 1u, 1u, 2};
     float df_scale = 0.f;
     unsigned df_crc_init = 0;
     DevBuf dfstage;               /* the soft rows of the packets a coded push completes, between the hunt and the decode */
@@ -415,6 +418,7 @@ static void free_deframer(qpsk_ctx *c)
     c->df_state = c->df_tables = nullptr;
     c->df_ready = false;
     c->df_coded = false;
+    c->df_punct = false;
     c->df_nstreams = 0;
 }
 
@@ -1362,28 +1366,85 @@ int qpsk_conv_encode_batch(qpsk_ctx *c, const uint8_t *d_bits, int nrows, int nb
     return QPSK_OK;
 }
 
+/* PUNCTURING (include/qpsk_hip.h): the pattern of a call, checked; who = the entry point's name */
+static int punct_make(const char *who, int period, uint32_t keep0, uint32_t keep1, Puncture *p)
+{
+    if (period < 1 || period > 32) return fail(QPSK_ERR_ARG, "%s: period = %d outside 1..32", who, period);
+    const uint32_t above = period == 32 ? 0u : ~((1u << period) - 1u);
+    if ((keep0 | keep1) & above) return fail(QPSK_ERR_ARG, "%s: keep0 = 0x%x / keep1 = 0x%x has a bit at or above period %d", who, keep0, keep1, period);
+    if (!(keep0 | keep1)) return fail(QPSK_ERR_ARG, "%s: keep0 and keep1 are both 0: nothing would be sent", who);
+    *p = Puncture{period, keep0, keep1, __builtin_popcount(keep0) + __builtin_popcount(keep1)};
+    return QPSK_OK;
+}
+
+int qpsk_punct_ntx(int nsteps, int period, uint32_t keep0, uint32_t keep1)
+{
+    Puncture p;
+    if (int rc = punct_make("qpsk_punct_ntx", period, keep0, keep1, &p)) return rc;
+    if (nsteps < 1 || nsteps > VITERBI_MAX_STEPS) return fail(QPSK_ERR_ARG, "qpsk_punct_ntx: nsteps = %d (1..%d)", nsteps, VITERBI_MAX_STEPS);
+    return (int)((punct_nsent(p, nsteps) + 1) / 2);
+}
+
+int qpsk_conv_encode_punct_batch(qpsk_ctx *c, const uint8_t *d_bits, int nrows, int nbits, int flags, int period, uint32_t keep0, uint32_t keep1,
+                                 uint8_t *d_dibits)
+{
+    if (!c || !d_bits || !d_dibits) return fail(QPSK_ERR_ARG, "qpsk_conv_encode_punct_batch: null argument");
+    if (flags & ~QPSK_CONV_TAIL) return fail(QPSK_ERR_ARG, "qpsk_conv_encode_punct_batch: unknown flags 0x%x", flags);
+    const int tail = (flags & QPSK_CONV_TAIL) ? 6 : 0;
+    if (nrows <= 0 || nbits <= 0 || nbits > VITERBI_MAX_STEPS - tail)
+        return fail(QPSK_ERR_ARG, "qpsk_conv_encode_punct_batch: nrows = %d, nbits = %d (1..%d)", nrows, nbits, VITERBI_MAX_STEPS - tail);
+    Puncture p;
+    if (int rc = punct_make("qpsk_conv_encode_punct_batch", period, keep0, keep1, &p)) return rc;
+    if (bind(c)) return QPSK_ERR_HIP;
+    if (punct_nsent(p, nbits + tail) == 0) return QPSK_OK;      /* every step of so short a row is deleted: nothing is sent */
+    KERNEL_TRY(launch_conv_encode_punct(d_bits, nrows, nbits, nbits + tail, p, d_dibits, c->stream));
+    c->last_kernel = "conv_encode_punct_kernel";
+    return QPSK_OK;
+}
+
 /* Where the decision words (8 bytes per step) wait for the trace-back: in LDS when a row's fit the launch limit and -- the library's own
  * choice -- every row of the call is resident at once (160 KB of LDS per compute unit), so that the LDS never costs a second round of
  * workgroups; otherwise in the context's scratch buffer, rows in chunks of at most VITERBI_SCRATCH_MAX bytes of it */
 static const size_t VITERBI_SCRATCH_MAX = (size_t)1 << 30;
 
+/* both decoders: who = the entry point's name; punct = NULL for rate 1/2, otherwise the checked pattern: the rows then hold the ntx
+ * transmitted dibits of nsteps steps, and row_pitch and d_flip go by ntx.  The residency rule, the scratch and the chunks go by nsteps */
+static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const Puncture *punct,
+                        const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info);
+
 int qpsk_viterbi_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const uint8_t *d_flip, int flags,
                        uint8_t *d_bits, int32_t *d_info)
 {
-    if (!c || !d_soft) return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: null context or input");
-    if (!d_bits && !d_info) return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: every output is NULL");
+    return viterbi_impl(c, "qpsk_viterbi_batch", d_soft, row_pitch, nrows, nsteps, nullptr, d_flip, flags, d_bits, d_info);
+}
+
+int qpsk_viterbi_punct_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, int period, uint32_t keep0,
+                             uint32_t keep1, const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info)
+{
+    Puncture p;
+    if (!c) return fail(QPSK_ERR_ARG, "qpsk_viterbi_punct_batch: null context or input");
+    if (int rc = punct_make("qpsk_viterbi_punct_batch", period, keep0, keep1, &p)) return rc;
+    return viterbi_impl(c, "qpsk_viterbi_punct_batch", d_soft, row_pitch, nrows, nsteps, &p, d_flip, flags, d_bits, d_info);
+}
+
+static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const Puncture *punct,
+                        const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info)
+{
+    if (!c || !d_soft) return fail(QPSK_ERR_ARG, "%s: null context or input", who);
+    if (!d_bits && !d_info) return fail(QPSK_ERR_ARG, "%s: every output is NULL", who);
     if (nrows <= 0 || nsteps <= 0 || nsteps > VITERBI_MAX_STEPS)
-        return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: nrows = %d, nsteps = %d (1..%d)", nrows, nsteps, VITERBI_MAX_STEPS);
+        return fail(QPSK_ERR_ARG, "%s: nrows = %d, nsteps = %d (1..%d)", who, nrows, nsteps, VITERBI_MAX_STEPS);
 #ifdef QPSK_VITERBI_PROFILE
     const int known = QPSK_VITERBI_OPEN_START | QPSK_VITERBI_OPEN_END | VITERBI_PROFILE_FORWARD_ONLY | VITERBI_PROFILE_CYCLES;
 #else
     const int known = QPSK_VITERBI_OPEN_START | QPSK_VITERBI_OPEN_END;
 #endif
-    if (flags & ~known) return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: unknown flags 0x%x", flags);
-    if (row_pitch == 0) row_pitch = nsteps;
-    if (row_pitch < nsteps) return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: row_pitch = %lld (0, or >= nsteps %d)", row_pitch, nsteps);
-    if ((uintptr_t)d_soft % 2) return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: d_soft is not 2-byte aligned");
-    if ((uintptr_t)d_info % 4) return fail(QPSK_ERR_ARG, "qpsk_viterbi_batch: d_info is not 4-byte aligned");
+    if (flags & ~known) return fail(QPSK_ERR_ARG, "%s: unknown flags 0x%x", who, flags);
+    const long long nrow = punct ? (punct_nsent(*punct, nsteps) + 1) / 2 : nsteps;      /* the dibits of a row */
+    if (row_pitch == 0) row_pitch = nrow;
+    if (row_pitch < nrow) return fail(QPSK_ERR_ARG, "%s: row_pitch = %lld (0, or >= %s %lld)", who, row_pitch, punct ? "ntx" : "nsteps", nrow);
+    if ((uintptr_t)d_soft % 2) return fail(QPSK_ERR_ARG, "%s: d_soft is not 2-byte aligned", who);
+    if ((uintptr_t)d_info % 4) return fail(QPSK_ERR_ARG, "%s: d_info is not 4-byte aligned", who);
     static_assert(QPSK_VITERBI_OPEN_START == VITERBI_OPEN_START && QPSK_VITERBI_OPEN_END == VITERBI_OPEN_END, "the kernel takes the header's flag values");
     if (bind(c)) return QPSK_ERR_HIP;
     const size_t per_row = viterbi_scratch_bytes_per_row(nsteps);
@@ -1392,18 +1453,19 @@ int qpsk_viterbi_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pitch, i
     const bool lds = fits && tuned(c->tune.viterbi_lds, resident ? 1 : 0) != 0;
     const size_t nbytes = ((size_t)nsteps + 7) / 8;
     if (lds) {
-        KERNEL_TRY(launch_viterbi(d_soft, (size_t)row_pitch, nrows, nsteps, d_flip, flags, nullptr, true, d_bits, d_info, c->stream));
-        c->last_kernel = "viterbi_lds_kernel";
+        KERNEL_TRY(launch_viterbi(d_soft, (size_t)row_pitch, nrows, nsteps, punct, d_flip, flags, nullptr, true, d_bits, d_info, c->stream));
+        c->last_kernel = punct ? "viterbi_punct_lds_kernel" : "viterbi_lds_kernel";
         return QPSK_OK;
     }
     const size_t chunk_rows = std::min<size_t>((size_t)nrows, std::max<size_t>(1, VITERBI_SCRATCH_MAX / per_row));
     if (int rg = ensure(c, c->vitdec, chunk_rows * per_row)) return rg;
     for (size_t r0 = 0; r0 < (size_t)nrows; r0 += chunk_rows) {      /* stream order: a chunk's trace-back is over before the next one's forward pass */
         const int n = (int)std::min<size_t>(chunk_rows, (size_t)nrows - r0);
-        KERNEL_TRY(launch_viterbi(d_soft + 2 * r0 * (size_t)row_pitch, (size_t)row_pitch, n, nsteps, d_flip, flags, (unsigned long long *)c->vitdec.p,
-                                  false, d_bits ? d_bits + r0 * nbytes : nullptr, d_info ? d_info + 4 * r0 : nullptr, c->stream));
+        KERNEL_TRY(launch_viterbi(d_soft + 2 * r0 * (size_t)row_pitch, (size_t)row_pitch, n, nsteps, punct, d_flip, flags,
+                                  (unsigned long long *)c->vitdec.p, false, d_bits ? d_bits + r0 * nbytes : nullptr, d_info ? d_info + 4 * r0 : nullptr,
+                                  c->stream));
     }
-    c->last_kernel = "viterbi_kernel";
+    c->last_kernel = punct ? "viterbi_punct_kernel" : "viterbi_kernel";
     return QPSK_OK;
 }
 
@@ -2021,7 +2083,7 @@ static const int DFC_ADV_OFFSET = (DEFRAME_CODED_MAX_STEPS + 15) & ~15;      /* 
 
 /* both resets: who = the entry point's name; coded: the body is 8 (nbytes + 2) + 6 coded dibits held as int8 pairs */
 static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes,
-                               int max_packets, bool coded, int mode, float scale);
+                               int max_packets, bool coded, int mode, float scale, const Puncture *punct = nullptr);
 
 int qpsk_deframer_reset(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets)
 {
@@ -2034,8 +2096,19 @@ int qpsk_deframer_reset_coded(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, 
     return deframer_reset_impl(c, "qpsk_deframer_reset_coded", nstreams, h_sync, nsync, min_score, nbytes, max_packets, true, mode, scale);
 }
 
+/* the coded mode behind a puncturing pattern: the body is the ntx(8 (nbytes + 2) + 6) transmitted dibits; the pattern lives in the
+ * deframer's state, and qpsk_deframer_push_coded decodes with the punctured kernels */
+int qpsk_deframer_reset_coded_punct(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets,
+                                    int mode, float scale, int period, uint32_t keep0, uint32_t keep1)
+{
+    Puncture p;
+    if (!c) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset_coded_punct: null context or sync word");
+    if (int rc = punct_make("qpsk_deframer_reset_coded_punct", period, keep0, keep1, &p)) return rc;
+    return deframer_reset_impl(c, "qpsk_deframer_reset_coded_punct", nstreams, h_sync, nsync, min_score, nbytes, max_packets, true, mode, scale, &p);
+}
+
 static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes,
-                               int max_packets, bool coded, int mode, float scale)
+                               int max_packets, bool coded, int mode, float scale, const Puncture *punct)
 {
     if (!c || !h_sync) return fail(QPSK_ERR_ARG, "%s: null context or sync word", who);
     if (nstreams <= 0) return fail(QPSK_ERR_ARG, "%s: nstreams = %d", who, nstreams);
@@ -2052,7 +2125,10 @@ static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const
     /* refused until this call has completed */
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_deframer(c);
-    const int nb = nbytes + 2, N = coded ? 8 * nb + 6 : 4 * nb;      /* dibits of a body */
+    const int nb = nbytes + 2, nsteps = 8 * nb + 6;
+    /* dibits of a body: a punctured one is shorter than 8 nb + 6, so the pending buffer and the keystream table's bound hold as they are.
+     * K >= 1 sent bit per period and nsteps > 32 >= period: at least one dibit */
+    const int N = !coded ? 4 * nb : punct ? (int)((punct_nsent(*punct, nsteps) + 1) / 2) : nsteps;
     const size_t stride = (size_t)DEFRAME_PEND_OFFSET + (((size_t)N * (coded ? 2 : 1) + 15) & ~(size_t)15);
     const size_t tab_bytes = coded ? (size_t)DFC_ADV_OFFSET + 2 * (size_t)DEFRAME_MAX_BYTES : (size_t)DF_ADV_OFFSET + 128;
     if (hipMalloc(&c->df_state, stride * (size_t)nstreams) != hipSuccess || hipMalloc(&c->df_tables, tab_bytes) != hipSuccess) {
@@ -2102,7 +2178,10 @@ static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const
     c->df_coded = coded;
     c->df_mode = mode;
     c->df_scale = scale;
-    c->df_nsteps = coded ? N : 0;
+    c->df_nsteps = coded ? nsteps : 0;
+    c->df_nbody = coded ? N : 0;
+    c->df_punct = coded && punct;
+    c->df_pattern = punct ? *punct : Puncture{1, 1u, 1u, 2};
     c->df_ready = true;
     return QPSK_OK;
 }
@@ -2186,16 +2265,16 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
         if (o0 < i1 && i0 < o1) return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: %s overlaps the input", o.name);
     }
     if (bind(c)) return QPSK_ERR_HIP;
-    const int Nc = c->df_nsteps;
+    const int Nc = c->df_nbody, pitch = (Nc + 1) & ~1;      /* the staging rows go by what is on air, the decision words by the steps */
     const int per = std::min<long long>(c->df_max_packets, (long long)nsym / (c->df_nsync + Nc) + 1);
     const size_t rows = S * (size_t)per;
     const bool decode = d_bytes || d_crc_ok || d_info;
-    const size_t per_row = viterbi_scratch_bytes_per_row(Nc);
+    const size_t per_row = viterbi_scratch_bytes_per_row(c->df_nsteps);
     const bool fits = per_row <= (size_t)VITERBI_LDS_MAX_BYTES;
     const bool resident = fits && rows <= (size_t)c->ncu * (((size_t)160 << 10) / per_row);
     const bool lds = fits && tuned(c->tune.viterbi_lds, resident ? 1 : 0) != 0;
     const size_t chunk_rows = std::min<size_t>(rows, std::max<size_t>(1, VITERBI_SCRATCH_MAX / per_row));
-    if (int rg = ensure(c, c->dfstage, rows * 2 * (size_t)Nc)) return rg;
+    if (int rg = ensure(c, c->dfstage, rows * 2 * (size_t)pitch)) return rg;
     if (!d_gain)
         if (int rg = ensure(c, c->softgain, sizeof(float) * S)) return rg;
     if (decode && !lds)
@@ -2211,7 +2290,7 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
     a.min_score = c->df_min_score;
     a.nbytes = c->df_nbytes;
     a.max_packets = c->df_max_packets;
-    a.nsteps = Nc;
+    a.nsteps = c->df_nsteps;
     a.per_stream = per;
     a.state = c->df_state;
     a.state_stride = c->df_stride;
@@ -2232,15 +2311,19 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
     if (!d_gain)      /* nothing of the deframer's has run yet: a failure here leaves its state as it was */
         KERNEL_TRY(launch_soft_sums(d_costas, (size_t)nsym, c->df_nstreams, nsym, 0, c->df_mode, c->df_scale, (float *)c->softgain.p, nullptr, nullptr,
                                     c->d_status, c->stream));
-    int e = launch_deframe_coded_hunt(a, c->stream);
+    const DeframeCodedBody body = {Nc, pitch, c->df_punct ? 1 : 0, c->df_pattern};
+    int e = launch_deframe_coded_hunt(a, body, c->stream);
     for (size_t r0 = 0; e == 0 && decode && r0 < rows; r0 += chunk_rows)      /* stream order: a chunk's trace-back is over before the next one's forward pass */
-        e = launch_deframe_coded_decode(a, (int)r0, (int)std::min<size_t>(chunk_rows, rows - r0), lds ? nullptr : (unsigned long long *)c->vitdec.p, lds, c->stream);
+        e = launch_deframe_coded_decode(a, body, (int)r0, (int)std::min<size_t>(chunk_rows, rows - r0), lds ? nullptr : (unsigned long long *)c->vitdec.p, lds, c->stream);
     if (e != 0) {
         c->df_ready = false;
         return fail(QPSK_ERR_HIP, "qpsk_deframer_push_coded launch: %s", hipGetErrorString((hipError_t)e));
     }
-    c->last_kernel = !decode ? "deframe_coded_hunt_kernel" : lds ? "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<lds>"
-                                                                 : "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<global>";
+    c->last_kernel = !decode       ? "deframe_coded_hunt_kernel"
+                     : c->df_punct ? (lds ? "deframe_coded_hunt_kernel + deframe_coded_decode_punct_kernel<lds>"
+                                          : "deframe_coded_hunt_kernel + deframe_coded_decode_punct_kernel<global>")
+                     : lds         ? "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<lds>"
+                                   : "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<global>";
     return QPSK_OK;
 }
 

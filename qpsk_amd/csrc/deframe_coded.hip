@@ -4,8 +4,8 @@
  * packets the hunt completes.
  *
  *   deframe_coded_hunt_kernel     one wave per stream, deframe_kernel's structure line for line (X, the bit planes, the wave-uniform walk
- *                                 over the candidate masks, the carried tail: see deframe.hip).  The body of a packet is Nc = 8 (nbytes + 2) + 6
- *                                 coded dibits; the lanes quantise the body symbols that lie in this push's row (soft_quant.h: the turn by
+ *                                 over the candidate masks, the carried tail: see deframe.hip).  The body of a packet is Nc = nbody dibits
+ *                                 (8 (nbytes + 2) + 6 at rate 1/2, fewer behind a puncturing pattern: the hunt only takes the number); the lanes quantise the body symbols that lie in this push's row (soft_quant.h: the turn by
  *                                 the packet's rotation and q(x) of qpsk_soft_batch, with this push's gain) lane-parallel, 8-byte loads and
  *                                 2-byte stores, into the packet's soft row.  An incomplete packet's row is the stream's pending buffer
  *                                 (int8 pairs: no float history is carried, every body symbol arrives in the push that completes the
@@ -20,7 +20,11 @@
  *
  * A staging row is addressed by (stream, slot), the packet's place in the outputs, so there is no list to append to and no atomic:
  * per_stream = min(max_packets, nsym / (nsync + Nc) + 1) bounds what one push can complete in a stream (packet ends lie nsync + Nc
- * apart), and the decode grid covers nstreams * per_stream rows.  Vector stores only.
+ * apart), and the decode grid covers nstreams * per_stream rows.  Staging rows lie stage_pitch = Nc rounded up to even dibits apart, so
+ * that copy_pairs' 4-byte accesses stay aligned when a punctured Nc is odd.  Vector stores only.
+ *
+ *   deframe_coded_decode_punct_kernel   (qpsk_deframer_reset_coded_punct) the same decode with viterbi_row.h's PunctLoader on the Nc staged
+ *                                 dibits: nsteps = 8 (nbytes + 2) + 6 trellis steps, the keystream flips the transmitted dibits.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -78,12 +82,12 @@ __device__ __forceinline__ void report(const DeframeCodedArgs &a, int stream, in
 }
 
 __global__ void __launch_bounds__(64 * DC_WAVES)
-deframe_coded_hunt_kernel(DeframeCodedArgs a)
+deframe_coded_hunt_kernel(DeframeCodedArgs a, int nbody, int stage_pitch)
 {
     const int lane = threadIdx.x & 63;
     const int stream = blockIdx.x * DC_WAVES + (int)(threadIdx.x >> 6);
     if (stream >= a.nstreams) return;
-    const int n = a.nsync, N = a.nsteps;
+    const int n = a.nsync, N = nbody;
     const long long nsym = a.nsym;
     const float2 *row = a.costas + (size_t)stream * (size_t)nsym;
     uint8_t *st = a.state + (size_t)stream * a.state_stride;
@@ -106,7 +110,7 @@ deframe_coded_hunt_kernel(DeframeCodedArgs a)
         const int need = N - have;
         if (nsym >= need) {
             if (count < a.per_stream) {
-                int8_t *dst = a.stage + 2 * ((size_t)stream * a.per_stream + count) * (size_t)N;
+                int8_t *dst = a.stage + 2 * ((size_t)stream * a.per_stream + count) * (size_t)stage_pitch;
                 copy_pairs(pend, have, dst, lane);
                 bad |= quantise_body(row, need, prot, g, dst + 2 * (size_t)have, lane);
                 report(a, stream, count, ppos, prot, pscore, lane);
@@ -189,7 +193,7 @@ deframe_coded_hunt_kernel(DeframeCodedArgs a)
                 break;
             }
             if (count < a.per_stream) {                                  /* row0 + N <= nsym: the whole body lies in the row */
-                int8_t *dst = a.stage + 2 * ((size_t)stream * a.per_stream + count) * (size_t)N;
+                int8_t *dst = a.stage + 2 * ((size_t)stream * a.per_stream + count) * (size_t)stage_pitch;
                 bad |= quantise_body(row + row0, N, pk & 3, g, dst, lane);
                 report(a, stream, count, base0 + px, pk & 3, pk >> 2, lane);
             }
@@ -246,6 +250,7 @@ struct PacketSink {
     }
 };
 
+/* rate 1/2: the staged row is [nsteps] pairs (stage_pitch = nbody = nsteps, even) */
 template <bool LDS>
 __global__ void __launch_bounds__(64)
 deframe_coded_decode_kernel(DeframeCodedArgs a, int row0, unsigned long long *scratch)
@@ -257,8 +262,30 @@ deframe_coded_decode_kernel(DeframeCodedArgs a, int row0, unsigned long long *sc
     const size_t r = (size_t)stream * a.max_packets + slot;
     const size_t nblk = ((size_t)a.nsteps + 63) >> 6;
     PacketSink sink = {a.bytes ? a.bytes + r * (size_t)(a.nbytes + 2) : nullptr, a.crc_adv, a.nbytes, 0u};
-    viterbi_row<LDS>(a.stage + 2 * (size_t)e * (size_t)a.nsteps, a.flip, a.nsteps, 0, LDS ? nullptr : scratch + (size_t)blockIdx.x * (nblk << 6),
-                     a.info ? a.info + 4 * r : nullptr, sink);
+    const PairLoader ld = {a.stage + 2 * (size_t)e * (size_t)a.nsteps, a.flip};
+    viterbi_row<LDS>(ld, a.nsteps, 0, LDS ? nullptr : scratch + (size_t)blockIdx.x * (nblk << 6), a.info ? a.info + 4 * r : nullptr, sink);
+    unsigned share = sink.share;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) share ^= (unsigned)__shfl_xor((int)share, o, 64);
+    if (lane == 0 && a.crc_ok) a.crc_ok[r] = (uint8_t)(((share & 0xFFFFu) ^ a.crc_init) == (share >> 16));
+}
+
+/* behind a pattern: the staged row holds the nbody transmitted dibits.  The same lines with the other loader, written out a second time
+ * and not shared through a function: routed through one, the rate-1/2 kernels above come out with two more scalar registers than
+ * DESIGN.md 4.4.7 records, and they are not to move */
+template <bool LDS>
+__global__ void __launch_bounds__(64)
+deframe_coded_decode_punct_kernel(DeframeCodedArgs a, int row0, unsigned long long *scratch, DeframeCodedBody b)
+{
+    const int lane = threadIdx.x;
+    const int e = row0 + (int)blockIdx.x;
+    const int stream = e / a.per_stream, slot = e - stream * a.per_stream;
+    if (slot >= a.count[stream]) return;                                 /* per_stream <= max_packets */
+    const size_t r = (size_t)stream * a.max_packets + slot;
+    const size_t nblk = ((size_t)a.nsteps + 63) >> 6;
+    PacketSink sink = {a.bytes ? a.bytes + r * (size_t)(a.nbytes + 2) : nullptr, a.crc_adv, a.nbytes, 0u};
+    const PunctLoader ld = {a.stage + 2 * (size_t)e * (size_t)b.stage_pitch, a.flip, b.punct};
+    viterbi_row<LDS>(ld, a.nsteps, 0, LDS ? nullptr : scratch + (size_t)blockIdx.x * (nblk << 6), a.info ? a.info + 4 * r : nullptr, sink);
     unsigned share = sink.share;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) share ^= (unsigned)__shfl_xor((int)share, o, 64);
@@ -267,22 +294,30 @@ deframe_coded_decode_kernel(DeframeCodedArgs a, int row0, unsigned long long *sc
 
 } // namespace
 
-int launch_deframe_coded_hunt(const DeframeCodedArgs &a, hipStream_t s)
+int launch_deframe_coded_hunt(const DeframeCodedArgs &a, const DeframeCodedBody &b, hipStream_t s)
 {
-    if (a.nstreams <= 0 || a.nsym <= 0 || a.per_stream < 1 || a.per_stream > a.max_packets || !a.costas || !a.gain || !a.stage || !a.count)
+    if (a.nstreams <= 0 || a.nsym <= 0 || a.per_stream < 1 || a.per_stream > a.max_packets || !a.costas || !a.gain || !a.stage || !a.count ||
+        b.nbody < 1 || b.stage_pitch < b.nbody || (b.stage_pitch & 1))
         return (int)hipErrorInvalidValue;
     const dim3 grid((a.nstreams + DC_WAVES - 1) / DC_WAVES), block(64 * DC_WAVES);
-    hipLaunchKernelGGL(deframe_coded_hunt_kernel, grid, block, 0, s, a);
+    hipLaunchKernelGGL(deframe_coded_hunt_kernel, grid, block, 0, s, a, b.nbody, b.stage_pitch);
     return (int)hipGetLastError();
 }
 
-int launch_deframe_coded_decode(const DeframeCodedArgs &a, int row0, int nrows, unsigned long long *scratch, bool lds, hipStream_t s)
+int launch_deframe_coded_decode(const DeframeCodedArgs &a, const DeframeCodedBody &b, int row0, int nrows, unsigned long long *scratch, bool lds,
+                                hipStream_t s)
 {
     if (row0 < 0 || nrows <= 0 || (long long)row0 + nrows > (long long)a.nstreams * a.per_stream || !a.stage || !a.count || !a.flip || !a.crc_adv)
         return (int)hipErrorInvalidValue;
+    if (b.punctured ? b.punct.period < 1 || b.punct.period > 32 || b.punct.K < 1 || 2LL * b.nbody < punct_nsent(b.punct, a.nsteps) || b.stage_pitch < b.nbody
+                    : b.nbody != a.nsteps || b.stage_pitch != a.nsteps)
+        return (int)hipErrorInvalidValue;
     const size_t bytes = viterbi_scratch_bytes_per_row(a.nsteps);
     if (lds ? bytes > (size_t)VITERBI_LDS_MAX_BYTES : !scratch) return (int)hipErrorInvalidValue;
-    if (lds) hipLaunchKernelGGL(deframe_coded_decode_kernel<true>, dim3(nrows), dim3(64), bytes, s, a, row0, scratch);
+    if (b.punctured) {
+        if (lds) hipLaunchKernelGGL(deframe_coded_decode_punct_kernel<true>, dim3(nrows), dim3(64), bytes, s, a, row0, scratch, b);
+        else hipLaunchKernelGGL(deframe_coded_decode_punct_kernel<false>, dim3(nrows), dim3(64), 0, s, a, row0, scratch, b);
+    } else if (lds) hipLaunchKernelGGL(deframe_coded_decode_kernel<true>, dim3(nrows), dim3(64), bytes, s, a, row0, scratch);
     else hipLaunchKernelGGL(deframe_coded_decode_kernel<false>, dim3(nrows), dim3(64), 0, s, a, row0, scratch);
     return (int)hipGetLastError();
 }

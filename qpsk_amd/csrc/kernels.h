@@ -251,9 +251,26 @@ constexpr int VITERBI_MAX_STEPS = 131072;
 constexpr int VITERBI_LDS_MAX_BYTES = 65536;
 constexpr int VITERBI_OPEN_START = 1, VITERBI_OPEN_END = 2, VITERBI_PROFILE_FORWARD_ONLY = 0x100, VITERBI_PROFILE_CYCLES = 0x200;
 size_t viterbi_scratch_bytes_per_row(int nsteps);
-int launch_viterbi(const int8_t *soft, size_t pitch, int nrows, int nsteps, const uint8_t *flip, int flags, unsigned long long *scratch,
-                   bool lds, uint8_t *bits, int32_t *info, hipStream_t s);
+/* a pattern of PUNCTURING (include/qpsk_hip.h), checked by the host (api.cpp, punct_make): 1 <= period <= 32, no mask bit at or above
+ * period, K = popc(keep0) + popc(keep1) > 0 = the sent bits of a period */
+struct Puncture {
+    int period;
+    unsigned keep0, keep1;
+    int K;
+};
+/* the sent bits of nsteps steps: idx(nsteps, 0) */
+inline long long punct_nsent(const Puncture &p, int nsteps)
+{
+    const unsigned r = (unsigned)(nsteps % p.period), low = (1u << r) - 1u;
+    return (long long)(nsteps / p.period) * p.K + __builtin_popcount(p.keep0 & low) + __builtin_popcount(p.keep1 & low);
+}
+/* punct = NULL: rate 1/2, pitch in steps, flip [nsteps].  Otherwise the punctured kernels (viterbi_punct_kernel, viterbi_punct_lds_kernel):
+ * pitch in transmitted dibits, flip [ntx]; the residency rule goes by nsteps either way */
+int launch_viterbi(const int8_t *soft, size_t pitch, int nrows, int nsteps, const Puncture *punct, const uint8_t *flip, int flags,
+                   unsigned long long *scratch, bool lds, uint8_t *bits, int32_t *info, hipStream_t s);
 int launch_conv_encode(const uint8_t *bits, int nrows, int nbits, int nsteps, uint8_t *dibits, hipStream_t s);
+/* conv_encode_punct_kernel: one thread per transmitted dibit, dibits [nrows][ntx], ntx = ceil(punct_nsent / 2) >= 1 */
+int launch_conv_encode_punct(const uint8_t *bits, int nrows, int nbits, int nsteps, const Puncture &punct, uint8_t *dibits, hipStream_t s);
 /* deframe.hip: qpsk_deframer_push.  Per stream, state_stride bytes of state: the header, the carried tail (the ring values of the last
  * min(len, nsync-1) dibits) at DEFRAME_TAIL_OFFSET, the pending packet's received payload (ring values) at DEFRAME_PEND_OFFSET */
 struct DeframeHeader {
@@ -283,7 +300,7 @@ struct DeframeArgs {
 };
 int launch_deframe(const DeframeArgs &a, hipStream_t s);
 /* deframe_coded.hip: qpsk_deframer_push_coded.  The same per-stream state, with the pending packet's received body as int8 soft pairs
- * (2 nsteps bytes) at DEFRAME_PEND_OFFSET.  Two launches: the hunt, which quantises the body symbols of this push and leaves every
+ * (2 nbody bytes) at DEFRAME_PEND_OFFSET.  Two launches: the hunt, which quantises the body symbols of this push and leaves every
  * packet it completes as a soft row in the staging buffer -- row stream * per_stream + slot, slot = the packet's output row -- and the
  * decode, one wave per staging row (rows at or beyond the stream's count retire at once) */
 constexpr int DEFRAME_CODED_MAX_STEPS = 8 * (DEFRAME_MAX_BYTES + 2) + 6;
@@ -293,13 +310,13 @@ struct DeframeCodedArgs {
     int check_gain;               /* the gains are the caller's: flag a NaN / Inf one */
     int nstreams, nsym;
     int nsync, min_score, nbytes, max_packets;
-    int nsteps;                   /* Nc = 8 (nbytes + 2) + 6 */
-    int per_stream;               /* staging rows per stream: min(max_packets, nsym / (nsync + nsteps) + 1), the most a push completes */
+    int nsteps;                   /* trellis steps of a packet: 8 (nbytes + 2) + 6 */
+    int per_stream;               /* staging rows per stream: min(max_packets, nsym / (nsync + Nc) + 1), the most a push completes */
     uint8_t *state;
     size_t state_stride;
     unsigned long long sync_lo[2], sync_hi[2];
-    int8_t *stage;                /* [nstreams * per_stream][nsteps][2] */
-    const uint8_t *flip;          /* [nsteps]: the scrambler's keystream dibits */
+    int8_t *stage;                /* [nstreams * per_stream][stage_pitch][2] (DeframeCodedBody) */
+    const uint8_t *flip;          /* [nbody]: the scrambler's keystream dibits, over the body on air */
     const uint16_t *crc_adv;      /* [nbytes]: x^(8 m) mod the CRC-16 polynomial */
     unsigned crc_init;            /* crc16()'s register after nbytes zero bytes from 0xFFFF */
     int32_t *count;
@@ -310,10 +327,18 @@ struct DeframeCodedArgs {
     int32_t *info;
     int *status;
 };
-int launch_deframe_coded_hunt(const DeframeCodedArgs &a, hipStream_t s);
+/* what a puncturing pattern adds, a kernel argument of its own so that the rate-1/2 decode kernels keep their arguments as they were */
+struct DeframeCodedBody {
+    int nbody;                    /* Nc, the dibits of a body on air: nsteps at rate 1/2, ntx(nsteps) of the pattern otherwise */
+    int stage_pitch;              /* dibits between staging rows: nbody rounded up to even, so that every row is 4-byte aligned */
+    int punctured;                /* qpsk_deframer_reset_coded_punct: the decode takes the punctured loader with punct */
+    Puncture punct;
+};
+int launch_deframe_coded_hunt(const DeframeCodedArgs &a, const DeframeCodedBody &b, hipStream_t s);
 /* rows [row0, row0 + nrows) of the staging buffer; lds: the decision words in LDS (viterbi_scratch_bytes_per_row(nsteps) <=
  * VITERBI_LDS_MAX_BYTES), otherwise in scratch ([nrows] rows of that many bytes) */
-int launch_deframe_coded_decode(const DeframeCodedArgs &a, int row0, int nrows, unsigned long long *scratch, bool lds, hipStream_t s);
+int launch_deframe_coded_decode(const DeframeCodedArgs &a, const DeframeCodedBody &b, int row0, int nrows, unsigned long long *scratch, bool lds,
+                                hipStream_t s);
 /* txchain.hip */
 int tx_history_symbols(void);          /* symbols of state per transmitter (uint8 each, 4 = none yet) */
 int launch_tx_shape(const uint8_t *sym, uint8_t *hist, const float *taps, float *sig, int nstreams, int nsym,

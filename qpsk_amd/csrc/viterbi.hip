@@ -27,6 +27,14 @@
  * The row's passes themselves live in viterbi_row.h, which deframe_coded.hip runs on the packets of a stream as well.
  *
  * conv_encode_kernel: one thread per coded dibit; a plain kernel so that a loopback stays on the device.
+ *
+ * PUNCTURED RATES (qpsk_viterbi_punct_batch, qpsk_conv_encode_punct_batch; PUNCTURING in include/qpsk_hip.h, restated by
+ * tests/test_punct_cpu.py).  A punctured decode IS the decode of the zero-filled row, and a zero is an erasure the passes above need no
+ * special case for, so viterbi_punct_kernel / viterbi_punct_lds_kernel are the same two kernels behind viterbi_row.h's PunctLoader: the
+ * lane that loaded the pair of step 64 k + l now works out where the (up to) two sent bits of that step lie in the transmitted row -- one
+ * division by the period and two popcounts per lane and 64 steps -- and loads them, and their flip bits, bytewise; unsent bits are 0.
+ * That happens where the load sat, lane-parallel and a block ahead; the per-step chain is untouched.  conv_encode_punct_kernel: one
+ * thread per transmitted dibit, its two sent bits mapped back to (step, generator) through a table of the period's K <= 64 sent bits.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,27 +48,37 @@ namespace {
 
 struct VitArgs {
     const int8_t *soft;
-    size_t pitch;                 /* steps between rows */
+    size_t pitch;                 /* dibits between rows: steps at rate 1/2, transmitted dibits behind a pattern */
     int nsteps, flags;
     const uint8_t *flip;
     unsigned long long *scratch;  /* [rows][nblk * 64] decision words (global route) */
     uint8_t *bits;
     int32_t *info;
+    Puncture punct;               /* the punctured kernels only */
 };
 
-/* workgroup = wave = row blockIdx.x of the call (viterbi_row.h) */
-template <bool LDS>
+/* workgroup = wave = row blockIdx.x of the call (viterbi_row.h); PUNCT: the row is what was transmitted and PunctLoader finds the steps in it */
+template <bool LDS, bool PUNCT>
 __device__ __forceinline__ void viterbi_batch_row(const VitArgs &a)
 {
     const size_t row = blockIdx.x;
     const size_t nblk = ((size_t)a.nsteps + 63) >> 6;
     BitsSink sink = {a.bits ? a.bits + row * (((size_t)a.nsteps + 7) >> 3) : nullptr};
-    viterbi_row<LDS>(a.soft + 2 * row * a.pitch, a.flip, a.nsteps, a.flags, LDS ? nullptr : a.scratch + row * (nblk << 6),
-                     a.info ? a.info + 4 * row : nullptr, sink);
+    unsigned long long *gdec = LDS ? nullptr : a.scratch + row * (nblk << 6);
+    int32_t *info = a.info ? a.info + 4 * row : nullptr;
+    if (PUNCT) {
+        const PunctLoader ld = {a.soft + 2 * row * a.pitch, a.flip, a.punct};
+        viterbi_row<LDS>(ld, a.nsteps, a.flags, gdec, info, sink);
+    } else {
+        const PairLoader ld = {a.soft + 2 * row * a.pitch, a.flip};
+        viterbi_row<LDS>(ld, a.nsteps, a.flags, gdec, info, sink);
+    }
 }
 
-__global__ void __launch_bounds__(64) viterbi_kernel(VitArgs a) { viterbi_batch_row<false>(a); }
-__global__ void __launch_bounds__(64) viterbi_lds_kernel(VitArgs a) { viterbi_batch_row<true>(a); }
+__global__ void __launch_bounds__(64) viterbi_kernel(VitArgs a) { viterbi_batch_row<false, false>(a); }
+__global__ void __launch_bounds__(64) viterbi_lds_kernel(VitArgs a) { viterbi_batch_row<true, false>(a); }
+__global__ void __launch_bounds__(64) viterbi_punct_kernel(VitArgs a) { viterbi_batch_row<false, true>(a); }
+__global__ void __launch_bounds__(64) viterbi_punct_lds_kernel(VitArgs a) { viterbi_batch_row<true, true>(a); }
 
 /* one thread per coded dibit: register r of step t = bits t-6 .. t (bit t in bit 0), zeros before the row and in the tail */
 __global__ void __launch_bounds__(256)
@@ -80,19 +98,54 @@ conv_encode_kernel(const uint8_t *__restrict__ in, size_t nrows, int nbits, int 
     out[i] = (uint8_t)(parity(r & 0x79u) | (parity(r & 0x5Bu) << 1));
 }
 
+/* sent bit m of a period -> its step within the period (bits 0..4) and which coded bit it is (bit 5): built by the host, passed by value */
+struct PunctTable {
+    uint8_t e[64];
+};
+
+/* one thread per transmitted dibit: sent bits 2 d and 2 d + 1 of the row, each mapped back to (t, j) through the table and encoded as
+ * conv_encode_kernel does; a sent bit at or beyond nsent -- the pad bit of an odd nsent -- is 0 */
+__global__ void __launch_bounds__(256)
+conv_encode_punct_kernel(const uint8_t *__restrict__ in, size_t nrows, int nbits, unsigned nsent, unsigned ntx, int period, int K, PunctTable tab,
+                         uint8_t *__restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nrows * (size_t)ntx) return;
+    const size_t row = i / ntx;
+    const unsigned d = (unsigned)(i - row * ntx);
+    const uint8_t *src = in + row * (size_t)((nbits + 7) >> 3);
+    unsigned dibit = 0;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const unsigned k = 2 * d + h;
+        if (k >= nsent) continue;
+        const unsigned q = k / (unsigned)K, e = tab.e[k - q * (unsigned)K];
+        const int t = (int)(q * (unsigned)period + (e & 31u));
+        unsigned r = 0;
+#pragma unroll
+        for (int b = 0; b < 7; b++) {
+            const int p = t - b;
+            if (p >= 0 && p < nbits) r |= ((unsigned)(src[p >> 3] >> (p & 7)) & 1u) << b;
+        }
+        dibit |= (unsigned)parity(r & ((e & 32u) ? 0x5Bu : 0x79u)) << h;
+    }
+    out[i] = (uint8_t)dibit;
+}
+
 } // namespace
 
 size_t viterbi_scratch_bytes_per_row(int nsteps) { return sizeof(unsigned long long) * (((size_t)nsteps + 63) & ~(size_t)63); }
 
-int launch_viterbi(const int8_t *soft, size_t pitch, int nrows, int nsteps, const uint8_t *flip, int flags, unsigned long long *scratch,
-                   bool lds, uint8_t *bits, int32_t *info, hipStream_t s)
+int launch_viterbi(const int8_t *soft, size_t pitch, int nrows, int nsteps, const Puncture *punct, const uint8_t *flip, int flags,
+                   unsigned long long *scratch, bool lds, uint8_t *bits, int32_t *info, hipStream_t s)
 {
     if (nrows <= 0 || nsteps <= 0 || nsteps > VITERBI_MAX_STEPS || !soft || (!bits && !info)) return (int)hipErrorInvalidValue;
+    if (punct && (punct->period < 1 || punct->period > 32 || punct->K < 1)) return (int)hipErrorInvalidValue;
     const size_t bytes = viterbi_scratch_bytes_per_row(nsteps);
     if (lds ? bytes > (size_t)VITERBI_LDS_MAX_BYTES : !scratch) return (int)hipErrorInvalidValue;
-    const VitArgs a = {soft, pitch, nsteps, flags, flip, scratch, bits, info};
-    if (lds) hipLaunchKernelGGL(viterbi_lds_kernel, dim3(nrows), dim3(64), bytes, s, a);
-    else hipLaunchKernelGGL(viterbi_kernel, dim3(nrows), dim3(64), 0, s, a);
+    const VitArgs a = {soft, pitch, nsteps, flags, flip, scratch, bits, info, punct ? *punct : Puncture{1, 1u, 1u, 2}};
+    if (lds) hipLaunchKernelGGL(punct ? viterbi_punct_lds_kernel : viterbi_lds_kernel, dim3(nrows), dim3(64), bytes, s, a);
+    else hipLaunchKernelGGL(punct ? viterbi_punct_kernel : viterbi_kernel, dim3(nrows), dim3(64), 0, s, a);
     return (int)hipGetLastError();
 }
 
@@ -102,6 +155,25 @@ int launch_conv_encode(const uint8_t *bits, int nrows, int nbits, int nsteps, ui
     const size_t n = (size_t)nrows * (size_t)nsteps;
     if ((n + 255) / 256 > 0x7fffffffull) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(conv_encode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bits, (size_t)nrows, nbits, nsteps, dibits);
+    return (int)hipGetLastError();
+}
+
+int launch_conv_encode_punct(const uint8_t *bits, int nrows, int nbits, int nsteps, const Puncture &p, uint8_t *dibits, hipStream_t s)
+{
+    if (nrows <= 0 || nbits <= 0 || nsteps < nbits || !bits || !dibits || p.period < 1 || p.period > 32 || p.K < 1 || p.K > 64)
+        return (int)hipErrorInvalidValue;
+    const long long nsent = punct_nsent(p, nsteps), ntx = (nsent + 1) / 2;
+    if (ntx < 1) return (int)hipErrorInvalidValue;
+    PunctTable tab = {};
+    int m = 0;
+    for (int r = 0; r < p.period; r++)
+        for (int j = 0; j < 2; j++)
+            if (((j ? p.keep1 : p.keep0) >> r) & 1u) tab.e[m++] = (uint8_t)(r | (j << 5));
+    if (m != p.K) return (int)hipErrorInvalidValue;
+    const size_t n = (size_t)nrows * (size_t)ntx;
+    if ((n + 255) / 256 > 0x7fffffffull) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(conv_encode_punct_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bits, (size_t)nrows, nbits, (unsigned)nsent,
+                       (unsigned)ntx, p.period, p.K, tab, dibits);
     return (int)hipGetLastError();
 }
 

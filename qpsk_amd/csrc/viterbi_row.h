@@ -1,7 +1,8 @@
 /*
  * viterbi_row.h -- one row of the K = 7, rate-1/2 Viterbi decoder by ONE WAVE (lane = new state): the forward pass, the trace-back and
  * the channel error count of qpsk_viterbi_batch (include/qpsk_hip.h), shared by viterbi.hip (rows of a caller's batch) and
- * deframe_coded.hip (the staged soft rows of packets found in a stream).  viterbi.hip's header describes the passes.
+ * deframe_coded.hip (the staged soft rows of packets found in a stream).  viterbi.hip's header describes the passes.  A punctured
+ * rate (qpsk_viterbi_punct_batch) is the same passes behind another LOADER of the soft pairs.
  *
  * The caller's kernel runs workgroups of exactly one wave (64 threads) and hands the row over as plain pointers; what happens to the
  * decoded bits is the caller's too: the trace-back gives every block of 64 steps to a SINK,
@@ -41,15 +42,55 @@ __device__ __forceinline__ void load_soft(const int8_t *__restrict__ row, const 
     }
 }
 
+/* LOADERS: where a step's soft pair lies is the only thing a punctured code changes, so the row's passes take it as a policy:
+ *     ld.load(t0, nsteps, lane, s0, s1)     lane `lane`: the pair of step t0 + lane after the -128 rule and d_flip; (0, 0) beyond the row
+ * always for 64 steps at once, lane-parallel and a block ahead of the steps that use them: nothing of a loader is in the per-step chain.
+ *
+ * PairLoader: rate 1/2, row = [nsteps][2] int8, flip [nsteps] or NULL */
+struct PairLoader {
+    const int8_t *__restrict__ row;
+    const uint8_t *__restrict__ flip;
+    __device__ __forceinline__ void load(int t0, int nsteps, int lane, int &s0, int &s1) const { load_soft(row, flip, t0, nsteps, lane, s0, s1); }
+};
+
+/* PunctLoader (p: kernels.h): row = the flat int8 of the TRANSMITTED dibits, flip [ntx] over those dibits or NULL.  Sent bit (t, j) is flat number
+ * idx(t, j); a lane works its two numbers out with one division and two popcounts per 64 steps and does byte loads; an unsent bit is 0,
+ * the erasure the decoder needs no special case for.  idx < nsent for every sent bit of a step below nsteps, so the pad bit of an odd
+ * nsent is never read */
+struct PunctLoader {
+    const int8_t *__restrict__ row;
+    const uint8_t *__restrict__ flip;
+    Puncture p;
+    __device__ __forceinline__ void load(int t0, int nsteps, int lane, int &s0, int &s1) const
+    {
+        const int t = t0 + lane;
+        s0 = s1 = 0;
+        if (t < nsteps) {
+            const unsigned q = (unsigned)t / (unsigned)p.period, r = (unsigned)t - q * (unsigned)p.period;
+            const unsigned low = (1u << r) - 1u;
+            const unsigned b0 = (p.keep0 >> r) & 1u, b1 = (p.keep1 >> r) & 1u;
+            const size_t k0 = (size_t)q * (unsigned)p.K + __popc(p.keep0 & low) + __popc(p.keep1 & low), k1 = k0 + b0;
+            if (b0) {
+                s0 = max((int)row[k0], -127);
+                if (flip && ((flip[k0 >> 1] >> (k0 & 1)) & 1u)) s0 = -s0;
+            }
+            if (b1) {
+                s1 = max((int)row[k1], -127);
+                if (flip && ((flip[k1 >> 1] >> (k1 & 1)) & 1u)) s1 = -s1;
+            }
+        }
+    }
+};
+
 /* the channel errors of block blk, lane-parallel: cur / prev = the decoded bits of blocks blk / blk - 1 (bit j = step 64 blk + j).
  * x = bits t-6 .. t of the row with bit t - 6 lowest, so the generators apply bit-reversed: 171 -> 0x4F, 133 -> 0x6D */
-__device__ __forceinline__ int block_errors(const int8_t *__restrict__ row, const uint8_t *__restrict__ flip, int blk, int nsteps, int lane,
-                                            unsigned long long cur, unsigned long long prev)
+template <class Loader>
+__device__ __forceinline__ int block_errors(const Loader &ld, int blk, int nsteps, int lane, unsigned long long cur, unsigned long long prev)
 {
     const unsigned long long lo = (cur << 6) | (prev >> 58), hi = cur >> 58;
     const unsigned x = (unsigned)((lo >> lane) | ((hi << 1) << (63 - lane))) & 127u;
     int s0, s1;
-    load_soft(row, flip, blk << 6, nsteps, lane, s0, s1);
+    ld.load(blk << 6, nsteps, lane, s0, s1);
     return (int)(s0 != 0 && (s0 < 0) != (bool)parity(x & 0x4Fu)) + (int)(s1 != 0 && (s1 < 0) != (bool)parity(x & 0x6Du));
 }
 
@@ -66,10 +107,9 @@ struct BitsSink {
 #define VIT_STAMP(t) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory")
 #endif
 
-/* soft: the row's [nsteps][2] int8; flip [nsteps] or NULL; flags = VITERBI_*; info: this row's four words or NULL (then nothing is counted) */
-template <bool LDS, class Sink>
-__device__ __forceinline__ void viterbi_row(const int8_t *__restrict__ soft, const uint8_t *__restrict__ flip, int nsteps, int flags,
-                                            unsigned long long *gdec, int32_t *info, Sink &sink)
+/* ld: the row's loader (above); flags = VITERBI_*; info: this row's four words or NULL (then nothing is counted) */
+template <bool LDS, class Loader, class Sink>
+__device__ __forceinline__ void viterbi_row(const Loader &ld, int nsteps, int flags, unsigned long long *gdec, int32_t *info, Sink &sink)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned long long ldec[];      /* LDS route: [nblk * 64] decision words */
     const int lane = threadIdx.x;
@@ -85,10 +125,10 @@ __device__ __forceinline__ void viterbi_row(const int8_t *__restrict__ soft, con
     const int from0 = (lane >> 1) << 2, from1 = from0 | 128;      /* byte addresses of lanes ns >> 1 and (ns >> 1) | 32 */
     int pm = ((flags & VITERBI_OPEN_START) || lane == 0) ? 0 : VITERBI_NEG;
     int n0, n1;
-    load_soft(soft, flip, 0, nsteps, lane, n0, n1);
+    ld.load(0, nsteps, lane, n0, n1);
     for (int blk = 0; blk < nblk; blk++) {
         const int s0v = n0, s1v = n1;
-        if (blk + 1 < nblk) load_soft(soft, flip, (blk + 1) << 6, nsteps, lane, n0, n1);      /* a block ahead: no step waits on memory */
+        if (blk + 1 < nblk) ld.load((blk + 1) << 6, nsteps, lane, n0, n1);      /* a block ahead: no step waits on memory */
         const int n = min(64, nsteps - (blk << 6));
         unsigned dh[2] = {0u, 0u};
 #pragma unroll
@@ -151,12 +191,12 @@ __device__ __forceinline__ void viterbi_row(const int8_t *__restrict__ soft, con
             word |= (unsigned long long)wh << (32 * half);
         }
         sink.block(blk, word, n, lane);
-        if (info && blk + 1 < nblk) errs += block_errors(soft, flip, blk + 1, nsteps, lane, later, word);
+        if (info && blk + 1 < nblk) errs += block_errors(ld, blk + 1, nsteps, lane, later, word);
         later = word;
     }
     if (info) {
         /* the six bits before the row are the state the trace-back arrived at (0 unless open start): state bit k = bit -1 - k */
-        errs += block_errors(soft, flip, 0, nsteps, lane, later, (unsigned long long)(__brev((unsigned)st) >> 26) << 58);
+        errs += block_errors(ld, 0, nsteps, lane, later, (unsigned long long)(__brev((unsigned)st) >> 26) << 58);
 #pragma unroll
         for (int h = 32; h >= 1; h >>= 1) errs += __shfl_xor(errs, h, 64);
 #ifdef QPSK_VITERBI_PROFILE

@@ -59,7 +59,20 @@ API_SYMBOLS = [
     "qpsk_rx_batch_data", "qpsk_sync_batch", "qpsk_multi_set_data", "qpsk_deframer_reset", "qpsk_deframer_push",
     "qpsk_deframer_reset_coded", "qpsk_deframer_push_coded",
     "qpsk_soft_batch", "qpsk_conv_encode_batch", "qpsk_viterbi_batch",
+    "qpsk_punct_ntx", "qpsk_conv_encode_punct_batch", "qpsk_viterbi_punct_batch", "qpsk_deframer_reset_coded_punct",
 ]
+# the named puncturing patterns of include/qpsk_hip.h (QPSK_PUNCT_*): rate -> (period, keep0, keep1), bit r of a mask = step r of the period
+PUNCTURE = {"1/2": (1, 0x1, 0x1), "2/3": (2, 0x1, 0x3), "3/4": (3, 0x5, 0x3), "5/6": (5, 0x15, 0x0B), "7/8": (7, 0x51, 0x2F)}
+
+
+def _pattern(puncture):
+    """a key of PUNCTURE or a (period, keep0, keep1) tuple -> the three ints (the library checks them)"""
+    if isinstance(puncture, str):
+        if puncture not in PUNCTURE:
+            raise ValueError("puncture must be one of %s or a (period, keep0, keep1) tuple" % sorted(PUNCTURE))
+        puncture = PUNCTURE[puncture]
+    period, keep0, keep1 = puncture
+    return int(period), int(keep0), int(keep1)
 # every symbol include/qpsk_dropin.h declares
 DROPIN_SYMBOLS = [
     "qpsk_dropin_configure", "qpsk_dropin_set_device", "qpsk_dropin_shutdown", "rrc_fir", "rrc_make",
@@ -124,6 +137,11 @@ def load():
     L.qpsk_soft_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, i32, f32, vp, vp, vp, i32, i32, vp, vp, vp]
     L.qpsk_conv_encode_batch.argtypes = [vp, vp, i32, i32, i32, vp]
     L.qpsk_viterbi_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, vp, i32, vp, vp]
+    u32 = C.c_uint32
+    L.qpsk_punct_ntx.argtypes = [i32, i32, u32, u32]
+    L.qpsk_conv_encode_punct_batch.argtypes = [vp, vp, i32, i32, i32, i32, u32, u32, vp]
+    L.qpsk_viterbi_punct_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, u32, u32, vp, i32, vp, vp]
+    L.qpsk_deframer_reset_coded_punct.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, u32, u32]
     L.qpsk_rrc_fir_batch.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_rrc_fir_batch_fast.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_timing_hist_batch.argtypes = [vp, vp, i32, vp, vp]
@@ -440,26 +458,59 @@ class Modem:
         return o
 
     # ---- the K = 7, rate-1/2 convolutional code
-    def conv_encode(self, bits_packed, nbits, tail=True):
+    def punct_ntx(self, nsteps, puncture):
+        """qpsk_punct_ntx: the transmitted dibits of nsteps trellis steps behind a puncturing pattern (a key of PUNCTURE or a (period,
+        keep0, keep1) tuple); host only"""
+        rc = self.L.qpsk_punct_ntx(int(nsteps), *_pattern(puncture))
+        self._check(min(rc, 0))
+        return rc
+
+    def conv_encode(self, bits_packed, nbits, tail=True, puncture=None):
         """qpsk_conv_encode_batch: bits_packed (R, ceil(nbits / 8)) uint8, bit t in byte t >> 3 at position t & 7 -> (R, nsteps) uint8 coded
-        dibits, nsteps = nbits + 6 with the tail (six zero bits that bring the encoder back to state 0)"""
+        dibits, nsteps = nbits + 6 with the tail (six zero bits that bring the encoder back to state 0).  With puncture (a key of PUNCTURE
+        or a (period, keep0, keep1) tuple) qpsk_conv_encode_punct_batch: (R, punct_ntx(nsteps)) transmitted dibits"""
         t = self.torch
         b = self._dev(bits_packed, t.uint8)
         if b.dim() != 2 or b.shape[1] != (int(nbits) + 7) // 8:
             raise ValueError("conv_encode() input must be (rows, ceil(nbits / 8)) uint8")
-        out = self.empty((b.shape[0], int(nbits) + (6 if tail else 0)), t.uint8)
+        nsteps = int(nbits) + (6 if tail else 0)
+        if puncture is not None:
+            pat = _pattern(puncture)
+            out = self.empty((b.shape[0], self.punct_ntx(nsteps, pat)), t.uint8)
+            self._check(self.L.qpsk_conv_encode_punct_batch(self.h, _ptr(b), b.shape[0], int(nbits), 1 if tail else 0, *pat, _ptr(out)))
+            return out
+        out = self.empty((b.shape[0], nsteps), t.uint8)
         self._check(self.L.qpsk_conv_encode_batch(self.h, _ptr(b), b.shape[0], int(nbits), 1 if tail else 0, _ptr(out)))
         return out
 
-    def viterbi(self, soft, flip=None, open_start=False, open_end=False, pitch=0, nsteps=None):
+    def viterbi(self, soft, flip=None, open_start=False, open_end=False, pitch=0, nsteps=None, puncture=None):
         """qpsk_viterbi_batch on soft (R, nsteps, 2) int8 -- what soft() returns under "soft" -- or, with pitch, (R, pitch, 2) of which the
         first nsteps steps of each row are decoded.  flip (nsteps,) uint8: the scrambler's keystream dibits, undone on the soft values.
         Dict of torch tensors bits (R, ceil(nsteps / 8)) uint8, packed low bits first, tail bits included, and info (R, 4) int32 = (end
-        metric, end state, state the trace-back arrives at, channel bit errors against the re-encoded path)."""
+        metric, end state, state the trace-back arrives at, channel bit errors against the re-encoded path).
+        With puncture (a key of PUNCTURE or a (period, keep0, keep1) tuple) qpsk_viterbi_punct_batch: soft (R, ntx, 2), or (R, pitch, 2),
+        holds the TRANSMITTED symbols, flip is (ntx,), and nsteps must be given (ntx does not determine it)."""
         t = self.torch
         if isinstance(soft, dict):
             soft = soft["soft"]
         q = self._dev(soft, t.int8)
+        if puncture is not None:
+            pat = _pattern(puncture)
+            if nsteps is None:
+                raise ValueError("viterbi(puncture=...) needs nsteps: the transmitted length does not determine it")
+            n = int(nsteps)
+            ntx = self.punct_ntx(n, pat)
+            if q.dim() != 3 or q.shape[2] != 2 or q.shape[1] != (pitch or ntx):
+                raise ValueError("viterbi(puncture=...) input must be (rows, ntx = %d or pitch, 2) int8" % ntx)
+            f = None if flip is None else self._dev(flip, t.uint8)
+            if f is not None and tuple(f.shape) != (ntx,):
+                raise ValueError("viterbi(puncture=...) flip must be (ntx = %d,) uint8" % ntx)
+            R = q.shape[0]
+            o = dict(bits=self.empty((R, (n + 7) // 8), t.uint8), info=self.empty((R, 4), t.int32))
+            self._check(self.L.qpsk_viterbi_punct_batch(self.h, _ptr(q), int(pitch), R, n, *pat, _ptr(f),
+                                                        (1 if open_start else 0) | (2 if open_end else 0), _ptr(o["bits"]), _ptr(o["info"])))
+            o["_keep"] = (q, f)
+            return o
         if q.dim() != 3 or q.shape[2] != 2 or (pitch and q.shape[1] != pitch):
             raise ValueError("viterbi() input must be (rows, nsteps or pitch, 2) int8")
         R = q.shape[0]
@@ -598,10 +649,18 @@ class Modem:
         o["_keep"] = (x,)
         return o
 
-    def deframer_reset_coded(self, nstreams, sync, nbytes, min_score, max_packets=8, mode="unit", scale=64.0):
+    def deframer_reset_coded(self, nstreams, sync, nbytes, min_score, max_packets=8, mode="unit", scale=64.0, puncture=None):
         """deframer_reset() for packets whose body carries the K = 7 rate-1/2 code: [sync][scrambled conv_encode(payload + CRC-16, tail)].
-        mode, scale: soft()'s, for the gain of a push that brings none of its own.  Replaces an uncoded deframer of the context."""
+        mode, scale: soft()'s, for the gain of a push that brings none of its own.  Replaces an uncoded deframer of the context.
+        With puncture (a key of PUNCTURE or a (period, keep0, keep1) tuple) qpsk_deframer_reset_coded_punct: the body is
+        conv_encode(..., puncture=...); deframe_coded() is the push of both."""
         sw = np.ascontiguousarray(np.asarray(sync, dtype=np.uint8))
+        if puncture is not None:
+            self._check(self.L.qpsk_deframer_reset_coded_punct(self.h, int(nstreams), sw.ctypes.data_as(C.c_void_p), len(sw), int(min_score),
+                                                               int(nbytes), int(max_packets), self.SOFT_MODES[mode], float(scale),
+                                                               *_pattern(puncture)))
+            self.df_shape = (int(nstreams), int(nbytes), int(max_packets))
+            return
         self._check(self.L.qpsk_deframer_reset_coded(self.h, int(nstreams), sw.ctypes.data_as(C.c_void_p), len(sw), int(min_score), int(nbytes),
                                                      int(max_packets), self.SOFT_MODES[mode], float(scale)))
         self.df_shape = (int(nstreams), int(nbytes), int(max_packets))

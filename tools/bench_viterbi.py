@@ -8,10 +8,16 @@ process, with events as bench.py times its steps; rounds of the legs interleaved
   forward   (with --profile-lib) the measurement build's flag that stops after the forward pass; and one call per shape with the cycle
             flag: the shader cycles of the forward pass and of the trace-back per wave, median over rows, divided by the steps
 
+  viterbi_punct / vit_punct_lds / vit_punct_scratch   (with --puncture RATE) qpsk_viterbi_punct_batch on the SAME number of trellis steps: the
+            first ntx symbols of the same soft rows (row_pitch = the row's symbols) are taken as what was transmitted, so the punctured and
+            the rate-1/2 call do the same steps and differ in the loader alone; same process, same interleaved rounds.  The record, with
+            the ratios punctured / rate 1/2 per route, also goes to --out (default profiles/viterbi_punct.txt)
+
 Shapes: 4096 x 2054 and 8192 x 2054 steps off rows of 2054 symbols of a 2054-symbol frame's costas_frame[]; 384 x 131072 off config 5's
 row.  The soft values are the receive chain's own (random payload symbols: the decoder's time does not depend on whether the row is a
 codeword, every step does the same work).  Prints one JSON line.
 Usage: python tools/bench_viterbi.py [--steps 50] [--rounds 5] [--profile-lib qpsk_amd/libqpsk_hip_vprof.so] [--shapes 4096x2054,...]
+                                     [--puncture 3/4 [--out profiles/viterbi_punct.txt]]
 """
 import argparse
 import ctypes as C
@@ -34,6 +40,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shapes", default="4096x2054,8192x2054,384x131072")
     ap.add_argument("--profile-lib", default=None, help="the measurement build (make -C qpsk_amd/csrc viterbi_profile)")
+    ap.add_argument("--puncture", default=None, metavar="RATE", help="also time qpsk_viterbi_punct_batch at this rate (a key of qpsk_amd.PUNCTURE)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "viterbi_punct.txt"), help="with --puncture: where the record is written")
     args = ap.parse_args()
     import torch
     import qpsk_amd
@@ -116,6 +124,14 @@ def main():
             legs["viterbi_profile_build"] = call(prof.qpsk_viterbi_batch, ph, *vit_args)
             syncs["forward"] = syncs["viterbi_profile_build"] = lambda: prof.qpsk_ctx_sync(ph)
             namers["viterbi_profile_build"] = lambda: prof.qpsk_ctx_last_kernel(ph).decode()
+        if args.puncture:
+            pat = qpsk_amd.PUNCTURE[args.puncture]
+            ntx = m.punct_ntx(N, pat)
+            punct_args = (P(soft), N, R, N) + tuple(pat) + (P(key), 0, P(bits), P(info))
+            for name, mm in [("viterbi_punct", m)] + [(n.replace("vit_", "vit_punct_"), e) for n, e in zip(("vit_lds", "vit_scratch"), extra)]:
+                legs[name] = call(mm.L.qpsk_viterbi_punct_batch, mm.h, *punct_args)
+                syncs[name] = mm.sync
+                namers[name] = mm.last_kernel
         legs["rx"]()
         legs["soft"]()
         m.sync()
@@ -130,6 +146,10 @@ def main():
         rec = {"ms_per_call": med, "min_ms": {k: float(np.min(v)) for k, v in res.items()}, "all": res, "routes": routes,
                "viterbi_over_rx": med["viterbi"] / med["rx"], "viterbi_over_rx_plus_soft": med["viterbi"] / (med["rx"] + med["soft"]),
                "decoded_Mbit_per_s": R * N / (med["viterbi"] * 1e-3) / 1e6}
+        if args.puncture:
+            pairs = [("viterbi_punct", "viterbi"), ("vit_punct_lds", "vit_lds"), ("vit_punct_scratch", "vit_scratch")]
+            rec["puncture"] = {"rate": args.puncture, "pattern": list(pat), "nsteps": N, "ntx": ntx,
+                               "punct_over_half": {a: med[a] / med[b] for a, b in pairs if a in med}}
         if prof is not None:
             rec["traceback_ms_by_difference"] = med["viterbi_profile_build"] - med["forward"]
             assert prof.qpsk_viterbi_batch(ph, P(soft), 0, R, N, P(key), CYCLES, P(bits), P(info)) == 0
@@ -145,6 +165,19 @@ def main():
         del legs, x, costas, soft, bits, info, sym
         torch.cuda.empty_cache()
     print(json.dumps(out))
+    if args.puncture:
+        with open(args.out, "w") as f:
+            f.write("qpsk_viterbi_punct_batch beside qpsk_viterbi_batch -- measurement record (tools/bench_viterbi.py --puncture %s; DESIGN.md 4.4.8)\n"
+                    "ms per call, medians of %d interleaved rounds of %d calls; the punctured call runs the same trellis steps on the first ntx\n"
+                    "symbols of the same soft rows\n\n" % (args.puncture, args.rounds, args.steps))
+            for shape, rec in out["shapes"].items():
+                med, pu = rec["ms_per_call"], rec["puncture"]
+                f.write("%s steps, rate %s (ntx %d)\n" % (shape, pu["rate"], pu["ntx"]))
+                for a, ratio in pu["punct_over_half"].items():
+                    b = {"viterbi_punct": "viterbi", "vit_punct_lds": "vit_lds", "vit_punct_scratch": "vit_scratch"}[a]
+                    f.write("  %-18s %9.4f ms (%s)   %-12s %9.4f ms (%s)   punctured / rate 1/2 = %.4f\n"
+                            % (a, med[a], rec["routes"].get(a, "?"), b, med[b], rec["routes"].get(b, "?"), ratio))
+            f.write("\n" + json.dumps(out) + "\n")
 
 
 if __name__ == "__main__":
