@@ -124,8 +124,12 @@ int qpsk_ctx_set_stream(qpsk_ctx *ctx, void *stream);
  * in-launch FFT timing estimate), "QPSK_LEAN_PAIR" (rx_lean_kernel's serial wave: 0 = one lane per Costas loop, 1 = two lanes per
  * loop -- they share the step's sine / cosine polynomial chains -- in workgroups of up to 16 frames, 2 = up to 32; the library's own choice is up to 24),
  * "QPSK_VITERBI_LDS" (qpsk_viterbi_batch: 0 = the decision words always wait in the context's scratch buffer, 1 = in LDS whenever a row's
- * fit -- up to 8192 steps; the library's own choice is LDS where every row of the call is resident at once); value < 0 = back to
- * the library's own choice.
+ * fit -- up to 8192 steps; the library's own choice is LDS where every row of the call is resident at once), "QPSK_VITERBI_CHUNK_ROWS"
+ * (qpsk_viterbi_batch, qpsk_viterbi_punct_batch and the decode of qpsk_deframer_push_coded off the LDS route: v >= 1 = at most v rows per
+ * launch where that is fewer than the scratch buffer's 1 GiB cap allows -- the key only lowers the cap, and the buffer is sized for the
+ * smaller chunk; 0 is refused with QPSK_ERR_ARG, here and as an environment value by qpsk_ctx_create(), where text that is not an
+ * integer leaves the key unset; no effect on the LDS route);
+ * value < 0 = back to the library's own choice.
  * Environment variables of the same names are read once, by qpsk_ctx_create(), as the context's initial values;
  * no other call reads the environment, and none of them can change a result. */
 int qpsk_ctx_set_tuning(qpsk_ctx *ctx, const char *name, int value);
@@ -714,6 +718,16 @@ int qpsk_test_inject_status(qpsk_ctx *ctx, int code);
 /* Test hook (the one-pass histogram route): synchronises, then out[5] = {the guess the next histogram-mode call will take (-1: none), frames
  * the last one-pass call's guess missed, and the statistics the host steers by: majority index, frames, frames off the majority or missed by the guess} */
 int qpsk_test_hist_state(qpsk_ctx *ctx, int32_t *out);
+/* Test hook (the chunk loops of the decoder's scratch route): *out = the decode launches of the context's last qpsk_viterbi_batch,
+ * qpsk_viterbi_punct_batch or qpsk_deframer_push_coded call -- 1 with the decision words in LDS, 0 for a push whose bytes, crc_ok and
+ * info were all NULL, or for a call that was refused.  Host bookkeeping only: no synchronisation, no device work. */
+int qpsk_test_viterbi_launches(qpsk_ctx *ctx, int *out);
+/* Test hook (stream positions beyond 32 bits): synchronises the context's stream, then adds delta to every stream's position counters
+ * (dibits pushed, where the hunt resumes, the pending packet's position) in either deframer mode; the carried tail, the pending body and
+ * the pending packet's rotation, score and fill stay.  Later packets are reported with pos + delta, everything else as without the
+ * call.  QPSK_ERR_ARG for delta < 0 or delta > 2^62; QPSK_ERR_STATE before a reset, after a failed push, or while a stream has seen fewer
+ * than nsync - 1 dibits. */
+int qpsk_test_deframer_advance(qpsk_ctx *ctx, long long delta);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@
 #include "kernels.h"
 
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -79,6 +80,7 @@ struct Tuning {
     int lean_pair = -1;                               /* rx_lean_kernel: 0 = one lane per loop in the serial wave, 1 = two lanes per loop up to 16 frames per workgroup, 2 = up to 32; unset: up to 24, where it pays in steady state (profiles/r06_step_cost.txt) */
     int viterbi_lds = -1;                             /* qpsk_viterbi_batch: 0 = decision words always through the global scratch buffer, 1 = in LDS whenever a row's fit (unset: in LDS where every row of the call is resident at once) */
     int fft_fused = -1;                               /* FFT timing estimate: 0 = always a launch of its own (1 / unset: inside rx_fused_pipe_kernel's launch for full workgroups) */
+    int viterbi_chunk_rows = -1;                      /* both Viterbi calls and the coded deframer's decode on the scratch route: at most this many rows per launch, where that is fewer than VITERBI_SCRATCH_MAX allows (>= 1; 0 is refused) */
 };
 
 static const struct { const char *name; int Tuning::*field; } TUNING_KEYS[] = {
@@ -92,7 +94,7 @@ static const struct { const char *name; int Tuning::*field; } TUNING_KEYS[] = {
     {"QPSK_STREAM_SCAN", &Tuning::stream_scan}, {"QPSK_STREAM_CARRIER", &Tuning::stream_carrier},
     {"QPSK_LEAN_DMA", &Tuning::lean_dma},     {"QPSK_LEAN_PAIR", &Tuning::lean_pair},
     {"QPSK_EST_WAVES", &Tuning::est_waves},   {"QPSK_HIST_ONEPASS", &Tuning::hist_onepass},
-    {"QPSK_VITERBI_LDS", &Tuning::viterbi_lds},
+    {"QPSK_VITERBI_LDS", &Tuning::viterbi_lds},   {"QPSK_VITERBI_CHUNK_ROWS", &Tuning::viterbi_chunk_rows},
 };
 
 /* layout bits a product build honours: 4 no spare waves, 8 C++ Costas step, 64/128 lane-mapping variants.  The
@@ -109,6 +111,7 @@ struct qpsk_ctx {
     Tuning tune;
     int ncu = 256;                /* compute units of the device (256 on MI355X) */
     const char *last_kernel = ""; /* the receive kernel the last rx batch launched (qpsk_ctx_last_kernel) */
+    int viterbi_launches = 0;     /* decode launches of the last qpsk_viterbi_batch / qpsk_viterbi_punct_batch / qpsk_deframer_push_coded (qpsk_test_viterbi_launches) */
     bool taps_symmetric = false;  /* taps[k] == taps[126 - k] bit for bit: rx_lean_kernel keeps the 64 distinct ones in SGPRs */
     hipStream_t stream = nullptr; /* caller's stream; nullptr = default stream */
     qpsk_params prm{};
@@ -363,7 +366,19 @@ int qpsk_ctx_create(qpsk_ctx **out, int device, const qpsk_params *p, void *stre
     c->device = device;
     for (const auto &k : TUNING_KEYS) {   /* the only place the environment is read */
         const char *v = getenv(k.name);
-        if (v && *v) c->tune.*(k.field) = atoi(v);
+        if (!v || !*v) continue;
+        if (k.field == &Tuning::viterbi_chunk_rows) {      /* a number or nothing: text that is no integer leaves the key unset, 0 is refused below */
+            char *end = nullptr;
+            const long n = strtol(v, &end, 10);
+            if (end == v || *end) continue;
+            c->tune.*(k.field) = n < 0 ? -1 : n > INT_MAX ? INT_MAX : (int)n;
+            continue;
+        }
+        c->tune.*(k.field) = atoi(v);
+    }
+    if (c->tune.viterbi_chunk_rows == 0) {      /* as qpsk_ctx_set_tuning: no chunk of no rows */
+        delete c;
+        return fail(QPSK_ERR_ARG, "qpsk_ctx_create: QPSK_VITERBI_CHUNK_ROWS = 0 in the environment (>= 1, or negative for the library's own choice)");
     }
     {
         int ncu = 0;
@@ -519,6 +534,8 @@ int qpsk_ctx_set_tuning(qpsk_ctx *c, const char *name, int value)
     if (!c || !name) return fail(QPSK_ERR_ARG, "null argument");
     for (const auto &k : TUNING_KEYS)
         if (!strcmp(k.name, name)) {
+            if (value == 0 && k.field == &Tuning::viterbi_chunk_rows)
+                return fail(QPSK_ERR_ARG, "qpsk_ctx_set_tuning: QPSK_VITERBI_CHUNK_ROWS = 0 (>= 1, or negative for the library's own choice)");
             c->tune.*(k.field) = value < 0 ? -1 : value;
             return QPSK_OK;
         }
@@ -1407,6 +1424,15 @@ int qpsk_conv_encode_punct_batch(qpsk_ctx *c, const uint8_t *d_bits, int nrows, 
  * workgroups; otherwise in the context's scratch buffer, rows in chunks of at most VITERBI_SCRATCH_MAX bytes of it */
 static const size_t VITERBI_SCRATCH_MAX = (size_t)1 << 30;
 
+/* rows per launch: what VITERBI_SCRATCH_MAX allows (one row at least); on the scratch route (lds false) fewer where
+ * QPSK_VITERBI_CHUNK_ROWS says so -- the key can only lower the cap, so the scratch buffer never grows by it */
+static size_t viterbi_chunk_rows(const qpsk_ctx *c, size_t rows, size_t per_row, bool lds)
+{
+    size_t cap = std::max<size_t>(1, VITERBI_SCRATCH_MAX / per_row);
+    if (!lds && c->tune.viterbi_chunk_rows >= 1) cap = std::min<size_t>(cap, (size_t)c->tune.viterbi_chunk_rows);
+    return std::min<size_t>(rows, cap);
+}
+
 /* both decoders: who = the entry point's name; punct = NULL for rate 1/2, otherwise the checked pattern: the rows then hold the ntx
  * transmitted dibits of nsteps steps, and row_pitch and d_flip go by ntx.  The residency rule, the scratch and the chunks go by nsteps */
 static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const Puncture *punct,
@@ -1423,6 +1449,7 @@ int qpsk_viterbi_punct_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pi
 {
     Puncture p;
     if (!c) return fail(QPSK_ERR_ARG, "qpsk_viterbi_punct_batch: null context or input");
+    c->viterbi_launches = 0;      /* a refused pattern made none */
     if (int rc = punct_make("qpsk_viterbi_punct_batch", period, keep0, keep1, &p)) return rc;
     return viterbi_impl(c, "qpsk_viterbi_punct_batch", d_soft, row_pitch, nrows, nsteps, &p, d_flip, flags, d_bits, d_info);
 }
@@ -1430,6 +1457,7 @@ int qpsk_viterbi_punct_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pi
 static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const Puncture *punct,
                         const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info)
 {
+    if (c) c->viterbi_launches = 0;      /* a refused call made none */
     if (!c || !d_soft) return fail(QPSK_ERR_ARG, "%s: null context or input", who);
     if (!d_bits && !d_info) return fail(QPSK_ERR_ARG, "%s: every output is NULL", who);
     if (nrows <= 0 || nsteps <= 0 || nsteps > VITERBI_MAX_STEPS)
@@ -1454,16 +1482,18 @@ static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long
     const size_t nbytes = ((size_t)nsteps + 7) / 8;
     if (lds) {
         KERNEL_TRY(launch_viterbi(d_soft, (size_t)row_pitch, nrows, nsteps, punct, d_flip, flags, nullptr, true, d_bits, d_info, c->stream));
+        c->viterbi_launches = 1;
         c->last_kernel = punct ? "viterbi_punct_lds_kernel" : "viterbi_lds_kernel";
         return QPSK_OK;
     }
-    const size_t chunk_rows = std::min<size_t>((size_t)nrows, std::max<size_t>(1, VITERBI_SCRATCH_MAX / per_row));
+    const size_t chunk_rows = viterbi_chunk_rows(c, (size_t)nrows, per_row, false);
     if (int rg = ensure(c, c->vitdec, chunk_rows * per_row)) return rg;
     for (size_t r0 = 0; r0 < (size_t)nrows; r0 += chunk_rows) {      /* stream order: a chunk's trace-back is over before the next one's forward pass */
         const int n = (int)std::min<size_t>(chunk_rows, (size_t)nrows - r0);
         KERNEL_TRY(launch_viterbi(d_soft + 2 * r0 * (size_t)row_pitch, (size_t)row_pitch, n, nsteps, punct, d_flip, flags,
                                   (unsigned long long *)c->vitdec.p, false, d_bits ? d_bits + r0 * nbytes : nullptr, d_info ? d_info + 4 * r0 : nullptr,
                                   c->stream));
+        c->viterbi_launches++;
     }
     c->last_kernel = punct ? "viterbi_punct_kernel" : "viterbi_kernel";
     return QPSK_OK;
@@ -2245,6 +2275,7 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
                              long long *d_pos, int32_t *d_rot, int32_t *d_score, uint8_t *d_crc_ok, int32_t *d_info)
 {
     if (!c) return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: null context");
+    c->viterbi_launches = 0;      /* a refused call made none */
     if (!d_costas) return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: d_costas is required");
     if (!d_count) return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: d_count is required");
     if (nsym < 1 || nsym > DEFRAME_MAX_NSYM) return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: nsym = %d outside 1..%d", nsym, DEFRAME_MAX_NSYM);
@@ -2273,7 +2304,7 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
     const bool fits = per_row <= (size_t)VITERBI_LDS_MAX_BYTES;
     const bool resident = fits && rows <= (size_t)c->ncu * (((size_t)160 << 10) / per_row);
     const bool lds = fits && tuned(c->tune.viterbi_lds, resident ? 1 : 0) != 0;
-    const size_t chunk_rows = std::min<size_t>(rows, std::max<size_t>(1, VITERBI_SCRATCH_MAX / per_row));
+    const size_t chunk_rows = viterbi_chunk_rows(c, rows, per_row, lds);
     if (int rg = ensure(c, c->dfstage, rows * 2 * (size_t)pitch)) return rg;
     if (!d_gain)
         if (int rg = ensure(c, c->softgain, sizeof(float) * S)) return rg;
@@ -2313,8 +2344,10 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
                                     c->d_status, c->stream));
     const DeframeCodedBody body = {Nc, pitch, c->df_punct ? 1 : 0, c->df_pattern};
     int e = launch_deframe_coded_hunt(a, body, c->stream);
-    for (size_t r0 = 0; e == 0 && decode && r0 < rows; r0 += chunk_rows)      /* stream order: a chunk's trace-back is over before the next one's forward pass */
+    for (size_t r0 = 0; e == 0 && decode && r0 < rows; r0 += chunk_rows) {      /* stream order: a chunk's trace-back is over before the next one's forward pass */
         e = launch_deframe_coded_decode(a, body, (int)r0, (int)std::min<size_t>(chunk_rows, rows - r0), lds ? nullptr : (unsigned long long *)c->vitdec.p, lds, c->stream);
+        if (e == 0) c->viterbi_launches++;
+    }
     if (e != 0) {
         c->df_ready = false;
         return fail(QPSK_ERR_HIP, "qpsk_deframer_push_coded launch: %s", hipGetErrorString((hipError_t)e));
@@ -2324,6 +2357,38 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
                                           : "deframe_coded_hunt_kernel + deframe_coded_decode_punct_kernel<global>")
                      : lds         ? "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<lds>"
                                    : "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<global>";
+    return QPSK_OK;
+}
+
+/* test hook (tests/test_viterbi_chunks_gpu.py): host bookkeeping only */
+int qpsk_test_viterbi_launches(qpsk_ctx *c, int *out)
+{
+    if (!c || !out) return fail(QPSK_ERR_ARG, "qpsk_test_viterbi_launches: null argument");
+    *out = c->viterbi_launches;
+    return QPSK_OK;
+}
+
+/* test hook (tests/test_deframe_positions_gpu.py): the stream positions of both deframers move on by delta, as if delta more dibits had
+ * been pushed whose words and packets all lay behind the carried tail.  Plain copies of the headers, no kernel */
+int qpsk_test_deframer_advance(qpsk_ctx *c, long long delta)
+{
+    if (!c) return fail(QPSK_ERR_ARG, "qpsk_test_deframer_advance: null context");
+    if (delta < 0 || delta > (1LL << 62)) return fail(QPSK_ERR_ARG, "qpsk_test_deframer_advance: delta = %lld outside 0..2^62", delta);
+    if (!c->df_state) return fail(QPSK_ERR_STATE, "qpsk_test_deframer_advance: no deframer reset yet");
+    if (!c->df_ready) return fail(QPSK_ERR_STATE, "qpsk_test_deframer_advance: the deframer's state is undefined after a failed push; reset it");
+    if (bind(c)) return QPSK_ERR_HIP;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t S = (size_t)c->df_nstreams;
+    std::vector<DeframeHeader> hd(S);
+    HIP_TRY(hipMemcpy2D(hd.data(), sizeof(DeframeHeader), c->df_state, c->df_stride, sizeof(DeframeHeader), S, hipMemcpyDeviceToHost));
+    for (const auto &h : hd) {
+        if (h.len < (long long)c->df_nsync - 1)      /* the hunt takes a tail of nsync - 1 dibits for granted once len says so */
+            return fail(QPSK_ERR_STATE, "qpsk_test_deframer_advance: a stream has seen %lld dibits, fewer than nsync - 1 = %d", h.len, c->df_nsync - 1);
+        if (h.len > LLONG_MAX - delta - (1LL << 32))
+            return fail(QPSK_ERR_ARG, "qpsk_test_deframer_advance: the positions would leave 64 bits");
+    }
+    for (auto &h : hd) { h.len += delta; h.h += delta; h.ppos += delta; }
+    HIP_TRY(hipMemcpy2D(c->df_state, c->df_stride, hd.data(), sizeof(DeframeHeader), sizeof(DeframeHeader), S, hipMemcpyHostToDevice));
     return QPSK_OK;
 }
 

@@ -60,6 +60,7 @@ API_SYMBOLS = [
     "qpsk_deframer_reset_coded", "qpsk_deframer_push_coded",
     "qpsk_soft_batch", "qpsk_conv_encode_batch", "qpsk_viterbi_batch",
     "qpsk_punct_ntx", "qpsk_conv_encode_punct_batch", "qpsk_viterbi_punct_batch", "qpsk_deframer_reset_coded_punct",
+    "qpsk_test_viterbi_launches", "qpsk_test_deframer_advance",
 ]
 # the named puncturing patterns of include/qpsk_hip.h (QPSK_PUNCT_*): rate -> (period, keep0, keep1), bit r of a mask = step r of the period
 PUNCTURE = {"1/2": (1, 0x1, 0x1), "2/3": (2, 0x1, 0x3), "3/4": (3, 0x5, 0x3), "5/6": (5, 0x15, 0x0B), "7/8": (7, 0x51, 0x2F)}
@@ -160,6 +161,8 @@ def load():
     L.qpsk_test_inject_status.argtypes = [vp, i32]
     L.qpsk_ctx_check.argtypes = [vp]
     L.qpsk_test_hist_state.argtypes = [vp, C.POINTER(i32)]
+    L.qpsk_test_viterbi_launches.argtypes = [vp, C.POINTER(i32)]
+    L.qpsk_test_deframer_advance.argtypes = [vp, C.c_longlong]
     L.qpsk_multi_create.argtypes = [C.POINTER(vp), C.POINTER(i32), i32, C.POINTER(Params)]
     L.qpsk_multi_destroy.argtypes = [vp]
     L.qpsk_multi_destroy.restype = None
@@ -252,6 +255,16 @@ class Modem:
         Keys are the QPSK_* names of qpsk_ctx_set_tuning() in lower case without the prefix."""
         for k, v in kw.items():
             self._check(self.L.qpsk_ctx_set_tuning(self.h, ("QPSK_" + k.upper()).encode(), -1 if v is None else int(v)))
+
+    def viterbi_launches(self):
+        """Test hook: decode launches of the last viterbi() / deframe_coded() call (qpsk_test_viterbi_launches)."""
+        n = C.c_int(-1)
+        self._check(self.L.qpsk_test_viterbi_launches(self.h, C.byref(n)))
+        return n.value
+
+    def deframer_advance(self, delta):
+        """Test hook: move both deframers' stream positions on by delta dibits (qpsk_test_deframer_advance)."""
+        self._check(self.L.qpsk_test_deframer_advance(self.h, int(delta)))
 
     def set_stream(self, stream):
         """Enqueue this context's work on another HIP stream (a torch.cuda.Stream or a raw handle; None = default)."""

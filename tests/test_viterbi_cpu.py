@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G0, G1 = 0x79, 0x5B                       # 171, 133 octal
 NEG = -(1 << 30)
 CONV_TAIL, OPEN_START, OPEN_END = 1, 1, 2
-VITERBI_SYMBOLS = ("qpsk_conv_encode_batch", "qpsk_viterbi_batch")
+VITERBI_SYMBOLS = ("qpsk_conv_encode_batch", "qpsk_viterbi_batch", "qpsk_test_viterbi_launches", "qpsk_test_deframer_advance")
 PAR = np.array([bin(v).count("1") & 1 for v in range(128)], np.int64)
 C0, C1 = PAR[np.arange(128) & G0], PAR[np.arange(128) & G1]      # the coded pair of register value r
 
@@ -126,7 +126,8 @@ def test_viterbi_entry_points_are_declared_bound_exported_and_refuse_without_a_c
     header = open(os.path.join(ROOT, "include", "qpsk_hip.h")).read()
     for word in ("QPSK_CONV_TAIL = 1", "QPSK_VITERBI_OPEN_START = 1", "QPSK_VITERBI_OPEN_END = 2"):
         assert word in header, word
-    for name in ("conv_encode", "viterbi"):
+    assert '"QPSK_VITERBI_CHUNK_ROWS"' in header and "none of them can change a result" in header
+    for name in ("conv_encode", "viterbi", "viterbi_launches", "deframer_advance"):
         assert callable(getattr(qpsk_amd.Modem, name, None)), name
     # no context, no work: without a GPU no context can exist (test_abi.py::test_no_gpu_means_error_not_fallback), and the entry points
     # refuse a NULL one with QPSK_ERR_ARG on any machine
@@ -134,6 +135,13 @@ def test_viterbi_entry_points_are_declared_bound_exported_and_refuse_without_a_c
     assert qpsk_lib.qpsk_conv_encode_batch(None, buf, 1, 8, 1, buf) == -2
     assert qpsk_lib.qpsk_viterbi_batch(None, buf, 0, 1, 8, None, 0, buf, None) == -2
     assert b"qpsk_viterbi_batch" in qpsk_lib.qpsk_last_error()
+    n = C.c_int(-9)
+    assert qpsk_lib.qpsk_test_viterbi_launches(None, C.byref(n)) == -2 and n.value == -9
+    assert b"qpsk_test_viterbi_launches" in qpsk_lib.qpsk_last_error()
+    for delta in (0, 1 << 40, -1):
+        assert qpsk_lib.qpsk_test_deframer_advance(None, delta) == -2
+    assert b"qpsk_test_deframer_advance" in qpsk_lib.qpsk_last_error()
+    assert qpsk_lib.qpsk_ctx_set_tuning(None, b"QPSK_VITERBI_CHUNK_ROWS", 1) == -2
     if not torch.cuda.is_available():
         with pytest.raises(qpsk_amd.QpskError):
             qpsk_amd.Modem().viterbi(np.zeros((1, 8, 2), np.int8))
