@@ -19,6 +19,7 @@
 #include <string.h>
 #include <time.h>
 #include <algorithm>
+#include <initializer_list>
 #include <map>
 #include <vector>
 
@@ -2216,6 +2217,34 @@ static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const
     return QPSK_OK;
 }
 
+/* what both pushes do behind their own argument checks (who = the entry point's name): the state checks, no output (the caller's
+ * list; NULL entries are skipped) may overlap the input of sym_bytes a symbol, the device, and the hunt's arguments from the context */
+struct DeframeOutput { const void *p; size_t bytes; const char *name; };
+static int deframer_push_begin(qpsk_ctx *c, const char *who, bool coded, const void *in, size_t sym_bytes, int nsym,
+                               std::initializer_list<DeframeOutput> outs, DeframeHuntArgs &a)
+{
+    if (!c->df_state) return fail(QPSK_ERR_STATE, "%s: no %s yet", who, coded ? "qpsk_deframer_reset_coded" : "qpsk_deframer_reset");
+    if (c->df_coded != coded)
+        return fail(QPSK_ERR_STATE, "%s: the deframer was reset in %s mode (%s)", who, coded ? "uncoded" : "coded",
+                    coded ? "qpsk_deframer_push" : "qpsk_deframer_push_coded");
+    if (!c->df_ready) return fail(QPSK_ERR_STATE, "%s: the deframer's state is undefined after a failed push; reset it", who);
+    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (size_t)c->df_nstreams * (size_t)nsym * sym_bytes;
+    for (const auto &o : outs) {
+        if (!o.p) continue;
+        const uintptr_t o0 = (uintptr_t)o.p, o1 = o0 + o.bytes;
+        if (o0 < i1 && i0 < o1) return fail(QPSK_ERR_ARG, "%s: %s overlaps the input", who, o.name);
+    }
+    if (bind(c)) return QPSK_ERR_HIP;
+    a.nstreams = c->df_nstreams;
+    a.nsym = nsym;
+    a.nsync = c->df_nsync;
+    a.min_score = c->df_min_score;
+    a.state = c->df_state;
+    a.state_stride = c->df_stride;
+    for (int i = 0; i < 2; i++) { a.sync_lo[i] = c->df_sync_lo[i]; a.sync_hi[i] = c->df_sync_hi[i]; }
+    return QPSK_OK;
+}
+
 int qpsk_deframer_push(qpsk_ctx *c, const float *d_costas, const uint8_t *d_data, int nsym, int32_t *d_count, uint8_t *d_bytes,
                        long long *d_pos, int32_t *d_rot, int32_t *d_score, uint8_t *d_crc_ok)
 {
@@ -2223,36 +2252,20 @@ int qpsk_deframer_push(qpsk_ctx *c, const float *d_costas, const uint8_t *d_data
     if ((d_costas != nullptr) == (d_data != nullptr)) return fail(QPSK_ERR_ARG, "qpsk_deframer_push: give exactly one of d_costas, d_data");
     if (!d_count) return fail(QPSK_ERR_ARG, "qpsk_deframer_push: d_count is required");
     if (nsym < 1 || nsym > DEFRAME_MAX_NSYM) return fail(QPSK_ERR_ARG, "qpsk_deframer_push: nsym = %d outside 1..%d", nsym, DEFRAME_MAX_NSYM);
-    if (!c->df_state) return fail(QPSK_ERR_STATE, "qpsk_deframer_push: no qpsk_deframer_reset yet");
-    if (c->df_coded) return fail(QPSK_ERR_STATE, "qpsk_deframer_push: the deframer was reset in coded mode (qpsk_deframer_push_coded)");
-    if (!c->df_ready) return fail(QPSK_ERR_STATE, "qpsk_deframer_push: the deframer's state is undefined after a failed push; reset it");
     const size_t S = (size_t)c->df_nstreams, M = (size_t)c->df_max_packets;
-    const uintptr_t i0 = d_costas ? (uintptr_t)d_costas : (uintptr_t)d_data;
-    const uintptr_t i1 = i0 + S * (size_t)nsym * (d_costas ? 2 * sizeof(float) : 1);
-    const struct { const void *p; size_t bytes; const char *name; } outs[] = {
-        {d_count, S * 4, "d_count"}, {d_bytes, S * M * (size_t)(c->df_nbytes + 2), "d_bytes"}, {d_pos, S * M * 8, "d_pos"},
-        {d_rot, S * M * 4, "d_rot"}, {d_score, S * M * 4, "d_score"}, {d_crc_ok, S * M, "d_crc_ok"}};
-    for (const auto &o : outs) {
-        if (!o.p) continue;
-        const uintptr_t o0 = (uintptr_t)o.p, o1 = o0 + o.bytes;
-        if (o0 < i1 && i0 < o1) return fail(QPSK_ERR_ARG, "qpsk_deframer_push: %s overlaps the input", o.name);
-    }
-    if (bind(c)) return QPSK_ERR_HIP;
     DeframeArgs a{};
+    if (int rc = deframer_push_begin(c, "qpsk_deframer_push", false, d_costas ? (const void *)d_costas : (const void *)d_data,
+                                     d_costas ? 2 * sizeof(float) : 1, nsym,
+                                     {{d_count, S * 4, "d_count"}, {d_bytes, S * M * (size_t)(c->df_nbytes + 2), "d_bytes"}, {d_pos, S * M * 8, "d_pos"},
+                                      {d_rot, S * M * 4, "d_rot"}, {d_score, S * M * 4, "d_score"}, {d_crc_ok, S * M, "d_crc_ok"}}, a))
+        return rc;
     a.data = d_data;
     a.costas = reinterpret_cast<const float2 *>(d_costas);
-    a.nstreams = c->df_nstreams;
-    a.nsym = nsym;
-    a.nsync = c->df_nsync;
-    a.min_score = c->df_min_score;
     a.nbytes = c->df_nbytes;
     a.max_packets = c->df_max_packets;
     a.bytes_per_lane = (c->df_nbytes + 2 + 63) / 64;
-    a.state = c->df_state;
-    a.state_stride = c->df_stride;
     a.keystream = c->df_tables;
     a.crc_adv = reinterpret_cast<const uint16_t *>(c->df_tables + DF_ADV_OFFSET);
-    for (int i = 0; i < 2; i++) { a.sync_lo[i] = c->df_sync_lo[i]; a.sync_hi[i] = c->df_sync_hi[i]; }
     a.count = d_count;
     a.bytes = d_bytes;
     a.pos = d_pos;
@@ -2282,20 +2295,13 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
     if ((uintptr_t)d_costas % 8) return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: d_costas is not 8-byte aligned");
     if ((uintptr_t)d_gain % 4 || (uintptr_t)d_count % 4 || (uintptr_t)d_rot % 4 || (uintptr_t)d_score % 4 || (uintptr_t)d_info % 4 || (uintptr_t)d_pos % 8)
         return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: a misaligned array");
-    if (!c->df_state) return fail(QPSK_ERR_STATE, "qpsk_deframer_push_coded: no qpsk_deframer_reset_coded yet");
-    if (!c->df_coded) return fail(QPSK_ERR_STATE, "qpsk_deframer_push_coded: the deframer was reset in uncoded mode (qpsk_deframer_push)");
-    if (!c->df_ready) return fail(QPSK_ERR_STATE, "qpsk_deframer_push_coded: the deframer's state is undefined after a failed push; reset it");
     const size_t S = (size_t)c->df_nstreams, M = (size_t)c->df_max_packets;
-    const uintptr_t i0 = (uintptr_t)d_costas, i1 = i0 + S * (size_t)nsym * 2 * sizeof(float);
-    const struct { const void *p; size_t bytes; const char *name; } outs[] = {
-        {d_count, S * 4, "d_count"}, {d_bytes, S * M * (size_t)(c->df_nbytes + 2), "d_bytes"}, {d_pos, S * M * 8, "d_pos"},
-        {d_rot, S * M * 4, "d_rot"}, {d_score, S * M * 4, "d_score"}, {d_crc_ok, S * M, "d_crc_ok"}, {d_info, S * M * 16, "d_info"}};
-    for (const auto &o : outs) {
-        if (!o.p) continue;
-        const uintptr_t o0 = (uintptr_t)o.p, o1 = o0 + o.bytes;
-        if (o0 < i1 && i0 < o1) return fail(QPSK_ERR_ARG, "qpsk_deframer_push_coded: %s overlaps the input", o.name);
-    }
-    if (bind(c)) return QPSK_ERR_HIP;
+    DeframeCodedArgs a{};
+    if (int rc = deframer_push_begin(c, "qpsk_deframer_push_coded", true, d_costas, 2 * sizeof(float), nsym,
+                                     {{d_count, S * 4, "d_count"}, {d_bytes, S * M * (size_t)(c->df_nbytes + 2), "d_bytes"}, {d_pos, S * M * 8, "d_pos"},
+                                      {d_rot, S * M * 4, "d_rot"}, {d_score, S * M * 4, "d_score"}, {d_crc_ok, S * M, "d_crc_ok"},
+                                      {d_info, S * M * 16, "d_info"}}, a))
+        return rc;
     const int Nc = c->df_nbody, pitch = (Nc + 1) & ~1;      /* the staging rows go by what is on air, the decision words by the steps */
     const int per = std::min<long long>(c->df_max_packets, (long long)nsym / (c->df_nsync + Nc) + 1);
     const size_t rows = S * (size_t)per;
@@ -2311,21 +2317,13 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
     if (decode && !lds)
         if (int rg = ensure(c, c->vitdec, chunk_rows * per_row)) return rg;
 
-    DeframeCodedArgs a{};
     a.costas = reinterpret_cast<const float2 *>(d_costas);
     a.gain = d_gain ? d_gain : (const float *)c->softgain.p;
     a.check_gain = d_gain != nullptr;
-    a.nstreams = c->df_nstreams;
-    a.nsym = nsym;
-    a.nsync = c->df_nsync;
-    a.min_score = c->df_min_score;
     a.nbytes = c->df_nbytes;
     a.max_packets = c->df_max_packets;
     a.nsteps = c->df_nsteps;
     a.per_stream = per;
-    a.state = c->df_state;
-    a.state_stride = c->df_stride;
-    for (int i = 0; i < 2; i++) { a.sync_lo[i] = c->df_sync_lo[i]; a.sync_hi[i] = c->df_sync_hi[i]; }
     a.stage = (int8_t *)c->dfstage.p;
     a.flip = c->df_tables;
     a.crc_adv = reinterpret_cast<const uint16_t *>(c->df_tables + DFC_ADV_OFFSET);

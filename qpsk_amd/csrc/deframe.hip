@@ -1,22 +1,9 @@
 /*
  * deframe.hip -- packets out of continuous streams of data decisions (include/qpsk_hip.h, qpsk_deframer_push):
  *
- *   deframe_kernel   one wave per stream: the new row behind the stream's carried tail, every position whose word is complete scored
- *                    against the sync word, the hunt / collect state walked over the candidates, each completed packet de-rotated,
- *                    descrambled, packed to bytes and checked against its CRC-16
- *
- * A stream's sequence D is everything pushed since the reset; X = [the last T = min(len, nsync-1) values of D][this push's row] is the
- * part this push reads.  Position p_x of X starts a word that completes in THIS push (its last dibit lies in the row), so every position
- * of D is scored exactly once, in the push that brings its last dibit.  A packet found in this push has its payload starting in the
- * row (p* + nsync > len); a packet still collecting at the end of a push keeps its received payload dibits in the stream's pending
- * buffer and is completed by a later push.
- *
- * Scoring in bit planes.  The ring values of X are two planes of bits (bit 0, bit 1), built 64 positions at a time by two ballots of a
- * coalesced load, so a plane word is wave-uniform.  Lane l of step s scores position 64 s + l: its 64-position windows are funnel
- * shifts of three consecutive plane words, and with the sync word's planes in the kernel arguments
- *     diff = (x - s) & 3:   diff0 = x0 ^ s0,   diff1 = x1 ^ s1 ^ (~x0 & s0)
- * one popcount per rotation counts the word's dibits matching under that rotation (sync.hip's score, the same tie rule).  A ballot of
- * "best score >= min_score" is the step's candidate mask; the hunt walks it in wave-uniform code: O(packets + steps).
+ *   deframe_kernel   one wave per stream: deframe_hunt.h's hunt (the sequence D, the window X, the scoring and the walk are described
+ *                    there) over data rows or costas_frame[] rows, each completed packet de-rotated, descrambled, packed to bytes and
+ *                    checked against its CRC-16; an incomplete packet's payload waits in the pending buffer as ring values
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,18 +11,16 @@
 #include "kernels.h"
 #include "qpsk_device.h"
 #include "deframe_bits.h"
+#include "deframe_hunt.h"
 
 namespace qpsk {
 
 namespace {
 
-constexpr int DF_WAVES = 4;       /* streams per workgroup: one wave each */
-constexpr int DF_CHUNK = 4;       /* steps of 64 positions per load batch (4 + 2 plane words): more spills SGPRs (103 of 106 at 4) */
-
 template <bool COSTAS>
 __device__ __forceinline__ unsigned ring_at(const void *row, long long i)
 {
-    if (COSTAS) return ring_of((unsigned)data_rule(reinterpret_cast<const float2 *>(row)[i]));
+    if (COSTAS) return qpsk::ring_at(reinterpret_cast<const float2 *>(row), i);      /* deframe_hunt.h's */
     return ring_of(reinterpret_cast<const uint8_t *>(row)[i] & 3u);
 }
 
@@ -75,157 +60,46 @@ __device__ void emit_packet(const DeframeArgs &a, int stream, int slot, long lon
     unsigned share = crc_mulmod(crc, a.crc_adv[lane]) | (rx << 16);
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) share ^= (unsigned)__shfl_xor((int)share, o, 64);
-    if (lane == 0) {
-        const size_t r = (size_t)stream * a.max_packets + slot;
-        if (a.pos) a.pos[r] = pos;
-        if (a.rot) a.rot[r] = rot;
-        if (a.score) a.score[r] = score;
-        if (a.crc_ok) a.crc_ok[r] = (uint8_t)((share & 0xFFFFu) == (share >> 16));
-    }
+    const size_t r = (size_t)stream * a.max_packets + slot;
+    report(a, r, pos, rot, score, lane);
+    if (lane == 0 && a.crc_ok) a.crc_ok[r] = (uint8_t)((share & 0xFFFFu) == (share >> 16));
 }
 
+/* the hunt's policy: packets as bytes, the pending payload as ring values */
 template <bool COSTAS>
-__global__ void __launch_bounds__(64 * DF_WAVES)
+struct BytePackets {
+    const DeframeArgs &a;
+    int stream;
+    const void *row;
+    uint8_t *pend;
+    __device__ __forceinline__ unsigned ring(long long i) const { return ring_at<COSTAS>(row, i); }
+    __device__ __forceinline__ void complete(int slot, long long pos, int rot, int score, int have, int row0) const
+    {
+        emit_packet<COSTAS>(a, stream, slot, pos, rot, score, pend, have, row, row0);
+    }
+    __device__ __forceinline__ void collect(int have, int row0, int cnt, int /* rot: the packet is turned when it is built */) const
+    {
+        for (int i = threadIdx.x & 63; i < cnt; i += 64) pend[have + i] = (uint8_t)ring(row0 + i);
+    }
+};
+
+template <bool COSTAS>
+__global__ void __launch_bounds__(64 * HUNT_WAVES)
 deframe_kernel(DeframeArgs a)
 {
-    const int lane = threadIdx.x & 63;
-    const int stream = blockIdx.x * DF_WAVES + (int)(threadIdx.x >> 6);
+    const int stream = blockIdx.x * HUNT_WAVES + (int)(threadIdx.x >> 6);
     if (stream >= a.nstreams) return;
-    const int n = a.nsync, N = 4 * (a.nbytes + 2);
-    const long long nsym = a.nsym;
-    const void *row = COSTAS ? (const void *)(a.costas + (size_t)stream * (size_t)nsym) : (const void *)(a.data + (size_t)stream * (size_t)nsym);
+    const void *row = COSTAS ? (const void *)(a.costas + (size_t)stream * (size_t)a.nsym) : (const void *)(a.data + (size_t)stream * (size_t)a.nsym);
     uint8_t *st = a.state + (size_t)stream * a.state_stride;
-    DeframeHeader *hd = reinterpret_cast<DeframeHeader *>(st);
-    uint8_t *tail = st + DEFRAME_TAIL_OFFSET;
-    uint8_t *pend = st + DEFRAME_PEND_OFFSET;
-
-    const long long len = hd->len;
-    long long h = hd->h;
-    int pending = hd->pending, have = hd->have;
-    const long long ppos = hd->ppos;
-    const int prot = hd->prot, pscore = hd->pscore;
-    const int T = (int)(len < (long long)(n - 1) ? len : (long long)(n - 1));
-    int count = 0;
-
-    /* 1. the packet collecting since an earlier push */
-    if (pending) {
-        const int need = N - have;
-        if (nsym >= need) {
-            if (count < a.max_packets) emit_packet<COSTAS>(a, stream, count, ppos, prot, pscore, pend, have, row, 0);
-            count++;
-            pending = 0;
-        } else {
-            for (int i = lane; i < nsym; i += 64) pend[have + i] = (uint8_t)ring_at<COSTAS>(row, i);
-            have += (int)nsym;
-        }
-    }
-
-    /* 2. the hunt over the positions whose word completes in this push: p_x in [0, P), global p = len - T + p_x; in-push offsets are
-     *    32-bit (X < 2^22), hx = h - (len - T) */
-    const long long base0 = len - T;
-    const int X = T + (int)nsym;
-    const int P = X - n + 1;
-    if (!pending && P > 0 && h < base0 + P) {
-        int hx = h > base0 ? (int)(h - base0) : 0;
-        const int s0 = hx >> 6;                                          /* steps below h hold no candidate */
-        const int steps = (P + 63) >> 6;
-        auto xload = [&](int w) -> unsigned {
-            const int j = 64 * w + lane;
-            if (j >= X) return 0u;
-            return j < T ? (unsigned)tail[j] : ring_at<COSTAS>(row, j - T);
-        };
-        const unsigned long long m0 = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
-        const unsigned long long m1 = n > 64 ? (n == 128 ? ~0ull : ((1ull << (n - 64)) - 1ull)) : 0ull;
-        bool moved = false;
-        /* a chunk: steps s .. s + DF_CHUNK - 1 from plane words s .. s + DF_CHUNK + 1.  The words are not kept across a packet (the
-         * packet's work needs the registers): the chunk after a packet starts at the step that holds the new hx */
-        for (int s = s0; s < steps;) {
-            unsigned long long lo[DF_CHUNK + 2], hi[DF_CHUNK + 2];
-            {
-                unsigned v[DF_CHUNK + 2];
-#pragma unroll
-                for (int k = 0; k < DF_CHUNK + 2; k++) v[k] = k < 2 || s + k - 2 < steps ? xload(s + k) : 0u;
-#pragma unroll
-                for (int k = 0; k < DF_CHUNK + 2; k++) { lo[k] = ballot64(v[k] & 1u); hi[k] = ballot64(v[k] & 2u); }
-            }
-            int px = -1, pk = 0;
-#pragma unroll
-            for (int k = 0; k < DF_CHUNK; k++) {
-                const int gx = 64 * (s + k);
-                if (px >= 0 || s + k >= steps || gx + 63 < hx) continue;
-                const unsigned long long x0 = funnel64(lo[k], lo[k + 1], lane), x1 = funnel64(hi[k], hi[k + 1], lane);
-                unsigned long long d0 = x0 ^ a.sync_lo[0];
-                unsigned long long d1 = x1 ^ a.sync_hi[0] ^ (~x0 & a.sync_lo[0]);
-                int c1 = __popcll(~d1 & d0 & m0), c2 = __popcll(d1 & ~d0 & m0), c3 = __popcll(d1 & d0 & m0);
-                if (n > 64) {
-                    const unsigned long long y0 = funnel64(lo[k + 1], lo[k + 2], lane), y1 = funnel64(hi[k + 1], hi[k + 2], lane);
-                    d0 = y0 ^ a.sync_lo[1];
-                    d1 = y1 ^ a.sync_hi[1] ^ (~y0 & a.sync_lo[1]);
-                    c1 += __popcll(~d1 & d0 & m1); c2 += __popcll(d1 & ~d0 & m1); c3 += __popcll(d1 & d0 & m1);
-                }
-                int best = n - c1 - c2 - c3, r = 0;                      /* the first rotation with the largest count */
-                if (c1 > best) { best = c1; r = 1; }
-                if (c2 > best) { best = c2; r = 2; }
-                if (c3 > best) { best = c3; r = 3; }
-                const unsigned long long mask = ballot64(gx + lane < P && gx + lane >= hx && best >= a.min_score);
-                if (mask) {
-                    const int l = __builtin_ctzll(mask);
-                    pk = __builtin_amdgcn_readlane(best * 4 + r, l);
-                    px = gx + l;
-                }
-            }
-            if (px < 0) {
-                s += DF_CHUNK;
-                continue;
-            }
-            hx = px + n + N;
-            moved = true;
-            const int row0 = px + n - T;                                 /* >= 0: the payload starts in the row */
-            if (hx > X) {                                                /* collects into the next pushes */
-                const int got = (int)nsym - row0;
-                for (int i = lane; i < got; i += 64) pend[i] = (uint8_t)ring_at<COSTAS>(row, row0 + i);
-                pending = 1;
-                have = got;
-                if (lane == 0) { hd->ppos = base0 + px; hd->prot = pk & 3; hd->pscore = pk >> 2; }
-                break;
-            }
-            if (count < a.max_packets) emit_packet<COSTAS>(a, stream, count, base0 + px, pk & 3, pk >> 2, pend, 0, row, row0);
-            count++;
-            s = hx >> 6;
-        }
-        if (moved) h = base0 + hx;
-    }
-
-    /* 3. the carried tail: the last min(len + nsym, nsync - 1) values of D, read before any lane writes */
-    const long long len2 = len + nsym;
-    const int T2 = X < n - 1 ? X : n - 1;
-    unsigned tv[2];
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        const int i = lane + 64 * q;
-        const int j = X - T2 + i;
-        tv[q] = i < T2 ? (j < T ? (unsigned)tail[j] : ring_at<COSTAS>(row, j - T)) : 0u;
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        const int i = lane + 64 * q;
-        if (i < T2) tail[i] = (uint8_t)tv[q];
-    }
-    if (lane == 0) {
-        hd->len = len2;
-        hd->h = h;
-        hd->pending = pending;
-        hd->have = have;
-        a.count[stream] = count;
-    }
+    BytePackets<COSTAS> p = {a, stream, row, st + DEFRAME_PEND_OFFSET};
+    deframe_hunt(a, stream, 4 * (a.nbytes + 2), a.max_packets, st, p);
 }
 
 } // namespace
 
 int launch_deframe(const DeframeArgs &a, hipStream_t s)
 {
-    const dim3 grid((a.nstreams + DF_WAVES - 1) / DF_WAVES), block(64 * DF_WAVES);
+    const dim3 grid((a.nstreams + HUNT_WAVES - 1) / HUNT_WAVES), block(64 * HUNT_WAVES);
     if (a.costas)
         hipLaunchKernelGGL(deframe_kernel<true>, grid, block, 0, s, a);
     else

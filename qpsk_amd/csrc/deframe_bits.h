@@ -1,4 +1,4 @@
-/* deframe_bits.h -- the bit-plane and CRC helpers the deframer kernels share (deframe.hip, deframe_coded.hip) */
+/* deframe_bits.h -- the bit-plane and CRC helpers the deframer kernels share (deframe_hunt.h, deframe.hip, deframe_coded.hip) */
 #ifndef QPSK_DEFRAME_BITS_H
 #define QPSK_DEFRAME_BITS_H
 

@@ -281,21 +281,38 @@ struct DeframeHeader {
 };
 constexpr int DEFRAME_TAIL_OFFSET = 64, DEFRAME_PEND_OFFSET = 192;
 constexpr int DEFRAME_MAX_BYTES = 1024, DEFRAME_MAX_PACKETS = 64, DEFRAME_MAX_NSYM = 1 << 21;
-struct DeframeArgs {
-    const uint8_t *data;          /* exactly one of data [nstreams][nsym] / costas [nstreams][nsym] */
-    const float2 *costas;
+/* what the one hunt (deframe_hunt.h) reads, the base of both pushes' arguments (api.cpp, deframer_hunt_args) */
+struct DeframeHuntArgs {
     int nstreams, nsym;
-    int nsync, min_score, nbytes, max_packets;
-    int bytes_per_lane;           /* ceil((nbytes + 2) / 64): the packet bytes one lane builds */
+    int nsync, min_score;
     uint8_t *state;
     size_t state_stride;
-    const uint8_t *keystream;     /* [nbytes + 2]: the scrambler's keystream packed four dibits to the byte */
-    const uint16_t *crc_adv;      /* [64]: x^(8 k) mod the CRC-16 polynomial, k = the data bytes behind lane l's chunk */
     unsigned long long sync_lo[2], sync_hi[2];   /* bit i % 64 of word i / 64: bit 0 / bit 1 of ring(sync[i]) */
-    int32_t *count;
-    uint8_t *bytes;
     long long *pos;
     int32_t *rot, *score;
+    int32_t *count;               /* last, with bytes first behind it: the decode kernels fetch the two with one scalar load */
+};
+/* a packet's record r = stream * max_packets + slot, by lane 0 */
+__device__ __forceinline__ void report(const DeframeHuntArgs &a, size_t r, long long pos, int rot, int score, int lane)
+{
+    if (a.pos) {                  /* the pointer tests stay scalar branches around lane 0's stores */
+        if (lane == 0) a.pos[r] = pos;
+    }
+    if (a.rot) {
+        if (lane == 0) a.rot[r] = rot;
+    }
+    if (a.score) {
+        if (lane == 0) a.score[r] = score;
+    }
+}
+struct DeframeArgs : DeframeHuntArgs {
+    uint8_t *bytes;
+    const uint8_t *data;          /* exactly one of data [nstreams][nsym] / costas [nstreams][nsym] */
+    const float2 *costas;
+    int nbytes, max_packets;
+    int bytes_per_lane;           /* ceil((nbytes + 2) / 64): the packet bytes one lane builds */
+    const uint8_t *keystream;     /* [nbytes + 2]: the scrambler's keystream packed four dibits to the byte */
+    const uint16_t *crc_adv;      /* [64]: x^(8 k) mod the CRC-16 polynomial, k = the data bytes behind lane l's chunk */
     uint8_t *crc_ok;
 };
 int launch_deframe(const DeframeArgs &a, hipStream_t s);
@@ -304,25 +321,18 @@ int launch_deframe(const DeframeArgs &a, hipStream_t s);
  * packet it completes as a soft row in the staging buffer -- row stream * per_stream + slot, slot = the packet's output row -- and the
  * decode, one wave per staging row (rows at or beyond the stream's count retire at once) */
 constexpr int DEFRAME_CODED_MAX_STEPS = 8 * (DEFRAME_MAX_BYTES + 2) + 6;
-struct DeframeCodedArgs {
+struct DeframeCodedArgs : DeframeHuntArgs {
+    uint8_t *bytes;
     const float2 *costas;         /* [nstreams][nsym] */
     const float *gain;            /* [nstreams]: this push's gain per stream */
     int check_gain;               /* the gains are the caller's: flag a NaN / Inf one */
-    int nstreams, nsym;
-    int nsync, min_score, nbytes, max_packets;
+    int nbytes, max_packets;
     int nsteps;                   /* trellis steps of a packet: 8 (nbytes + 2) + 6 */
     int per_stream;               /* staging rows per stream: min(max_packets, nsym / (nsync + Nc) + 1), the most a push completes */
-    uint8_t *state;
-    size_t state_stride;
-    unsigned long long sync_lo[2], sync_hi[2];
     int8_t *stage;                /* [nstreams * per_stream][stage_pitch][2] (DeframeCodedBody) */
     const uint8_t *flip;          /* [nbody]: the scrambler's keystream dibits, over the body on air */
     const uint16_t *crc_adv;      /* [nbytes]: x^(8 m) mod the CRC-16 polynomial */
     unsigned crc_init;            /* crc16()'s register after nbytes zero bytes from 0xFFFF */
-    int32_t *count;
-    uint8_t *bytes;
-    long long *pos;
-    int32_t *rot, *score;
     uint8_t *crc_ok;
     int32_t *info;
     int *status;

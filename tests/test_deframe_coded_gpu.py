@@ -49,18 +49,18 @@ def want_all(rows, gains, sync, min_score, nbytes, mode="unit", scale=64.0):
     return out
 
 
-def planted_costas(rng, S, total, sync, nbytes, max_err=3, noise=0.3, gap=300):
+def planted_costas(rng, S, total, sync, nbytes, max_err=3, noise=0.3, gap=300, burst=40):
     """S streams of dibits on the diagonals at a random amplitude plus Gaussian noise; packets at random gaps and rotations with
-    0..max_err dibit errors in the word, one in eight with a wrong CRC, one in eight with a stretch of its body replaced by random
-    dibits (beyond the code)"""
+    0..max_err dibit errors in the word, one in eight with a wrong CRC, one in eight with a stretch of `burst` dibits of its body
+    replaced by random dibits (beyond the code)"""
     d = rng.integers(0, 4, (S, total), dtype=np.uint8)
     for s in range(S):
         t = int(rng.integers(0, gap))
         while True:
             pkt, _ = make_coded_packet(rng, sync, nbytes, corrupt=bool(rng.integers(0, 8) == 0))
             if rng.integers(0, 8) == 0:
-                a = len(sync) + int(rng.integers(0, len(pkt) - len(sync) - 40))
-                pkt[a:a + 40] = rng.integers(0, 4, 40, dtype=np.uint8)
+                a = len(sync) + int(rng.integers(0, len(pkt) - len(sync) - burst))
+                pkt[a:a + burst] = rng.integers(0, 4, burst, dtype=np.uint8)
             pkt = turn(pkt, int(rng.integers(0, 4)))
             for i in rng.choice(len(sync), int(rng.integers(0, max_err + 1)), replace=False):
                 pkt[i] = (pkt[i] + 1 + rng.integers(0, 3)) & 3
@@ -119,6 +119,38 @@ def test_one_symbol_per_push_on_a_short_stream():
     m.deframer_reset_coded(S, sync, nbytes, nsync - 3, max_packets=4)
     whole = push_all(m, [z], g[:1])
     assert [[r[1:] for r in x] for x in whole] == [[r[1:] for r in x] for x in got]      # a constant gain: the cuts do not show
+    m.close()
+
+
+EDGE_CUTTINGS = ([1] * 200 + [1300], [97] * 15 + [45])
+
+
+def edge_case(nsync, nbytes):
+    """6 streams of 1500 symbols for a word of nsync dibits, and per cutting the rows, the caller's gains and the reference's records.
+    The seed is chosen so that the reference, before anything is compared with it, shows two packets in every stream and, under either
+    cutting, a packet that ends in a later push than the one that completed its sync word"""
+    rng = np.random.default_rng(200 + nsync)
+    sync = rng.integers(0, 4, nsync, dtype=np.uint8)
+    z = planted_costas(rng, 6, 1500, sync, nbytes, max_err=1, burst=10)
+    cases = []
+    for cuts in EDGE_CUTTINGS:
+        ends = np.cumsum(cuts)
+        rows = rows_of(z, cuts)
+        gains = rng.uniform(20.0, 90.0, (len(rows), 6)).astype(np.float32)
+        want = want_all(rows, gains, sync, nsync - 1, nbytes)
+        assert all(len(w) >= 2 for w in want), [len(w) for w in want]
+        assert any(r[0] > np.searchsorted(ends, r[1] + nsync) for w in want for r in w)
+        cases.append((rows, gains, want))
+    return sync, cases
+
+
+@pytest.mark.parametrize("nsync,nbytes", [(7, 1), (65, 2)])
+def test_words_of_7_and_65_dibits_with_the_caller_s_gains(nsync, nbytes):
+    sync, cases = edge_case(nsync, nbytes)
+    m = modem()
+    for rows, gains, want in cases:
+        m.deframer_reset_coded(6, sync, nbytes, nsync - 1, max_packets=64)
+        assert push_all(m, rows, gains) == want, (nsync, len(rows))
     m.close()
 
 

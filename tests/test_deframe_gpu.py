@@ -94,6 +94,42 @@ def test_planted_words_bit_for_bit_for_every_cut(nsync, nbytes):
     m.close()
 
 
+# ------------------------------------------------------------------- 1b. one and two plane words, on both inputs
+EDGE_CUTTINGS = ([1] * 200 + [1300], [97] * 15 + [45])
+
+
+def edge_case(nsync, nbytes):
+    """6 streams of 1500 dibits for a word of nsync dibits, and per cutting the reference's records.  The seed is chosen so that the
+    reference, before anything is compared with it, shows two packets in every stream and, under either cutting, a packet that ends in
+    a later push than the one that completed its sync word"""
+    rng = np.random.default_rng(101 + nsync)
+    sync = rng.integers(0, 4, nsync, dtype=np.uint8)
+    D = planted_streams(rng, 6, 1500, sync, nbytes, max_err=1)
+    wants = []
+    for cuts in EDGE_CUTTINGS:
+        ends = np.cumsum(cuts)
+        want = [want_of(D[s], cuts, sync, nsync - 1, nbytes) for s in range(6)]
+        assert all(len(w) >= 2 for w in want), [len(w) for w in want]
+        assert any(r[0] > np.searchsorted(ends, r[1] + nsync) for w in want for r in w)
+        wants.append(want)
+    return sync, D, wants
+
+
+@pytest.mark.parametrize("nsync,nbytes", [(7, 1), (65, 2), (128, 5)])
+def test_words_of_7_65_and_128_dibits_on_data_rows_and_on_costas_input(nsync, nbytes):
+    sync, D, wants = edge_case(nsync, nbytes)
+    z = np.stack([np.where(D & 1, -1.0, 1.0), np.where(D & 2, -0.5, 0.5)], axis=-1).astype(np.float32)
+    assert np.array_equal(data_rule(z), D)
+    m = modem()
+    for cuts, want in zip(EDGE_CUTTINGS, wants):
+        at = np.cumsum([0] + cuts)
+        for costas, x in ((False, D), (True, z)):
+            m.deframer_reset(6, sync, nbytes, nsync - 1, max_packets=64)
+            got = push_all(m, [np.ascontiguousarray(x[:, a:b]) for a, b in zip(at[:-1], at[1:])], costas=costas)
+            assert got == want, (nsync, cuts[:2], costas)
+    m.close()
+
+
 # ------------------------------------------------------------------- 2. costas input = its data rule
 def test_costas_input_equals_its_data_rule():
     rng = np.random.default_rng(11)
