@@ -718,6 +718,201 @@ struct ExtAcq {
     const float *seed;
 };
 
+/* ---- which kernel takes a receive batch: decided ONCE, as a route.  rx_route() only reads -- the context and the filled arguments are
+ * const, so it cannot allocate, launch or touch last_kernel -- and everything behind it reads the route: the buffers, the timing
+ * estimate's placement, the launch.  Nothing restates the choice (round 4 restated it for the in-launch FFT estimate and missed a tuning
+ * key: QPSK_PIPE_G above 16 sent the batch to rx_lean_kernel with no index computed).
+ * The pipeline kernels [measured, DESIGN.md 4.1]: rx_lean_kernel wherever its stream serves the shape; rx_fused_pipe_kernel (16-frame
+ * workgroups, four-symbol FIR lanes) for batches below four frames per workgroup, several loops per frame, a costas_frame[] dump and
+ * config 3; rx_pipe2_kernel for those above 16 frames per CU; the generic chunked kernel (kernels.hip) for any other shape. */
+enum RxKind { K_GENERIC, K_FUSED_PIPE, K_PIPE2, K_LEAN };
+
+struct RxRoute {
+    RxKind kind = K_GENERIC;
+    int G = 0;                        /* K_PIPE2, K_LEAN: frames per workgroup */
+    int nf = 0;                       /* K_FUSED_PIPE: FIR waves per workgroup */
+    unsigned long long layout = 0;    /* K_PIPE2, K_LEAN: units per hardware wave */
+    bool pipe_ok = false;             /* the shape the pipeline kernels (rx_fused.hip) are built for */
+    bool fused_fft = false;           /* the FFT timing estimate runs inside the receive launch, not in a launch in front */
+    bool need_pad = false;            /* the caller provides -- K_LEAN on a batch that is not whole workgroups: FusedArgs::sym_pad, G rows */
+    bool data_rule = false;           /* qpsk_rx_batch_data: the kernel writes the data rule's decisions itself (FusedArgs::data_rule) */
+    bool need_dump = false;           /* qpsk_rx_batch_data on any other route: a costas_frame[] dump of the library's own to take them from */
+};
+
+/* the caller's wave layout (measurements): 4 bits per hardware wave = units it owns, waves 1-5 in QPSK_PIPE_LAYOUT_LO, 6-11 in
+ * QPSK_PIPE_LAYOUT_HI; false = neither is set, the library's own layout */
+static bool tuned_layout(const qpsk_ctx *c, unsigned long long *layout)
+{
+    if (c->tune.layout_lo < 0 && c->tune.layout_hi < 0) return false;
+    *layout = ((unsigned long long)(unsigned)tuned(c->tune.layout_lo, 0) << 4) | ((unsigned long long)(unsigned)tuned(c->tune.layout_hi, 0) << 24);
+    return true;
+}
+
+/* a: as rx_batch_common fills it (a.index = the caller's own offsets, a.data_rule = data decisions wanted WITHOUT the slicer's); want_data: a qpsk_rx_batch_data call */
+static int rx_route(const qpsk_ctx *c, const FusedArgs &a, bool want_data, RxRoute *rt)
+{
+    const int nframes = a.nframes, nbw = a.nbw;
+    *rt = RxRoute{};
+    /* the pipeline kernels are built for CYCLES = 8, 16-byte aligned frames and an index below CYCLES */
+    const bool pipe_ok = rt->pipe_ok = c->cycles == pipe_cycles() && (a.frame_size % 2) == 0 && (a.frame_pitch % 2) == 0 &&
+                                       ((uintptr_t)a.x % 16) == 0 && nbw * pipe_frames(1) <= 64 && tuned(c->tune.generic, 0) == 0;
+    /* QPSK_PIPE_V = 3 asks for rx_lean_kernel at any batch size, 1 / 2 for the older kernels */
+    const int by_size = nframes > 16 * c->ncu ? 2 : 1;
+    int pipe_v = tuned(c->tune.pipe_v, by_size);
+    unsigned long long own_layout = 0;
+    const bool has_layout = tuned_layout(c, &own_layout);
+
+    /* rx_lean_kernel (the FIR waves' chunk loop as one hand-written stream) serves even workgroups of frames made of whole chunks, one
+     * loop per frame, symmetric filter, no costas_frame[] dump -- so not a caller who wants data decisions AND the slicer's.  Above 16
+     * frames per CU always (the filter is the limit there); below, both kernels sit on the serial wave and this one is 1-3 % ahead
+     * from four frames per workgroup on (profiles/r05_config2_lean.txt).  A batch that is not whole workgroups rides in the same launch:
+     * the last workgroup's pad frames read the batch's last frame and leave their symbols in the pad rows (round 5's second launch for
+     * them cost one more serial chain, 0.25 + 0.15 ms for 8193 frames against 0.25 for 8192). */
+    if (pipe_ok && c->taps_symmetric && (pipe_v == 3 || c->tune.pipe_v < 0) && !(want_data && !a.data_rule)) {
+        int G = tuned(c->tune.pipe_g, (nframes + c->ncu - 1) / c->ncu);
+        if (G > pipe2_max_frames()) G = pipe2_max_frames();
+        G += G & 1;
+        const bool wanted = pipe_v == 3 || G >= 4;
+        const unsigned long long layout = has_layout ? own_layout : G >= 2 ? lean_default_layout(G / 2) : 0;
+        if (wanted && layout && lean_shape_ok(a, G)) {
+            const LayoutCount n = layout_count(layout);
+            if (n.units == G / 2 && lean_lds_bytes(G, n.nwin) <= (size_t)MAX_LDS_BYTES) {
+                rt->kind = K_LEAN;
+                rt->G = G;
+                rt->layout = layout;
+                rt->need_pad = nframes % G != 0;
+                rt->data_rule = a.data_rule != 0;
+            }
+        }
+    }
+    /* every other shape: the pipeline kernels of rounds 1-2, or the generic chunked kernel */
+    const bool older = rt->kind != K_LEAN && pipe_ok;
+    if (pipe_v == 3) pipe_v = by_size;
+    if (older && pipe_v == 2) {
+        /* rx_pipe2_kernel: up to 32 frames per workgroup, one workgroup per CU when the batch allows it */
+        int G = tuned(c->tune.pipe_g, (nframes + c->ncu - 1) / c->ncu);
+        if (G > pipe2_max_frames()) G = pipe2_max_frames();
+        if (G * nbw > 64) G = 64 / nbw;
+        if (G < 1) G = 1;
+        unsigned long long layout = own_layout;
+        if (has_layout) {      /* its units fix G */
+            const LayoutCount n = layout_count(layout);
+            if (n.units < 1 || (G + 1) / 2 != n.units || pipe2_lds_bytes(G, n.nwin, nbw) > (size_t)MAX_LDS_BYTES)
+                return fail(QPSK_ERR_ARG, "QPSK_PIPE_LAYOUT_*: %d units on %d waves do not match %d frames per workgroup", n.units, n.nwin, G);
+        } else {
+            for (;;) {   /* many loops per frame: the record rings grow, fewer frames fit */
+                layout = pipe2_default_layout((G + 1) / 2);
+                if (layout && pipe2_lds_bytes(G, layout_count(layout).nwin, nbw) <= (size_t)MAX_LDS_BYTES) break;
+                if (G == 1) return fail(QPSK_ERR_ARG, "pipeline geometry does not fit: %d loops per frame", nbw);
+                G--;
+            }
+        }
+        rt->kind = K_PIPE2;
+        rt->G = G;
+        rt->layout = layout;
+    } else if (older) {
+        /* rx_fused_pipe_kernel: 16-frame workgroups (four FIR waves of four frames, fewer when the batch gives a CU fewer frames); a
+         * batch above 16 frames per CU would run them in rounds.  One lane of the serial wave per (frame, loop); rings grow with the loops */
+        const int full = pipe_max_nf();
+        int nf = 1;
+        while (nf < full && (long long)c->ncu * pipe_frames(nf) < nframes) nf++;
+        nf = tuned(c->tune.pipe_nf, nf);
+        if (nf < 1) nf = 1;
+        if (nf > full) nf = full;
+        while (pipe_frames(nf) * nbw > 64 || pipe_lds_bytes(nf, nbw) > (size_t)MAX_LDS_BYTES) {
+            if (nf == 1) return fail(QPSK_ERR_ARG, "pipeline geometry does not fit: nf %d, %d loops per frame", nf, nbw);
+            nf--;
+        }
+        rt->kind = K_FUSED_PIPE;
+        rt->nf = nf;
+    }
+    rt->need_dump = want_data && !rt->data_rule && !a.costas;
+    /* BASELINE config 3's shape -- FFT estimate, rx_fused_pipe_kernel in full 16-frame workgroups -- and rx_lean_kernel where the
+     * estimate fits beside its geometry run the estimate inside the receive launch; every other route gets its indices from a launch in
+     * front (timing_fft_kernel / timing_scan_kernel / ...) */
+    rt->fused_fft = c->prm.timing_mode == QPSK_TIMING_FFT && !a.index && nbw == 1 && tuned(c->tune.fft_fused, 1) != 0 &&
+                    a.frame_size >= timing_fft_first() + timing_fft_nfft() &&
+                    ((rt->kind == K_FUSED_PIPE && rt->nf == pipe_max_nf() && !(a.dbg & (128 | 4))) ||
+                     (rt->kind == K_LEAN && lean_est_ok(a, rt->G, rt->layout)));
+    return QPSK_OK;
+}
+
+/* ---- histogram timing in ONE pass (round 6; rx_fused.hip, rx_hist_kernel): where the context has a guess -- the majority index of its
+ * previous histogram-mode batch -- the scan kernel's workgroup runs the receive path on that guess while it scans, the frames whose true
+ * index differs are redone by a fall-back pass over their list (usually empty), and the batch's own majority becomes the next guess.
+ * *taken = false and nothing launched: no guess yet, a shape the kernel does not serve, or a last batch that missed frames (the caller
+ * goes on with the two-launch route).  Not for an ext call: with its own offsets it needs no estimate, without them it takes the
+ * two-launch route and neither reads nor updates the guess. */
+static int rx_hist_onepass(qpsk_ctx *c, const FusedArgs &a, const RxRoute &rt, int32_t *d_index, bool *taken)
+{
+    *taken = false;
+    /* (QPSK_PIPE_V asks for one of the receive kernels by name) */
+    if (!rt.pipe_ok || !c->taps_symmetric || !scan_fused_ok(c, (const float *)a.x) || c->tune.pipe_v >= 0) return QPSK_OK;
+    if (!c->d_hint) {
+        HIP_TRY(hipMalloc((void **)&c->d_hint, 2 * sizeof(int32_t)));
+        HIP_TRY(hipMemset(c->d_hint, 0, 2 * sizeof(int32_t)));
+        HIP_TRY(hipHostMalloc((void **)&c->h_hist_stats, 4 * sizeof(int32_t), hipHostMallocMapped));
+        HIP_TRY(hipHostGetDevicePointer((void **)&c->d_hist_stats, c->h_hist_stats, 0));
+        c->h_hist_stats[0] = c->h_hist_stats[1] = c->h_hist_stats[2] = -1;
+        c->hint_valid = false;
+    }
+    const int op = tuned(c->tune.hist_onepass, -1);
+    /* the route pays only while the guess holds for EVERY frame: a frame it misses goes through the fall-back pass, whose one
+     * workgroup takes 0.4 ms whatever the count (a serial chain again) against the 0.07 ms the route saves.  Every histogram-mode call
+     * leaves behind how many frames of its batch were off the batch's majority index (or missed by its guess): zero = try the route */
+    const int seen = __atomic_load_n(&c->h_hist_stats[1], __ATOMIC_ACQUIRE), off_majority = __atomic_load_n(&c->h_hist_stats[2], __ATOMIC_ACQUIRE);
+    const bool guess_is_good = seen > 0 && off_majority == 0;
+    if (op == 0 || !c->hint_valid || !(op == 1 || guess_is_good) || !rx_hist_shape_ok(a)) return QPSK_OK;
+    if (int rc = ensure(c, c->index, sizeof(int32_t) * (size_t)a.nframes)) return rc;
+    if (int rc = ensure(c, c->mislist, sizeof(int32_t) * (size_t)a.nframes)) return rc;
+    int32_t *mis_count = c->d_hint + 1;      /* zero: allocation, then every index_majority_kernel */
+    KERNEL_TRY(launch_rx_hist(a, (int32_t *)c->index.p, c->d_hint, (int32_t *)c->mislist.p, mis_count, c->d_status, c->stream));
+    /* the fall-back pass: the generic chunked kernel over the listed frames with their true indices (its grid is sized for the
+     * whole batch: the list's length is known on the device only; workgroups beyond it retire at once) */
+    FusedArgs af = a;
+    af.index = (const int32_t *)c->index.p;
+    af.frame_list = (const int32_t *)c->mislist.p;
+    af.frame_list_count = mis_count;
+    af.G = 4;
+    af.S = 64;
+    KERNEL_TRY(launch_rx_fused(af, c->stream));
+    KERNEL_TRY(launch_index_majority((const int32_t *)c->index.p, a.nframes, c->d_hint, mis_count, c->d_hist_stats, c->stream));
+    c->last_kernel = "rx_hist_kernel (one pass on the guessed index) + rx_fused_kernel (fall-back list)";
+    if (d_index)
+        HIP_TRY(hipMemcpyAsync(d_index, c->index.p, sizeof(int32_t) * (size_t)a.nframes, hipMemcpyDeviceToDevice, c->stream));
+    *taken = true;
+    return QPSK_OK;
+}
+
+/* the receive launch the route names */
+static int rx_launch(qpsk_ctx *c, const FusedArgs &a, const RxRoute &rt)
+{
+    /* only rx_fused_pipe_kernel's full workgroups and rx_lean_kernel look at est_tw; any other kernel would demodulate with fixed_index */
+    if (a.est_tw && !(rt.kind == K_FUSED_PIPE && rt.nf == pipe_max_nf()) && rt.kind != K_LEAN)
+        return fail(QPSK_ERR_STATE, "internal: in-launch FFT timing estimate planned for a kernel that has none");
+    if (a.data_rule && rt.kind != K_LEAN)
+        return fail(QPSK_ERR_STATE, "internal: data rule planned for a kernel that has none");
+    switch (rt.kind) {
+    case K_LEAN:
+        KERNEL_TRY(launch_rx_lean(a, rt.G, rt.layout, c->d_status, c->stream));
+        c->last_kernel = a.est_tw ? "rx_lean_kernel (FFT timing estimate inside the launch)" : "rx_lean_kernel";
+        break;
+    case K_PIPE2:
+        KERNEL_TRY(launch_rx_pipe2(a, rt.G, rt.layout, c->d_status, c->stream));
+        c->last_kernel = "rx_pipe2_kernel";
+        break;
+    case K_FUSED_PIPE:
+        KERNEL_TRY(launch_rx_fused_pipe(a, rt.nf, c->d_status, c->stream));
+        c->last_kernel = a.est_tw ? "rx_fused_pipe_kernel (FFT timing estimate inside the launch)" : "rx_fused_pipe_kernel";
+        break;
+    default:
+        KERNEL_TRY(launch_rx_fused(a, c->stream));
+        c->last_kernel = "rx_fused_kernel";
+    }
+    return QPSK_OK;
+}
+
+/* every qpsk_rx_batch* entry point: check, fill the arguments, route, buffers, one-pass attempt, timing estimate, launch, epilogue */
 static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch, int nframes, int nbw, uint8_t *d_sym,
                            float *d_freq, float *d_phase, float *d_costas, int32_t *d_index, float *d_hz,
                            const ExtAcq *ext = nullptr, uint8_t *d_data = nullptr)
@@ -728,11 +923,6 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
     if (frame_pitch < c->prm.frame_size)
         return fail(QPSK_ERR_ARG, "qpsk_rx_batch_pitched: frame_pitch %lld below frame_size %d", frame_pitch, c->prm.frame_size);
     if (bind(c)) return QPSK_ERR_HIP;
-    /* the pipeline kernel (rx_fused.hip) is built for CYCLES = 8, 16-byte aligned frames and an index
-     * below CYCLES; everything else takes the generic chunked kernel (kernels.hip) */
-    const bool pipe_ok = c->cycles == pipe_cycles() && (c->prm.frame_size % 2) == 0 && (frame_pitch % 2) == 0 &&
-                         ((uintptr_t)d_in % 16) == 0 && nbw * pipe_frames(1) <= 64 &&
-                         tuned(c->tune.generic, 0) == 0;
     FusedArgs a{};
     a.x = reinterpret_cast<const float2 *>(d_in);
     a.frame_pitch = (size_t)frame_pitch;
@@ -754,278 +944,72 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
     a.max_freq = c->max_freq;
     a.rs = c->prm.rs;
     /* qpsk_rx_batch_data: with d_sym NULL, rx_lean_kernel writes the data rule's decisions where the slicer's go (FusedArgs::data_rule);
-     * every other route dumps costas_frame[] and takes the data rule from it behind the launch (below) */
+     * every other route dumps costas_frame[] and takes the data rule from it behind the launch (the epilogue) */
     a.sym = d_sym ? d_sym : d_data;
     a.data_rule = d_data && !d_sym;
-    if (d_data && d_sym && !d_costas) {
-        if (int rd = ensure(c, c->datacostas, sizeof(float2) * (size_t)nframes * (size_t)c->nsym)) return rd;
-        d_costas = (float *)c->datacostas.p;
-    }
     a.freq = d_freq;
     a.phase = d_phase;
     a.costas = reinterpret_cast<float2 *>(d_costas);
     a.hz = d_hz;
     a.status = c->d_status;
-    /* an ext call's seeds: the serial waves apply set_phase() / set_frequency() at the load (kernels.h, seed_setters) */
-    const bool ext_index = ext && ext->index;
+    /* an ext call's offsets: every timing estimate skipped, the kernels check each value where they read it (STATUS_BAD_INDEX); its
+     * seeds: the serial waves apply set_phase() / set_frequency() at the load (kernels.h, seed_setters) */
+    if (ext) a.index = ext->index;
     if (ext && ext->seed) {
         a.state_in = ext->seed;
         a.seed_setters = 1;
     }
 
-    /* ---- which kernel takes the batch: decided ONCE, here, as a plan; the timing estimate's placement (below) reads the plan and
-     * the launches execute it -- nothing restates the choice (round 4 restated it for the in-launch FFT estimate and missed a
-     * tuning key: QPSK_PIPE_G above 16 sent the batch to rx_lean_kernel with no index computed).
-     * The pipeline kernels [measured, DESIGN.md 4.1]: rx_lean_kernel wherever its stream serves the shape in one launch (see below);
-     * rx_fused_pipe_kernel (16-frame workgroups, four-symbol FIR lanes, the FFT timing estimate inside the launch) for ragged batches
-     * up to 16 frames per CU, several loops per frame, a costas_frame[] dump and config 3; rx_pipe2_kernel for those above 16. */
-    enum { K_GENERIC, K_FUSED_PIPE, K_PIPE2, K_LEAN };
-    struct Plan {
-        int kind = K_GENERIC, nframes = 0, G = 0, nf = 0;
-        unsigned long long layout = 0;
-    };
-    const int pipe_v = tuned(c->tune.pipe_v, nframes > 16 * c->ncu ? 2 : 1);
-    /* the pipeline kernels of rounds 1-2 (and the generic chunked kernel): any shape */
-    auto plan_general = [&](int nfr, int pv, Plan *pl) -> int {
-        pl->nframes = nfr;
-        if (pipe_ok && pv == 2) {
-            /* rx_pipe2_kernel: up to 32 frames per workgroup, one workgroup per CU when the batch allows it */
-            int G = (nfr + c->ncu - 1) / c->ncu;
-            if (G > pipe2_max_frames()) G = pipe2_max_frames();
-            G = tuned(c->tune.pipe_g, G);
-            if (G > pipe2_max_frames()) G = pipe2_max_frames();
-            if (G * nbw > 64) G = 64 / nbw;
-            if (G < 1) G = 1;
-            /* wave layout: the library's (pipe2_default_layout), or the caller's for measurements: 4 bits per hardware wave
-             * = units it owns, waves 1-5 in QPSK_PIPE_LAYOUT_LO, 6-11 in QPSK_PIPE_LAYOUT_HI (their sum fixes G's units) */
-            unsigned long long layout = 0;
-            if (c->tune.layout_lo >= 0 || c->tune.layout_hi >= 0) {
-                layout = ((unsigned long long)(unsigned)tuned(c->tune.layout_lo, 0) << 4) |
-                         ((unsigned long long)(unsigned)tuned(c->tune.layout_hi, 0) << 24);
-                int units = 0, nwin = 0;
-                for (int w = 1; w < 16; w++) { const int cw = (int)((layout >> (4 * w)) & 15); units += cw; nwin += cw != 0; }
-                if (units < 1 || (G + 1) / 2 != units || pipe2_lds_bytes(G, nwin, nbw) > (size_t)MAX_LDS_BYTES)
-                    return fail(QPSK_ERR_ARG, "QPSK_PIPE_LAYOUT_*: %d units on %d waves do not match %d frames per workgroup", units, nwin, G);
-            } else {
-                for (;;) {   /* many loops per frame: the record rings grow, fewer frames fit */
-                    layout = pipe2_default_layout((G + 1) / 2);
-                    int nwin = 0;
-                    for (int w = 1; w < 16; w++) nwin += ((layout >> (4 * w)) & 15) != 0;
-                    if (layout && pipe2_lds_bytes(G, nwin, nbw) <= (size_t)MAX_LDS_BYTES) break;
-                    if (G == 1) return fail(QPSK_ERR_ARG, "pipeline geometry does not fit: %d loops per frame", nbw);
-                    G--;
-                }
-            }
-            pl->kind = K_PIPE2;
-            pl->G = G;
-            pl->layout = layout;
-        } else if (pipe_ok) {
-            /* 16-frame workgroups (four FIR waves of four frames, fewer when the batch gives a CU fewer frames); a batch
-             * above 16 frames per CU would run them in rounds */
-            auto fits = [&](int nf_) {   /* one lane of the serial wave per (frame, loop); rings grow with the loops */
-                return pipe_frames(nf_) * nbw <= 64 && pipe_lds_bytes(nf_, nbw) <= (size_t)MAX_LDS_BYTES;
-            };
-            const int full = pipe_max_nf();
-            int nf = 1;
-            while (nf < full && (long long)c->ncu * pipe_frames(nf) < nfr) nf++;
-            nf = tuned(c->tune.pipe_nf, nf);
-            if (nf < 1) nf = 1;
-            if (nf > full) nf = full;
-            while (nf > 1 && !fits(nf)) nf--;
-            if (!fits(nf))
-                return fail(QPSK_ERR_ARG, "pipeline geometry does not fit: nf %d, %d loops per frame", nf, nbw);
-            pl->kind = K_FUSED_PIPE;
-            pl->nf = nf;
-        } else {
-            pl->kind = K_GENERIC;
-        }
-        return QPSK_OK;
-    };
-    /* rx_lean_kernel (the FIR waves' chunk loop as one hand-written stream) serves whole even workgroups of frames made of
-     * whole chunks, one loop per frame, symmetric filter, no costas_frame[] dump; a batch's last partial workgroup and every
-     * other shape go to the kernels above.  QPSK_PIPE_V = 3 asks for it at any batch size, 1 / 2 for the older kernels. */
-    Plan main_pl, rem_pl;
-    bool lean = false;
-    if (pipe_ok && c->taps_symmetric && (pipe_v == 3 || c->tune.pipe_v < 0)) {
-        int G = (nframes + c->ncu - 1) / c->ncu;
-        G = tuned(c->tune.pipe_g, G);
-        if (G > pipe2_max_frames()) G = pipe2_max_frames();
-        G += G & 1;
-        /* above 16 frames per CU: always (the filter is the limit there).  Up to 16 frames per CU both kernels sit on the serial wave,
-         * and since round 5 (LDS-DMA staging, a window per unit, two-unit FIR waves) this one is ahead there too -- 0.1519 against 0.1560 ms
-         * at config 2, 1-2 % at 1024-3584 frames (profiles/r05_config2_lean.txt) -- for batches it takes in ONE launch (whole workgroups
-         * of at least four frames). */
-        /* Round 6: a batch that is not whole workgroups rides in the same launch -- the last workgroup's pad frames read the batch's last
-         * frame and leave their symbols in a pad buffer (round 5 sent the remainder to a SECOND launch: one more 2048-step serial chain,
-         * 0.25 + 0.15 ms for 8193 frames against 0.25 for 8192). */
-        const bool wanted = pipe_v == 3 || G >= 4;
-        unsigned long long layout = 0;
-        if (c->tune.layout_lo >= 0 || c->tune.layout_hi >= 0)
-            layout = ((unsigned long long)(unsigned)tuned(c->tune.layout_lo, 0) << 4) |
-                     ((unsigned long long)(unsigned)tuned(c->tune.layout_hi, 0) << 24);
-        else if (G >= 2)
-            layout = lean_default_layout(G / 2);
-        FusedArgs am = a;
-        if (G >= 2 && nframes % G) {
-            int rp = ensure(c, c->sympad, (size_t)G * (size_t)c->nsym);
-            if (rp) return rp;
-            a.sym_pad = am.sym_pad = (uint8_t *)c->sympad.p;
-        }
-        if (wanted && layout && lean_shape_ok(am, G)) {
-            int nwin = 0, units = 0;
-            for (int w = 1; w < 16; w++) { const int cw = (int)((layout >> (4 * w)) & 15); units += cw; nwin += cw != 0; }
-            if (units == G / 2 && lean_lds_bytes(G, nwin) <= (size_t)MAX_LDS_BYTES) {
-                lean = true;
-                main_pl.kind = K_LEAN;
-                main_pl.nframes = am.nframes;
-                main_pl.G = G;
-                main_pl.layout = layout;
-            }
-        }
+    RxRoute rt;
+    if (int rc = rx_route(c, a, d_data != nullptr, &rt)) return rc;
+
+    /* ---- what the route asks the caller for */
+    a.data_rule = rt.data_rule;
+    if (rt.need_pad) {
+        if (int rc = ensure(c, c->sympad, (size_t)rt.G * (size_t)c->nsym)) return rc;
+        a.sym_pad = (uint8_t *)c->sympad.p;
     }
-    if (!lean) {
-        int rp = plan_general(nframes, pipe_v == 3 ? (nframes > 16 * c->ncu ? 2 : 1) : pipe_v, &main_pl);
-        if (rp) return rp;
-        if (d_data && !a.costas) {
-            if (int rd = ensure(c, c->datacostas, sizeof(float2) * (size_t)nframes * (size_t)c->nsym)) return rd;
-            a.costas = (float2 *)c->datacostas.p;
-        }
-        a.data_rule = 0;
+    if (rt.need_dump) {
+        if (int rc = ensure(c, c->datacostas, sizeof(float2) * (size_t)nframes * (size_t)c->nsym)) return rc;
+        a.costas = (float2 *)c->datacostas.p;
     }
 
-    /* ---- histogram timing in ONE pass (round 6; rx_fused.hip, rx_hist_kernel): where the context has a guess -- the majority index of
-     * its previous histogram-mode batch -- the scan kernel's workgroup runs the receive path on that guess while it scans, the frames
-     * whose true index differs are redone by a fall-back pass over their list (usually empty), and the batch's own majority becomes
-     * the next guess.  No guess yet, a shape the kernel does not serve, or a last batch that missed more than an eighth of its frames
-     * (a batch of mixed indices: the fall-back pass would carry it): the two-launch route below. */
-    const bool hist_mode = c->prm.timing_mode == QPSK_TIMING_HIST;
-    /* (an ext call neither reads nor updates the guess: with its own offsets it needs no estimate, without them it takes the two-launch route) */
-    if (hist_mode && !ext && pipe_ok && c->taps_symmetric && scan_fused_ok(c, d_in) && c->tune.pipe_v < 0) {      /* (QPSK_PIPE_V asks for one of the receive kernels by name) */
-        if (!c->d_hint) {
-            HIP_TRY(hipMalloc((void **)&c->d_hint, 2 * sizeof(int32_t)));
-            HIP_TRY(hipMemset(c->d_hint, 0, 2 * sizeof(int32_t)));
-            HIP_TRY(hipHostMalloc((void **)&c->h_hist_stats, 4 * sizeof(int32_t), hipHostMallocMapped));
-            HIP_TRY(hipHostGetDevicePointer((void **)&c->d_hist_stats, c->h_hist_stats, 0));
-            c->h_hist_stats[0] = c->h_hist_stats[1] = c->h_hist_stats[2] = -1;
-            c->hint_valid = false;
-        }
-        FusedArgs ah = a;
-        const int op = tuned(c->tune.hist_onepass, -1);
-        /* the route pays only while the guess holds for EVERY frame: a frame it misses goes through the fall-back pass, whose one
-         * workgroup takes 0.4 ms whatever the count (a serial chain again) against the 0.07 ms the route saves.  Every histogram-mode call
-         * leaves behind how many frames of its batch were off the batch's majority index (or missed by its guess): zero = try the route */
-        const int seen = __atomic_load_n(&c->h_hist_stats[1], __ATOMIC_ACQUIRE), off_majority = __atomic_load_n(&c->h_hist_stats[2], __ATOMIC_ACQUIRE);
-        const bool guess_is_good = seen > 0 && off_majority == 0;
-        if (op != 0 && c->hint_valid && (op == 1 || guess_is_good) && rx_hist_shape_ok(ah)) {
-            int r1 = ensure(c, c->index, sizeof(int32_t) * (size_t)nframes);
-            if (r1) return r1;
-            r1 = ensure(c, c->mislist, sizeof(int32_t) * (size_t)nframes);
-            if (r1) return r1;
-            int32_t *mis_count = c->d_hint + 1;      /* zero: allocation, then every index_majority_kernel */
-            KERNEL_TRY(launch_rx_hist(ah, (int32_t *)c->index.p, c->d_hint, (int32_t *)c->mislist.p, mis_count, c->d_status, c->stream));
-            /* the fall-back pass: the generic chunked kernel over the listed frames with their true indices (its grid is sized for the
-             * whole batch: the list's length is known on the device only; workgroups beyond it retire at once) */
-            FusedArgs af = a;
-            af.index = (const int32_t *)c->index.p;
-            af.frame_list = (const int32_t *)c->mislist.p;
-            af.frame_list_count = mis_count;
-            af.G = 4;
-            af.S = 64;
-            KERNEL_TRY(launch_rx_fused(af, c->stream));
-            KERNEL_TRY(launch_index_majority((const int32_t *)c->index.p, nframes, c->d_hint, mis_count, c->d_hist_stats, c->stream));
-            c->last_kernel = "rx_hist_kernel (one pass on the guessed index) + rx_fused_kernel (fall-back list)";
-            if (d_index)
-                HIP_TRY(hipMemcpyAsync(d_index, c->index.p, sizeof(int32_t) * (size_t)nframes, hipMemcpyDeviceToDevice, c->stream));
-            return QPSK_OK;
-        }
+    const bool hist_guess = c->prm.timing_mode == QPSK_TIMING_HIST && !ext;      /* the call reads and updates the one-pass route's guess */
+    if (hist_guess) {
+        bool taken = false;
+        const int rc = rx_hist_onepass(c, a, rt, d_index, &taken);
+        if (rc || taken) return rc;
     }
 
-    /* ---- the timing estimate.  BASELINE config 3's shape -- FFT estimate, ONE launch of rx_fused_pipe_kernel in full 16-frame
-     * workgroups, as the plan says -- runs the estimate inside the receive launch (rx_fused.hip); every other plan gets its indices
-     * from a launch in front (timing_fft_kernel / timing_scan_kernel / ...). */
-    bool fused_fft = false;
-    double *est_tw = nullptr, *est_cs = nullptr;
-    if (c->prm.timing_mode == QPSK_TIMING_FFT && !ext_index && rem_pl.nframes == 0 && nbw == 1 && tuned(c->tune.fft_fused, 1) != 0 &&
-        c->prm.frame_size >= timing_fft_first() + timing_fft_nfft() &&
-        ((main_pl.kind == K_FUSED_PIPE && main_pl.nf == pipe_max_nf() && !(tuned(c->tune.pipe_variant, 0) & (128 | 4))) ||
-         (main_pl.kind == K_LEAN && lean_est_ok(a, main_pl.G, main_pl.layout)))) {
-        int rt = fft_timing_tables(c, &est_tw, &est_cs);
-        if (rt) return rt;
-        fused_fft = true;
+    /* ---- the timing estimate: inside the receive launch where the route says so (the kernel leaves the indices in c->index when the
+     * caller wants them), else from a launch in front */
+    const int32_t *idx = a.index;
+    if (!idx) {
+        if (int rc = timing_indices(c, d_in, (size_t)frame_pitch, nframes, &idx, rt.fused_fft)) return rc;
+        a.index = idx;
     }
-    const int32_t *idx = nullptr;
-    if (ext_index) {
-        idx = ext->index;      /* every timing estimate skipped; the kernels check each value where they read it (STATUS_BAD_INDEX) */
-    } else {
-        int rc = timing_indices(c, d_in, (size_t)frame_pitch, nframes, &idx, fused_fft);
-        if (rc) return rc;
-    }
-    a.index = idx;
-    if (fused_fft) {
+    if (rt.fused_fft) {
+        double *est_tw = nullptr, *est_cs = nullptr;
+        if (int rc = fft_timing_tables(c, &est_tw, &est_cs)) return rc;
         a.est_tw = reinterpret_cast<const double2 *>(est_tw);
         a.est_cs = reinterpret_cast<const double2 *>(est_cs);
         a.index_out = d_index ? (int32_t *)c->index.p : nullptr;
         if (d_index) idx = (const int32_t *)c->index.p;      /* copied to the caller's array behind the launch, below */
     }
 
-    /* ---- the launches */
-    auto execute = [&](const FusedArgs &fa, const Plan &pl) -> int {
-        /* only rx_fused_pipe_kernel's full workgroups and rx_lean_kernel look at est_tw; any other kernel would demodulate with fixed_index */
-        if (fa.est_tw && !(pl.kind == K_FUSED_PIPE && pl.nf == pipe_max_nf()) && pl.kind != K_LEAN)
-            return fail(QPSK_ERR_STATE, "internal: in-launch FFT timing estimate planned for a kernel that has none");
-        if (fa.data_rule && pl.kind != K_LEAN)
-            return fail(QPSK_ERR_STATE, "internal: data rule planned for a kernel that has none");
-        switch (pl.kind) {
-        case K_LEAN:
-            KERNEL_TRY(launch_rx_lean(fa, pl.G, pl.layout, c->d_status, c->stream));
-            c->last_kernel = fa.est_tw ? "rx_lean_kernel (FFT timing estimate inside the launch)" : "rx_lean_kernel";
-            break;
-        case K_PIPE2:
-            KERNEL_TRY(launch_rx_pipe2(fa, pl.G, pl.layout, c->d_status, c->stream));
-            c->last_kernel = "rx_pipe2_kernel";
-            break;
-        case K_FUSED_PIPE:
-            KERNEL_TRY(launch_rx_fused_pipe(fa, pl.nf, c->d_status, c->stream));
-            c->last_kernel = fa.est_tw ? "rx_fused_pipe_kernel (FFT timing estimate inside the launch)" : "rx_fused_pipe_kernel";
-            break;
-        default:
-            KERNEL_TRY(launch_rx_fused(fa, c->stream));
-            c->last_kernel = "rx_fused_kernel";
-        }
-        return QPSK_OK;
-    };
-    {
-        FusedArgs am = a;
-        am.nframes = main_pl.nframes;
-        int rc2 = execute(am, main_pl);
-        if (rc2) return rc2;
-        if (rem_pl.nframes > 0) {
-            FusedArgs ar = a;
-            const size_t o = (size_t)main_pl.nframes;
-            ar.nframes = rem_pl.nframes;
-            ar.x += o * a.frame_pitch;
-            if (ar.index) ar.index += o;
-            if (ar.state_in) ar.state_in += 2 * o * (size_t)nbw;
-            ar.sym += o * (size_t)a.nsym;
-            if (ar.freq) ar.freq += o;
-            if (ar.phase) ar.phase += o;
-            if (ar.hz) ar.hz += o;
-            const char *lk = c->last_kernel;
-            rc2 = execute(ar, rem_pl);
-            if (rc2) return rc2;
-            c->last_kernel = lk;
-        }
-    }
-    if (hist_mode && !ext && c->d_hint && idx && tuned(c->tune.hist_onepass, -1) != 0) {
+    if (int rc = rx_launch(c, a, rt)) return rc;
+
+    /* ---- the epilogue */
+    if (hist_guess && c->d_hint && idx && tuned(c->tune.hist_onepass, -1) != 0) {
         /* the batch's majority index as the next histogram-mode call's guess (one workgroup, in stream order) */
         KERNEL_TRY(launch_index_majority(idx, nframes, c->d_hint, c->d_hint + 1, c->d_hist_stats, c->stream));
         c->hint_valid = true;
     }
-    if (main_pl.kind == K_LEAN && (nframes & 1)) {
+    if (rt.kind == K_LEAN && (nframes & 1)) {
         /* the last frame of an odd batch shares its two-frame unit with a pad frame: the unit's rows are pad rows (rx_fused.hip,
          * lean_unit_rows); its own row goes to its place behind the launch */
-        const size_t last0 = (size_t)((nframes - 1) / main_pl.G) * (size_t)main_pl.G;      /* the last workgroup's first frame */
-        HIP_TRY(hipMemcpyAsync(a.sym + (size_t)(nframes - 1) * (size_t)c->nsym, (const uint8_t *)c->sympad.p + ((size_t)(nframes - 1) - last0) * (size_t)c->nsym,
+        const size_t last0 = (size_t)((nframes - 1) / rt.G) * (size_t)rt.G;      /* the last workgroup's first frame */
+        HIP_TRY(hipMemcpyAsync(a.sym + (size_t)(nframes - 1) * (size_t)c->nsym, a.sym_pad + ((size_t)(nframes - 1) - last0) * (size_t)c->nsym,
                                (size_t)c->nsym, hipMemcpyDeviceToDevice, c->stream));
     }
     if (d_data && !a.data_rule)      /* qpsk_rx_batch_data off rx_lean_kernel: the data rule over the costas_frame[] just written */
@@ -1041,23 +1025,26 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
     return QPSK_OK;
 }
 
+/* what every single-loop entry point does first, ahead of its own argument checks: the context's device, and its own (alpha, beta) back
+ * in d_gains[0].  A null context passes: rx_batch_common reports it, behind those checks */
+static int rx_prologue(qpsk_ctx *c)
+{
+    if (!c) return QPSK_OK;
+    if (bind(c)) return QPSK_ERR_HIP;
+    return use_context_gains(c);
+}
+
 int qpsk_rx_batch(qpsk_ctx *c, const float *d_in, int nframes, uint8_t *d_sym, float *d_freq, float *d_phase,
                   float *d_costas, int32_t *d_index, float *d_hz)
 {
-    if (c) {
-        if (bind(c)) return QPSK_ERR_HIP;
-        if (int rg = use_context_gains(c)) return rg;
-    }
+    if (int rp = rx_prologue(c)) return rp;
     return rx_batch_common(c, d_in, 0, nframes, 1, d_sym, d_freq, d_phase, d_costas, d_index, d_hz);
 }
 
 int qpsk_rx_batch_pitched(qpsk_ctx *c, const float *d_in, long long frame_pitch, int nframes, uint8_t *d_sym, float *d_freq,
                           float *d_phase, float *d_costas, int32_t *d_index, float *d_hz)
 {
-    if (c) {
-        if (bind(c)) return QPSK_ERR_HIP;
-        if (int rg = use_context_gains(c)) return rg;
-    }
+    if (int rp = rx_prologue(c)) return rp;
     if (frame_pitch <= 0) return fail(QPSK_ERR_ARG, "qpsk_rx_batch_pitched: frame_pitch = %lld", frame_pitch);
     return rx_batch_common(c, d_in, frame_pitch, nframes, 1, d_sym, d_freq, d_phase, d_costas, d_index, d_hz);
 }
@@ -1088,10 +1075,7 @@ int qpsk_rx_batch_bw(qpsk_ctx *c, const float *d_in, int nframes, const float *h
 int qpsk_rx_batch_ext(qpsk_ctx *c, const float *d_in, long long frame_pitch, int nframes, const int32_t *d_index_in, const float *d_seed,
                       uint8_t *d_sym, float *d_freq, float *d_phase, float *d_costas, int32_t *d_index, float *d_hz)
 {
-    if (c) {
-        if (bind(c)) return QPSK_ERR_HIP;
-        if (int rg = use_context_gains(c)) return rg;
-    }
+    if (int rp = rx_prologue(c)) return rp;
     if (frame_pitch < 0) return fail(QPSK_ERR_ARG, "qpsk_rx_batch_ext: frame_pitch = %lld", frame_pitch);
     const ExtAcq ext = {d_index_in, d_seed};
     return rx_batch_common(c, d_in, frame_pitch, nframes, 1, d_sym, d_freq, d_phase, d_costas, d_index, d_hz, &ext);
@@ -1100,10 +1084,7 @@ int qpsk_rx_batch_ext(qpsk_ctx *c, const float *d_in, long long frame_pitch, int
 int qpsk_rx_batch_data(qpsk_ctx *c, const float *d_in, long long frame_pitch, int nframes, const int32_t *d_index_in, const float *d_seed,
                        uint8_t *d_data, uint8_t *d_sym, float *d_freq, float *d_phase, int32_t *d_index, float *d_hz)
 {
-    if (c) {
-        if (bind(c)) return QPSK_ERR_HIP;
-        if (int rg = use_context_gains(c)) return rg;
-    }
+    if (int rp = rx_prologue(c)) return rp;
     if (frame_pitch < 0) return fail(QPSK_ERR_ARG, "qpsk_rx_batch_data: frame_pitch = %lld", frame_pitch);
     if (!d_data) return fail(QPSK_ERR_ARG, "qpsk_rx_batch_data: d_data is NULL");
     const ExtAcq ext = {d_index_in, d_seed};

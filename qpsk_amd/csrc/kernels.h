@@ -108,11 +108,23 @@ int pipe2_max_frames(void);
 int pipe2_max_units_per_wave(void);
 int pipe2_max_hw_waves(void);
 unsigned long long pipe2_default_layout(int NU);        /* 4 bits per hardware wave: units it owns; 0 if NU does not fit */
+/* what a wave layout adds up to: the two-frame units of all its waves, and the waves that own any (one frame window each) */
+struct LayoutCount { int units, nwin; };
+inline LayoutCount layout_count(unsigned long long layout)
+{
+    LayoutCount n = {0, 0};
+    for (int w = 1; w < 16; w++) {
+        const int cw = (int)((layout >> (4 * w)) & 15);
+        n.units += cw;
+        n.nwin += cw != 0;
+    }
+    return n;
+}
 int launch_rx_pipe2(const FusedArgs &a, int G, unsigned long long layout, int *status, hipStream_t s);
 /* rx_fused.hip: the same pipeline with the FIR waves' chunk loop as one hand-written stream (fir_lean_asm.h) */
 size_t lean_lds_bytes(int G, int nwin);
 unsigned long long lean_default_layout(int NU);         /* rx_lean_kernel: 1, 5, 5, 5 units on SIMDs 0-3 for a full workgroup */
-bool lean_shape_ok(const FusedArgs &a, int G);          /* one loop per frame, whole chunks, whole even workgroups, ... */
+bool lean_shape_ok(const FusedArgs &a, int G);          /* one loop per frame, whole chunks, an even workgroup size, ... */
 int launch_rx_lean(const FusedArgs &a, int G, unsigned long long layout, int *status, hipStream_t s);
 bool lean_est_ok(const FusedArgs &a, int G, unsigned long long layout);   /* the FFT timing estimate inside rx_lean_kernel's launch fits this geometry */
 /* rx_fused.hip: the reference's histogram timing mode in ONE pass (timing scan + receive path on a guessed index, verified per frame) */
