@@ -1418,25 +1418,6 @@ static size_t viterbi_chunk_rows(const qpsk_ctx *c, size_t rows, size_t per_row,
 /* both decoders: who = the entry point's name; punct = NULL for rate 1/2, otherwise the checked pattern: the rows then hold the ntx
  * transmitted dibits of nsteps steps, and row_pitch and d_flip go by ntx.  The residency rule, the scratch and the chunks go by nsteps */
 static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const Puncture *punct,
-                        const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info);
-
-int qpsk_viterbi_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const uint8_t *d_flip, int flags,
-                       uint8_t *d_bits, int32_t *d_info)
-{
-    return viterbi_impl(c, "qpsk_viterbi_batch", d_soft, row_pitch, nrows, nsteps, nullptr, d_flip, flags, d_bits, d_info);
-}
-
-int qpsk_viterbi_punct_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, int period, uint32_t keep0,
-                             uint32_t keep1, const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info)
-{
-    Puncture p;
-    if (!c) return fail(QPSK_ERR_ARG, "qpsk_viterbi_punct_batch: null context or input");
-    c->viterbi_launches = 0;      /* a refused pattern made none */
-    if (int rc = punct_make("qpsk_viterbi_punct_batch", period, keep0, keep1, &p)) return rc;
-    return viterbi_impl(c, "qpsk_viterbi_punct_batch", d_soft, row_pitch, nrows, nsteps, &p, d_flip, flags, d_bits, d_info);
-}
-
-static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const Puncture *punct,
                         const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info)
 {
     if (c) c->viterbi_launches = 0;      /* a refused call made none */
@@ -1481,6 +1462,22 @@ static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long
     return QPSK_OK;
 }
 
+int qpsk_viterbi_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const uint8_t *d_flip, int flags,
+                       uint8_t *d_bits, int32_t *d_info)
+{
+    return viterbi_impl(c, "qpsk_viterbi_batch", d_soft, row_pitch, nrows, nsteps, nullptr, d_flip, flags, d_bits, d_info);
+}
+
+int qpsk_viterbi_punct_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, int period, uint32_t keep0,
+                             uint32_t keep1, const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info)
+{
+    Puncture p;
+    if (!c) return fail(QPSK_ERR_ARG, "qpsk_viterbi_punct_batch: null context or input");
+    c->viterbi_launches = 0;      /* a refused pattern made none */
+    if (int rc = punct_make("qpsk_viterbi_punct_batch", period, keep0, keep1, &p)) return rc;
+    return viterbi_impl(c, "qpsk_viterbi_punct_batch", d_soft, row_pitch, nrows, nsteps, &p, d_flip, flags, d_bits, d_info);
+}
+
 int qpsk_costas_batch(qpsk_ctx *c, const float *d_symbols_in, int nframes, int nsym, float *d_state, uint8_t *d_sym,
                       float *d_costas)
 {
@@ -1523,9 +1520,101 @@ int qpsk_fft_batch(qpsk_ctx *c, const double *d_in, double *d_out, int nbatch, i
 }
 
 /* --------------------------------------------------------------- streams */
-static bool stream_scan_ok(const qpsk_ctx *c, bool pcm, bool shared_carrier);
-static int streams_usable(qpsk_ctx *c, const char *who);
-static bool stream_block_ok(const qpsk_ctx *c, bool pcm = true);
+/* A stream call enqueues several launches and keeps host-side books about them (which carrier table is current, the relay's turn, a
+ * table half built).  If it fails between its launches -- or a kernel reports that it gave up (QPSK_ERR_HIP from the status word) -- the
+ * carried state of the streams is undefined: the shared carrier is dropped and every later stream call is refused until
+ * qpsk_streams_reset().  Argument errors and flagged NUMBERS (QPSK_ERR_RANGE: NaN samples, a phase beyond the bounded wrap) do not
+ * poison: the kernels completed and the state is what the reference's would be or fenced as documented. */
+static int stream_call_done(qpsk_ctx *c, int rc)
+{
+    if (rc == QPSK_ERR_HIP || rc == QPSK_ERR_ALLOC) {
+        c->streams_poisoned = true;
+        c->carrier_shared = false;
+        c->carrier_pending = nullptr;
+    }
+    return rc;
+}
+
+static int streams_usable(qpsk_ctx *c, const char *who)
+{
+    if (c->nstreams <= 0) return fail(QPSK_ERR_STATE, "call qpsk_streams_reset() first");
+    if (c->streams_poisoned)
+        return fail(QPSK_ERR_STATE, "%s: an earlier stream call failed between its launches; the streams' carried state is undefined until qpsk_streams_reset()", who);
+    c->stream_work_unchecked = true;      /* every caller goes on to enqueue stream work (or to read what such work left) */
+    return QPSK_OK;
+}
+
+/* ---- which kernels take a block of the running streams: decided ONCE per call, as a route (rx_route()'s twin).  stream_route() only
+ * reads -- the context is const, so it cannot launch, allocate or touch the carrier's books, last_kernel or streams_poisoned -- and
+ * stream_run() and the host entry execute what it says.  tests/test_stream_route_gpu.py pins the route on either side of every threshold. */
+enum StreamKind { SK_BLOCK, SK_SCAN, SK_APART };      /* stream_block_kernel; stream_scan_kernel + costas_pipe_kernel; the kernels apart */
+struct StreamRoute {
+    StreamKind kind = SK_APART;
+    bool mixer = false;        /* PCM that neither kernel takes: mixer_kernel first, and kind is the route of the MIXED block, as complex input */
+    bool carrier = false;      /* the launch that reads the PCM takes its phases from the streams' one carrier table (carrier.h) */
+};
+
+/* One launch per block (streamblock.hip) instead of the five-kernel composition: few, short streams -- the reference's call
+ * pattern, where the launches are the cost.  Histogram or fixed timing (the FFT estimate keeps its own kernel). */
+static bool stream_block_ok(const qpsk_ctx *c, bool pcm)
+{
+    const int t = tuned(c->tune.stream_block, -1);
+    if (t == 0 || c->prm.timing_mode == QPSK_TIMING_FFT || c->prm.frame_size > stream_block_max_frame() ||
+        c->nsym * c->cycles > c->prm.frame_size || tuned(c->tune.generic, 0) != 0 ||
+        stream_block_lds_bytes(c->prm.frame_size, c->nsym) > (size_t)MAX_LDS_BYTES)
+        return false;
+    /* [measured, profiles/r04_streams_short_blocks.txt: PCM streams back to back] the kernels apart cost 70 us (512-sample blocks) to
+     * 220 us (2048) whatever the count -- launches and serial chains -- and this kernel ~17 us + 13.5 ns per 512 samples of a stream:
+     * it wins up to ~4 M samples per block of all streams (7800 x 512, 4400 x 1024, 2400 x 2048).  Complex input: round 4's first rule */
+    const long long nl = (long long)c->nstreams * c->prm.frame_size;
+    /* complex input has no carrier chain in front of it: at CYCLES = 8 the kernels apart (hand-scheduled filter, 8-lane scan) take 29 us
+     * at 1024 x 512 and 55 us at 256 x 2048, where this kernel takes 27 and 73 -- it keeps the small batches (<= 0.4 M samples); at other
+     * rates the kernels apart run the generic scan (72 us at 2048 x 512 against 40 here) and the PCM rule holds */
+    return t == 1 || (pcm || c->cycles != 8 ? nl <= 3500000LL : nl <= 400000LL);
+}
+
+/* Many streams, histogram timing: mixer, filter and scan as ONE kernel (streamscan.hip) -- the carrier recurrences run a tile ahead
+ * of the filter waves of the same workgroup, PCM comes in at 2 bytes per sample, no mixed block goes through HBM and the scan
+ * reads the filtered samples from LDS.  A workgroup takes 16 streams through the whole block (its time does not shrink with the
+ * batch), so it pays from about 2500 streams on; below that the kernels apart are quicker. */
+static bool stream_scan_ok(const qpsk_ctx *c, bool pcm, bool shared_carrier)
+{
+    /* [measured, profiles/r04_streams_blocks.txt] 2560 streams: PCM input 0.94 against 1.03 ms per block with the kernels apart, complex
+     * input 0.79 against 0.70; 4096 streams: 1.00 against 1.27 and 0.92 against 1.01.  With the streams' one carrier from the table
+     * (MODE 2: no mixer wave, no mixer kernel) PCM input pays from 1024 streams on: 0.73 against 0.79 ms there, 0.75 against 0.93 at
+     * 2048, 0.76 against 1.00 at 2560 (profiles/r04_streams_carrier.txt) */
+    const int from = pcm ? (shared_carrier ? 1024 : 2560) : 3584;
+    bool wanted = c->nstreams >= from;
+    /* short blocks (the one-launch kernel's range), shared carrier: a workgroup's time shrinks with the block, so the kernel pays from
+     * ~1.4 M samples per block of all streams on -- 106.7 us against 151.9 (one launch per block) and 117.1 (kernels apart) at
+     * 1024 x 2048, 61.8 against 95.9 and 80.6 at 2048 x 1024, 41.7 against 71.7 and 61.8 at 4096 x 512; below that the one-launch
+     * kernel is ahead (profiles/r04_streams_short_blocks.txt) */
+    if (pcm && shared_carrier && c->prm.frame_size <= stream_block_max_frame())
+        wanted = (long long)c->nstreams * c->prm.frame_size >= 1400000LL && c->nstreams >= 256;
+    return c->taps_symmetric && tuned(c->tune.fir_generic, 0) == 0 && tuned(c->tune.generic, 0) == 0 && (c->cycles == 8 || c->cycles == 4) &&
+           (c->prm.timing_mode == QPSK_TIMING_HIST || c->prm.timing_mode == QPSK_TIMING_FIXED) && c->prm.frame_size % stream_scan_tile() == 0 &&
+           tuned(c->tune.stream_scan, wanted ? 1 : 0) != 0;
+}
+
+/* pcm: in is int16 PCM, otherwise complex float samples; want_sym: the caller takes the symbols (the one-launch kernel always writes them) */
+static void stream_route(const qpsk_ctx *c, bool pcm, const void *in, bool want_sym, StreamRoute *rt)
+{
+    *rt = StreamRoute{};
+    rt->carrier = pcm && c->carrier_shared && tuned(c->tune.stream_carrier, 1) != 0;      /* the one carrier is in use */
+    bool aligned = (uintptr_t)in % (pcm ? 4 : 16) == 0;      /* what stream_scan_kernel loads: 4 bytes of PCM, 16 of complex samples */
+    for (;;) {
+        const bool scan = aligned && stream_scan_ok(c, pcm, rt->carrier);
+        /* streams that both stream_scan_kernel and the one-launch kernel would take: which of the two */
+        const bool block = want_sym && stream_block_ok(c, pcm) && !(scan && tuned(c->tune.stream_block, -1) != 1);
+        rt->kind = block ? SK_BLOCK : scan ? SK_SCAN : SK_APART;
+        if (!pcm || rt->kind != SK_APART) return;
+        /* PCM that neither kernel takes: mixer_kernel in front, and a second decision for the mixed block -- complex input like a caller's,
+         * so many streams of it still go to stream_scan_kernel.  Its alignment needs no pointer: the block lies at the start of the
+         * context's `mixed` buffer, which hipMalloc (ensure()) aligns to 256 bytes whenever it comes to be allocated */
+        rt->mixer = aligned = true;
+        rt->carrier = pcm = false;
+    }
+}
 
 int qpsk_streams_reset(qpsk_ctx *c, int nstreams, double mixer_hz)
 {
@@ -1566,7 +1655,7 @@ int qpsk_streams_reset(qpsk_ctx *c, int nstreams, double mixer_hz)
     c->carrier_blocks = 0;
     c->carrier_scans = 0;
     c->carrier_pending = nullptr;
-    if (c->prm.frame_size % 2 == 0 && (stream_scan_ok(c, true, true) || stream_block_ok(c))) {      /* (a kernel that uses it would take these streams) */
+    if (c->prm.frame_size % 2 == 0 && (stream_scan_ok(c, true, true) || stream_block_ok(c, true))) {      /* (a kernel that uses it would take these streams) */
         KERNEL_TRY(launch_carrier_table(c->s_cstate, c->s_ctab, c->prm.frame_size, false, c->stream));
         c->carrier_shared = true;
     }
@@ -1585,6 +1674,19 @@ static int carrier_to_streams(qpsk_ctx *c)
     if (!c->carrier_shared) return QPSK_OK;
     KERNEL_TRY(launch_carrier_broadcast(c->s_cstate, c->s_mixer, c->nstreams, c->stream));
     c->carrier_shared = false;
+    return QPSK_OK;
+}
+
+/* In front of a launch that reads PCM.  use (StreamRoute::carrier): *cur = the table of this block's phases, *next = the one the launch fills for
+ * the block after it (s_ctab's halves take turns; the caller commits the books once its launch is in the stream).  Otherwise both stay NULL:
+ * the launch runs every stream's own mixer state, and the carrier, if there was one, ends here */
+static int stream_carrier(qpsk_ctx *c, bool use, const float **cur, float **next)
+{
+    *cur = *next = nullptr;
+    if (!use) return carrier_to_streams(c);
+    const size_t L2 = 2 * (size_t)c->prm.frame_size;
+    *cur = c->s_ctab + L2 * (c->carrier_blocks & 1u);
+    *next = c->s_ctab + L2 * ((c->carrier_blocks + 1u) & 1u);
     return QPSK_OK;
 }
 
@@ -1608,48 +1710,20 @@ int qpsk_streams_get_loop_state(qpsk_ctx *c, float *h_state)
     return check_status(c);
 }
 
-/* One launch per block (streamblock.hip) instead of the five-kernel composition: few, short streams -- the reference's call
- * pattern, where the launches are the cost.  Histogram or fixed timing (the FFT estimate keeps its own kernel). */
-static bool stream_block_ok(const qpsk_ctx *c, bool pcm)
-{
-    const int t = tuned(c->tune.stream_block, -1);
-    if (t == 0 || c->prm.timing_mode == QPSK_TIMING_FFT || c->prm.frame_size > stream_block_max_frame() ||
-        c->nsym * c->cycles > c->prm.frame_size || tuned(c->tune.generic, 0) != 0 ||
-        stream_block_lds_bytes(c->prm.frame_size, c->nsym) > (size_t)MAX_LDS_BYTES)
-        return false;
-    /* [measured, profiles/r04_streams_short_blocks.txt: PCM streams back to back] the kernels apart cost 70 us (512-sample blocks) to
-     * 220 us (2048) whatever the count -- launches and serial chains -- and this kernel ~17 us + 13.5 ns per 512 samples of a stream:
-     * it wins up to ~4 M samples per block of all streams (7800 x 512, 4400 x 1024, 2400 x 2048).  Complex input: round 4's first rule */
-    const long long nl = (long long)c->nstreams * c->prm.frame_size;
-    /* complex input has no carrier chain in front of it: at CYCLES = 8 the kernels apart (hand-scheduled filter, 8-lane scan) take 29 us
-     * at 1024 x 512 and 55 us at 256 x 2048, where this kernel takes 27 and 73 -- it keeps the small batches (<= 0.4 M samples); at other
-     * rates the kernels apart run the generic scan (72 us at 2048 x 512 against 40 here) and the PCM rule holds */
-    return t == 1 || (pcm || c->cycles != 8 ? nl <= 3500000LL : nl <= 400000LL);
-}
-
-/* PCM streams that both stream_scan_kernel and the one-launch kernel would take: which of the two */
-static bool prefer_stream_scan(const qpsk_ctx *c, bool scan_ok)
-{
-    return scan_ok && tuned(c->tune.stream_block, -1) != 1;
-}
-
 /* pcm / cplx: exactly one of them; every pointer device-visible (device memory or mapped pinned host memory) */
-static int streams_block_launch(qpsk_ctx *c, const int16_t *pcm, const float *cplx, const float *loop_in, float *loop_out,
+static int streams_block_launch(qpsk_ctx *c, const StreamRoute &rt, const int16_t *pcm, const float *cplx, const float *loop_in, float *loop_out,
                                 uint8_t *sym, float *costas, int32_t *index, const StreamBlockInline *inl = nullptr, bool count = false)
 {
     if (int rg = use_context_gains(c)) return rg;
     StreamBlockArgs a{};
-    if (pcm) {
-        if (c->carrier_shared && tuned(c->tune.stream_carrier, 1) != 0 && c->prm.frame_size % 2 == 0) {
-            /* the streams' one carrier (carrier.h): this block's phases from the table, the next block's by workgroup 0's third wave */
-            const size_t L2 = 2 * (size_t)c->prm.frame_size;
-            a.ctab = reinterpret_cast<const float2 *>(c->s_ctab + L2 * (c->carrier_blocks & 1u));
-            a.ctab_next = reinterpret_cast<float2 *>(c->s_ctab + L2 * ((c->carrier_blocks + 1u) & 1u));
-            a.cstate = c->s_cstate;
-        } else if (int rb = carrier_to_streams(c)) {
-            return rb;
-        }
-    }
+    /* the streams' one carrier (carrier.h): this block's phases from the table, the next block's by workgroup 0's third wave */
+    const float *ctab = nullptr;
+    float *ctab_next = nullptr;
+    if (pcm)
+        if (int rb = stream_carrier(c, rt.carrier, &ctab, &ctab_next)) return rb;
+    a.ctab = reinterpret_cast<const float2 *>(ctab);
+    a.ctab_next = reinterpret_cast<float2 *>(ctab_next);
+    a.cstate = ctab ? c->s_cstate : nullptr;
     a.pcm = pcm;
     a.cplx = reinterpret_cast<const float2 *>(cplx);
     a.mixer = c->s_mixer;
@@ -1673,7 +1747,7 @@ static int streams_block_launch(qpsk_ctx *c, const int16_t *pcm, const float *cp
     a.status = c->d_status;
     a.done = count ? c->d_done : nullptr;
     KERNEL_TRY(launch_stream_block(a, c->nstreams, c->stream, inl));
-    if (a.ctab) c->carrier_blocks++;      /* the tables flip only once the launch that fills the next one is in the stream */
+    if (ctab) c->carrier_blocks++;      /* the tables flip only once the launch that fills the next one is in the stream */
     c->last_kernel = "stream_block_kernel";
     return QPSK_OK;
 }
@@ -1686,96 +1760,72 @@ static int streams_copy_loop(qpsk_ctx *c, float *d_freq, float *d_phase)
     return QPSK_OK;
 }
 
-/* A block of the running streams from the rrc_fir() call on (qpsk.c:125-212).  filtered: c->filtered already holds the filtered
- * block and the delay lines are updated (mix_fir_kernel did both); otherwise d_in is the complex block to filter. */
-static int streams_from_filter(qpsk_ctx *c, const float *d_in, bool filtered, uint8_t *d_sym, float *d_freq, float *d_phase,
-                               float *d_costas, int32_t *d_index, bool scanned = false)
+/* A block of the running streams from the rrc_fir() call on (qpsk.c:125-212), in the context's `filtered` and `index` buffers (stream_run()
+ * has sized them).  scanned: stream_scan_kernel has left the filtered block there, planar by decimation phase, and the index, and has
+ * updated the delay lines; otherwise d_in is the complex block to filter. */
+static int streams_from_filter(qpsk_ctx *c, const float *d_in, bool scanned, uint8_t *d_sym, float *d_freq, float *d_phase,
+                               float *d_costas, int32_t *d_index)
 {
     const int n = c->nstreams, L = c->prm.frame_size, N = c->nsym;
-    int rc = ensure(c, c->filtered, sizeof(float) * 2 * (size_t)n * L);
-    if (rc) return rc;
-    rc = ensure(c, c->index, sizeof(int32_t) * (size_t)n);
-    if (rc) return rc;
     float *filt = (float *)c->filtered.p;
     int32_t *idx = (int32_t *)c->index.p;
-    if (!filtered) {
+    if (!scanned) {
         /* qpsk.c:125 */
         KERNEL_TRY(fir_full_rate(c, d_in, c->s_memory, filt, n, L));
         KERNEL_TRY(launch_delay_line(d_in, c->s_memory, n, L, c->stream));
     }
-    /* qpsk.c:127-180 (scanned: stream_scan_kernel has left the index, and the filtered block planar by decimation phase) */
-    if (scanned) {
-        /* fixed timing rides on the same kernel (its scan waves have slack; their index is simply replaced) */
-        if (c->prm.timing_mode == QPSK_TIMING_FIXED) KERNEL_TRY(launch_fill_i32(idx, n, c->prm.fixed_index, c->stream));
-    } else if (c->prm.timing_mode == QPSK_TIMING_HIST)
-        KERNEL_TRY(launch_timing_hist(filt, n, L, c->cycles, idx, nullptr, tuned(c->tune.hist_generic, 0) == 2, c->stream));
-    else if (c->prm.timing_mode == QPSK_TIMING_FIXED)
+    /* qpsk.c:127-180 (scanned: fixed timing rides on the same kernel -- its scan waves have slack; their index is simply replaced) */
+    if (c->prm.timing_mode == QPSK_TIMING_FIXED) {
         KERNEL_TRY(launch_fill_i32(idx, n, c->prm.fixed_index, c->stream));
-    else if (!d_in)
-        return fail(QPSK_ERR_STATE, "internal: the FFT timing estimate needs the unfiltered block");
-    else if (int rf = fft_timing_indices(c, d_in, n, idx))   /* stateless: it looks at the raw block from sample 2 on */
-        return rf;
+    } else if (!scanned && c->prm.timing_mode == QPSK_TIMING_HIST) {
+        KERNEL_TRY(launch_timing_hist(filt, n, L, c->cycles, idx, nullptr, tuned(c->tune.hist_generic, 0) == 2, c->stream));
+    } else if (!scanned) {
+        if (int rf = fft_timing_indices(c, d_in, n, idx)) return rf;   /* stateless: it looks at the raw block from sample 2 on */
+    }
     /* qpsk.c:196-212 over decimated_frame[0..N) = the PREVIOUS block's picks, which s_dec holds; qpsk.c:186-191:
      * this block's picks replace them for the next call */
     if (int rg = use_context_gains(c)) return rg;
-    rc = costas_over_symbols(c, c->s_dec, n, N, N, c->s_loop, d_sym, d_costas, filt, idx, scanned);
-    if (rc) return rc;
+    if (int rc = costas_over_symbols(c, c->s_dec, n, N, N, c->s_loop, d_sym, d_costas, filt, idx, scanned)) return rc;
     if (d_index) HIP_TRY(hipMemcpyAsync(d_index, idx, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
     c->last_kernel = scanned ? "stream_scan_kernel + costas_pipe_kernel"
                              : tuned(c->tune.generic, 0) ? "filter, timing, costas_kernel, decimate_kernel" : "filter, timing, costas_pipe_kernel";
     return streams_copy_loop(c, d_freq, d_phase);
 }
 
-/* Many streams, histogram timing: mixer, filter and scan as ONE kernel (streamscan.hip) -- the carrier recurrences run a tile ahead
- * of the filter waves of the same workgroup, PCM comes in at 2 bytes per sample, no mixed block goes through HBM and the scan
- * reads the filtered samples from LDS.  A workgroup takes 16 streams through the whole block (its time does not shrink with the
- * batch), so it pays from about 2500 streams on; below that the kernels apart are quicker. */
-static bool stream_scan_ok(const qpsk_ctx *c, bool pcm, bool shared_carrier)
-{
-    /* [measured, profiles/r04_streams_blocks.txt] 2560 streams: PCM input 0.94 against 1.03 ms per block with the kernels apart, complex
-     * input 0.79 against 0.70; 4096 streams: 1.00 against 1.27 and 0.92 against 1.01.  With the streams' one carrier from the table
-     * (MODE 2: no mixer wave, no mixer kernel) PCM input pays from 1024 streams on: 0.73 against 0.79 ms there, 0.75 against 0.93 at
-     * 2048, 0.76 against 1.00 at 2560 (profiles/r04_streams_carrier.txt) */
-    const int from = pcm ? (shared_carrier ? 1024 : 2560) : 3584;
-    bool wanted = c->nstreams >= from;
-    /* short blocks (the one-launch kernel's range), shared carrier: a workgroup's time shrinks with the block, so the kernel pays from
-     * ~1.4 M samples per block of all streams on -- 106.7 us against 151.9 (one launch per block) and 117.1 (kernels apart) at
-     * 1024 x 2048, 61.8 against 95.9 and 80.6 at 2048 x 1024, 41.7 against 71.7 and 61.8 at 4096 x 512; below that the one-launch
-     * kernel is ahead (profiles/r04_streams_short_blocks.txt) */
-    if (pcm && shared_carrier && c->prm.frame_size <= stream_block_max_frame())
-        wanted = (long long)c->nstreams * c->prm.frame_size >= 1400000LL && c->nstreams >= 256;
-    return c->taps_symmetric && tuned(c->tune.fir_generic, 0) == 0 && tuned(c->tune.generic, 0) == 0 && (c->cycles == 8 || c->cycles == 4) &&
-           (c->prm.timing_mode == QPSK_TIMING_HIST || c->prm.timing_mode == QPSK_TIMING_FIXED) && c->prm.frame_size % stream_scan_tile() == 0 &&
-           tuned(c->tune.stream_scan, wanted ? 1 : 0) != 0;
-}
-
-static int streams_scanned(qpsk_ctx *c, const int16_t *d_pcm, const float *d_cplx, uint8_t *d_sym, float *d_freq, float *d_phase,
-                           float *d_costas, int32_t *d_index)
+/* Executes a route.  d_pcm / d_cplx: the block the route was made for, in device memory, exactly one of them */
+static int stream_run(qpsk_ctx *c, const StreamRoute &rt, const int16_t *d_pcm, const float *d_cplx, uint8_t *d_sym, float *d_freq,
+                      float *d_phase, float *d_costas, int32_t *d_index)
 {
     const int n = c->nstreams, L = c->prm.frame_size;
-    int rf = ensure(c, c->filtered, sizeof(float) * 2 * (size_t)n * L);
-    if (rf) return rf;
-    rf = ensure(c, c->index, sizeof(int32_t) * (size_t)n);
-    if (rf) return rf;
-    const float *ctab = nullptr;
-    float *ctab_next = nullptr;
-    if (d_pcm) {
-        if (c->carrier_shared && tuned(c->tune.stream_carrier, 1) != 0) {
-            ctab = c->s_ctab + 2 * (size_t)L * (c->carrier_blocks & 1u);
-            ctab_next = c->s_ctab + 2 * (size_t)L * ((c->carrier_blocks + 1u) & 1u);
-        } else if (int rb = carrier_to_streams(c)) {
-            return rb;
+    if (rt.mixer) {
+        if (int rc = ensure(c, c->mixed, sizeof(float) * 2 * (size_t)n * L)) return rc;
+        /* qpsk.c:114-120 */
+        if (int rb = carrier_to_streams(c)) return rb;
+        KERNEL_TRY(launch_mixer(d_pcm, (float *)c->mixed.p, c->s_mixer, n, L, c->stream));
+        d_pcm = nullptr;
+        d_cplx = (const float *)c->mixed.p;
+    }
+    if (rt.kind == SK_BLOCK) {
+        if (int rb = streams_block_launch(c, rt, d_pcm, d_cplx, nullptr, nullptr, d_sym, d_costas, d_index)) return rb;
+        return streams_copy_loop(c, d_freq, d_phase);
+    }
+    if (int rc = ensure(c, c->filtered, sizeof(float) * 2 * (size_t)n * L)) return rc;
+    if (int rc = ensure(c, c->index, sizeof(int32_t) * (size_t)n)) return rc;
+    if (rt.kind == SK_SCAN) {
+        const float *ctab = nullptr;
+        float *ctab_next = nullptr;
+        if (d_pcm)
+            if (int rb = stream_carrier(c, rt.carrier, &ctab, &ctab_next)) return rb;
+        KERNEL_TRY(launch_stream_scan(d_pcm, d_cplx, c->s_mixer, c->s_memory, (float *)c->filtered.p, c->d_taps, (int32_t *)c->index.p, n, L,
+                                      c->d_status, c->stream, ctab, ctab_next, c->s_cstate, ctab ? c->carrier_scans : 0u, c->cycles));
+        if (ctab) {      /* the bookkeeping describes launches that ARE in the stream: the tables flip, the relay's turn advances, the rest of the
+                          * next table is owed (a failure between here and the launch that pays it poisons the streams: stream_call_done) */
+            c->carrier_blocks++;
+            c->carrier_scans++;
+            c->carrier_pending = ctab_next;
         }
     }
-    KERNEL_TRY(launch_stream_scan(d_pcm, d_cplx, c->s_mixer, c->s_memory, (float *)c->filtered.p, c->d_taps, (int32_t *)c->index.p, n, L,
-                                  c->d_status, c->stream, ctab, ctab_next, c->s_cstate, ctab ? c->carrier_scans : 0u, c->cycles));
-    if (ctab) {      /* the bookkeeping describes launches that ARE in the stream: the tables flip, the relay's turn advances, the rest of the
-                      * next table is owed (a failure between here and the launch that pays it poisons the streams: stream_call_done) */
-        c->carrier_blocks++;
-        c->carrier_scans++;
-        c->carrier_pending = ctab_next;
-    }
-    const int rc = streams_from_filter(c, nullptr, true, d_sym, d_freq, d_phase, d_costas, d_index, true);
+    const int rc = streams_from_filter(c, d_cplx, rt.kind == SK_SCAN, d_sym, d_freq, d_phase, d_costas, d_index);
     if (c->carrier_pending) {      /* the loop kernel was never reached: the table is finished all the same */
         float *tab = c->carrier_pending;
         c->carrier_pending = nullptr;
@@ -1784,69 +1834,15 @@ static int streams_scanned(qpsk_ctx *c, const int16_t *d_pcm, const float *d_cpl
     return rc;
 }
 
-/* A stream call enqueues several launches and keeps host-side books about them (which carrier table is current, the relay's turn, a
- * table half built).  If it fails between its launches -- or a kernel reports that it gave up (QPSK_ERR_HIP from the status word) -- the
- * carried state of the streams is undefined: the shared carrier is dropped and every later stream call is refused until
- * qpsk_streams_reset().  Argument errors and flagged NUMBERS (QPSK_ERR_RANGE: NaN samples, a phase beyond the bounded wrap) do not
- * poison: the kernels completed and the state is what the reference's would be or fenced as documented. */
-static int stream_call_done(qpsk_ctx *c, int rc)
-{
-    if (rc == QPSK_ERR_HIP || rc == QPSK_ERR_ALLOC) {
-        c->streams_poisoned = true;
-        c->carrier_shared = false;
-        c->carrier_pending = nullptr;
-    }
-    return rc;
-}
-
-static int streams_usable(qpsk_ctx *c, const char *who)
-{
-    if (c->nstreams <= 0) return fail(QPSK_ERR_STATE, "call qpsk_streams_reset() first");
-    if (c->streams_poisoned)
-        return fail(QPSK_ERR_STATE, "%s: an earlier stream call failed between its launches; the streams' carried state is undefined until qpsk_streams_reset()", who);
-    c->stream_work_unchecked = true;      /* every caller goes on to enqueue stream work (or to read what such work left) */
-    return QPSK_OK;
-}
-
-static int streams_rx_cplx_impl(qpsk_ctx *c, const float *d_in, uint8_t *d_sym, float *d_freq, float *d_phase,
-                                float *d_costas, int32_t *d_index)
-{
-    const bool scan = stream_scan_ok(c, false, false) && ((uintptr_t)d_in % 16) == 0;
-    if (d_sym && stream_block_ok(c, false) && !prefer_stream_scan(c, scan)) {
-        if (int rb = streams_block_launch(c, nullptr, d_in, nullptr, nullptr, d_sym, d_costas, d_index)) return rb;
-        return streams_copy_loop(c, d_freq, d_phase);
-    }
-    if (scan)
-        return streams_scanned(c, nullptr, d_in, d_sym, d_freq, d_phase, d_costas, d_index);
-    return streams_from_filter(c, d_in, false, d_sym, d_freq, d_phase, d_costas, d_index);
-}
-
 int qpsk_streams_rx_cplx(qpsk_ctx *c, const float *d_in, uint8_t *d_sym, float *d_freq, float *d_phase,
                          float *d_costas, int32_t *d_index)
 {
     if (!c || !d_in) return fail(QPSK_ERR_ARG, "qpsk_streams_rx_cplx: null argument");
     if (int ru = streams_usable(c, "qpsk_streams_rx_cplx")) return ru;
     if (bind(c)) return QPSK_ERR_HIP;
-    return stream_call_done(c, streams_rx_cplx_impl(c, d_in, d_sym, d_freq, d_phase, d_costas, d_index));
-}
-
-static int streams_rx_pcm_impl(qpsk_ctx *c, const int16_t *d_pcm, uint8_t *d_sym, float *d_freq, float *d_phase,
-                               float *d_costas, int32_t *d_index)
-{
-    const bool scan = stream_scan_ok(c, true, c->carrier_shared && tuned(c->tune.stream_carrier, 1) != 0) && ((uintptr_t)d_pcm % 4) == 0;
-    if (d_sym && stream_block_ok(c) && !prefer_stream_scan(c, scan)) {
-        if (int rb = streams_block_launch(c, d_pcm, nullptr, nullptr, nullptr, d_sym, d_costas, d_index)) return rb;
-        return streams_copy_loop(c, d_freq, d_phase);
-    }
-    const int n = c->nstreams, L = c->prm.frame_size;
-    if (scan)
-        return streams_scanned(c, d_pcm, nullptr, d_sym, d_freq, d_phase, d_costas, d_index);
-    int rc = ensure(c, c->mixed, sizeof(float) * 2 * (size_t)n * L);
-    if (rc) return rc;
-    /* qpsk.c:114-120 */
-    if (int rb = carrier_to_streams(c)) return rb;
-    KERNEL_TRY(launch_mixer(d_pcm, (float *)c->mixed.p, c->s_mixer, n, L, c->stream));
-    return streams_rx_cplx_impl(c, (const float *)c->mixed.p, d_sym, d_freq, d_phase, d_costas, d_index);
+    StreamRoute rt;
+    stream_route(c, false, d_in, d_sym != nullptr, &rt);
+    return stream_call_done(c, stream_run(c, rt, nullptr, d_in, d_sym, d_freq, d_phase, d_costas, d_index));
 }
 
 int qpsk_streams_rx_pcm(qpsk_ctx *c, const int16_t *d_pcm, uint8_t *d_sym, float *d_freq, float *d_phase,
@@ -1855,7 +1851,18 @@ int qpsk_streams_rx_pcm(qpsk_ctx *c, const int16_t *d_pcm, uint8_t *d_sym, float
     if (!c || !d_pcm) return fail(QPSK_ERR_ARG, "qpsk_streams_rx_pcm: null argument");
     if (int ru = streams_usable(c, "qpsk_streams_rx_pcm")) return ru;
     if (bind(c)) return QPSK_ERR_HIP;
-    return stream_call_done(c, streams_rx_pcm_impl(c, d_pcm, d_sym, d_freq, d_phase, d_costas, d_index));
+    StreamRoute rt;
+    stream_route(c, true, d_pcm, d_sym != nullptr, &rt);
+    return stream_call_done(c, stream_run(c, rt, d_pcm, nullptr, d_sym, d_freq, d_phase, d_costas, d_index));
+}
+
+static inline void cpu_relax(void)
+{
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#elif defined(__aarch64__)
+    __asm__ __volatile__("yield");
+#endif
 }
 
 /*
@@ -1869,24 +1876,6 @@ int qpsk_streams_rx_pcm(qpsk_ctx *c, const int16_t *d_pcm, uint8_t *d_sym, float
  *   h_sym [nstreams][nsym] uint8                h_costas [nstreams][nsym][2] float, may be NULL
  *   h_index [nstreams] int32, may be NULL
  */
-static int streams_rx_pcm_host_impl(qpsk_ctx *c, const int16_t *h_pcm, float *h_loop_io, uint8_t *h_sym, float *h_costas, int32_t *h_index);
-int qpsk_streams_rx_pcm_host(qpsk_ctx *c, const int16_t *h_pcm, float *h_loop_io, uint8_t *h_sym, float *h_costas, int32_t *h_index)
-{
-    if (!c || !h_pcm || !h_sym) return fail(QPSK_ERR_ARG, "qpsk_streams_rx_pcm_host: null argument");
-    if (int ru = streams_usable(c, "qpsk_streams_rx_pcm_host")) return ru;
-    if (bind(c)) return QPSK_ERR_HIP;
-    return stream_call_done(c, streams_rx_pcm_host_impl(c, h_pcm, h_loop_io, h_sym, h_costas, h_index));
-}
-
-static inline void cpu_relax(void)
-{
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#elif defined(__aarch64__)
-    __asm__ __volatile__("yield");
-#endif
-}
-
 static int streams_rx_pcm_host_impl(qpsk_ctx *c, const int16_t *h_pcm, float *h_loop_io, uint8_t *h_sym, float *h_costas, int32_t *h_index)
 {
     const size_t n = (size_t)c->nstreams, L = (size_t)c->prm.frame_size, N = (size_t)c->nsym;
@@ -1908,7 +1897,11 @@ static int streams_rx_pcm_host_impl(qpsk_ctx *c, const int16_t *h_pcm, float *h_
     }
     if (h_loop_io) memcpy(c->h_stage + o_loop, h_loop_io, 8 * n);
     memcpy(c->h_stage + o_pcm, h_pcm, 2 * n * L);
-    if (stream_block_ok(c) && !prefer_stream_scan(c, stream_scan_ok(c, true, c->carrier_shared && tuned(c->tune.stream_carrier, 1) != 0))) {
+    /* the route of the block where the kernels apart would read it, in the device arena (16-byte aligned, symbols always wanted) */
+    StreamRoute rt;
+    stream_route(c, true, c->d_stage + o_pcm, true, &rt);
+    bool polled = false;
+    if (rt.kind == SK_BLOCK && !rt.mixer) {
         /* one launch, no copy engine: the kernel reads the PCM (and the loop state) from the pinned staging buffer and leaves its
          * results there -- a kilobyte in, a few hundred bytes out per stream */
         unsigned char *m = nullptr;
@@ -1917,18 +1910,18 @@ static int streams_rx_pcm_host_impl(qpsk_ctx *c, const int16_t *h_pcm, float *h_
          * memory at all -- a read of pinned host memory from the GPU costs 8-14 us on this pool, a posted write a fraction of that */
         /* few streams: the waves count themselves off in pinned memory (a system-scope atomic each: ~1 us apiece over PCIe, so only
          * for a handful -- 64 streams took 156 us that way against 47 with the stream's own completion signal) */
-        const bool poll = tuned(c->tune.stream_poll, n <= (size_t)StreamBlockInline::MAX_STREAMS ? 1 : 0) != 0;
+        polled = tuned(c->tune.stream_poll, n <= (size_t)StreamBlockInline::MAX_STREAMS ? 1 : 0) != 0;
         StreamBlockInline inl;
         const bool use_inl = n <= (size_t)StreamBlockInline::MAX_STREAMS && n * L <= (size_t)StreamBlockInline::MAX_SAMPLES;
         if (use_inl) {
             if (h_loop_io) memcpy(inl.loop, h_loop_io, 8 * n);
             memcpy(inl.pcm, h_pcm, 2 * n * L);
         }
-        if (int rb = streams_block_launch(c, (const int16_t *)(m + o_pcm), nullptr, h_loop_io ? (const float *)(m + o_loop) : nullptr,
+        if (int rb = streams_block_launch(c, rt, (const int16_t *)(m + o_pcm), nullptr, h_loop_io ? (const float *)(m + o_loop) : nullptr,
                                           (float *)(m + o_lout), m + o_sym, h_costas ? (float *)(m + o_cos) : nullptr, (int32_t *)(m + o_idx),
-                                          use_inl ? &inl : nullptr, poll))
+                                          use_inl ? &inl : nullptr, polled))
             return rb;
-        if (poll) {
+        if (polled) {
             /* the kernel's two waves per stream count themselves off in pinned memory behind their last store: watching that word
              * is quicker than the stream's completion signal.  Bounded by the WALL CLOCK (2 s, looked at every 4096 spins): then the
              * ordinary synchronisation takes over, and a counter that is still short after THAT is an error -- the kernel did not run to
@@ -1956,40 +1949,39 @@ static int streams_rx_pcm_host_impl(qpsk_ctx *c, const int16_t *h_pcm, float *h_
                                 2u * (unsigned)n - (want - have), 2u * (unsigned)n);
                 }
             }
-        } else {
-            HIP_TRY(hipStreamSynchronize(c->stream));
         }
-        if (int st = check_status(c)) return st;
-        memcpy(h_sym, c->h_stage + o_sym, n * N);
-        if (h_costas) memcpy(h_costas, c->h_stage + o_cos, 8 * n * N);
-        if (h_loop_io) memcpy(h_loop_io, c->h_stage + o_lout, 8 * n);
-        if (h_index) memcpy(h_index, c->h_stage + o_idx, 4 * n);
-        return QPSK_OK;
-    }
-    const size_t up0 = h_loop_io ? o_loop : o_pcm;
-    HIP_TRY(hipMemcpyAsync(c->d_stage + up0, c->h_stage + up0, in_bytes - up0, hipMemcpyHostToDevice, c->stream));
-    if (h_loop_io) HIP_TRY(hipMemcpyAsync(c->s_loop, c->d_stage + o_loop, 8 * n, hipMemcpyDeviceToDevice, c->stream));
-    uint8_t *d_sym = c->d_stage + o_sym;
-    float *d_cos = h_costas ? (float *)(c->d_stage + o_cos) : nullptr;
-    int32_t *d_idx = (int32_t *)(c->d_stage + o_idx);
-    int rc = streams_rx_pcm_impl(c, (const int16_t *)(c->d_stage + o_pcm), d_sym, nullptr, nullptr, d_cos, d_idx);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_stage + o_lout, c->s_loop, 8 * n, hipMemcpyDeviceToDevice, c->stream));
-    /* one copy down: from the symbols to the index (costas_frame[] in between travels even when it is not wanted
-     * only if it was computed: without it the two parts around it go separately) */
-    if (h_costas) {
-        HIP_TRY(hipMemcpyAsync(c->h_stage + o_sym, c->d_stage + o_sym, total - o_sym, hipMemcpyDeviceToHost, c->stream));
     } else {
-        HIP_TRY(hipMemcpyAsync(c->h_stage + o_sym, c->d_stage + o_sym, al(n * N), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->h_stage + o_lout, c->d_stage + o_lout, total - o_lout, hipMemcpyDeviceToHost, c->stream));
+        const size_t up0 = h_loop_io ? o_loop : o_pcm;
+        HIP_TRY(hipMemcpyAsync(c->d_stage + up0, c->h_stage + up0, in_bytes - up0, hipMemcpyHostToDevice, c->stream));
+        if (h_loop_io) HIP_TRY(hipMemcpyAsync(c->s_loop, c->d_stage + o_loop, 8 * n, hipMemcpyDeviceToDevice, c->stream));
+        if (int rc = stream_run(c, rt, (const int16_t *)(c->d_stage + o_pcm), nullptr, c->d_stage + o_sym, nullptr, nullptr,
+                                h_costas ? (float *)(c->d_stage + o_cos) : nullptr, (int32_t *)(c->d_stage + o_idx)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(c->d_stage + o_lout, c->s_loop, 8 * n, hipMemcpyDeviceToDevice, c->stream));
+        /* one copy down: from the symbols to the index (costas_frame[] in between travels even when it is not wanted
+         * only if it was computed: without it the two parts around it go separately) */
+        if (h_costas) {
+            HIP_TRY(hipMemcpyAsync(c->h_stage + o_sym, c->d_stage + o_sym, total - o_sym, hipMemcpyDeviceToHost, c->stream));
+        } else {
+            HIP_TRY(hipMemcpyAsync(c->h_stage + o_sym, c->d_stage + o_sym, al(n * N), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->h_stage + o_lout, c->d_stage + o_lout, total - o_lout, hipMemcpyDeviceToHost, c->stream));
+        }
     }
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!polled) HIP_TRY(hipStreamSynchronize(c->stream));
     if (int st = check_status(c)) return st;
     memcpy(h_sym, c->h_stage + o_sym, n * N);
     if (h_costas) memcpy(h_costas, c->h_stage + o_cos, 8 * n * N);
     if (h_loop_io) memcpy(h_loop_io, c->h_stage + o_lout, 8 * n);
     if (h_index) memcpy(h_index, c->h_stage + o_idx, 4 * n);
     return QPSK_OK;
+}
+
+int qpsk_streams_rx_pcm_host(qpsk_ctx *c, const int16_t *h_pcm, float *h_loop_io, uint8_t *h_sym, float *h_costas, int32_t *h_index)
+{
+    if (!c || !h_pcm || !h_sym) return fail(QPSK_ERR_ARG, "qpsk_streams_rx_pcm_host: null argument");
+    if (int ru = streams_usable(c, "qpsk_streams_rx_pcm_host")) return ru;
+    if (bind(c)) return QPSK_ERR_HIP;
+    return stream_call_done(c, streams_rx_pcm_host_impl(c, h_pcm, h_loop_io, h_sym, h_costas, h_index));
 }
 
 /* ------------------------------------------------------------ transmit side (N2) */
@@ -2095,32 +2087,7 @@ static const int DFC_ADV_OFFSET = (DEFRAME_CODED_MAX_STEPS + 15) & ~15;      /* 
 
 /* both resets: who = the entry point's name; coded: the body is 8 (nbytes + 2) + 6 coded dibits held as int8 pairs */
 static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes,
-                               int max_packets, bool coded, int mode, float scale, const Puncture *punct = nullptr);
-
-int qpsk_deframer_reset(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets)
-{
-    return deframer_reset_impl(c, "qpsk_deframer_reset", nstreams, h_sync, nsync, min_score, nbytes, max_packets, false, 0, 1.0f);
-}
-
-int qpsk_deframer_reset_coded(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets,
-                              int mode, float scale)
-{
-    return deframer_reset_impl(c, "qpsk_deframer_reset_coded", nstreams, h_sync, nsync, min_score, nbytes, max_packets, true, mode, scale);
-}
-
-/* the coded mode behind a puncturing pattern: the body is the ntx(8 (nbytes + 2) + 6) transmitted dibits; the pattern lives in the
- * deframer's state, and qpsk_deframer_push_coded decodes with the punctured kernels */
-int qpsk_deframer_reset_coded_punct(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets,
-                                    int mode, float scale, int period, uint32_t keep0, uint32_t keep1)
-{
-    Puncture p;
-    if (!c) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset_coded_punct: null context or sync word");
-    if (int rc = punct_make("qpsk_deframer_reset_coded_punct", period, keep0, keep1, &p)) return rc;
-    return deframer_reset_impl(c, "qpsk_deframer_reset_coded_punct", nstreams, h_sync, nsync, min_score, nbytes, max_packets, true, mode, scale, &p);
-}
-
-static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes,
-                               int max_packets, bool coded, int mode, float scale, const Puncture *punct)
+                               int max_packets, bool coded, int mode, float scale, const Puncture *punct = nullptr)
 {
     if (!c || !h_sync) return fail(QPSK_ERR_ARG, "%s: null context or sync word", who);
     if (nstreams <= 0) return fail(QPSK_ERR_ARG, "%s: nstreams = %d", who, nstreams);
@@ -2196,6 +2163,28 @@ static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const
     c->df_pattern = punct ? *punct : Puncture{1, 1u, 1u, 2};
     c->df_ready = true;
     return QPSK_OK;
+}
+
+int qpsk_deframer_reset(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets)
+{
+    return deframer_reset_impl(c, "qpsk_deframer_reset", nstreams, h_sync, nsync, min_score, nbytes, max_packets, false, 0, 1.0f);
+}
+
+int qpsk_deframer_reset_coded(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets,
+                              int mode, float scale)
+{
+    return deframer_reset_impl(c, "qpsk_deframer_reset_coded", nstreams, h_sync, nsync, min_score, nbytes, max_packets, true, mode, scale);
+}
+
+/* the coded mode behind a puncturing pattern: the body is the ntx(8 (nbytes + 2) + 6) transmitted dibits; the pattern lives in the
+ * deframer's state, and qpsk_deframer_push_coded decodes with the punctured kernels */
+int qpsk_deframer_reset_coded_punct(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets,
+                                    int mode, float scale, int period, uint32_t keep0, uint32_t keep1)
+{
+    Puncture p;
+    if (!c) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset_coded_punct: null context or sync word");
+    if (int rc = punct_make("qpsk_deframer_reset_coded_punct", period, keep0, keep1, &p)) return rc;
+    return deframer_reset_impl(c, "qpsk_deframer_reset_coded_punct", nstreams, h_sync, nsync, min_score, nbytes, max_packets, true, mode, scale, &p);
 }
 
 /* what both pushes do behind their own argument checks (who = the entry point's name): the state checks, no output (the caller's
