@@ -665,6 +665,29 @@ int qpsk_scramble_batch(qpsk_ctx *ctx, uint8_t *d_sym, int npackets, int nsym);
  * bounds a host that wants every step's symbols (examples/shard_devices.c,
  * bench.py `gather`).  One caller thread at a time per qpsk_multi (the
  * object runs its own thread per shard; its entry points are not reentrant).
+ * The entry points leave the caller's current HIP device as they found it.
+ *
+ * The verdict, per slot.  A shard's context has ONE kernel status word, which
+ * the kernels of either slot's step may set.  A non-zero kernel status seen
+ * by qpsk_multi_rx_end(k) on a shard fails that call.  It also fails the
+ * rx_end of every other slot that was in flight on that shard at that
+ * moment, with the same code and text.  On a failing rx_end the caller's
+ * arrays are unspecified.  The slot is free afterwards.  (Conservative: a
+ * good step may be reported bad next to a bad one; a bad step is never
+ * reported good.  Once both slots have ended nothing stays behind.)
+ *
+ * A failed rx_begin.  When rx_begin(slot) fails on any shard -- a geometry
+ * the context's tuning keys make rx_batch refuse, a HIP error -- it returns
+ * the first failing shard's code and text, and the shards that did enqueue
+ * are waited for and disarmed: the slot is free on EVERY shard, rx_end(slot)
+ * answers "nothing in flight", rx_begin(slot) may be called again.  The
+ * other slot is not touched.  (A rx_begin refused because the slot is still
+ * in flight -- QPSK_ERR_STATE -- leaves that earlier step in flight.)
+ *
+ * A load with a step in flight.  qpsk_multi_load waits for every step in
+ * flight and DROPS it, results and verdict: both slots are free afterwards,
+ * rx_end for the dropped step answers "nothing in flight", and the new job
+ * starts clean.
  * ------------------------------------------------------------------------- */
 typedef struct qpsk_multi qpsk_multi;
 int qpsk_multi_create(qpsk_multi **out, const int *devices, int ndev, const qpsk_params *p);
@@ -678,7 +701,7 @@ int qpsk_multi_use_device_input(qpsk_multi *mj, int r, const float *d_in);
 /* Direct mode for a slot: its copy-back goes by DMA straight to the caller's arrays (each shard at its place) instead of to the library's
  * pinned staging, and qpsk_multi_rx_end(slot, NULL, NULL, NULL) only waits -- no concatenating memcpy on the host (16 MiB per 8192-frame
  * step: ~1.4 ms of one host core, five times the kernel).  The arrays must be page-locked (qpsk_host_alloc) and stay valid while the
- * slot is used; all NULL = back to staging. */
+ * slot is used; all NULL = back to staging.  QPSK_ERR_STATE while the slot is in flight on any shard, and then no shard is changed. */
 int qpsk_multi_set_direct_output(qpsk_multi *mj, int slot, uint8_t *h_sym, float *h_freq, float *h_phase);
 /* Packed mode: the symbols come back FOUR PER BYTE -- h_sym rows of ceil(nsym / 4) bytes, byte k = sym[4k] | sym[4k+1] << 2 | sym[4k+2] << 4 |
  * sym[4k+3] << 6 (qpsk_pack_symbols on the device, 16 MiB -> 4 MiB per 8192-frame step): the copy-back drops under the kernel's time and

@@ -14,6 +14,11 @@
  *                  copy stream waits for the event; three hipMemcpyAsync to the slot's pinned staging; event
  *     end(slot):   host waits for the slot's copy event, looks at the context's status word, copies staging -> the caller's arrays
  * The two result slots are what makes the overlap legal: the kernel of step k + 1 writes the OTHER slot.
+ *
+ * The verdict is per CONTEXT (one status word, which every kernel of either slot's step may set), the results are per SLOT.  So a
+ * status that end(k) takes from the word also fails the end() of the other slot, if that slot is in flight on the shard at that
+ * moment (Shard::pending): a good step may be reported bad, a bad step is never reported good.  A begin() that fails on one shard
+ * waits for and disarms the shards that did enqueue (command 4), so that the slot is free on every shard afterwards.
  */
 #include <hip/hip_runtime.h>
 
@@ -48,6 +53,10 @@ struct Shard {
     float *h_fp[2] = {nullptr, nullptr};
     hipEvent_t done[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
     bool in_flight[2] = {false, false};
+    bool begun = false;               /* the last begin command armed its slot on this shard (what an abort undoes) */
+    /* a kernel status that the OTHER slot's end() took from the context's status word while this slot was in flight: this slot's verdict too */
+    int pending[2] = {0, 0};
+    char pending_err[2][512] = {{0}, {0}};
     /* direct mode: the slot's copy-back goes straight to the caller's (pinned) arrays, at this shard's place */
     uint8_t *dir_sym[2] = {nullptr, nullptr};
     float *dir_freq[2] = {nullptr, nullptr}, *dir_phase[2] = {nullptr, nullptr};
@@ -55,7 +64,7 @@ struct Shard {
     std::thread th;
     std::mutex mu;
     std::condition_variable cv;
-    int cmd = 0;                      /* 0 idle, 1 begin, 2 end, 3 quit */
+    int cmd = 0;                      /* 0 idle, 1 begin, 2 end, 3 quit, 4 abort (undo the begin just run) */
     int cmd_slot = 0;
     uint8_t *out_sym = nullptr;
     float *out_freq = nullptr, *out_phase = nullptr;
@@ -87,8 +96,19 @@ namespace {
         }                                                                                                        \
     } while (0)
 
+/* the entry points that run on the caller's thread select the shards' devices: the caller gets its own device back */
+struct DeviceGuard {
+    int prev = 0;
+    bool have = false;
+    DeviceGuard() { have = hipGetDevice(&prev) == hipSuccess; }
+    ~DeviceGuard() { if (have) hipSetDevice(prev); }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+
 int shard_begin(qpsk_multi *mj, Shard *s, int slot)
 {
+    s->begun = false;
     if (s->count == 0) return QPSK_OK;
     M_HIP(s, hipSetDevice(s->device));
     if (s->in_flight[slot]) {
@@ -132,7 +152,24 @@ int shard_begin(qpsk_multi *mj, Shard *s, int slot)
     }
     M_HIP(s, hipEventRecord(s->copied[slot], s->copy));
     s->in_flight[slot] = true;
+    s->begun = true;
     return QPSK_OK;
+}
+
+/* the context's status word, taken (it reads 0 afterwards) once `slot` has left the device.  The word does not say which step's kernel
+ * set it: what it holds is the verdict of `slot` AND of the other slot if that one is in flight -- kept for its end() in `pending`.
+ * Leaves the text in s->err. */
+int take_verdict(Shard *s, int slot)
+{
+    const int rc = qpsk_ctx_check(s->ctx);
+    if (!rc) return QPSK_OK;
+    snprintf(s->err, sizeof(s->err), "device %d: %s", s->device, qpsk_last_error());
+    const int other = slot ^ 1;
+    if (s->in_flight[other] && !s->pending[other]) {
+        s->pending[other] = rc;
+        memcpy(s->pending_err[other], s->err, sizeof(s->err));
+    }
+    return rc;
 }
 
 int shard_end(qpsk_multi *mj, Shard *s, int slot)
@@ -144,17 +181,33 @@ int shard_end(qpsk_multi *mj, Shard *s, int slot)
         return QPSK_ERR_STATE;
     }
     s->in_flight[slot] = false;
+    const int held = s->pending[slot];      /* what the other slot's end() saw while this step was in flight */
+    s->pending[slot] = 0;
     M_HIP(s, hipEventSynchronize(s->copied[slot]));
     /* did a kernel flag its results?  (the status word, without waiting for the step that may already run behind this one) */
-    const int rc = qpsk_ctx_check(s->ctx);
-    if (rc) {
-        snprintf(s->err, sizeof(s->err), "device %d: %s", s->device, qpsk_last_error());
-        return rc;
+    const int rc = take_verdict(s, slot);
+    if (held) {
+        memcpy(s->err, s->pending_err[slot], sizeof(s->err));
+        return held;
     }
+    if (rc) return rc;
     if (s->dir_sym[slot] || s->dir_freq[slot] || s->dir_phase[slot]) return QPSK_OK;      /* already where the caller wants it */
     if (s->out_sym) memcpy(s->out_sym + (size_t)s->first * mj->row_bytes(), s->h_sym[slot], (size_t)s->count * mj->row_bytes());
     if (s->out_freq) memcpy(s->out_freq + s->first, s->h_fp[slot], sizeof(float) * (size_t)s->count);
     if (s->out_phase) memcpy(s->out_phase + s->first, s->h_fp[slot] + s->count, sizeof(float) * (size_t)s->count);
+    return QPSK_OK;
+}
+
+/* behind a begin() that failed on another shard: wait for what this shard enqueued and free the slot, as an end() without results would */
+int shard_abort(Shard *s, int slot)
+{
+    if (!s->begun || !s->in_flight[slot]) return QPSK_OK;
+    s->begun = false;
+    s->in_flight[slot] = false;
+    s->pending[slot] = 0;
+    M_HIP(s, hipSetDevice(s->device));
+    M_HIP(s, hipEventSynchronize(s->copied[slot]));
+    take_verdict(s, slot);      /* the dropped step's own verdict goes with it; the other slot, if in flight, keeps it */
     return QPSK_OK;
 }
 
@@ -171,6 +224,7 @@ void shard_thread(qpsk_multi *mj, Shard *s)
         int rc = QPSK_OK;
         if (cmd == 1) rc = shard_begin(mj, s, slot);
         else if (cmd == 2) rc = shard_end(mj, s, slot);
+        else if (cmd == 4) rc = shard_abort(s, slot);
         {
             std::lock_guard<std::mutex> lk(s->mu);
             s->result = rc;
@@ -182,8 +236,8 @@ void shard_thread(qpsk_multi *mj, Shard *s)
     }
 }
 
-/* every shard's thread runs `cmd`; returns the first failure with that shard's text */
-int run_all(qpsk_multi *mj, int cmd, int slot, uint8_t *h_sym, float *h_freq, float *h_phase)
+/* every shard's thread runs `cmd`; returns the first failure, that shard's text in err[512] */
+int dispatch(qpsk_multi *mj, int cmd, int slot, uint8_t *h_sym, float *h_freq, float *h_phase, char *err)
 {
     for (Shard *s : mj->shards) {
         std::lock_guard<std::mutex> lk(s->mu);
@@ -200,9 +254,22 @@ int run_all(qpsk_multi *mj, int cmd, int slot, uint8_t *h_sym, float *h_freq, fl
     for (Shard *s : mj->shards) {
         std::unique_lock<std::mutex> lk(s->mu);
         s->cv.wait(lk, [&] { return !s->busy; });
-        if (s->result && !first_rc) first_rc = qpsk_set_error(s->result, s->err);
+        if (s->result && !first_rc) {
+            first_rc = s->result;
+            memcpy(err, s->err, sizeof(s->err));
+        }
     }
     return first_rc;
+}
+
+/* a begin or an end on every shard.  A begin that fails on any shard leaves the slot free on ALL of them: the shards that did enqueue
+ * are waited for and disarmed (a half-armed job would refuse both the end and the retry) */
+int run_all(qpsk_multi *mj, int cmd, int slot, uint8_t *h_sym, float *h_freq, float *h_phase)
+{
+    char err[512] = {0}, err_abort[512] = {0};
+    const int rc = dispatch(mj, cmd, slot, h_sym, h_freq, h_phase, err);
+    if (rc && cmd == 1) dispatch(mj, 4, slot, nullptr, nullptr, nullptr, err_abort);
+    return rc ? qpsk_set_error(rc, err) : QPSK_OK;
 }
 
 void free_shard_buffers(Shard *s)
@@ -210,6 +277,9 @@ void free_shard_buffers(Shard *s)
     hipSetDevice(s->device);
     if (s->compute) hipStreamSynchronize(s->compute);
     if (s->copy) hipStreamSynchronize(s->copy);
+    /* a step in flight is dropped here, its verdict with it */
+    if ((s->in_flight[0] || s->in_flight[1]) && s->ctx) qpsk_ctx_check(s->ctx);
+    s->begun = false;
     if (s->d_in && !s->borrowed) hipFree(s->d_in);
     s->d_in = nullptr;
     s->borrowed = false;
@@ -227,6 +297,7 @@ void free_shard_buffers(Shard *s)
         if (s->h_fp[k]) hipHostFree(s->h_fp[k]);
         s->d_sym[k] = nullptr; s->d_fp[k] = nullptr; s->h_sym[k] = nullptr; s->h_fp[k] = nullptr;
         s->in_flight[k] = false;
+        s->pending[k] = 0;
     }
 }
 
@@ -237,6 +308,7 @@ extern "C" {
 int qpsk_multi_create(qpsk_multi **out, const int *devices, int ndev, const qpsk_params *p)
 {
     if (!out || !devices || ndev <= 0 || !p) return qpsk_set_error(QPSK_ERR_ARG, "qpsk_multi_create: null argument or no device");
+    DeviceGuard guard;
     qpsk_multi *mj = new qpsk_multi;
     mj->prm = *p;
     for (int r = 0; r < ndev; r++) {
@@ -268,6 +340,7 @@ int qpsk_multi_create(qpsk_multi **out, const int *devices, int ndev, const qpsk
 void qpsk_multi_destroy(qpsk_multi *mj)
 {
     if (!mj) return;
+    DeviceGuard guard;
     for (Shard *s : mj->shards) {
         if (s->th.joinable()) {
             {
@@ -297,6 +370,7 @@ int qpsk_multi_shards(const qpsk_multi *mj) { return mj ? (int)mj->shards.size()
 int qpsk_multi_load(qpsk_multi *mj, long long total_frames, const float *h_in)
 {
     if (!mj || total_frames <= 0) return qpsk_set_error(QPSK_ERR_ARG, "qpsk_multi_load: null job or no frames");
+    DeviceGuard guard;
     const long long N = (long long)mj->shards.size();
     const size_t frame_bytes = sizeof(float) * 2 * (size_t)mj->prm.frame_size;
     mj->total = 0;      /* no job until every shard stands: a failed load leaves nothing qpsk_multi_rx_begin would run on */
@@ -351,6 +425,7 @@ int qpsk_multi_use_device_input(qpsk_multi *mj, int r, const float *d_in)
     Shard *s = mj->shards[(size_t)r];
     if (s->count == 0) return qpsk_set_error(QPSK_ERR_STATE, "qpsk_multi_use_device_input: call qpsk_multi_load first");
     if (s->in_flight[0] || s->in_flight[1]) return qpsk_set_error(QPSK_ERR_STATE, "qpsk_multi_use_device_input: a slot is in flight");
+    DeviceGuard guard;
     if (hipSetDevice(s->device) != hipSuccess || hipStreamSynchronize(s->compute) != hipSuccess)
         return qpsk_set_error(QPSK_ERR_HIP, "qpsk_multi_use_device_input: the shard's device or stream is not usable");
     if (s->d_in && !s->borrowed) hipFree(s->d_in);
@@ -362,8 +437,9 @@ int qpsk_multi_use_device_input(qpsk_multi *mj, int r, const float *d_in)
 int qpsk_multi_set_direct_output(qpsk_multi *mj, int slot, uint8_t *h_sym, float *h_freq, float *h_phase)
 {
     if (!mj || (slot != 0 && slot != 1)) return qpsk_set_error(QPSK_ERR_ARG, "qpsk_multi_set_direct_output: bad job or slot");
-    for (Shard *s : mj->shards) {
+    for (Shard *s : mj->shards)      /* every shard first: a refusal changes none */
         if (s->in_flight[slot]) return qpsk_set_error(QPSK_ERR_STATE, "qpsk_multi_set_direct_output: the slot is in flight");
+    for (Shard *s : mj->shards) {
         s->dir_sym[slot] = h_sym;
         s->dir_freq[slot] = h_freq;
         s->dir_phase[slot] = h_phase;
@@ -406,6 +482,7 @@ int qpsk_multi_set_acquisition(qpsk_multi *mj, const int32_t *h_index, const flo
     if (!mj || mj->total <= 0) return qpsk_set_error(QPSK_ERR_ARG, "qpsk_multi_set_acquisition: null job or no frames loaded");
     for (Shard *s : mj->shards)
         if (s->in_flight[0] || s->in_flight[1]) return qpsk_set_error(QPSK_ERR_STATE, "qpsk_multi_set_acquisition: a slot is in flight");
+    DeviceGuard guard;
     /* every shard's new slices first; only when all stand do they replace the old ones (a failure leaves every shard as it was) */
     const size_t ns = mj->shards.size();
     std::vector<int32_t *> ni(ns, nullptr);

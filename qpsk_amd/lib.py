@@ -789,6 +789,26 @@ class MultiJob:
         self._check(self.L.qpsk_multi_shard(self.h, r, C.byref(dev), C.byref(first), C.byref(count), C.byref(ctx), C.byref(d_in)))
         return dict(device=dev.value, first=first.value, count=count.value, ctx=ctx, d_in=d_in.value)
 
+    def tune_shard(self, r, **kw):
+        """Modem.tune() on shard r's context: tune_shard(1, hist_onepass=1, pipe_g=4); None = the library's choice"""
+        ctx = self.shard(r)["ctx"]
+        for k, v in kw.items():
+            self._check(self.L.qpsk_ctx_set_tuning(ctx, ("QPSK_" + k.upper()).encode(), -1 if v is None else int(v)))
+
+    def inject_status(self, r, code):
+        """Test hook: a kernel status code into the status word of shard r's context (qpsk_test_inject_status)"""
+        self._check(self.L.qpsk_test_inject_status(self.shard(r)["ctx"], int(code)))
+
+    def hist_state(self, r):
+        """Test hook: qpsk_test_hist_state of shard r's context -> [guess, missed, majority, frames, off the majority] (synchronises)"""
+        st = (C.c_int32 * 5)()
+        self._check(self.L.qpsk_test_hist_state(self.shard(r)["ctx"], st))
+        return list(st)
+
+    def last_kernel(self, r):
+        """Name of the receive kernel shard r's last begin() launched"""
+        return self.L.qpsk_ctx_last_kernel(self.shard(r)["ctx"]).decode()
+
     def use_device_input(self, r, tensor):
         self._check(self.L.qpsk_multi_use_device_input(self.h, r, C.c_void_p(tensor.data_ptr())))
 
