@@ -849,11 +849,21 @@ static int rx_hist_onepass(qpsk_ctx *c, const FusedArgs &a, const RxRoute &rt, i
     /* (QPSK_PIPE_V asks for one of the receive kernels by name) */
     if (!rt.pipe_ok || !c->taps_symmetric || !scan_fused_ok(c, (const float *)a.x) || c->tune.pipe_v >= 0) return QPSK_OK;
     if (!c->d_hint) {
-        HIP_TRY(hipMalloc((void **)&c->d_hint, 2 * sizeof(int32_t)));
-        HIP_TRY(hipMemset(c->d_hint, 0, 2 * sizeof(int32_t)));
-        HIP_TRY(hipHostMalloc((void **)&c->h_hist_stats, 4 * sizeof(int32_t), hipHostMallocMapped));
-        HIP_TRY(hipHostGetDevicePointer((void **)&c->d_hist_stats, c->h_hist_stats, 0));
-        c->h_hist_stats[0] = c->h_hist_stats[1] = c->h_hist_stats[2] = -1;
+        /* all three or none: a failure half way leaves the context without the route's books, and the next call starts over */
+        int32_t *hint = nullptr, *h_stats = nullptr, *d_stats = nullptr;
+        hipError_t e = hipMalloc((void **)&hint, 2 * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMemset(hint, 0, 2 * sizeof(int32_t));
+        if (e == hipSuccess) e = hipHostMalloc((void **)&h_stats, 4 * sizeof(int32_t), hipHostMallocMapped);
+        if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&d_stats, h_stats, 0);
+        if (e != hipSuccess) {
+            if (h_stats) hipHostFree(h_stats);
+            if (hint) hipFree(hint);
+            return fail(QPSK_ERR_ALLOC, "one-pass histogram route: %s", hipGetErrorString(e));
+        }
+        h_stats[0] = h_stats[1] = h_stats[2] = -1;
+        c->d_hint = hint;
+        c->h_hist_stats = h_stats;
+        c->d_hist_stats = d_stats;
         c->hint_valid = false;
     }
     const int op = tuned(c->tune.hist_onepass, -1);
@@ -865,7 +875,10 @@ static int rx_hist_onepass(qpsk_ctx *c, const FusedArgs &a, const RxRoute &rt, i
     if (op == 0 || !c->hint_valid || !(op == 1 || guess_is_good) || !rx_hist_shape_ok(a)) return QPSK_OK;
     if (int rc = ensure(c, c->index, sizeof(int32_t) * (size_t)a.nframes)) return rc;
     if (int rc = ensure(c, c->mislist, sizeof(int32_t) * (size_t)a.nframes)) return rc;
-    int32_t *mis_count = c->d_hint + 1;      /* zero: allocation, then every index_majority_kernel */
+    /* the miss counter starts from zero whatever the last call left: index_majority_kernel resets it, but a call that failed between its
+     * launches never got that far, and rx_hist_kernel appends from the count it finds */
+    int32_t *mis_count = c->d_hint + 1;
+    HIP_TRY(hipMemsetAsync(mis_count, 0, sizeof(int32_t), c->stream));
     KERNEL_TRY(launch_rx_hist(a, (int32_t *)c->index.p, c->d_hint, (int32_t *)c->mislist.p, mis_count, c->d_status, c->stream));
     /* the fall-back pass: the generic chunked kernel over the listed frames with their true indices (its grid is sized for the
      * whole batch: the list's length is known on the device only; workgroups beyond it retire at once) */
