@@ -506,6 +506,50 @@ int qpsk_viterbi_punct_batch(qpsk_ctx *ctx, const int8_t *d_soft, long long row_
                              uint32_t keep1, const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info);
 
 /* -------------------------------------------------------------------------
+ * FRAMER: the transmit twin of the three deframers -- payloads in, rows of on-air dibits out, ready for qpsk_tx_symbols, in one launch.
+ * A composition of definitions pinned above (crc16, qpsk_scramble_batch's keystream, qpsk_pack_symbols' packing, CONVOLUTIONAL CODE,
+ * PUNCTURING): integers only, no tolerance anywhere.  Restated in numpy by tests/test_frame_cpu.py (frame_ref).
+ *
+ *       n = nsync;   pkt = payload[0 .. nbytes) ++ (crc >> 8) ++ (crc & 255),  crc = crc16(payload)               (CRC big-endian)
+ *       ks[i] = dibit i of qpsk_scramble_batch's keystream from SEED (the keystream of a longer frame extends a shorter one's)
+ * BODY, B dibits:
+ *       QPSK_FRAME_UNCODED   B = 4 (nbytes + 2);   body[i] = ((pkt[i >> 2] >> 2 (i & 3)) & 3) ^ ks[i]              (bits low first)
+ *       QPSK_FRAME_CODED     with the pattern (period, keep0, keep1):   B = qpsk_punct_ntx(8 (nbytes + 2) + 6, pattern);
+ *                            body[i] = ks[i] ^ E[i],  E = qpsk_conv_encode_punct_batch(pkt, nbits = 8 (nbytes + 2), QPSK_CONV_TAIL, pattern)
+ *                            The keystream runs over the TRANSMITTED dibits; the pad bit of an odd nsent is 0 before the xor.  The pattern
+ *                            (1, 1, 1) -- QPSK_PUNCT_1_2 -- is the rate-1/2 format of qpsk_deframer_reset_coded.
+ *       Either way the keystream is reloaded at the body's first dibit.
+ * PACKET  [h_sync[0 .. n) & 3][body]:  P = n + B dibits -- what qpsk_deframer_push, qpsk_deframer_push_coded and the deframer of
+ *       qpsk_deframer_reset_coded_punct receive.
+ * ROWS  row r < nrows holds per_row packets, numbers r per_row + j, j < per_row; packet j starts at column lead + j (P + gap).  Every column
+ *       i < row_len outside a packet is IDLE FILL ks[i]: scrambled zeros with the keystream started at column 0 of each row -- transitions
+ *       for the timing estimate and the loop, and no sync word for a deframer to find (checked for the shapes of tests/test_frame_cpu.py at
+ *       min_score = nsync; no guarantee for every word).  Rows lie row_len bytes apart and nothing else is written; every value is 0..3.
+ *
+ *   qpsk_frame_len     host only, no context: P = nsync + B, or QPSK_ERR_ARG
+ *   qpsk_frame_batch
+ *       d_payload      [nrows * per_row][nbytes] uint8, rows payload_pitch bytes apart (0 = nbytes; otherwise >= nbytes; what lies between
+ *                      rows is never read)
+ *       h_sync         [nsync] dibits on the host, taken & 3: it travels in the kernel arguments as in qpsk_sync_batch
+ *       coding         QPSK_FRAME_UNCODED (the pattern is ignored) or QPSK_FRAME_CODED (the pattern is checked as
+ *                      qpsk_conv_encode_punct_batch checks it)
+ *       d_out          [nrows][row_len] uint8, must not overlap d_payload
+ *       d_crc          [nrows * per_row] uint16, the CRC sent, or NULL
+ *       limits         1 <= nsync <= 128, 1 <= nbytes <= 1024 (the deframers'), nrows >= 1, 1 <= per_row <= 64, nrows * per_row < 2^31,
+ *                      lead, gap >= 0, lead + per_row P + (per_row - 1) gap <= row_len <= 2^21
+ * QPSK_ERR_ARG at the call for a bad argument, nothing launched.  The call keeps a keystream table of max(row_len, B) dibits of its own
+ * per context, which only grows: when it cannot, QPSK_ERR_ALLOC, nothing launched, the context usable.  Stream-ordered on the context's
+ * stream; neither reads nor updates the receive streams, the transmitters, the deframer, the histogram mode's guess or
+ * qpsk_scramble_batch's cached keystream.  qpsk_ctx_last_kernel() names frame_kernel<uncoded> or frame_kernel<coded>.  Not built: a
+ * streaming framer with state across calls, interleaving, qpsk_multi, host-pointer payloads.  Usage: INTEGRATION.md 2.0.
+ * ------------------------------------------------------------------------- */
+enum { QPSK_FRAME_UNCODED = 0, QPSK_FRAME_CODED = 1 };
+int qpsk_frame_len(int nsync, int nbytes, int coding, int period, uint32_t keep0, uint32_t keep1);
+int qpsk_frame_batch(qpsk_ctx *ctx, const uint8_t *d_payload, long long payload_pitch, int nrows, int per_row, int nbytes,
+                     const uint8_t *h_sync, int nsync, int coding, int period, uint32_t keep0, uint32_t keep1, int lead, int gap,
+                     int row_len, uint8_t *d_out, uint16_t *d_crc);
+
+/* -------------------------------------------------------------------------
  * The stages on their own (each is what the corresponding reference function
  * computes, batched).
  * ------------------------------------------------------------------------- */

@@ -186,6 +186,10 @@ struct qpsk_ctx {
     float df_scale = 0.f;
     unsigned df_crc_init = 0;
     DevBuf dfstage;               /* the soft rows of the packets a coded push completes, between the hunt and the decode */
+    /* the framer (qpsk_frame_batch): its own keystream table, frame_ks_len dibits from SEED -- a prefix serves every shorter row and body, so
+     * it only ever grows; qpsk_scramble_batch's table (keystream, above) is another buffer and is left alone */
+    uint8_t *frame_ks = nullptr;
+    int frame_ks_len = 0;
 };
 
 static const int MAX_BW = 64;
@@ -465,6 +469,7 @@ void qpsk_ctx_destroy(qpsk_ctx *c)
     hipFree(c->softgain.p);
     hipFree(c->vitdec.p);
     hipFree(c->dfstage.p);
+    hipFree(c->frame_ks);
     if (c->d_hint) hipFree(c->d_hint);
     if (c->h_hist_stats) hipHostFree(c->h_hist_stats);
     for (auto &kv : c->twiddles) hipFree(kv.second);
@@ -2338,6 +2343,121 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
                                           : "deframe_coded_hunt_kernel + deframe_coded_decode_punct_kernel<global>")
                      : lds         ? "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<lds>"
                                    : "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<global>";
+    return QPSK_OK;
+}
+
+
+/* ------------------------------------------------------------------ framer */
+/* FRAMER (include/qpsk_hip.h): the dibits of a body on air, B; who = the entry point's name.  The pattern is looked at only when coded */
+static int frame_body(const char *who, int nbytes, int coding, int period, uint32_t keep0, uint32_t keep1, Puncture *p, int *nbody)
+{
+    if (nbytes < 1 || nbytes > FRAME_MAX_BYTES) return fail(QPSK_ERR_ARG, "%s: nbytes = %d outside 1..%d", who, nbytes, FRAME_MAX_BYTES);
+    if (coding != QPSK_FRAME_UNCODED && coding != QPSK_FRAME_CODED) return fail(QPSK_ERR_ARG, "%s: unknown coding %d", who, coding);
+    *p = Puncture{1, 1u, 1u, 2};
+    if (coding == QPSK_FRAME_UNCODED) {
+        *nbody = 4 * (nbytes + 2);
+        return QPSK_OK;
+    }
+    if (int rc = punct_make(who, period, keep0, keep1, p)) return rc;
+    /* K >= 1 sent bit per period and 8 (nbytes + 2) + 6 > 32 >= period steps: at least one dibit */
+    *nbody = (int)((punct_nsent(*p, 8 * (nbytes + 2) + 6) + 1) / 2);
+    return QPSK_OK;
+}
+
+int qpsk_frame_len(int nsync, int nbytes, int coding, int period, uint32_t keep0, uint32_t keep1)
+{
+    if (nsync < 1 || nsync > SYNC_MAX_WORD) return fail(QPSK_ERR_ARG, "qpsk_frame_len: nsync = %d outside 1..%d", nsync, SYNC_MAX_WORD);
+    Puncture p;
+    int nbody = 0;
+    if (int rc = frame_body("qpsk_frame_len", nbytes, coding, period, keep0, keep1, &p, &nbody)) return rc;
+    return nsync + nbody;
+}
+
+/* The framer's keystream table holds at least n dibits.  It grows into a NEW buffer, filled by a blocking copy before anything can read it;
+ * the old one is freed only behind a synchronisation of the context's stream, the one stream every launch that reads it was enqueued on
+ * (qpsk_ctx_set_stream synchronises the stream it leaves), so no enqueued launch still reads a table that is freed.  A failed allocation
+ * leaves the old table, and the context, as they were */
+static int frame_keystream(qpsk_ctx *c, int n)
+{
+    if (c->frame_ks_len >= n) return QPSK_OK;
+    void *p = nullptr;
+    const hipError_t e = hipMalloc(&p, (size_t)n);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(QPSK_ERR_ALLOC, "qpsk_frame_batch: hipMalloc(%d bytes of keystream): %s", n, hipGetErrorString(e));
+    }
+    std::vector<unsigned char> ks((size_t)n);
+    qpsk_host_scramble_keystream(ks.data(), n);
+    hipError_t e2 = hipMemcpy(p, ks.data(), (size_t)n, hipMemcpyHostToDevice);
+    if (e2 == hipSuccess && c->frame_ks) e2 = hipStreamSynchronize(c->stream);
+    if (e2 != hipSuccess) {
+        hipFree(p);
+        return fail(QPSK_ERR_HIP, "qpsk_frame_batch: keystream upload: %s", hipGetErrorString(e2));
+    }
+    hipFree(c->frame_ks);
+    c->frame_ks = (uint8_t *)p;
+    c->frame_ks_len = n;
+    return QPSK_OK;
+}
+
+int qpsk_frame_batch(qpsk_ctx *c, const uint8_t *d_payload, long long payload_pitch, int nrows, int per_row, int nbytes,
+                     const uint8_t *h_sync, int nsync, int coding, int period, uint32_t keep0, uint32_t keep1, int lead, int gap,
+                     int row_len, uint8_t *d_out, uint16_t *d_crc)
+{
+    if (!c || !d_payload || !h_sync || !d_out) return fail(QPSK_ERR_ARG, "qpsk_frame_batch: null context, payload, sync word or output");
+    if (nsync < 1 || nsync > SYNC_MAX_WORD) return fail(QPSK_ERR_ARG, "qpsk_frame_batch: nsync = %d outside 1..%d", nsync, SYNC_MAX_WORD);
+    Puncture p;
+    int nbody = 0;
+    if (int rc = frame_body("qpsk_frame_batch", nbytes, coding, period, keep0, keep1, &p, &nbody)) return rc;
+    if (nrows < 1 || per_row < 1 || per_row > FRAME_MAX_PER_ROW || (long long)nrows * per_row > INT_MAX)
+        return fail(QPSK_ERR_ARG, "qpsk_frame_batch: nrows = %d, per_row = %d (1..%d, nrows * per_row < 2^31)", nrows, per_row, FRAME_MAX_PER_ROW);
+    if (payload_pitch != 0 && payload_pitch < nbytes)
+        return fail(QPSK_ERR_ARG, "qpsk_frame_batch: payload_pitch = %lld below nbytes = %d", payload_pitch, nbytes);
+    if (lead < 0 || gap < 0) return fail(QPSK_ERR_ARG, "qpsk_frame_batch: lead = %d, gap = %d", lead, gap);
+    const long long need = (long long)lead + (long long)per_row * (nsync + nbody) + (long long)(per_row - 1) * gap;
+    if (row_len < 1 || row_len > FRAME_MAX_ROW || need > row_len)
+        return fail(QPSK_ERR_ARG, "qpsk_frame_batch: lead %d + %d packets of %d dibits + gaps of %d = %lld do not fit row_len = %d (up to %d)", lead,
+                    per_row, nsync + nbody, gap, need, row_len, FRAME_MAX_ROW);
+    const size_t npk = (size_t)nrows * (size_t)per_row, pitch = payload_pitch ? (size_t)payload_pitch : (size_t)nbytes;
+    const uintptr_t i0 = (uintptr_t)d_payload, i1 = i0 + (npk - 1) * pitch + (size_t)nbytes;
+    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)nrows * (size_t)row_len;
+    if (o0 < i1 && i0 < o1) return fail(QPSK_ERR_ARG, "qpsk_frame_batch: d_out overlaps d_payload");
+    if (d_crc) {
+        const uintptr_t r0 = (uintptr_t)d_crc, r1 = r0 + 2 * npk;
+        if (((uintptr_t)d_crc & 1) || (r0 < i1 && i0 < r1) || (r0 < o1 && o0 < r1))
+            return fail(QPSK_ERR_ARG, "qpsk_frame_batch: d_crc is not 2-byte aligned, or overlaps d_payload or d_out");
+    }
+    if (bind(c)) return QPSK_ERR_HIP;
+    if (int rc = frame_keystream(c, row_len > nbody ? row_len : nbody)) return rc;
+    FrameArgs a{};
+    a.payload = d_payload;
+    a.pitch = pitch;
+    a.out = d_out;
+    a.crc = d_crc;
+    a.ks = c->frame_ks;
+    a.npackets = (int)npk;
+    a.per_row = per_row;
+    a.nbytes = nbytes;
+    a.nsync = nsync;
+    a.nbody = nbody;
+    a.lead = lead;
+    a.gap = gap;
+    a.row_len = row_len;
+    a.bytes_per_lane = (nbytes + 63) / 64;
+    a.coded = coding == QPSK_FRAME_CODED;
+    a.nsent = a.coded ? (unsigned)punct_nsent(p, 8 * (nbytes + 2) + 6) : 0u;
+    a.punct = p;
+    /* lane l's share of the CRC covers payload bytes [l c, min((l + 1) c, nbytes)): x^(8 k), k = the bytes behind them; then the init value's */
+    uint16_t adv[65];
+    for (int l = 0; l < 64; l++) {
+        const int end = (l + 1) * a.bytes_per_lane < nbytes ? (l + 1) * a.bytes_per_lane : nbytes;
+        adv[l] = crc_advance(nbytes - end);
+    }
+    unsigned init = 0xFFFFu;
+    for (int i = 0; i < 8 * nbytes; i++) init = ((init << 1) ^ ((init & 0x8000u) ? 0x1021u : 0u)) & 0xFFFFu;
+    adv[64] = (uint16_t)init;
+    KERNEL_TRY(launch_frame(a, h_sync, adv, c->stream));
+    c->last_kernel = a.coded ? "frame_kernel<coded>" : "frame_kernel<uncoded>";
     return QPSK_OK;
 }
 

@@ -361,6 +361,25 @@ int launch_deframe_coded_hunt(const DeframeCodedArgs &a, const DeframeCodedBody 
  * VITERBI_LDS_MAX_BYTES), otherwise in scratch ([nrows] rows of that many bytes) */
 int launch_deframe_coded_decode(const DeframeCodedArgs &a, const DeframeCodedBody &b, int row0, int nrows, unsigned long long *scratch, bool lds,
                                 hipStream_t s);
+/* frame.hip: qpsk_frame_batch (the definition: include/qpsk_hip.h, FRAMER).  One wave per packet; the caller has checked every bound */
+constexpr int FRAME_MAX_BYTES = DEFRAME_MAX_BYTES, FRAME_MAX_PER_ROW = 64, FRAME_MAX_ROW = DEFRAME_MAX_NSYM;
+struct FrameArgs {
+    const uint8_t *payload;       /* [npackets] payloads of nbytes bytes, pitch bytes apart */
+    size_t pitch;
+    uint8_t *out;                 /* [npackets / per_row][row_len] dibits */
+    uint16_t *crc;                /* [npackets] or NULL */
+    const uint8_t *ks;            /* [max(row_len, nbody)]: the scrambler's keystream dibits */
+    int npackets, per_row, nbytes, nsync;
+    int nbody;                    /* B, the dibits of a body on air */
+    int lead, gap, row_len;
+    int bytes_per_lane;           /* ceil(nbytes / 64): the payload bytes one lane's CRC share covers */
+    int coded;                    /* frame_kernel<coded>: punct is the body's pattern and nsent its sent bits */
+    unsigned nsent;
+    Puncture punct;
+};
+/* h_sync [nsync] dibits (taken & 3); h_crc_adv [65]: x^(8 k_l) mod the CRC-16 polynomial, k_l = the payload bytes behind lane l's chunk, then
+ * the init value's share 0xFFFF x^(8 nbytes).  Both travel in the kernel arguments */
+int launch_frame(const FrameArgs &a, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s);
 /* txchain.hip */
 int tx_history_symbols(void);          /* symbols of state per transmitter (uint8 each, 4 = none yet) */
 int launch_tx_shape(const uint8_t *sym, uint8_t *hist, const float *taps, float *sig, int nstreams, int nsym,

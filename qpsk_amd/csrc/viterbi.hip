@@ -40,6 +40,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "punct_table.h"
 #include "viterbi_row.h"
 
 namespace qpsk {
@@ -98,12 +99,7 @@ conv_encode_kernel(const uint8_t *__restrict__ in, size_t nrows, int nbits, int 
     out[i] = (uint8_t)(parity(r & 0x79u) | (parity(r & 0x5Bu) << 1));
 }
 
-/* sent bit m of a period -> its step within the period (bits 0..4) and which coded bit it is (bit 5): built by the host, passed by value */
-struct PunctTable {
-    uint8_t e[64];
-};
-
-/* one thread per transmitted dibit: sent bits 2 d and 2 d + 1 of the row, each mapped back to (t, j) through the table and encoded as
+/* one thread per transmitted dibit: sent bits 2 d and 2 d + 1 of the row, each mapped back to (t, j) through the table (punct_table.h) and encoded as
  * conv_encode_kernel does; a sent bit at or beyond nsent -- the pad bit of an odd nsent -- is 0 */
 __global__ void __launch_bounds__(256)
 conv_encode_punct_kernel(const uint8_t *__restrict__ in, size_t nrows, int nbits, unsigned nsent, unsigned ntx, int period, int K, PunctTable tab,
@@ -119,15 +115,15 @@ conv_encode_punct_kernel(const uint8_t *__restrict__ in, size_t nrows, int nbits
     for (int h = 0; h < 2; h++) {
         const unsigned k = 2 * d + h;
         if (k >= nsent) continue;
-        const unsigned q = k / (unsigned)K, e = tab.e[k - q * (unsigned)K];
-        const int t = (int)(q * (unsigned)period + (e & 31u));
+        int t;
+        const unsigned j = punct_sent_step(k, period, K, tab, &t);
         unsigned r = 0;
 #pragma unroll
         for (int b = 0; b < 7; b++) {
             const int p = t - b;
             if (p >= 0 && p < nbits) r |= ((unsigned)(src[p >> 3] >> (p & 7)) & 1u) << b;
         }
-        dibit |= (unsigned)parity(r & ((e & 32u) ? 0x5Bu : 0x79u)) << h;
+        dibit |= (unsigned)parity(r & (j ? 0x5Bu : 0x79u)) << h;
     }
     out[i] = (uint8_t)dibit;
 }
@@ -164,12 +160,8 @@ int launch_conv_encode_punct(const uint8_t *bits, int nrows, int nbits, int nste
         return (int)hipErrorInvalidValue;
     const long long nsent = punct_nsent(p, nsteps), ntx = (nsent + 1) / 2;
     if (ntx < 1) return (int)hipErrorInvalidValue;
-    PunctTable tab = {};
-    int m = 0;
-    for (int r = 0; r < p.period; r++)
-        for (int j = 0; j < 2; j++)
-            if (((j ? p.keep1 : p.keep0) >> r) & 1u) tab.e[m++] = (uint8_t)(r | (j << 5));
-    if (m != p.K) return (int)hipErrorInvalidValue;
+    PunctTable tab;
+    if (!punct_table_make(p, &tab)) return (int)hipErrorInvalidValue;
     const size_t n = (size_t)nrows * (size_t)ntx;
     if ((n + 255) / 256 > 0x7fffffffull) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(conv_encode_punct_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bits, (size_t)nrows, nbits, (unsigned)nsent,

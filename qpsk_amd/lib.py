@@ -61,6 +61,7 @@ API_SYMBOLS = [
     "qpsk_soft_batch", "qpsk_conv_encode_batch", "qpsk_viterbi_batch",
     "qpsk_punct_ntx", "qpsk_conv_encode_punct_batch", "qpsk_viterbi_punct_batch", "qpsk_deframer_reset_coded_punct",
     "qpsk_test_viterbi_launches", "qpsk_test_deframer_advance",
+    "qpsk_frame_len", "qpsk_frame_batch",
 ]
 # the named puncturing patterns of include/qpsk_hip.h (QPSK_PUNCT_*): rate -> (period, keep0, keep1), bit r of a mask = step r of the period
 PUNCTURE = {"1/2": (1, 0x1, 0x1), "2/3": (2, 0x1, 0x3), "3/4": (3, 0x5, 0x3), "5/6": (5, 0x15, 0x0B), "7/8": (7, 0x51, 0x2F)}
@@ -143,6 +144,8 @@ def load():
     L.qpsk_conv_encode_punct_batch.argtypes = [vp, vp, i32, i32, i32, i32, u32, u32, vp]
     L.qpsk_viterbi_punct_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, u32, u32, vp, i32, vp, vp]
     L.qpsk_deframer_reset_coded_punct.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, u32, u32]
+    L.qpsk_frame_len.argtypes = [i32, i32, i32, i32, u32, u32]
+    L.qpsk_frame_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, vp, i32, i32, i32, u32, u32, i32, i32, i32, vp, vp]
     L.qpsk_rrc_fir_batch.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_rrc_fir_batch_fast.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_timing_hist_batch.argtypes = [vp, vp, i32, vp, vp]
@@ -190,6 +193,26 @@ def load():
 def version():
     """qpsk_version() of the loaded library"""
     return load().qpsk_version().decode()
+
+
+FRAME_UNCODED, FRAME_CODED = 0, 1      # QPSK_FRAME_UNCODED, QPSK_FRAME_CODED
+
+
+def _coding(coded, puncture):
+    """frame()'s coded / puncture -> qpsk_frame_batch's (coding, period, keep0, keep1); coded with no pattern is rate 1/2"""
+    if not coded:
+        return (FRAME_UNCODED, 1, 1, 1)
+    return (FRAME_CODED,) + _pattern("1/2" if puncture is None else puncture)
+
+
+def frame_len(nsync, nbytes, coded=True, puncture=None):
+    """qpsk_frame_len: the dibits of one packet on air, sync word and body, as Modem.frame() builds it (coded, puncture as there); host
+    only, needs no GPU"""
+    L = load()
+    rc = L.qpsk_frame_len(int(nsync), int(nbytes), *_coding(coded, puncture))
+    if rc < 0:
+        raise QpskError("libqpsk_hip error %d: %s" % (rc, L.qpsk_last_error().decode()))
+    return rc
 
 
 def _ptr(t):
@@ -699,6 +722,34 @@ class Modem:
         self._check(self.L.qpsk_deframer_push_coded(self.h, _ptr(x), x.shape[1], _ptr(g), _ptr(o["count"]), _ptr(o["bytes"]), _ptr(o["pos"]),
                                                     _ptr(o["rot"]), _ptr(o["score"]), _ptr(o["crc_ok"]), _ptr(o["info"])))
         o["_keep"] = (x, g)
+        return o
+
+    # ---- packets onto the air (qpsk_frame_batch), the transmit twin of the deframers
+    def frame(self, payloads, sync, coded=True, puncture=None, per_row=1, lead=0, gap=0, row_len=None):
+        """qpsk_frame_batch: payloads (nrows * per_row, nbytes) or (nrows, per_row, nbytes) uint8 -> dict of torch tensors dibits (nrows,
+        row_len) uint8 -- per row per_row packets [sync][scrambled body], the first at column lead, gap idle columns between two, idle fill
+        (the scrambler's keystream from column 0) everywhere else: rows for tx_symbols() -- and crc (nrows * per_row,) int16, the CRC-16
+        sent (view it as uint16, as crc16() does).  sync: 1..128 dibits.  coded=False: the body deframe() receives; coded=True: the K = 7
+        code, rate 1/2 (deframer_reset_coded) or, with puncture (a key of PUNCTURE or a (period, keep0, keep1) tuple), the punctured
+        body.  row_len None = the exact fit."""
+        t = self.torch
+        p = self._dev(payloads, t.uint8)
+        per_row, lead, gap = int(per_row), int(lead), int(gap)
+        if p.dim() == 3 and p.shape[1] == per_row:
+            p = p.reshape(-1, p.shape[2])
+        if p.dim() != 2 or per_row < 1 or p.shape[0] < 1 or p.shape[0] % per_row:
+            raise ValueError("frame() payloads must be (nrows * per_row, nbytes) or (nrows, per_row, nbytes) uint8")
+        npk, nbytes = p.shape
+        sw = np.ascontiguousarray(np.asarray(sync, dtype=np.uint8))
+        code = _coding(coded, puncture)
+        if row_len is None:
+            P = self.L.qpsk_frame_len(len(sw), nbytes, *code)
+            self._check(min(P, 0))
+            row_len = lead + per_row * P + (per_row - 1) * gap
+        o = dict(dibits=self.empty((npk // per_row, int(row_len)), t.uint8), crc=self.empty((npk,), t.int16))
+        self._check(self.L.qpsk_frame_batch(self.h, _ptr(p), 0, npk // per_row, per_row, nbytes, sw.ctypes.data_as(C.c_void_p), len(sw), *code,
+                                            lead, gap, int(row_len), _ptr(o["dibits"]), _ptr(o["crc"])))
+        o["_keep"] = (p,)      # the input stays alive until the caller is done with the outputs (stream order)
         return o
 
     def streams_loop_state(self):
