@@ -125,7 +125,7 @@ int qpsk_ctx_set_stream(qpsk_ctx *ctx, void *stream);
  * loop -- they share the step's sine / cosine polynomial chains -- in workgroups of up to 16 frames, 2 = up to 32; the library's own choice is up to 24),
  * "QPSK_VITERBI_LDS" (qpsk_viterbi_batch: 0 = the decision words always wait in the context's scratch buffer, 1 = in LDS whenever a row's
  * fit -- up to 8192 steps; the library's own choice is LDS where every row of the call is resident at once), "QPSK_VITERBI_CHUNK_ROWS"
- * (qpsk_viterbi_batch, qpsk_viterbi_punct_batch and the decode of qpsk_deframer_push_coded off the LDS route: v >= 1 = at most v rows per
+ * (qpsk_viterbi_batch, qpsk_viterbi_punct_batch, qpsk_viterbi_ilv_batch and the decode of qpsk_deframer_push_coded off the LDS route: v >= 1 = at most v rows per
  * launch where that is fewer than the scratch buffer's 1 GiB cap allows -- the key only lowers the cap, and the buffer is sized for the
  * smaller chunk; 0 is refused with QPSK_ERR_ARG, here and as an environment value by qpsk_ctx_create(), where text that is not an
  * integer leaves the key unset; no effect on the LDS route);
@@ -541,13 +541,60 @@ int qpsk_viterbi_punct_batch(qpsk_ctx *ctx, const int8_t *d_soft, long long row_
  * per context, which only grows: when it cannot, QPSK_ERR_ALLOC, nothing launched, the context usable.  Stream-ordered on the context's
  * stream; neither reads nor updates the receive streams, the transmitters, the deframer, the histogram mode's guess or
  * qpsk_scramble_batch's cached keystream.  qpsk_ctx_last_kernel() names frame_kernel<uncoded> or frame_kernel<coded>.  Not built: a
- * streaming framer with state across calls, interleaving, qpsk_multi, host-pointer payloads.  Usage: INTEGRATION.md 2.0.
+ * streaming framer with state across calls, qpsk_multi, host-pointer payloads; interleaving is qpsk_frame_batch_ilv (INTERLEAVING below).  Usage: INTEGRATION.md 2.0.
  * ------------------------------------------------------------------------- */
 enum { QPSK_FRAME_UNCODED = 0, QPSK_FRAME_CODED = 1 };
 int qpsk_frame_len(int nsync, int nbytes, int coding, int period, uint32_t keep0, uint32_t keep1);
 int qpsk_frame_batch(qpsk_ctx *ctx, const uint8_t *d_payload, long long payload_pitch, int nrows, int per_row, int nbytes,
                      const uint8_t *h_sync, int nsync, int coding, int period, uint32_t keep0, uint32_t keep1, int lead, int gap,
                      int row_len, uint8_t *d_out, uint16_t *d_crc);
+
+/* -------------------------------------------------------------------------
+ * INTERLEAVING: the coded bits of a body spread over the body on air, so that a burst of bad symbols -- a fade, an interferer, a Costas
+ * loop that slips a quarter turn for a few symbols -- meets the decoder as isolated errors instead of a run, which a convolutional code
+ * does not survive.  The library's own definition, integers only (parity unpinned like PUNCTURING), restated in numpy
+ * by tests/test_ilv_cpu.py.  Everything is stated on PUNCTURING's terms idx(t, j), nsent, ntx; rate 1/2 is the pattern QPSK_PUNCT_1_2.
+ * (qpsk_interleave_batch below is the reference's byte interleaver and another thing: packed bytes, a prime table that ends at 347 bits.)
+ *
+ * DOMAIN.  n = 2 ntx(nsteps) bits: the transmitted body's bits, the pad bit of an odd nsent included.
+ * STRIDE.  stride = s with 1 <= s < max(n, 2) and gcd(s, n) = 1.  n is even, so s is odd.  s = 1 is the identity.
+ * PERMUTATION.  pi(k) = (k s) mod n for k in 0 .. n-1, the product formed in 64 bits (n reaches 2^18).  A bijection, since gcd(s, n) = 1.
+ * ENCODER.  On-air bit pi(k) is sent bit k, for k < nsent.  When nsent is odd, on-air bit pi(nsent) is the pad, 0.  On-air dibit
+ *   i = air[2 i] | air[2 i + 1] << 1.  A scrambler then acts on the on-air dibits exactly as before.
+ * DECODER INPUT.  v(a) = flat int8 number a of the transmitted row after the -128 rule, negated iff bit a & 1 of d_flip[a >> 1] is set: d_flip
+ *   still runs over the transmitted dibits.  Step t's input is
+ *       s_j = sent(t, j) ? v(pi(idx(t, j))) : 0
+ *   and everything after that is word for word qpsk_viterbi_batch.  The pad position is never read.
+ * Hence, and tested:  (1) the interleaved call equals qpsk_viterbi_punct_batch on the row gathered on the host, row'[k] = row[pi(k)], with
+ *   the flip bits gathered the same way, in d_bits and all four d_info words;  (2) stride 1 equals the punctured twin bit for bit, in every
+ *   call below.
+ * BURSTS.  On-air bits a and a + d carry coded bits that lie d s^-1 mod n apart; adjacent coded bits lie s apart on air.  A stride near
+ *   n / 16, qpsk_ilv_stride(n, n / 16), is a starting point, not a claim of optimality.
+ *
+ *   qpsk_ilv_stride                host only, no context: the smallest s >= min(want, nbits - 1) with gcd(s, nbits) = 1 (the search ends by
+ *                nbits - 1); nbits >= 2 and want >= 1, or QPSK_ERR_ARG
+ *   qpsk_conv_encode_ilv_batch     as qpsk_conv_encode_punct_batch -> d_dibits [nrows][ntx] on-air dibits
+ *   qpsk_viterbi_ilv_batch         as qpsk_viterbi_punct_batch in arguments, limits, row_pitch, where the decision words wait and the chunks
+ *   qpsk_frame_batch_ilv           qpsk_frame_batch with the stride, honoured for QPSK_FRAME_CODED (E above is then
+ *                qpsk_conv_encode_ilv_batch's output); with QPSK_FRAME_UNCODED a stride other than 1 is QPSK_ERR_ARG.  qpsk_frame_len is
+ *                unchanged: the length does not change
+ *   qpsk_deframer_reset_coded_ilv  qpsk_deframer_reset_coded_punct with the stride, kept in the deframer's state; qpsk_deframer_push_coded
+ *                stays the one push of all coded resets.  A bad stride resets nothing: the deframer stays as it was
+ * A bad stride (0, negative, even with n > 2, >= n, not coprime to n), or ntx = 0, gives QPSK_ERR_ARG at the call with nothing launched.
+ * qpsk_ctx_last_kernel() names conv_encode_ilv_kernel, viterbi_ilv_lds_kernel / viterbi_ilv_kernel, frame_kernel<coded,ilv> (stride 1 takes
+ * frame_kernel<coded>) and deframe_coded_decode_ilv_kernel<lds> / <global>.  Not built: interleaving for the uncoded format, for qpsk_multi,
+ * or across packets.  Usage: INTEGRATION.md 2.0.
+ * ------------------------------------------------------------------------- */
+int qpsk_ilv_stride(int nbits, int want);
+int qpsk_conv_encode_ilv_batch(qpsk_ctx *ctx, const uint8_t *d_bits, int nrows, int nbits, int flags, int period, uint32_t keep0,
+                               uint32_t keep1, int stride, uint8_t *d_dibits);
+int qpsk_viterbi_ilv_batch(qpsk_ctx *ctx, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, int period, uint32_t keep0,
+                           uint32_t keep1, int stride, const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info);
+int qpsk_frame_batch_ilv(qpsk_ctx *ctx, const uint8_t *d_payload, long long payload_pitch, int nrows, int per_row, int nbytes,
+                         const uint8_t *h_sync, int nsync, int coding, int period, uint32_t keep0, uint32_t keep1, int stride, int lead,
+                         int gap, int row_len, uint8_t *d_out, uint16_t *d_crc);
+int qpsk_deframer_reset_coded_ilv(qpsk_ctx *ctx, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes,
+                                  int max_packets, int mode, float scale, int period, uint32_t keep0, uint32_t keep1, int stride);
 
 /* -------------------------------------------------------------------------
  * The stages on their own (each is what the corresponding reference function
@@ -786,7 +833,7 @@ int qpsk_test_inject_status(qpsk_ctx *ctx, int code);
  * the last one-pass call's guess missed, and the statistics the host steers by: majority index, frames, frames off the majority or missed by the guess} */
 int qpsk_test_hist_state(qpsk_ctx *ctx, int32_t *out);
 /* Test hook (the chunk loops of the decoder's scratch route): *out = the decode launches of the context's last qpsk_viterbi_batch,
- * qpsk_viterbi_punct_batch or qpsk_deframer_push_coded call -- 1 with the decision words in LDS, 0 for a push whose bytes, crc_ok and
+ * qpsk_viterbi_punct_batch, qpsk_viterbi_ilv_batch or qpsk_deframer_push_coded call -- 1 with the decision words in LDS, 0 for a push whose bytes, crc_ok and
  * info were all NULL, or for a call that was refused.  Host bookkeeping only: no synchronisation, no device work. */
 int qpsk_test_viterbi_launches(qpsk_ctx *ctx, int *out);
 /* Test hook (stream positions beyond 32 bits): synchronises the context's stream, then adds delta to every stream's position counters

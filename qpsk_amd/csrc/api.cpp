@@ -112,7 +112,7 @@ struct qpsk_ctx {
     Tuning tune;
     int ncu = 256;                /* compute units of the device (256 on MI355X) */
     const char *last_kernel = ""; /* the receive kernel the last rx batch launched (qpsk_ctx_last_kernel) */
-    int viterbi_launches = 0;     /* decode launches of the last qpsk_viterbi_batch / qpsk_viterbi_punct_batch / qpsk_deframer_push_coded (qpsk_test_viterbi_launches) */
+    int viterbi_launches = 0;     /* decode launches of the last qpsk_viterbi_batch / _punct_batch / _ilv_batch / qpsk_deframer_push_coded (qpsk_test_viterbi_launches) */
     bool taps_symmetric = false;  /* taps[k] == taps[126 - k] bit for bit: rx_lean_kernel keeps the 64 distinct ones in SGPRs */
     hipStream_t stream = nullptr; /* caller's stream; nullptr = default stream */
     qpsk_params prm{};
@@ -183,6 +183,8 @@ struct qpsk_ctx {
     int df_nbody = 0;             /* Nc: a body's dibits on air (df_nsteps; ntx(df_nsteps) after qpsk_deframer_reset_coded_punct) */
     bool df_punct = false;        /* reset by qpsk_deframer_reset_coded_punct: the decode takes the punctured kernels, whatever the pattern */
     Puncture df_pattern = {1, 1u, 1u, 2};
+    bool df_ilv = false;          /* reset by qpsk_deframer_reset_coded_ilv: the decode takes the interleaved kernels, whatever the stride */
+    Interleave df_ilv_stride = {2u, 1u, 1u};
     float df_scale = 0.f;
     unsigned df_crc_init = 0;
     DevBuf dfstage;               /* the soft rows of the packets a coded push completes, between the hunt and the decode */
@@ -439,6 +441,7 @@ static void free_deframer(qpsk_ctx *c)
     c->df_ready = false;
     c->df_coded = false;
     c->df_punct = false;
+    c->df_ilv = false;
     c->df_nstreams = 0;
 }
 
@@ -1419,6 +1422,43 @@ int qpsk_conv_encode_punct_batch(qpsk_ctx *c, const uint8_t *d_bits, int nrows, 
     return QPSK_OK;
 }
 
+/* INTERLEAVING (include/qpsk_hip.h): the stride of a call over the ntx transmitted dibits of its rows, checked; who = the entry point's name */
+static int ilv_make(const char *who, long long ntx, int stride, Interleave *v)
+{
+    if (ntx < 1) return fail(QPSK_ERR_ARG, "%s: nothing is sent (ntx = 0), so there is nothing to interleave", who);
+    const unsigned n = 2u * (unsigned)ntx;
+    if (stride < 1 || (unsigned)stride >= std::max(n, 2u)) return fail(QPSK_ERR_ARG, "%s: stride = %d outside 1..%u", who, stride, std::max(n, 2u) - 1);
+    if (qpsk_host_gcd((unsigned)stride, n) != 1) return fail(QPSK_ERR_ARG, "%s: stride = %d is not coprime to the row's %u bits", who, stride, n);
+    *v = Interleave{n, (unsigned)stride, qpsk_host_mod_inverse((unsigned)stride, n)};
+    return QPSK_OK;
+}
+
+int qpsk_ilv_stride(int nbits, int want)
+{
+    if (nbits < 2 || want < 1) return fail(QPSK_ERR_ARG, "qpsk_ilv_stride: nbits = %d (>= 2), want = %d (>= 1)", nbits, want);
+    int s = std::min(want, nbits - 1);
+    while (qpsk_host_gcd((unsigned)s, (unsigned)nbits) != 1) s++;      /* gcd(nbits - 1, nbits) = 1 ends it */
+    return s;
+}
+
+int qpsk_conv_encode_ilv_batch(qpsk_ctx *c, const uint8_t *d_bits, int nrows, int nbits, int flags, int period, uint32_t keep0, uint32_t keep1,
+                               int stride, uint8_t *d_dibits)
+{
+    if (!c || !d_bits || !d_dibits) return fail(QPSK_ERR_ARG, "qpsk_conv_encode_ilv_batch: null argument");
+    if (flags & ~QPSK_CONV_TAIL) return fail(QPSK_ERR_ARG, "qpsk_conv_encode_ilv_batch: unknown flags 0x%x", flags);
+    const int tail = (flags & QPSK_CONV_TAIL) ? 6 : 0;
+    if (nrows <= 0 || nbits <= 0 || nbits > VITERBI_MAX_STEPS - tail)
+        return fail(QPSK_ERR_ARG, "qpsk_conv_encode_ilv_batch: nrows = %d, nbits = %d (1..%d)", nrows, nbits, VITERBI_MAX_STEPS - tail);
+    Puncture p;
+    if (int rc = punct_make("qpsk_conv_encode_ilv_batch", period, keep0, keep1, &p)) return rc;
+    Interleave v;
+    if (int rc = ilv_make("qpsk_conv_encode_ilv_batch", (punct_nsent(p, nbits + tail) + 1) / 2, stride, &v)) return rc;
+    if (bind(c)) return QPSK_ERR_HIP;
+    KERNEL_TRY(launch_conv_encode_ilv(d_bits, nrows, nbits, nbits + tail, p, v, d_dibits, c->stream));
+    c->last_kernel = "conv_encode_ilv_kernel";
+    return QPSK_OK;
+}
+
 /* Where the decision words (8 bytes per step) wait for the trace-back: in LDS when a row's fit the launch limit and -- the library's own
  * choice -- every row of the call is resident at once (160 KB of LDS per compute unit), so that the LDS never costs a second round of
  * workgroups; otherwise in the context's scratch buffer, rows in chunks of at most VITERBI_SCRATCH_MAX bytes of it */
@@ -1433,10 +1473,11 @@ static size_t viterbi_chunk_rows(const qpsk_ctx *c, size_t rows, size_t per_row,
     return std::min<size_t>(rows, cap);
 }
 
-/* both decoders: who = the entry point's name; punct = NULL for rate 1/2, otherwise the checked pattern: the rows then hold the ntx
- * transmitted dibits of nsteps steps, and row_pitch and d_flip go by ntx.  The residency rule, the scratch and the chunks go by nsteps */
+/* the decoders: who = the entry point's name; punct = NULL for rate 1/2, otherwise the checked pattern: the rows then hold the ntx
+ * transmitted dibits of nsteps steps, and row_pitch and d_flip go by ntx.  The residency rule, the scratch and the chunks go by nsteps.
+ * stride != NULL (with a pattern): qpsk_viterbi_ilv_batch; the stride is checked here, once nsteps is known to be in range */
 static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const Puncture *punct,
-                        const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info)
+                        const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info, const int *stride = nullptr)
 {
     if (c) c->viterbi_launches = 0;      /* a refused call made none */
     if (!c || !d_soft) return fail(QPSK_ERR_ARG, "%s: null context or input", who);
@@ -1454,6 +1495,17 @@ static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long
     if (row_pitch < nrow) return fail(QPSK_ERR_ARG, "%s: row_pitch = %lld (0, or >= %s %lld)", who, row_pitch, punct ? "ntx" : "nsteps", nrow);
     if ((uintptr_t)d_soft % 2) return fail(QPSK_ERR_ARG, "%s: d_soft is not 2-byte aligned", who);
     if ((uintptr_t)d_info % 4) return fail(QPSK_ERR_ARG, "%s: d_info is not 4-byte aligned", who);
+    Interleave ilv = {2u, 1u, 1u};
+    if (stride)
+        if (int rc = ilv_make(who, nrow, *stride, &ilv)) return rc;
+    /* one launch of rows [r0, r0 + n) */
+    const auto launch = [&](size_t r0, int n, unsigned long long *scratch, bool lds, size_t nbytes) {
+        const int8_t *soft = d_soft + 2 * r0 * (size_t)row_pitch;
+        uint8_t *bits = d_bits ? d_bits + r0 * nbytes : nullptr;
+        int32_t *info = d_info ? d_info + 4 * r0 : nullptr;
+        return stride ? launch_viterbi_ilv(soft, (size_t)row_pitch, n, nsteps, *punct, ilv, d_flip, flags, scratch, lds, bits, info, c->stream)
+                      : launch_viterbi(soft, (size_t)row_pitch, n, nsteps, punct, d_flip, flags, scratch, lds, bits, info, c->stream);
+    };
     static_assert(QPSK_VITERBI_OPEN_START == VITERBI_OPEN_START && QPSK_VITERBI_OPEN_END == VITERBI_OPEN_END, "the kernel takes the header's flag values");
     if (bind(c)) return QPSK_ERR_HIP;
     const size_t per_row = viterbi_scratch_bytes_per_row(nsteps);
@@ -1462,21 +1514,19 @@ static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long
     const bool lds = fits && tuned(c->tune.viterbi_lds, resident ? 1 : 0) != 0;
     const size_t nbytes = ((size_t)nsteps + 7) / 8;
     if (lds) {
-        KERNEL_TRY(launch_viterbi(d_soft, (size_t)row_pitch, nrows, nsteps, punct, d_flip, flags, nullptr, true, d_bits, d_info, c->stream));
+        KERNEL_TRY(launch(0, nrows, nullptr, true, nbytes));
         c->viterbi_launches = 1;
-        c->last_kernel = punct ? "viterbi_punct_lds_kernel" : "viterbi_lds_kernel";
+        c->last_kernel = stride ? "viterbi_ilv_lds_kernel" : punct ? "viterbi_punct_lds_kernel" : "viterbi_lds_kernel";
         return QPSK_OK;
     }
     const size_t chunk_rows = viterbi_chunk_rows(c, (size_t)nrows, per_row, false);
     if (int rg = ensure(c, c->vitdec, chunk_rows * per_row)) return rg;
     for (size_t r0 = 0; r0 < (size_t)nrows; r0 += chunk_rows) {      /* stream order: a chunk's trace-back is over before the next one's forward pass */
         const int n = (int)std::min<size_t>(chunk_rows, (size_t)nrows - r0);
-        KERNEL_TRY(launch_viterbi(d_soft + 2 * r0 * (size_t)row_pitch, (size_t)row_pitch, n, nsteps, punct, d_flip, flags,
-                                  (unsigned long long *)c->vitdec.p, false, d_bits ? d_bits + r0 * nbytes : nullptr, d_info ? d_info + 4 * r0 : nullptr,
-                                  c->stream));
+        KERNEL_TRY(launch(r0, n, (unsigned long long *)c->vitdec.p, false, nbytes));
         c->viterbi_launches++;
     }
-    c->last_kernel = punct ? "viterbi_punct_kernel" : "viterbi_kernel";
+    c->last_kernel = stride ? "viterbi_ilv_kernel" : punct ? "viterbi_punct_kernel" : "viterbi_kernel";
     return QPSK_OK;
 }
 
@@ -1494,6 +1544,16 @@ int qpsk_viterbi_punct_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pi
     c->viterbi_launches = 0;      /* a refused pattern made none */
     if (int rc = punct_make("qpsk_viterbi_punct_batch", period, keep0, keep1, &p)) return rc;
     return viterbi_impl(c, "qpsk_viterbi_punct_batch", d_soft, row_pitch, nrows, nsteps, &p, d_flip, flags, d_bits, d_info);
+}
+
+int qpsk_viterbi_ilv_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, int period, uint32_t keep0,
+                           uint32_t keep1, int stride, const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info)
+{
+    Puncture p;
+    if (!c) return fail(QPSK_ERR_ARG, "qpsk_viterbi_ilv_batch: null context or input");
+    c->viterbi_launches = 0;      /* a refused pattern made none */
+    if (int rc = punct_make("qpsk_viterbi_ilv_batch", period, keep0, keep1, &p)) return rc;
+    return viterbi_impl(c, "qpsk_viterbi_ilv_batch", d_soft, row_pitch, nrows, nsteps, &p, d_flip, flags, d_bits, d_info, &stride);
 }
 
 int qpsk_costas_batch(qpsk_ctx *c, const float *d_symbols_in, int nframes, int nsym, float *d_state, uint8_t *d_sym,
@@ -2105,7 +2165,7 @@ static const int DFC_ADV_OFFSET = (DEFRAME_CODED_MAX_STEPS + 15) & ~15;      /* 
 
 /* both resets: who = the entry point's name; coded: the body is 8 (nbytes + 2) + 6 coded dibits held as int8 pairs */
 static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes,
-                               int max_packets, bool coded, int mode, float scale, const Puncture *punct = nullptr)
+                               int max_packets, bool coded, int mode, float scale, const Puncture *punct = nullptr, const int *ilv_stride = nullptr)
 {
     if (!c || !h_sync) return fail(QPSK_ERR_ARG, "%s: null context or sync word", who);
     if (nstreams <= 0) return fail(QPSK_ERR_ARG, "%s: nstreams = %d", who, nstreams);
@@ -2118,14 +2178,17 @@ static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const
         if (h_sync[i] > 3) return fail(QPSK_ERR_ARG, "%s: sync[%d] = %d is not a dibit", who, i, (int)h_sync[i]);
     if (coded && mode != QPSK_SOFT_UNIT && mode != QPSK_SOFT_LLR) return fail(QPSK_ERR_ARG, "%s: unknown mode %d", who, mode);
     if (coded && !(scale > 0.0f && scale <= 3.402823466e+38f)) return fail(QPSK_ERR_ARG, "%s: scale = %g is not finite and > 0", who, (double)scale);
-    if (bind(c)) return QPSK_ERR_HIP;
-    /* refused until this call has completed */
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    free_deframer(c);
     const int nb = nbytes + 2, nsteps = 8 * nb + 6;
     /* dibits of a body: a punctured one is shorter than 8 nb + 6, so the pending buffer and the keystream table's bound hold as they are.
      * K >= 1 sent bit per period and nsteps > 32 >= period: at least one dibit */
     const int N = !coded ? 4 * nb : punct ? (int)((punct_nsent(*punct, nsteps) + 1) / 2) : nsteps;
+    Interleave ilv = {2u, 1u, 1u};
+    if (ilv_stride)      /* a bad stride resets nothing */
+        if (int rc = ilv_make(who, N, *ilv_stride, &ilv)) return rc;
+    if (bind(c)) return QPSK_ERR_HIP;
+    /* refused until this call has completed */
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    free_deframer(c);
     const size_t stride = (size_t)DEFRAME_PEND_OFFSET + (((size_t)N * (coded ? 2 : 1) + 15) & ~(size_t)15);
     const size_t tab_bytes = coded ? (size_t)DFC_ADV_OFFSET + 2 * (size_t)DEFRAME_MAX_BYTES : (size_t)DF_ADV_OFFSET + 128;
     if (hipMalloc(&c->df_state, stride * (size_t)nstreams) != hipSuccess || hipMalloc(&c->df_tables, tab_bytes) != hipSuccess) {
@@ -2179,6 +2242,8 @@ static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const
     c->df_nbody = coded ? N : 0;
     c->df_punct = coded && punct;
     c->df_pattern = punct ? *punct : Puncture{1, 1u, 1u, 2};
+    c->df_ilv = coded && punct && ilv_stride;
+    c->df_ilv_stride = ilv;
     c->df_ready = true;
     return QPSK_OK;
 }
@@ -2203,6 +2268,18 @@ int qpsk_deframer_reset_coded_punct(qpsk_ctx *c, int nstreams, const uint8_t *h_
     if (!c) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset_coded_punct: null context or sync word");
     if (int rc = punct_make("qpsk_deframer_reset_coded_punct", period, keep0, keep1, &p)) return rc;
     return deframer_reset_impl(c, "qpsk_deframer_reset_coded_punct", nstreams, h_sync, nsync, min_score, nbytes, max_packets, true, mode, scale, &p);
+}
+
+/* the same behind a stride of INTERLEAVING as well: the body is as long, its bits lie at pi(k) on air, and qpsk_deframer_push_coded decodes
+ * with the interleaved kernels */
+int qpsk_deframer_reset_coded_ilv(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets,
+                                  int mode, float scale, int period, uint32_t keep0, uint32_t keep1, int stride)
+{
+    Puncture p;
+    if (!c) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset_coded_ilv: null context or sync word");
+    if (int rc = punct_make("qpsk_deframer_reset_coded_ilv", period, keep0, keep1, &p)) return rc;
+    return deframer_reset_impl(c, "qpsk_deframer_reset_coded_ilv", nstreams, h_sync, nsync, min_score, nbytes, max_packets, true, mode, scale, &p,
+                               &stride);
 }
 
 /* what both pushes do behind their own argument checks (who = the entry point's name): the state checks, no output (the caller's
@@ -2331,7 +2408,10 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
     const DeframeCodedBody body = {Nc, pitch, c->df_punct ? 1 : 0, c->df_pattern};
     int e = launch_deframe_coded_hunt(a, body, c->stream);
     for (size_t r0 = 0; e == 0 && decode && r0 < rows; r0 += chunk_rows) {      /* stream order: a chunk's trace-back is over before the next one's forward pass */
-        e = launch_deframe_coded_decode(a, body, (int)r0, (int)std::min<size_t>(chunk_rows, rows - r0), lds ? nullptr : (unsigned long long *)c->vitdec.p, lds, c->stream);
+        const int n = (int)std::min<size_t>(chunk_rows, rows - r0);
+        unsigned long long *scratch = lds ? nullptr : (unsigned long long *)c->vitdec.p;
+        e = c->df_ilv ? launch_deframe_coded_decode_ilv(a, body, c->df_ilv_stride, (int)r0, n, scratch, lds, c->stream)
+                      : launch_deframe_coded_decode(a, body, (int)r0, n, scratch, lds, c->stream);
         if (e == 0) c->viterbi_launches++;
     }
     if (e != 0) {
@@ -2339,6 +2419,8 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
         return fail(QPSK_ERR_HIP, "qpsk_deframer_push_coded launch: %s", hipGetErrorString((hipError_t)e));
     }
     c->last_kernel = !decode       ? "deframe_coded_hunt_kernel"
+                     : c->df_ilv   ? (lds ? "deframe_coded_hunt_kernel + deframe_coded_decode_ilv_kernel<lds>"
+                                          : "deframe_coded_hunt_kernel + deframe_coded_decode_ilv_kernel<global>")
                      : c->df_punct ? (lds ? "deframe_coded_hunt_kernel + deframe_coded_decode_punct_kernel<lds>"
                                           : "deframe_coded_hunt_kernel + deframe_coded_decode_punct_kernel<global>")
                      : lds         ? "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<lds>"
@@ -2400,33 +2482,39 @@ static int frame_keystream(qpsk_ctx *c, int n)
     return QPSK_OK;
 }
 
-int qpsk_frame_batch(qpsk_ctx *c, const uint8_t *d_payload, long long payload_pitch, int nrows, int per_row, int nbytes,
-                     const uint8_t *h_sync, int nsync, int coding, int period, uint32_t keep0, uint32_t keep1, int lead, int gap,
-                     int row_len, uint8_t *d_out, uint16_t *d_crc)
+/* both framers: who = the entry point's name; stride = NULL for qpsk_frame_batch */
+static int frame_impl(qpsk_ctx *c, const char *who, const uint8_t *d_payload, long long payload_pitch, int nrows, int per_row, int nbytes,
+                      const uint8_t *h_sync, int nsync, int coding, int period, uint32_t keep0, uint32_t keep1, const int *stride, int lead, int gap,
+                      int row_len, uint8_t *d_out, uint16_t *d_crc)
 {
-    if (!c || !d_payload || !h_sync || !d_out) return fail(QPSK_ERR_ARG, "qpsk_frame_batch: null context, payload, sync word or output");
-    if (nsync < 1 || nsync > SYNC_MAX_WORD) return fail(QPSK_ERR_ARG, "qpsk_frame_batch: nsync = %d outside 1..%d", nsync, SYNC_MAX_WORD);
+    if (!c || !d_payload || !h_sync || !d_out) return fail(QPSK_ERR_ARG, "%s: null context, payload, sync word or output", who);
+    if (nsync < 1 || nsync > SYNC_MAX_WORD) return fail(QPSK_ERR_ARG, "%s: nsync = %d outside 1..%d", who, nsync, SYNC_MAX_WORD);
     Puncture p;
     int nbody = 0;
-    if (int rc = frame_body("qpsk_frame_batch", nbytes, coding, period, keep0, keep1, &p, &nbody)) return rc;
+    if (int rc = frame_body(who, nbytes, coding, period, keep0, keep1, &p, &nbody)) return rc;
     if (nrows < 1 || per_row < 1 || per_row > FRAME_MAX_PER_ROW || (long long)nrows * per_row > INT_MAX)
-        return fail(QPSK_ERR_ARG, "qpsk_frame_batch: nrows = %d, per_row = %d (1..%d, nrows * per_row < 2^31)", nrows, per_row, FRAME_MAX_PER_ROW);
+        return fail(QPSK_ERR_ARG, "%s: nrows = %d, per_row = %d (1..%d, nrows * per_row < 2^31)", who, nrows, per_row, FRAME_MAX_PER_ROW);
     if (payload_pitch != 0 && payload_pitch < nbytes)
-        return fail(QPSK_ERR_ARG, "qpsk_frame_batch: payload_pitch = %lld below nbytes = %d", payload_pitch, nbytes);
-    if (lead < 0 || gap < 0) return fail(QPSK_ERR_ARG, "qpsk_frame_batch: lead = %d, gap = %d", lead, gap);
+        return fail(QPSK_ERR_ARG, "%s: payload_pitch = %lld below nbytes = %d", who, payload_pitch, nbytes);
+    if (lead < 0 || gap < 0) return fail(QPSK_ERR_ARG, "%s: lead = %d, gap = %d", who, lead, gap);
     const long long need = (long long)lead + (long long)per_row * (nsync + nbody) + (long long)(per_row - 1) * gap;
     if (row_len < 1 || row_len > FRAME_MAX_ROW || need > row_len)
-        return fail(QPSK_ERR_ARG, "qpsk_frame_batch: lead %d + %d packets of %d dibits + gaps of %d = %lld do not fit row_len = %d (up to %d)", lead,
+        return fail(QPSK_ERR_ARG, "%s: lead %d + %d packets of %d dibits + gaps of %d = %lld do not fit row_len = %d (up to %d)", who, lead,
                     per_row, nsync + nbody, gap, need, row_len, FRAME_MAX_ROW);
     const size_t npk = (size_t)nrows * (size_t)per_row, pitch = payload_pitch ? (size_t)payload_pitch : (size_t)nbytes;
     const uintptr_t i0 = (uintptr_t)d_payload, i1 = i0 + (npk - 1) * pitch + (size_t)nbytes;
     const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)nrows * (size_t)row_len;
-    if (o0 < i1 && i0 < o1) return fail(QPSK_ERR_ARG, "qpsk_frame_batch: d_out overlaps d_payload");
+    if (o0 < i1 && i0 < o1) return fail(QPSK_ERR_ARG, "%s: d_out overlaps d_payload", who);
     if (d_crc) {
         const uintptr_t r0 = (uintptr_t)d_crc, r1 = r0 + 2 * npk;
         if (((uintptr_t)d_crc & 1) || (r0 < i1 && i0 < r1) || (r0 < o1 && o0 < r1))
-            return fail(QPSK_ERR_ARG, "qpsk_frame_batch: d_crc is not 2-byte aligned, or overlaps d_payload or d_out");
+            return fail(QPSK_ERR_ARG, "%s: d_crc is not 2-byte aligned, or overlaps d_payload or d_out", who);
     }
+    /* the stride: 1 is no interleaving at all and takes frame_kernel; the uncoded format has none */
+    Interleave ilv = {2u, 1u, 1u};
+    if (stride && coding == QPSK_FRAME_UNCODED && *stride != 1) return fail(QPSK_ERR_ARG, "%s: stride = %d with QPSK_FRAME_UNCODED (1 only)", who, *stride);
+    if (stride && coding == QPSK_FRAME_CODED)
+        if (int rc = ilv_make(who, nbody, *stride, &ilv)) return rc;
     if (bind(c)) return QPSK_ERR_HIP;
     if (int rc = frame_keystream(c, row_len > nbody ? row_len : nbody)) return rc;
     FrameArgs a{};
@@ -2456,9 +2544,30 @@ int qpsk_frame_batch(qpsk_ctx *c, const uint8_t *d_payload, long long payload_pi
     unsigned init = 0xFFFFu;
     for (int i = 0; i < 8 * nbytes; i++) init = ((init << 1) ^ ((init & 0x8000u) ? 0x1021u : 0u)) & 0xFFFFu;
     adv[64] = (uint16_t)init;
+    if (ilv.s != 1) {
+        KERNEL_TRY(launch_frame_ilv(a, ilv, h_sync, adv, c->stream));
+        c->last_kernel = "frame_kernel<coded,ilv>";
+        return QPSK_OK;
+    }
     KERNEL_TRY(launch_frame(a, h_sync, adv, c->stream));
     c->last_kernel = a.coded ? "frame_kernel<coded>" : "frame_kernel<uncoded>";
     return QPSK_OK;
+}
+
+int qpsk_frame_batch(qpsk_ctx *c, const uint8_t *d_payload, long long payload_pitch, int nrows, int per_row, int nbytes,
+                     const uint8_t *h_sync, int nsync, int coding, int period, uint32_t keep0, uint32_t keep1, int lead, int gap,
+                     int row_len, uint8_t *d_out, uint16_t *d_crc)
+{
+    return frame_impl(c, "qpsk_frame_batch", d_payload, payload_pitch, nrows, per_row, nbytes, h_sync, nsync, coding, period, keep0, keep1, nullptr,
+                      lead, gap, row_len, d_out, d_crc);
+}
+
+int qpsk_frame_batch_ilv(qpsk_ctx *c, const uint8_t *d_payload, long long payload_pitch, int nrows, int per_row, int nbytes,
+                         const uint8_t *h_sync, int nsync, int coding, int period, uint32_t keep0, uint32_t keep1, int stride, int lead, int gap,
+                         int row_len, uint8_t *d_out, uint16_t *d_crc)
+{
+    return frame_impl(c, "qpsk_frame_batch_ilv", d_payload, payload_pitch, nrows, per_row, nbytes, h_sync, nsync, coding, period, keep0, keep1,
+                      &stride, lead, gap, row_len, d_out, d_crc);
 }
 
 /* test hook (tests/test_viterbi_chunks_gpu.py): host bookkeeping only */

@@ -21,6 +21,9 @@
  *                                 come from a table -- and a wave xor behind the trace-back sums the shares.  One template: <LDS, PUNCT>.
  *                                 PUNCT (qpsk_deframer_reset_coded_punct) takes viterbi_row.h's PunctLoader on the Nc staged dibits:
  *                                 nsteps = 8 (nbytes + 2) + 6 trellis steps, the keystream flips the transmitted dibits.
+ *   deframe_coded_decode_ilv_kernel   the PUNCT instance behind viterbi_row.h's IlvLoader (qpsk_deframer_reset_coded_ilv): the staged row is
+ *                                 the body as it was on air, and the loader reads sent bit k and its keystream bit at pi(k).  The hunt is
+ *                                 the same: it only takes the body's length.
  *
  * A staging row is addressed by (stream, slot), the packet's place in the outputs, so there is no list to append to and no atomic:
  * per_stream = min(max_packets, nsym / (nsync + Nc) + 1) bounds what one push can complete in a stream (packet ends lie nsync + Nc
@@ -151,6 +154,28 @@ deframe_coded_decode_kernel(DeframeCodedArgs a, int row0, unsigned long long *sc
     if (lane == 0 && a.crc_ok) a.crc_ok[r] = (uint8_t)(((share & 0xFFFFu) ^ a.crc_init) == (share >> 16));
 }
 
+/* deframe_coded_decode_kernel<LDS, true> with the stride: a kernel of its own, so that the four above keep their names and arguments */
+template <bool LDS>
+__global__ void __launch_bounds__(64)
+deframe_coded_decode_ilv_kernel(DeframeCodedArgs a, int row0, unsigned long long *scratch, DeframeCodedBody b, IlvMul pi)
+{
+    const int lane = threadIdx.x;
+    const int e = row0 + (int)blockIdx.x;
+    const int stream = e / a.per_stream, slot = e - stream * a.per_stream;
+    if (slot >= a.count[stream]) return;
+    const size_t r = (size_t)stream * a.max_packets + slot;
+    const size_t nblk = ((size_t)a.nsteps + 63) >> 6;
+    PacketSink sink = {a.bytes ? a.bytes + r * (size_t)(a.nbytes + 2) : nullptr, a.crc_adv, a.nbytes, 0u};
+    unsigned long long *gdec = LDS ? nullptr : scratch + (size_t)blockIdx.x * (nblk << 6);
+    int32_t *info = a.info ? a.info + 4 * r : nullptr;
+    const IlvLoader ld = {a.stage + 2 * (size_t)e * (size_t)b.stage_pitch, a.flip, b.punct, pi};
+    viterbi_row<LDS>(ld, a.nsteps, 0, gdec, info, sink);
+    unsigned share = sink.share;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) share ^= (unsigned)__shfl_xor((int)share, o, 64);
+    if (lane == 0 && a.crc_ok) a.crc_ok[r] = (uint8_t)(((share & 0xFFFFu) ^ a.crc_init) == (share >> 16));
+}
+
 } // namespace
 
 int launch_deframe_coded_hunt(const DeframeCodedArgs &a, const DeframeCodedBody &b, hipStream_t s)
@@ -179,6 +204,23 @@ int launch_deframe_coded_decode(const DeframeCodedArgs &a, const DeframeCodedBod
         else hipLaunchKernelGGL((deframe_coded_decode_kernel<false, true>), grid, block, 0, s, a, row0, scratch, b);
     } else if (lds) hipLaunchKernelGGL((deframe_coded_decode_kernel<true, false>), grid, block, bytes, s, a, row0, scratch, b);
     else hipLaunchKernelGGL((deframe_coded_decode_kernel<false, false>), grid, block, 0, s, a, row0, scratch, b);
+    return (int)hipGetLastError();
+}
+
+int launch_deframe_coded_decode_ilv(const DeframeCodedArgs &a, const DeframeCodedBody &b, const Interleave &ilv, int row0, int nrows,
+                                    unsigned long long *scratch, bool lds, hipStream_t s)
+{
+    if (row0 < 0 || nrows <= 0 || (long long)row0 + nrows > (long long)a.nstreams * a.per_stream || !a.stage || !a.count || !a.flip || !a.crc_adv)
+        return (int)hipErrorInvalidValue;
+    if (b.punct.period < 1 || b.punct.period > 32 || b.punct.K < 1 || 2LL * b.nbody != 2 * ((punct_nsent(b.punct, a.nsteps) + 1) / 2) ||
+        b.stage_pitch < b.nbody || ilv.n != 2u * (unsigned)b.nbody || ilv.s < 1 || ilv.s >= ilv.n)
+        return (int)hipErrorInvalidValue;
+    const size_t bytes = viterbi_scratch_bytes_per_row(a.nsteps);
+    if (lds ? bytes > (size_t)VITERBI_LDS_MAX_BYTES : !scratch) return (int)hipErrorInvalidValue;
+    const dim3 grid(nrows), block(64);
+    const IlvMul pi = ilv_mul(ilv.n, ilv.s);
+    if (lds) hipLaunchKernelGGL((deframe_coded_decode_ilv_kernel<true>), grid, block, bytes, s, a, row0, scratch, b, pi);
+    else hipLaunchKernelGGL((deframe_coded_decode_ilv_kernel<false>), grid, block, 0, s, a, row0, scratch, b, pi);
     return (int)hipGetLastError();
 }
 

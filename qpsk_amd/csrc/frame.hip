@@ -24,6 +24,9 @@
  *           does the same).  The pad bit of an odd nsent stays 0 before the xor.
  *   stores  byte-wise up to the first 4-byte aligned ADDRESS of the range (d_out, row_len and the start column are arbitrary), then one
  *           dword of four dibits per lane, 256 contiguous bytes per wave instruction, then a byte-wise tail.
+ * frame_ilv_kernel (qpsk_frame_batch_ilv, INTERLEAVING in include/qpsk_hip.h): the coded kernel with the gather turned round -- on-air bit
+ * 2 i + h of the body takes sent bit (2 i + h) s^-1 mod n, or 0 when that is at or beyond nsent (the pad's place) -- and everything else,
+ * the stores included, as it is.  One body, frame_packet<CODED, ILV>, behind both kernel names.
  * No atomics, no scratch, no inter-wave traffic beyond the two barriers that order a wave's own LDS writes before its reads.
  */
 #include <hip/hip_runtime.h>
@@ -49,14 +52,15 @@ struct FrameTables {
     PunctTable punct;
 };
 
-template <bool CODED>
-__device__ __forceinline__ unsigned body_dibit(const FrameArgs &a, const FrameTables &t, const uint8_t *slice, int i)
+template <bool CODED, bool ILV>
+__device__ __forceinline__ unsigned body_dibit(const FrameArgs &a, const FrameTables &t, const IlvMul &inv, const uint8_t *slice, int i)
 {
     if (!CODED) return ((unsigned)slice[1 + (i >> 2)] >> (2 * (i & 3))) & 3u;
-    unsigned dibit = 0;
+    unsigned dibit = 0, at = ILV ? inv.at(2u * (unsigned)i) : 0u;
 #pragma unroll
     for (int h = 0; h < 2; h++) {
-        const unsigned k = 2u * (unsigned)i + (unsigned)h;
+        const unsigned k = ILV ? at : 2u * (unsigned)i + (unsigned)h;
+        if (ILV) at = inv.next(at);
         if (k >= a.nsent) continue;
         int step;
         const unsigned j = punct_sent_step(k, a.punct.period, a.punct.K, t.punct, &step);
@@ -68,9 +72,8 @@ __device__ __forceinline__ unsigned body_dibit(const FrameArgs &a, const FrameTa
     return dibit;
 }
 
-template <bool CODED>
-__global__ void __launch_bounds__(64 * FRAME_WAVES)
-frame_kernel(FrameArgs a, FrameTables t)
+template <bool CODED, bool ILV>
+__device__ __forceinline__ void frame_packet(const FrameArgs &a, const FrameTables &t, const IlvMul &inv)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[FRAME_WAVES][FRAME_SLICE];
     const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6);
@@ -118,7 +121,7 @@ frame_kernel(FrameArgs a, FrameTables t)
         const int i = c - start;
         if (i < 0 || i >= P) return a.ks[c];
         if (i < a.nsync) return t.sync[i];
-        return (unsigned)a.ks[i - a.nsync] ^ body_dibit<CODED>(a, t, slice, i - a.nsync);
+        return (unsigned)a.ks[i - a.nsync] ^ body_dibit<CODED, ILV>(a, t, inv, slice, i - a.nsync);
     };
     int head = (int)((4u - (unsigned)((uintptr_t)(out + c0) & 3u)) & 3u);
     if (head > c1 - c0) head = c1 - c0;
@@ -133,9 +136,23 @@ frame_kernel(FrameArgs a, FrameTables t)
     if (lane < c1 - ct) out[ct + lane] = (uint8_t)dibit_at(ct + lane);
 }
 
+template <bool CODED>
+__global__ void __launch_bounds__(64 * FRAME_WAVES)
+frame_kernel(FrameArgs a, FrameTables t)
+{
+    frame_packet<CODED, false>(a, t, IlvMul{});
+}
+
+__global__ void __launch_bounds__(64 * FRAME_WAVES)
+frame_ilv_kernel(FrameArgs a, FrameTables t, IlvMul inv)
+{
+    frame_packet<true, true>(a, t, inv);
+}
+
 } // namespace
 
-int launch_frame(const FrameArgs &a, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s)
+/* ilv = NULL: frame_kernel<coded> / <uncoded> */
+static int launch_frame_impl(const FrameArgs &a, const Interleave *ilv, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s)
 {
     if (!a.payload || !a.out || !a.ks || !h_sync || !h_crc_adv || a.npackets < 1 || a.per_row < 1 || a.nbytes < 1 || a.nbytes > FRAME_MAX_BYTES ||
         a.nsync < 1 || a.nsync > SYNC_MAX_WORD || a.nbody < 1 || a.lead < 0 || a.gap < 0 || a.bytes_per_lane * 64 < a.nbytes)
@@ -147,11 +164,24 @@ int launch_frame(const FrameArgs &a, const uint8_t *h_sync, const uint16_t *h_cr
     for (int i = 0; i < 65; i++) t.crc_adv[i] = h_crc_adv[i];
     if (a.coded && !punct_table_make(a.punct, &t.punct)) return (int)hipErrorInvalidValue;
     const dim3 grid(((unsigned)a.npackets + FRAME_WAVES - 1) / FRAME_WAVES), block(64 * FRAME_WAVES);
-    if (a.coded)
+    if (ilv) {
+        if (!a.coded || ilv->n != 2u * (unsigned)a.nbody || a.nsent > ilv->n || ilv->sinv < 1 || ilv->sinv >= ilv->n) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(frame_ilv_kernel, grid, block, 0, s, a, t, ilv_mul(ilv->n, ilv->sinv));
+    } else if (a.coded)
         hipLaunchKernelGGL(frame_kernel<true>, grid, block, 0, s, a, t);
     else
         hipLaunchKernelGGL(frame_kernel<false>, grid, block, 0, s, a, t);
     return (int)hipGetLastError();
+}
+
+int launch_frame(const FrameArgs &a, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s)
+{
+    return launch_frame_impl(a, nullptr, h_sync, h_crc_adv, s);
+}
+
+int launch_frame_ilv(const FrameArgs &a, const Interleave &ilv, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s)
+{
+    return launch_frame_impl(a, &ilv, h_sync, h_crc_adv, s);
 }
 
 } // namespace qpsk

@@ -125,6 +125,34 @@ void qpsk_host_scramble_keystream(unsigned char *ks, int nsym)
     }
 }
 
+unsigned qpsk_host_gcd(unsigned a, unsigned b)
+{
+    while (b) {
+        const unsigned r = a % b;
+        a = b;
+        b = r;
+    }
+    return a;
+}
+
+/* the extended Euclidean algorithm on (n, s mod n), the coefficient of s kept mod n; n = 2 has the inverse 1 of s = 1 */
+unsigned qpsk_host_mod_inverse(unsigned s, unsigned n)
+{
+    if (n < 2)
+        return 0;
+    long long r0 = n, r1 = s % n, x0 = 0, x1 = 1;
+    while (r1) {
+        const long long q = r0 / r1, r = r0 - q * r1, x = x0 - q * x1;
+        r0 = r1;
+        r1 = r;
+        x0 = x1;
+        x1 = x;
+    }
+    if (r0 != 1)
+        return 0;
+    return (unsigned)((x0 % (long long)n + (long long)n) % (long long)n);
+}
+
 void qpsk_host_fir_fast_tables(const float taps[QPSK_HOST_NTAPS], float *H, float *tw)
 {
     const int n = 512;

@@ -19,6 +19,9 @@ void qpsk_host_phases(int n, double *cs);   /* cs[n][2]   = cos, sin of 2 pi i /
 void qpsk_host_fir_fast_tables(const float taps[QPSK_HOST_NTAPS], float *H, float *tw);
 unsigned qpsk_host_interleave_prime(unsigned nbits);
 void qpsk_host_scramble_keystream(unsigned char *ks, int nsym);
+/* INTERLEAVING (include/qpsk_hip.h): gcd(a, b) with gcd(a, 0) = a, and the x in 1..n-1 with s x = 1 mod n (0: there is none, or n < 2) */
+unsigned qpsk_host_gcd(unsigned a, unsigned b);
+unsigned qpsk_host_mod_inverse(unsigned s, unsigned n);
 
 #ifdef __cplusplus
 }

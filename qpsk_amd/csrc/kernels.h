@@ -276,13 +276,34 @@ inline long long punct_nsent(const Puncture &p, int nsteps)
     const unsigned r = (unsigned)(nsteps % p.period), low = (1u << r) - 1u;
     return (long long)(nsteps / p.period) * p.K + __builtin_popcount(p.keep0 & low) + __builtin_popcount(p.keep1 & low);
 }
+/* a stride of INTERLEAVING (include/qpsk_hip.h), checked by the host (api.cpp, ilv_make): n = 2 ntx bits on air, 1 <= s < max(n, 2),
+ * gcd(s, n) = 1, s sinv = 1 mod n.  pi(k) = k s mod n is where sent bit k lies on air; on-air bit a is sent bit a sinv mod n */
+struct Interleave {
+    unsigned n, s, sinv;
+};
+/* what a kernel takes of it: k -> k m mod n for k < n <= 2^18, m = s (the decoder's pi) or sinv (the encoders' gather).  The definition forms
+ * the product in 64 bits; here it is split at 2^9 -- k m = (k >> 9) (2^9 m mod n) + (k & 511) m < 2^28 -- so that one 32-bit remainder
+ * reduces it and no 64-bit division is ever expanded.  m9 = 2^9 m mod n comes from the host */
+struct IlvMul {
+    unsigned n, m, m9;
+    __host__ __device__ __forceinline__ unsigned at(unsigned k) const { return ((k >> 9) * m9 + (k & 511u) * m) % n; }
+    /* at(k + 1) from at(k): one conditional subtract */
+    __host__ __device__ __forceinline__ unsigned next(unsigned a) const { return a + m >= n ? a + m - n : a + m; }
+};
+inline IlvMul ilv_mul(unsigned n, unsigned m) { return IlvMul{n, m, (unsigned)(((unsigned long long)m << 9) % n)}; }
 /* punct = NULL: rate 1/2, pitch in steps, flip [nsteps].  Otherwise the punctured kernels (viterbi_punct_kernel, viterbi_punct_lds_kernel):
  * pitch in transmitted dibits, flip [ntx]; the residency rule goes by nsteps either way */
 int launch_viterbi(const int8_t *soft, size_t pitch, int nrows, int nsteps, const Puncture *punct, const uint8_t *flip, int flags,
                    unsigned long long *scratch, bool lds, uint8_t *bits, int32_t *info, hipStream_t s);
+/* viterbi_ilv_kernel / viterbi_ilv_lds_kernel: launch_viterbi behind a pattern and a stride (ilv.n = 2 ntx of the pattern) */
+int launch_viterbi_ilv(const int8_t *soft, size_t pitch, int nrows, int nsteps, const Puncture &punct, const Interleave &ilv, const uint8_t *flip,
+                       int flags, unsigned long long *scratch, bool lds, uint8_t *bits, int32_t *info, hipStream_t s);
 int launch_conv_encode(const uint8_t *bits, int nrows, int nbits, int nsteps, uint8_t *dibits, hipStream_t s);
 /* conv_encode_punct_kernel: one thread per transmitted dibit, dibits [nrows][ntx], ntx = ceil(punct_nsent / 2) >= 1 */
 int launch_conv_encode_punct(const uint8_t *bits, int nrows, int nbits, int nsteps, const Puncture &punct, uint8_t *dibits, hipStream_t s);
+/* conv_encode_ilv_kernel: the same thread per transmitted dibit; on-air bit a is sent bit a sinv mod n */
+int launch_conv_encode_ilv(const uint8_t *bits, int nrows, int nbits, int nsteps, const Puncture &punct, const Interleave &ilv, uint8_t *dibits,
+                           hipStream_t s);
 /* deframe.hip: qpsk_deframer_push.  Per stream, state_stride bytes of state: the header, the carried tail (the ring values of the last
  * min(len, nsync-1) dibits) at DEFRAME_TAIL_OFFSET, the pending packet's received payload (ring values) at DEFRAME_PEND_OFFSET */
 struct DeframeHeader {
@@ -361,6 +382,10 @@ int launch_deframe_coded_hunt(const DeframeCodedArgs &a, const DeframeCodedBody 
  * VITERBI_LDS_MAX_BYTES), otherwise in scratch ([nrows] rows of that many bytes) */
 int launch_deframe_coded_decode(const DeframeCodedArgs &a, const DeframeCodedBody &b, int row0, int nrows, unsigned long long *scratch, bool lds,
                                 hipStream_t s);
+/* qpsk_deframer_reset_coded_ilv: the same rows through deframe_coded_decode_ilv_kernel<lds>; b as behind the pattern, ilv.n = 2 b.nbody.
+ * The stride is an argument of these kernels alone, so that the others keep theirs as they were */
+int launch_deframe_coded_decode_ilv(const DeframeCodedArgs &a, const DeframeCodedBody &b, const Interleave &ilv, int row0, int nrows,
+                                    unsigned long long *scratch, bool lds, hipStream_t s);
 /* frame.hip: qpsk_frame_batch (the definition: include/qpsk_hip.h, FRAMER).  One wave per packet; the caller has checked every bound */
 constexpr int FRAME_MAX_BYTES = DEFRAME_MAX_BYTES, FRAME_MAX_PER_ROW = 64, FRAME_MAX_ROW = DEFRAME_MAX_NSYM;
 struct FrameArgs {
@@ -380,6 +405,8 @@ struct FrameArgs {
 /* h_sync [nsync] dibits (taken & 3); h_crc_adv [65]: x^(8 k_l) mod the CRC-16 polynomial, k_l = the payload bytes behind lane l's chunk, then
  * the init value's share 0xFFFF x^(8 nbytes).  Both travel in the kernel arguments */
 int launch_frame(const FrameArgs &a, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s);
+/* qpsk_frame_batch_ilv with a stride other than 1: frame_ilv_kernel, a.coded set, ilv.n = 2 a.nbody */
+int launch_frame_ilv(const FrameArgs &a, const Interleave &ilv, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s);
 /* txchain.hip */
 int tx_history_symbols(void);          /* symbols of state per transmitter (uint8 each, 4 = none yet) */
 int launch_tx_shape(const uint8_t *sym, uint8_t *hist, const float *taps, float *sig, int nstreams, int nsym,

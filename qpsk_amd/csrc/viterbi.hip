@@ -35,6 +35,12 @@
  * division by the period and two popcounts per lane and 64 steps -- and loads them, and their flip bits, bytewise; unsent bits are 0.
  * That happens where the load sat, lane-parallel and a block ahead; the per-step chain is untouched.  conv_encode_punct_kernel: one
  * thread per transmitted dibit, its two sent bits mapped back to (step, generator) through a table of the period's K <= 64 sent bits.
+ *
+ * INTERLEAVING (qpsk_viterbi_ilv_batch, qpsk_conv_encode_ilv_batch; INTERLEAVING in include/qpsk_hip.h, restated by tests/test_ilv_cpu.py).
+ * The coded bits of a row are spread over the row on air by pi(k) = k s mod n.  Both sides gather: viterbi_ilv_kernel /
+ * viterbi_ilv_lds_kernel are the punctured kernels behind viterbi_row.h's IlvLoader, which reads sent bit k's soft value and flip bit at
+ * pi(k); conv_encode_ilv_kernel is conv_encode_punct_kernel whose on-air bit a takes sent bit a s^-1 mod n.  No scatter, no atomics, no
+ * pass of its own over memory, and nothing in the per-step chain.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -80,6 +86,22 @@ __global__ void __launch_bounds__(64) viterbi_kernel(VitArgs a) { viterbi_batch_
 __global__ void __launch_bounds__(64) viterbi_lds_kernel(VitArgs a) { viterbi_batch_row<true, false>(a); }
 __global__ void __launch_bounds__(64) viterbi_punct_kernel(VitArgs a) { viterbi_batch_row<false, true>(a); }
 __global__ void __launch_bounds__(64) viterbi_punct_lds_kernel(VitArgs a) { viterbi_batch_row<true, true>(a); }
+
+/* the same row behind IlvLoader; the stride is an argument of these two kernels alone */
+template <bool LDS>
+__device__ __forceinline__ void viterbi_ilv_row(const VitArgs &a, const IlvMul &pi)
+{
+    const size_t row = blockIdx.x;
+    const size_t nblk = ((size_t)a.nsteps + 63) >> 6;
+    BitsSink sink = {a.bits ? a.bits + row * (((size_t)a.nsteps + 7) >> 3) : nullptr};
+    unsigned long long *gdec = LDS ? nullptr : a.scratch + row * (nblk << 6);
+    int32_t *info = a.info ? a.info + 4 * row : nullptr;
+    const IlvLoader ld = {a.soft + 2 * row * a.pitch, a.flip, a.punct, pi};
+    viterbi_row<LDS>(ld, a.nsteps, a.flags, gdec, info, sink);
+}
+
+__global__ void __launch_bounds__(64) viterbi_ilv_kernel(VitArgs a, IlvMul pi) { viterbi_ilv_row<false>(a, pi); }
+__global__ void __launch_bounds__(64) viterbi_ilv_lds_kernel(VitArgs a, IlvMul pi) { viterbi_ilv_row<true>(a, pi); }
 
 /* one thread per coded dibit: register r of step t = bits t-6 .. t (bit t in bit 0), zeros before the row and in the tail */
 __global__ void __launch_bounds__(256)
@@ -128,6 +150,34 @@ conv_encode_punct_kernel(const uint8_t *__restrict__ in, size_t nrows, int nbits
     out[i] = (uint8_t)dibit;
 }
 
+/* conv_encode_punct_kernel behind the permutation: on-air bits 2 d and 2 d + 1 take sent bits (2 d) s^-1 mod n and that + s^-1 (mod n); a sent
+ * bit number at or beyond nsent is the pad of an odd nsent, 0 */
+__global__ void __launch_bounds__(256)
+conv_encode_ilv_kernel(const uint8_t *__restrict__ in, size_t nrows, int nbits, unsigned nsent, unsigned ntx, int period, int K, PunctTable tab,
+                       IlvMul inv, uint8_t *__restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nrows * (size_t)ntx) return;
+    const size_t row = i / ntx;
+    const unsigned d = (unsigned)(i - row * ntx);
+    const uint8_t *src = in + row * (size_t)((nbits + 7) >> 3);
+    unsigned dibit = 0, k = inv.at(2 * d);
+#pragma unroll
+    for (int h = 0; h < 2; h++, k = inv.next(k)) {
+        if (k >= nsent) continue;
+        int t;
+        const unsigned j = punct_sent_step(k, period, K, tab, &t);
+        unsigned r = 0;
+#pragma unroll
+        for (int b = 0; b < 7; b++) {
+            const int p = t - b;
+            if (p >= 0 && p < nbits) r |= ((unsigned)(src[p >> 3] >> (p & 7)) & 1u) << b;
+        }
+        dibit |= (unsigned)parity(r & (j ? 0x5Bu : 0x79u)) << h;
+    }
+    out[i] = (uint8_t)dibit;
+}
+
 } // namespace
 
 size_t viterbi_scratch_bytes_per_row(int nsteps) { return sizeof(unsigned long long) * (((size_t)nsteps + 63) & ~(size_t)63); }
@@ -142,6 +192,26 @@ int launch_viterbi(const int8_t *soft, size_t pitch, int nrows, int nsteps, cons
     const VitArgs a = {soft, pitch, nsteps, flags, flip, scratch, bits, info, punct ? *punct : Puncture{1, 1u, 1u, 2}};
     if (lds) hipLaunchKernelGGL(punct ? viterbi_punct_lds_kernel : viterbi_lds_kernel, dim3(nrows), dim3(64), bytes, s, a);
     else hipLaunchKernelGGL(punct ? viterbi_punct_kernel : viterbi_kernel, dim3(nrows), dim3(64), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+/* n = 2 ntx of the pattern, 1 <= s < max(n, 2); that s is coprime to n and sinv its inverse is the caller's (api.cpp, ilv_make) */
+static bool ilv_fits(const Interleave &v, long long ntx)
+{
+    return ntx >= 1 && ntx <= (long long)VITERBI_MAX_STEPS && v.n == 2u * (unsigned)ntx && v.s >= 1 && v.s < v.n && v.sinv >= 1 && v.sinv < v.n;
+}
+
+int launch_viterbi_ilv(const int8_t *soft, size_t pitch, int nrows, int nsteps, const Puncture &punct, const Interleave &ilv, const uint8_t *flip,
+                       int flags, unsigned long long *scratch, bool lds, uint8_t *bits, int32_t *info, hipStream_t s)
+{
+    if (nrows <= 0 || nsteps <= 0 || nsteps > VITERBI_MAX_STEPS || !soft || (!bits && !info)) return (int)hipErrorInvalidValue;
+    if (punct.period < 1 || punct.period > 32 || punct.K < 1 || !ilv_fits(ilv, (punct_nsent(punct, nsteps) + 1) / 2)) return (int)hipErrorInvalidValue;
+    const size_t bytes = viterbi_scratch_bytes_per_row(nsteps);
+    if (lds ? bytes > (size_t)VITERBI_LDS_MAX_BYTES : !scratch) return (int)hipErrorInvalidValue;
+    const VitArgs a = {soft, pitch, nsteps, flags, flip, scratch, bits, info, punct};
+    const IlvMul pi = ilv_mul(ilv.n, ilv.s);
+    if (lds) hipLaunchKernelGGL(viterbi_ilv_lds_kernel, dim3(nrows), dim3(64), bytes, s, a, pi);
+    else hipLaunchKernelGGL(viterbi_ilv_kernel, dim3(nrows), dim3(64), 0, s, a, pi);
     return (int)hipGetLastError();
 }
 
@@ -166,6 +236,22 @@ int launch_conv_encode_punct(const uint8_t *bits, int nrows, int nbits, int nste
     if ((n + 255) / 256 > 0x7fffffffull) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(conv_encode_punct_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bits, (size_t)nrows, nbits, (unsigned)nsent,
                        (unsigned)ntx, p.period, p.K, tab, dibits);
+    return (int)hipGetLastError();
+}
+
+int launch_conv_encode_ilv(const uint8_t *bits, int nrows, int nbits, int nsteps, const Puncture &p, const Interleave &ilv, uint8_t *dibits,
+                           hipStream_t s)
+{
+    if (nrows <= 0 || nbits <= 0 || nsteps < nbits || !bits || !dibits || p.period < 1 || p.period > 32 || p.K < 1 || p.K > 64)
+        return (int)hipErrorInvalidValue;
+    const long long nsent = punct_nsent(p, nsteps), ntx = (nsent + 1) / 2;
+    if (!ilv_fits(ilv, ntx)) return (int)hipErrorInvalidValue;
+    PunctTable tab;
+    if (!punct_table_make(p, &tab)) return (int)hipErrorInvalidValue;
+    const size_t n = (size_t)nrows * (size_t)ntx;
+    if ((n + 255) / 256 > 0x7fffffffull) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(conv_encode_ilv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bits, (size_t)nrows, nbits, (unsigned)nsent,
+                       (unsigned)ntx, p.period, p.K, tab, ilv_mul(ilv.n, ilv.sinv), dibits);
     return (int)hipGetLastError();
 }
 

@@ -2,7 +2,7 @@
  * viterbi_row.h -- one row of the K = 7, rate-1/2 Viterbi decoder by ONE WAVE (lane = new state): the forward pass, the trace-back and
  * the channel error count of qpsk_viterbi_batch (include/qpsk_hip.h), shared by viterbi.hip (rows of a caller's batch) and
  * deframe_coded.hip (the staged soft rows of packets found in a stream).  viterbi.hip's header describes the passes.  A punctured
- * rate (qpsk_viterbi_punct_batch) is the same passes behind another LOADER of the soft pairs.
+ * rate (qpsk_viterbi_punct_batch) is the same passes behind another LOADER of the soft pairs, an interleaved row (qpsk_viterbi_ilv_batch) behind a third.
  *
  * The caller's kernel runs workgroups of exactly one wave (64 threads) and hands the row over as plain pointers; what happens to the
  * decoded bits is the caller's too: the trace-back gives every block of 64 steps to a SINK,
@@ -78,6 +78,37 @@ struct PunctLoader {
                 s1 = max((int)row[k1], -127);
                 if (flip && ((flip[k1 >> 1] >> (k1 & 1)) & 1u)) s1 = -s1;
             }
+        }
+    }
+};
+
+/* IlvLoader (INTERLEAVING in include/qpsk_hip.h): PunctLoader's row behind the permutation pi(k) = k s mod n: sent bit k lies at flat
+ * number pi(k) of the transmitted row and its flip bit at the same on-air position.  Per lane and 64 steps: PunctLoader's index, one
+ * modular product (IlvMul: 32-bit, no 64-bit division) for the step's first sent bit, a conditional subtract for its second --
+ * idx(t, 1) = idx(t, 0) + 1 when both are sent -- and the same byte loads, now s apart instead of adjacent.  Lane-parallel and a block
+ * ahead like the others.  pi is a bijection and idx < nsent, so the pad position pi(nsent) of an odd nsent is never read */
+struct IlvLoader {
+    const int8_t *__restrict__ row;
+    const uint8_t *__restrict__ flip;
+    Puncture p;
+    IlvMul pi;
+    __device__ __forceinline__ int value(unsigned a) const
+    {
+        const int v = max((int)row[a], -127);
+        return (flip && ((flip[a >> 1] >> (a & 1u)) & 1u)) ? -v : v;
+    }
+    __device__ __forceinline__ void load(int t0, int nsteps, int lane, int &s0, int &s1) const
+    {
+        const int t = t0 + lane;
+        s0 = s1 = 0;
+        if (t < nsteps) {
+            const unsigned q = (unsigned)t / (unsigned)p.period, r = (unsigned)t - q * (unsigned)p.period;
+            const unsigned low = (1u << r) - 1u;
+            const unsigned b0 = (p.keep0 >> r) & 1u, b1 = (p.keep1 >> r) & 1u;
+            const unsigned k0 = q * (unsigned)p.K + __popc(p.keep0 & low) + __popc(p.keep1 & low);
+            const unsigned a0 = pi.at(k0), a1 = b0 ? pi.next(a0) : a0;
+            if (b0) s0 = value(a0);
+            if (b1) s1 = value(a1);
         }
     }
 };

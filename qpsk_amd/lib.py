@@ -62,6 +62,7 @@ API_SYMBOLS = [
     "qpsk_punct_ntx", "qpsk_conv_encode_punct_batch", "qpsk_viterbi_punct_batch", "qpsk_deframer_reset_coded_punct",
     "qpsk_test_viterbi_launches", "qpsk_test_deframer_advance",
     "qpsk_frame_len", "qpsk_frame_batch",
+    "qpsk_ilv_stride", "qpsk_conv_encode_ilv_batch", "qpsk_viterbi_ilv_batch", "qpsk_frame_batch_ilv", "qpsk_deframer_reset_coded_ilv",
 ]
 # the named puncturing patterns of include/qpsk_hip.h (QPSK_PUNCT_*): rate -> (period, keep0, keep1), bit r of a mask = step r of the period
 PUNCTURE = {"1/2": (1, 0x1, 0x1), "2/3": (2, 0x1, 0x3), "3/4": (3, 0x5, 0x3), "5/6": (5, 0x15, 0x0B), "7/8": (7, 0x51, 0x2F)}
@@ -146,6 +147,11 @@ def load():
     L.qpsk_deframer_reset_coded_punct.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, u32, u32]
     L.qpsk_frame_len.argtypes = [i32, i32, i32, i32, u32, u32]
     L.qpsk_frame_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, vp, i32, i32, i32, u32, u32, i32, i32, i32, vp, vp]
+    L.qpsk_ilv_stride.argtypes = [i32, i32]
+    L.qpsk_conv_encode_ilv_batch.argtypes = [vp, vp, i32, i32, i32, i32, u32, u32, i32, vp]
+    L.qpsk_viterbi_ilv_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, u32, u32, i32, vp, i32, vp, vp]
+    L.qpsk_frame_batch_ilv.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, vp, i32, i32, i32, u32, u32, i32, i32, i32, i32, vp, vp]
+    L.qpsk_deframer_reset_coded_ilv.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, u32, u32, i32]
     L.qpsk_rrc_fir_batch.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_rrc_fir_batch_fast.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_timing_hist_batch.argtypes = [vp, vp, i32, vp, vp]
@@ -213,6 +219,21 @@ def frame_len(nsync, nbytes, coded=True, puncture=None):
     if rc < 0:
         raise QpskError("libqpsk_hip error %d: %s" % (rc, L.qpsk_last_error().decode()))
     return rc
+
+
+def ilv_stride(nbits, want):
+    """qpsk_ilv_stride: the smallest interleaver stride s >= min(want, nbits - 1) coprime to nbits, the bits of a body on air (2 ntx);
+    ilv_stride(n, n // 16) is a starting point against bursts.  Host only, needs no GPU"""
+    L = load()
+    rc = L.qpsk_ilv_stride(int(nbits), int(want))
+    if rc < 0:
+        raise QpskError("libqpsk_hip error %d: %s" % (rc, L.qpsk_last_error().decode()))
+    return rc
+
+
+def _interleaved(interleave):
+    """interleave= of the Modem calls: None or 1 is off (the existing entry points are called), an integer stride takes the ilv ones"""
+    return interleave is not None and int(interleave) != 1
 
 
 def _ptr(t):
@@ -501,15 +522,23 @@ class Modem:
         self._check(min(rc, 0))
         return rc
 
-    def conv_encode(self, bits_packed, nbits, tail=True, puncture=None):
+    def conv_encode(self, bits_packed, nbits, tail=True, puncture=None, interleave=None):
         """qpsk_conv_encode_batch: bits_packed (R, ceil(nbits / 8)) uint8, bit t in byte t >> 3 at position t & 7 -> (R, nsteps) uint8 coded
         dibits, nsteps = nbits + 6 with the tail (six zero bits that bring the encoder back to state 0).  With puncture (a key of PUNCTURE
-        or a (period, keep0, keep1) tuple) qpsk_conv_encode_punct_batch: (R, punct_ntx(nsteps)) transmitted dibits"""
+        or a (period, keep0, keep1) tuple) qpsk_conv_encode_punct_batch: (R, punct_ntx(nsteps)) transmitted dibits.  With interleave (a
+        stride of INTERLEAVING, coprime to the 2 ntx bits of a row; None or 1 = off) qpsk_conv_encode_ilv_batch: the same dibits, their
+        bits spread over the row (no puncture = rate 1/2)"""
         t = self.torch
         b = self._dev(bits_packed, t.uint8)
         if b.dim() != 2 or b.shape[1] != (int(nbits) + 7) // 8:
             raise ValueError("conv_encode() input must be (rows, ceil(nbits / 8)) uint8")
         nsteps = int(nbits) + (6 if tail else 0)
+        if _interleaved(interleave):
+            pat = _pattern("1/2" if puncture is None else puncture)
+            out = self.empty((b.shape[0], self.punct_ntx(nsteps, pat)), t.uint8)
+            self._check(self.L.qpsk_conv_encode_ilv_batch(self.h, _ptr(b), b.shape[0], int(nbits), 1 if tail else 0, *pat, int(interleave),
+                                                          _ptr(out)))
+            return out
         if puncture is not None:
             pat = _pattern(puncture)
             out = self.empty((b.shape[0], self.punct_ntx(nsteps, pat)), t.uint8)
@@ -519,17 +548,24 @@ class Modem:
         self._check(self.L.qpsk_conv_encode_batch(self.h, _ptr(b), b.shape[0], int(nbits), 1 if tail else 0, _ptr(out)))
         return out
 
-    def viterbi(self, soft, flip=None, open_start=False, open_end=False, pitch=0, nsteps=None, puncture=None):
+    def viterbi(self, soft, flip=None, open_start=False, open_end=False, pitch=0, nsteps=None, puncture=None, interleave=None):
         """qpsk_viterbi_batch on soft (R, nsteps, 2) int8 -- what soft() returns under "soft" -- or, with pitch, (R, pitch, 2) of which the
         first nsteps steps of each row are decoded.  flip (nsteps,) uint8: the scrambler's keystream dibits, undone on the soft values.
         Dict of torch tensors bits (R, ceil(nsteps / 8)) uint8, packed low bits first, tail bits included, and info (R, 4) int32 = (end
         metric, end state, state the trace-back arrives at, channel bit errors against the re-encoded path).
         With puncture (a key of PUNCTURE or a (period, keep0, keep1) tuple) qpsk_viterbi_punct_batch: soft (R, ntx, 2), or (R, pitch, 2),
-        holds the TRANSMITTED symbols, flip is (ntx,), and nsteps must be given (ntx does not determine it)."""
+        holds the TRANSMITTED symbols, flip is (ntx,), and nsteps must be given (ntx does not determine it).
+        With interleave (a stride of INTERLEAVING; None or 1 = off) qpsk_viterbi_ilv_batch on the rows as they were on air, shapes as with
+        puncture (no puncture = rate 1/2, and nsteps defaults to the row's length)."""
         t = self.torch
         if isinstance(soft, dict):
             soft = soft["soft"]
         q = self._dev(soft, t.int8)
+        ilv = _interleaved(interleave)
+        if ilv and puncture is None:
+            puncture = "1/2"
+            if nsteps is None and q.dim() == 3 and not pitch:
+                nsteps = q.shape[1]
         if puncture is not None:
             pat = _pattern(puncture)
             if nsteps is None:
@@ -543,8 +579,13 @@ class Modem:
                 raise ValueError("viterbi(puncture=...) flip must be (ntx = %d,) uint8" % ntx)
             R = q.shape[0]
             o = dict(bits=self.empty((R, (n + 7) // 8), t.uint8), info=self.empty((R, 4), t.int32))
-            self._check(self.L.qpsk_viterbi_punct_batch(self.h, _ptr(q), int(pitch), R, n, *pat, _ptr(f),
-                                                        (1 if open_start else 0) | (2 if open_end else 0), _ptr(o["bits"]), _ptr(o["info"])))
+            flags = (1 if open_start else 0) | (2 if open_end else 0)
+            if ilv:
+                self._check(self.L.qpsk_viterbi_ilv_batch(self.h, _ptr(q), int(pitch), R, n, *pat, int(interleave), _ptr(f), flags,
+                                                          _ptr(o["bits"]), _ptr(o["info"])))
+            else:
+                self._check(self.L.qpsk_viterbi_punct_batch(self.h, _ptr(q), int(pitch), R, n, *pat, _ptr(f), flags, _ptr(o["bits"]),
+                                                            _ptr(o["info"])))
             o["_keep"] = (q, f)
             return o
         if q.dim() != 3 or q.shape[2] != 2 or (pitch and q.shape[1] != pitch):
@@ -685,12 +726,19 @@ class Modem:
         o["_keep"] = (x,)
         return o
 
-    def deframer_reset_coded(self, nstreams, sync, nbytes, min_score, max_packets=8, mode="unit", scale=64.0, puncture=None):
+    def deframer_reset_coded(self, nstreams, sync, nbytes, min_score, max_packets=8, mode="unit", scale=64.0, puncture=None, interleave=None):
         """deframer_reset() for packets whose body carries the K = 7 rate-1/2 code: [sync][scrambled conv_encode(payload + CRC-16, tail)].
         mode, scale: soft()'s, for the gain of a push that brings none of its own.  Replaces an uncoded deframer of the context.
         With puncture (a key of PUNCTURE or a (period, keep0, keep1) tuple) qpsk_deframer_reset_coded_punct: the body is
-        conv_encode(..., puncture=...); deframe_coded() is the push of both."""
+        conv_encode(..., puncture=...); deframe_coded() is the push of both.  With interleave (a stride of INTERLEAVING; None or 1 = off)
+        qpsk_deframer_reset_coded_ilv: the body frame(..., interleave=...) sends; a refused stride leaves the deframer as it was."""
         sw = np.ascontiguousarray(np.asarray(sync, dtype=np.uint8))
+        if _interleaved(interleave):
+            self._check(self.L.qpsk_deframer_reset_coded_ilv(self.h, int(nstreams), sw.ctypes.data_as(C.c_void_p), len(sw), int(min_score),
+                                                             int(nbytes), int(max_packets), self.SOFT_MODES[mode], float(scale),
+                                                             *_pattern("1/2" if puncture is None else puncture), int(interleave)))
+            self.df_shape = (int(nstreams), int(nbytes), int(max_packets))
+            return
         if puncture is not None:
             self._check(self.L.qpsk_deframer_reset_coded_punct(self.h, int(nstreams), sw.ctypes.data_as(C.c_void_p), len(sw), int(min_score),
                                                                int(nbytes), int(max_packets), self.SOFT_MODES[mode], float(scale),
@@ -725,13 +773,14 @@ class Modem:
         return o
 
     # ---- packets onto the air (qpsk_frame_batch), the transmit twin of the deframers
-    def frame(self, payloads, sync, coded=True, puncture=None, per_row=1, lead=0, gap=0, row_len=None):
+    def frame(self, payloads, sync, coded=True, puncture=None, per_row=1, lead=0, gap=0, row_len=None, interleave=None):
         """qpsk_frame_batch: payloads (nrows * per_row, nbytes) or (nrows, per_row, nbytes) uint8 -> dict of torch tensors dibits (nrows,
         row_len) uint8 -- per row per_row packets [sync][scrambled body], the first at column lead, gap idle columns between two, idle fill
         (the scrambler's keystream from column 0) everywhere else: rows for tx_symbols() -- and crc (nrows * per_row,) int16, the CRC-16
         sent (view it as uint16, as crc16() does).  sync: 1..128 dibits.  coded=False: the body deframe() receives; coded=True: the K = 7
         code, rate 1/2 (deframer_reset_coded) or, with puncture (a key of PUNCTURE or a (period, keep0, keep1) tuple), the punctured
-        body.  row_len None = the exact fit."""
+        body.  row_len None = the exact fit.  interleave: a stride of INTERLEAVING for the coded body (None or 1 = off), which
+        qpsk_frame_batch_ilv spreads over the body on air; deframer_reset_coded(..., interleave=...) receives it."""
         t = self.torch
         p = self._dev(payloads, t.uint8)
         per_row, lead, gap = int(per_row), int(lead), int(gap)
@@ -747,8 +796,12 @@ class Modem:
             self._check(min(P, 0))
             row_len = lead + per_row * P + (per_row - 1) * gap
         o = dict(dibits=self.empty((npk // per_row, int(row_len)), t.uint8), crc=self.empty((npk,), t.int16))
-        self._check(self.L.qpsk_frame_batch(self.h, _ptr(p), 0, npk // per_row, per_row, nbytes, sw.ctypes.data_as(C.c_void_p), len(sw), *code,
-                                            lead, gap, int(row_len), _ptr(o["dibits"]), _ptr(o["crc"])))
+        if _interleaved(interleave):
+            self._check(self.L.qpsk_frame_batch_ilv(self.h, _ptr(p), 0, npk // per_row, per_row, nbytes, sw.ctypes.data_as(C.c_void_p), len(sw),
+                                                    *code, int(interleave), lead, gap, int(row_len), _ptr(o["dibits"]), _ptr(o["crc"])))
+        else:
+            self._check(self.L.qpsk_frame_batch(self.h, _ptr(p), 0, npk // per_row, per_row, nbytes, sw.ctypes.data_as(C.c_void_p), len(sw),
+                                                *code, lead, gap, int(row_len), _ptr(o["dibits"]), _ptr(o["crc"])))
         o["_keep"] = (p,)      # the input stays alive until the caller is done with the outputs (stream order)
         return o
 
