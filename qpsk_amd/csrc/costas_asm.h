@@ -27,8 +27,10 @@
  *   - the 2*pi wrap is out of line AND late: step k+1 starts from the unwrapped phase; its 2*pi test is the step's FIRST instruction and
  *     the branch stands behind the head and the first rows of the polynomial chains (round 6), and the rare wrap block corrects the phase
  *     where it stands and redoes what stood in front of the branch;
- *   - groups of 16 steps: the per-group bookkeeping (state snapshot, flag test, taken loop branch) costs
- *     ~60 cycles;
+ *   - groups of 16 steps in costas_asm_run(): the per-group bookkeeping (state snapshot, address set-up, flag test, taken loop
+ *     branch) costs ~60 cycles; the ring streams below run groups of one whole 64-step ring chunk (COSTAS_RING_GROUP, round 7), where
+ *     all of it happens once per chunk and the "inside a chunk?" test is gone: 141.5 against 148.7 cycles per step for the paired
+ *     stream alone on a CU, 150.5 against 157.6 for the one-lane stream, 32-step groups in between (profiles/r07_ring_groups.txt);
  *   - the exact-zero test of the detector input is a running min over the group; with zeros out of the way
  *     the error is e = s (|T.y| - |T.x|) with s = sgn(T.x) sgn(T.y) (negating both operands of a float
  *     subtraction negates its result), so d = |T.y| - |T.x| is one subtract with abs modifiers and s rejoins it
@@ -74,6 +76,20 @@ namespace qpsk {
 
 /* steps per group of the stream; the caller hands over multiples of it */
 constexpr int COSTAS_ASM_GROUP = 16;
+/* steps per group of the stream that runs through the ring hand-overs (costas_asm_run_ring*): 16, 32 or 64 -- a ring chunk is 64 steps,
+ * and with one group per chunk everything that happens per group happens once per chunk (profiles/r07_ring_groups.txt) */
+#ifndef COSTAS_RING_STEPS
+#define COSTAS_RING_STEPS 64
+#endif
+constexpr int COSTAS_RING_GROUP = COSTAS_RING_STEPS;
+static_assert(COSTAS_RING_GROUP == 16 || COSTAS_RING_GROUP == 32 || COSTAS_RING_GROUP == 64, "ring groups of 16, 32 or 64 steps");
+/* ... and of costas_asm_lo.h's copy of it: 16.  rx_hist_kernel is bound by its twelve scan waves, not by the serial wave, and the
+ * longer text only costs it instruction cache: 0.6736 ms with 16-step groups, 0.6767 with 32, 0.6752 with 64 (profiles/r07_ring_groups.txt) */
+#ifndef COSTAS_RING_STEPS_LO
+#define COSTAS_RING_STEPS_LO 16
+#endif
+constexpr int COSTAS_RING_GROUP_LO = COSTAS_RING_STEPS_LO;
+static_assert(COSTAS_RING_GROUP_LO == 16 || COSTAS_RING_GROUP_LO == 32 || COSTAS_RING_GROUP_LO == 64, "ring groups of 16, 32 or 64 steps");
 
 /* 32-bit LDS byte address of a __shared__ object (what ds_read / ds_write take) */
 __device__ __forceinline__ unsigned lds_addr(const void *p)
@@ -373,93 +389,163 @@ __device__ __forceinline__ unsigned costas_asm_run(float &phase, float &freq, un
 
 /*
  * The same stream running THROUGH the chunk hand-overs of the pipeline kernels' rings (rx_fused.hip): symbol ring and
- * record ring of 128 symbols = 8 groups per lane (two 64-symbol chunks), group k at ring position k % 8.  What the
- * serial wave did between two costas_asm_run() calls per chunk -- ready[] poll, acquire, address set-up, an exposed
- * LDS read of the first symbol pair, waiting out the last record write, release, consumed -- cost ~0.5-0.7 k cycles
- * per chunk, every cycle of it on the kernel's critical path (config 2 sits on this wave).  Here:
- *   - every group reads the lane's producer counter ready[] (one 4-byte LDS read per 16 steps, in the shadow of the
- *     steps); at a chunk boundary the value read at the START of the chunk's last group decides: LDS operations of
- *     a wave execute in order, so everything read after a counter read that showed the next chunk is that chunk
- *     -- including the usual fetch of the next group's first symbol pair two steps before the group ends;
+ * record ring of 128 symbols per lane (two 64-symbol chunks) = 128 / G groups of G = COSTAS_RING_GROUP steps, group k at ring
+ * position k % (128 / G).  G is 64: one group per chunk (the text macro also builds 16 and 32; tools/ubench_step.py --groups
+ * measures all three; costas_asm_lo.h's copy for rx_hist_kernel keeps 16, COSTAS_RING_GROUP_LO).  What the serial wave did
+ * between two costas_asm_run() calls per chunk -- ready[] poll, acquire, address
+ * set-up, an exposed LDS read of the first symbol pair, waiting out the last record write, release, consumed -- cost ~0.5-0.7 k
+ * cycles per chunk, every cycle of it on the kernel's critical path (config 2 sits on this wave).  Here:
+ *   - a group reads the lane's producer counter ready[] 16 steps before its end (one 4-byte LDS read in the shadow of the
+ *     steps; with one group per chunk: 16 steps before the CHUNK's end, as late as the 16-step groups of rounds 2-6 read it -- at
+ *     the chunk's start the next chunk is usually not there yet, the FIR waves have ~10 % of slack); at a chunk boundary that
+ *     value decides: LDS operations of a wave execute in order, so everything read after a counter read that showed the next
+ *     chunk is that chunk -- including the usual fetch of the next group's first symbol pair two steps before the group ends;
  *   - consumed = chunk + 1 is one LDS write by lane 0 behind the chunk's last record write (same order argument:
  *     the FIR waves read the counter, then the records);
  *   - the stream stops at a boundary whose next chunk was not yet there (the caller waits, comes back), at kend,
- *     or inside a group it abandons (as costas_asm_run: state restored, caller redoes that group).
- * k (in/out): absolute group number, a multiple of 4 on entry unless the caller resumes behind a group it redid.
+ *     or at the end of a group it abandons (as costas_asm_run: state restored, caller redoes that group -- the whole chunk).
+ * k (in/out): absolute group number; kend a whole number of chunks.  A caller that redid a group resumes at the group behind it.
  * Registers: as costas_asm_run, plus v132 / v134 / v124 = symbol address, record address, address of the next
  * group's first symbol pair, v125 = the counter read.
  */
-/* INVARIANT of the ring stream's LDS traffic (nothing checks it at compile time -- keep it when editing; the test
- * test_stream_across_ring_handovers_takes_its_fallbacks exercises every hand-over): LDS operations of a wave complete in
- * issue order and lgkmcnt counts them, so the wait in front of a group's first symbol use, `s_waitcnt lgkmcnt(2)`, is right
- * exactly while at most TWO LDS operations are issued between the fetch of that group's first pair (QPSK_RDN, in step 14
- * of the group before) and the wait: the last record write of that group (QPSK_QW(48), step 15) and this group's counter
- * read (ds_read_b32 v125).  The optional `consumed` write at a chunk boundary sits between them in program order only on
- * paths that LEAVE the stream or re-enter at label 2 after it -- there three operations follow the fetch and the wait
- * lets two of them stay outstanding, i.e. it still covers the fetch (the oldest).  One more LDS instruction anywhere
- * between QPSK_RDN and that wait needs lgkmcnt(3), one fewer lgkmcnt(1); no ordering fence is needed for the hand-over
- * itself (counter read before data reads, data writes before counter write, same wave, in order). */
+/* INVARIANT of the ring stream's LDS traffic (nothing checks it at compile time -- keep it when editing; the tests of
+ * tests/test_ring_groups_gpu.py and test_stream_across_ring_handovers_takes_its_fallbacks exercise every hand-over): LDS
+ * operations of a wave complete in issue order and lgkmcnt counts them.  Inside a group every fetch of a symbol pair is
+ * followed by at most ONE LDS operation before the wait in front of its first use (the record write of the step behind an
+ * odd pair: QPSK_WAIT1) or, where something else was issued in between, the wait is for everything (QPSK_WAIT0).  The
+ * producer counter read (QPSK_RING_CR, ds_read_b32 v125) stands 16 steps before the group's end -- in a group of one
+ * whole chunk that is 16 steps before the CHUNK's end, where the 16-step groups of rounds 2-6 had it -- directly BEHIND
+ * the fetch issued by that step (step G - 16: QPSK_WAIT1, fetch, counter read), so the next wait is step G - 14's
+ * QPSK_WAIT0, which covers both.  In a 16-step group step G - 16 is step 0: the counter read stands behind QPSK_RDB(16).
+ * Across the group boundary: the wait in front of a group's first symbol use is `s_waitcnt lgkmcnt(1)`, right exactly
+ * while at most ONE LDS operation is issued between the fetch of that group's first pair (QPSK_RDN, in step G - 2 of the
+ * group before) and the wait: the last record write of that group (QPSK_QW, step G - 1).  The `consumed` write at a
+ * chunk boundary sits between them in program order -- there two operations follow the fetch and the wait lets one of
+ * them stay outstanding, i.e. it still covers the fetch (the oldest).  One more LDS instruction anywhere between QPSK_RDN
+ * and that wait needs lgkmcnt(2).  No ordering fence is needed for the hand-over itself (counter read before data reads,
+ * data writes before counter write, same wave, in order): everything read after a counter read that showed the next chunk
+ * is that chunk, QPSK_RDN (two steps before the end) included, and `consumed` is written behind the chunk's last record
+ * write. */
 #define QPSK_DA "v132"
 #define QPSK_ZA "v134"
 #define QPSK_RDN "ds_read_b128 v[120:123], v124\n\t"
-/* where the group loop's head sits relative to the 64-byte lines, per stream (tools/ubench_step.py --align) */
-#define QPSK_RING_ALIGN_1 ".p2align 6\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n"
-#define QPSK_RING_ALIGN_P ".p2align 6\n\ts_nop 0\n\ts_nop 0\n"
-#define QPSK_RING_TEXT(HC, HD, BD, WH, INIT, ALIGN)                                                                           \
+#define QPSK_RING_CR "ds_read_b32 v125, %[ra]\n\t"
+#define QPSK_CAT_(a, b) a##b
+#define QPSK_CAT(a, b) QPSK_CAT_(a, b)
+/* where the group loop's head sits relative to the 64-byte lines, per stream (tools/ubench_step.py --align --groups,
+ * profiles/r07_ring_groups.txt: with 64-step groups the one-lane stream is flat, 150.5-151.2 cycles per step over all twelve
+ * placements; the paired one runs 141.5 here and 142.4-145.3 elsewhere) */
+#define QPSK_RING_ALIGN_1 ".p2align 6\n"
+#define QPSK_RING_ALIGN_P ".p2align 6\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n"
+/*
+ * The steps of a group, in blocks of 16: block number B (a one-digit string, part of the wrap labels "1" B "ss" / "2" B "ss"), symbols at
+ * byte offset B8 = 128 B from the group's first, records at B4 = 64 B.  QPSK_RING_Q0 = the group's first four steps (the first has no
+ * predecessor in the group), QPSK_RING_QN = the first four of a later block, QPSK_RING_Q4_15 = steps 4..15 of a block: RDLAST fetches the
+ * pair behind the block (QPSK_RDA(B8 + 128), or QPSK_RDN at the group's end), PLAST is where its last step leaves the phase.  CR = the
+ * counter read in the group's last block, nothing elsewhere.
+ */
+#define QPSK_RQ(HD, BD, ...) QPSK_STEP_QUAD_(HD, BD, "v[120:121]", "v[122:123]", "v[136:137]", "v[138:139]", __VA_ARGS__)
+#define QPSK_RING_Q0(HC, HD, BD, CR)                                                                                          \
+    HC("v140")                                                                                                         \
+    BD("v140", "v141", "v[120:121]", QPSK_WAIT1, QPSK_RDB(16) CR, "")                                                  \
+    HD("v141", "1001", "2001")                                                                                         \
+    BD("v141", "v142", "v[122:123]", "", "", "")                                                                       \
+    HD("v142", "1002", "2002")                                                                                         \
+    BD("v142", "v143", "v[136:137]", QPSK_WAIT0, QPSK_RDA(32), "")                                                     \
+    HD("v143", "1003", "2003")                                                                                         \
+    BD("v143", "v140", "v[138:139]", "", "", QPSK_QW(0))
+#define QPSK_RING_QN(HD, BD, B8, B4, B, CR)                                                                                   \
+    QPSK_RQ(HD, BD, QPSK_RDB(B8+16) CR, QPSK_RDA(B8+32), B4+0, "v140", B "00", B "01", B "02", B "03")
+#define QPSK_RING_Q4_15(HD, BD, B8, B4, B, RDLAST, PLAST)                                                                     \
+    QPSK_RQ(HD, BD, QPSK_RDB(B8+48), QPSK_RDA(B8+64), B4+16, "v140", B "04", B "05", B "06", B "07")                \
+    QPSK_RQ(HD, BD, QPSK_RDB(B8+80), QPSK_RDA(B8+96), B4+32, "v140", B "08", B "09", B "10", B "11")                \
+    QPSK_RQ(HD, BD, QPSK_RDB(B8+112), RDLAST, B4+48, PLAST, B "12", B "13", B "14", B "15")
+/* the out-of-line wrap blocks of a block's steps 1..15 and of a later block's step 0 */
+#define QPSK_RING_W1_15(WH, B)                                                                                                \
+    WH("v141", "1" B "01", "2" B "01") WH("v142", "1" B "02", "2" B "02") WH("v143", "1" B "03", "2" B "03")            \
+    WH("v140", "1" B "04", "2" B "04") WH("v141", "1" B "05", "2" B "05") WH("v142", "1" B "06", "2" B "06")            \
+    WH("v143", "1" B "07", "2" B "07") WH("v140", "1" B "08", "2" B "08") WH("v141", "1" B "09", "2" B "09")            \
+    WH("v142", "1" B "10", "2" B "10") WH("v143", "1" B "11", "2" B "11") WH("v140", "1" B "12", "2" B "12")            \
+    WH("v141", "1" B "13", "2" B "13") WH("v142", "1" B "14", "2" B "14") WH("v143", "1" B "15", "2" B "15")
+#define QPSK_RING_W0(WH, B) WH("v140", "1" B "00", "2" B "00")
+/*
+ * Per group length G (16, 32 or 64 steps; a ring chunk is 64): the ring holds 128 / G groups (POS = that minus one), a group's symbols
+ * are G * 8 = 1 << DSH bytes and its records 1 << ZSH, a chunk is 1 << CSH groups, INCHUNK is the "inside a chunk?" test behind a group
+ * (nothing when the group IS the chunk), STEPS the group's steps and WRAPS their wrap blocks.
+ */
+#define QPSK_RING_POS_16 "7"
+#define QPSK_RING_DSH_16 "7"
+#define QPSK_RING_ZSH_16 "6"
+#define QPSK_RING_CSH_16 "2"
+#define QPSK_RING_INCHUNK_16 "s_and_b32 %[t0], %[k], 3\n\ts_cmp_lg_u32 %[t0], 0\n\ts_cbranch_scc1 2b\n\t"
+#define QPSK_RING_STEPS_16(HC, HD, BD)                                                                                        \
+    QPSK_RING_Q0(HC, HD, BD, QPSK_RING_CR) QPSK_RING_Q4_15(HD, BD, 0, 0, "0", QPSK_RDN, "%[p]")
+#define QPSK_RING_WRAPS_16(WH) QPSK_RING_W1_15(WH, "0")
+#define QPSK_RING_POS_32 "3"
+#define QPSK_RING_DSH_32 "8"
+#define QPSK_RING_ZSH_32 "7"
+#define QPSK_RING_CSH_32 "1"
+#define QPSK_RING_INCHUNK_32 "s_and_b32 %[t0], %[k], 1\n\ts_cmp_lg_u32 %[t0], 0\n\ts_cbranch_scc1 2b\n\t"
+#define QPSK_RING_STEPS_32(HC, HD, BD)                                                                                        \
+    QPSK_RING_Q0(HC, HD, BD, "") QPSK_RING_Q4_15(HD, BD, 0, 0, "0", QPSK_RDA(128), "v140")                                    \
+    QPSK_RING_QN(HD, BD, 128, 64, "1", QPSK_RING_CR) QPSK_RING_Q4_15(HD, BD, 128, 64, "1", QPSK_RDN, "%[p]")
+#define QPSK_RING_WRAPS_32(WH) QPSK_RING_W1_15(WH, "0") QPSK_RING_W0(WH, "1") QPSK_RING_W1_15(WH, "1")
+#define QPSK_RING_POS_64 "1"
+#define QPSK_RING_DSH_64 "9"
+#define QPSK_RING_ZSH_64 "8"
+#define QPSK_RING_CSH_64 "0"
+#define QPSK_RING_INCHUNK_64 ""
+#define QPSK_RING_STEPS_64(HC, HD, BD)                                                                                        \
+    QPSK_RING_Q0(HC, HD, BD, "") QPSK_RING_Q4_15(HD, BD, 0, 0, "0", QPSK_RDA(128), "v140")                                    \
+    QPSK_RING_QN(HD, BD, 128, 64, "1", "") QPSK_RING_Q4_15(HD, BD, 128, 64, "1", QPSK_RDA(256), "v140")                       \
+    QPSK_RING_QN(HD, BD, 256, 128, "2", "") QPSK_RING_Q4_15(HD, BD, 256, 128, "2", QPSK_RDA(384), "v140")                     \
+    QPSK_RING_QN(HD, BD, 384, 192, "3", QPSK_RING_CR) QPSK_RING_Q4_15(HD, BD, 384, 192, "3", QPSK_RDN, "%[p]")
+#define QPSK_RING_WRAPS_64(WH)                                                                                                \
+    QPSK_RING_W1_15(WH, "0") QPSK_RING_W0(WH, "1") QPSK_RING_W1_15(WH, "1") QPSK_RING_W0(WH, "2") QPSK_RING_W1_15(WH, "2")      \
+    QPSK_RING_W0(WH, "3") QPSK_RING_W1_15(WH, "3")
+/* G: the group length, 16, 32 or 64 (COSTAS_RING_STEPS) */
+#define QPSK_RING_TEXT(HC, HD, BD, WH, INIT, ALIGN, G)                                                                        \
     "v_mov_b32 v128, 0x54442d18\n\t"        /* 2*pi = 0x401921FB54442D18 */                                            \
     "v_mov_b32 v127, 0x401921fb\n\t" INIT                                                                                   \
-    "s_and_b32 %[t0], %[k], 7\n\t"                                                                                     \
-    "s_lshl_b32 %[t0], %[t0], 7\n\t"                                                                                   \
+    "s_and_b32 %[t0], %[k], " QPSK_CAT(QPSK_RING_POS_, G) "\n\t"                                                       \
+    "s_lshl_b32 %[t0], %[t0], " QPSK_CAT(QPSK_RING_DSH_, G) "\n\t"                                                     \
     "v_add_u32_e32 v132, %[t0], %[db]\n\t"                                                                             \
     "ds_read_b128 v[120:123], v132\n\t"                                                                                \
     "s_mov_b64 %[fl], 0\n\t"                                                                                           \
     "s_waitcnt lgkmcnt(0)\n"                                                                                           \
-    /* the group loop's head 12 bytes behind a 64-byte boundary: a lone wave is limited by instruction fetch (header), and where \
-     * the 8-byte instructions of the 16-step body fall relative to the 32-byte fetch lines is worth 4 % -- 157.2 cycles \
-     * per step at this offset, 160.9 as the compiler placed it, 163.4 at the worst (tools/ubench_step.py --align,     \
-     * profiles/r03_step_cost.txt; re-measure after any edit of the stream) */                                         \
+    /* the group loop's head a few bytes behind a 64-byte boundary: a lone wave is limited by instruction fetch (header), and where \
+     * the 8-byte instructions of the body fall relative to the 32-byte fetch lines was worth 4 % with 16-step groups  \
+     * (tools/ubench_step.py --align, profiles/r03_step_cost.txt, profiles/r07_ring_groups.txt; re-measure after any   \
+     * edit of the stream) */                                                                                          \
     ALIGN                                                                                                              \
     "2:\n\t"                                                                                                           \
-    /* ring addresses of group k and of group k + 1's first pair; the producer counter */                              \
-    "s_and_b32 %[t0], %[k], 7\n\t"                                                                                     \
-    "s_lshl_b32 %[t1], %[t0], 7\n\t"                                                                                   \
+    /* ring addresses of group k and of group k + 1's first pair */                                                    \
+    "s_and_b32 %[t0], %[k], " QPSK_CAT(QPSK_RING_POS_, G) "\n\t"                                                       \
+    "s_lshl_b32 %[t1], %[t0], " QPSK_CAT(QPSK_RING_DSH_, G) "\n\t"                                                     \
     "v_add_u32_e32 v132, %[t1], %[db]\n\t"                                                                             \
-    "s_lshl_b32 %[t1], %[t0], 6\n\t"                                                                                   \
+    "s_lshl_b32 %[t1], %[t0], " QPSK_CAT(QPSK_RING_ZSH_, G) "\n\t"                                                     \
     "v_add_u32_e32 v134, %[t1], %[zb]\n\t"                                                                             \
     "s_add_u32 %[t0], %[k], 1\n\t"                                                                                     \
-    "s_and_b32 %[t0], %[t0], 7\n\t"                                                                                    \
-    "s_lshl_b32 %[t0], %[t0], 7\n\t"                                                                                   \
+    "s_and_b32 %[t0], %[t0], " QPSK_CAT(QPSK_RING_POS_, G) "\n\t"                                                      \
+    "s_lshl_b32 %[t0], %[t0], " QPSK_CAT(QPSK_RING_DSH_, G) "\n\t"                                                     \
     "v_add_u32_e32 v124, %[t0], %[db]\n\t"                                                                             \
-    "ds_read_b32 v125, %[ra]\n\t"                                                                                      \
     "v_mov_b32 v130, %[p]\n\t"                                                                                         \
     "v_mov_b32 v131, %[f]\n\t"                                                                                         \
     "v_mov_b32 v118, %[f]\n\t"            /* the frequency accumulates in place (v_fmac) */                            \
     "v_mov_b32 v126, 0x7f800000\n\t"                                                                                   \
     "v_mov_b32 v140, %[p]\n\t"                                                                                         \
-    /* steps 0..3; outstanding in front of the first pair's use: the last group's record write and the counter read */ \
-    HC("v140")                                                                                            \
-    BD("v140", "v141", "v[120:121]", "s_waitcnt lgkmcnt(2)\n\t", QPSK_RDB(16), "")                                     \
-    HD("v141", "101", "201")                                                                                           \
-    BD("v141", "v142", "v[122:123]", "", "", "")                                                                       \
-    HD("v142", "102", "202")                                                                                           \
-    BD("v142", "v143", "v[136:137]", QPSK_WAIT0, QPSK_RDA(32), "")                                                     \
-    HD("v143", "103", "203")                                                                                           \
-    BD("v143", "v140", "v[138:139]", "", "", QPSK_QW(0))                                                               \
-    QPSK_STEP_QUAD_(HD, BD, "v[120:121]", "v[122:123]", "v[136:137]", "v[138:139]", QPSK_RDB(48), QPSK_RDA(64), 16, "v140", "04", "05", "06", "07") \
-    QPSK_STEP_QUAD_(HD, BD, "v[120:121]", "v[122:123]", "v[136:137]", "v[138:139]", QPSK_RDB(80), QPSK_RDA(96), 32, "v140", "08", "09", "10", "11") \
-    QPSK_STEP_QUAD_(HD, BD, "v[120:121]", "v[122:123]", "v[136:137]", "v[138:139]", QPSK_RDB(112), QPSK_RDN, 48, "%[p]", "12", "13", "14", "15") \
-    QPSK_TAIL("%[p]", "%[f]", "116", "216")                                                                            \
+    /* the steps; outstanding in front of the first pair's use: the last group's last record write */                  \
+    QPSK_CAT(QPSK_RING_STEPS_, G)(HC, HD, BD)                                                                          \
+    QPSK_TAIL("%[p]", "%[f]", "1900", "2900")                                                                          \
     "v_cmp_eq_f32_e64 %[tm], 0, v126\n\t"                                                                              \
     "s_andn2_b64 %[tm], %[tm], %[ign]\n\t"   /* lanes the caller has looked at: nothing but +0.0 symbols ahead of them (below) */ \
     "s_or_b64 %[fl], %[fl], %[tm]\n\t"                                                                                 \
     "s_cmp_lg_u64 %[fl], 0\n\t"                                                                                        \
     "s_cbranch_scc1 3f\n\t"                                                                                            \
     "s_add_u32 %[k], %[k], 1\n\t"                                                                                      \
-    "s_and_b32 %[t0], %[k], 3\n\t"                                                                                     \
-    "s_cmp_lg_u32 %[t0], 0\n\t"                                                                                        \
-    "s_cbranch_scc1 2b\n\t"                 /* inside a chunk (kend is a multiple of 4) */                             \
-    /* chunk k / 4 - 1 is done: consumed = k / 4, by lane 0, behind the record writes */                               \
-    "s_lshr_b32 %[t0], %[k], 2\n\t"                                                                                    \
+    QPSK_CAT(QPSK_RING_INCHUNK_, G)         /* inside a chunk (kend is a whole number of chunks) */                    \
+    /* chunk k' - 1 is done (k' = k >> CSH): consumed = k', by lane 0, behind the record writes */                     \
+    "s_lshr_b32 %[t0], %[k], " QPSK_CAT(QPSK_RING_CSH_, G) "\n\t"                                                      \
     "v_mov_b32 v104, %[t0]\n\t"                                                                                        \
     "s_mov_b64 %[ex], exec\n\t"                                                                                        \
     "s_mov_b64 exec, 1\n\t"                                                                                            \
@@ -467,7 +553,7 @@ __device__ __forceinline__ unsigned costas_asm_run(float &phase, float &freq, un
     "s_mov_b64 exec, %[ex]\n\t"                                                                                        \
     "s_cmp_ge_u32 %[k], %[ke]\n\t"                                                                                     \
     "s_cbranch_scc1 4f\n\t"                                                                                            \
-    /* next chunk there?  ready[] >= k / 4 + 1 in every lane, as read at the start of the group just done */           \
+    /* next chunk there?  ready[] >= k' + 1 in every lane, as read 16 steps before the end of the group just done */   \
     "v_cmp_le_i32_e64 %[tm], v125, %[t0]\n\t"                                                                          \
     "s_cmp_lg_u64 %[tm], 0\n\t"                                                                                        \
     "s_cbranch_scc0 2b\n\t"                                                                                            \
@@ -476,22 +562,8 @@ __device__ __forceinline__ unsigned costas_asm_run(float &phase, float &freq, un
     "v_mov_b32 %[p], v130\n\t"                                                                                         \
     "v_mov_b32 %[f], v131\n\t"                                                                                         \
     "s_branch 4f\n"                                                                                                    \
-    WH("v141", "101", "201")                                                                               \
-    WH("v142", "102", "202")                                                                               \
-    WH("v143", "103", "203")                                                                               \
-    WH("v140", "104", "204")                                                                               \
-    WH("v141", "105", "205")                                                                               \
-    WH("v142", "106", "206")                                                                               \
-    WH("v143", "107", "207")                                                                               \
-    WH("v140", "108", "208")                                                                               \
-    WH("v141", "109", "209")                                                                               \
-    WH("v142", "110", "210")                                                                               \
-    WH("v143", "111", "211")                                                                               \
-    WH("v140", "112", "212")                                                                               \
-    WH("v141", "113", "213")                                                                               \
-    WH("v142", "114", "214")                                                                               \
-    WH("v143", "115", "215")                                                                               \
-    QPSK_WRAP_TAIL("%[p]", "116", "216")                                                                               \
+    QPSK_CAT(QPSK_RING_WRAPS_, G)(WH)                                                                                  \
+    QPSK_WRAP_TAIL("%[p]", "1900", "2900")                                                                             \
     "4:\n\t"                                                                                                           \
     "s_waitcnt lgkmcnt(0)"
 
@@ -511,7 +583,7 @@ __device__ __forceinline__ void costas_asm_run_ring(float &phase, float &freq, u
         __builtin_memcpy(&beal, &ba, 8);
     }
     asm volatile(
-        QPSK_RING_TEXT(QPSK_HEAD_CHAIN, QPSK_HEAD_DEFERRED, QPSK_BODY, QPSK_WRAP_HEAD, "", QPSK_RING_ALIGN_1)
+        QPSK_RING_TEXT(QPSK_HEAD_CHAIN, QPSK_HEAD_DEFERRED, QPSK_BODY, QPSK_WRAP_HEAD, "", QPSK_RING_ALIGN_1, COSTAS_RING_STEPS)
         : [p] "+v"(phase), [f] "+v"(freq), [k] "+s"(k), [fl] "=&s"(flags), [tm] "=&s"(tmp), [ex] "=&s"(ex),
           [t0] "=&s"(t0), [t1] "=&s"(t1)
         : [db] "v"(d_base), [zb] "v"(z_base), [ra] "v"(ready_addr), [ca] "v"(consumed_addr), [ke] "s"(kend),
@@ -553,7 +625,7 @@ __device__ __forceinline__ void costas_asm_run_ring_pair(float &phase, float &fr
     }
     asm volatile(
         /* the first step's zero test looks at the T of "the step before": anything but a zero */
-        QPSK_RING_TEXT(QPSK_HEAD_CHAIN_P, QPSK_HEAD_DEFERRED_P, QPSK_BODY_P, QPSK_WRAP_HEAD_P, "v_mov_b32 v114, 1.0\n\tv_mov_b32 v115, 1.0\n\t", QPSK_RING_ALIGN_P)
+        QPSK_RING_TEXT(QPSK_HEAD_CHAIN_P, QPSK_HEAD_DEFERRED_P, QPSK_BODY_P, QPSK_WRAP_HEAD_P, "v_mov_b32 v114, 1.0\n\tv_mov_b32 v115, 1.0\n\t", QPSK_RING_ALIGN_P, COSTAS_RING_STEPS)
         : [p] "+v"(phase), [f] "+v"(freq), [k] "+s"(k), [fl] "=&s"(flags), [tm] "=&s"(tmp), [ex] "=&s"(ex),
           [t0] "=&s"(t0), [t1] "=&s"(t1)
         : [db] "v"(d_base), [zb] "v"(z_base), [ra] "v"(ready_addr), [ca] "v"(consumed_addr), [ke] "s"(kend),

@@ -8,6 +8,13 @@
 #include COSTAS_HEADER
 #define CHECK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 using namespace qpsk;
+/* steps per group of the ring stream (k counts groups): COSTAS_RING_STEPS of the header, 16 in headers from before round 7 */
+#ifdef COSTAS_RING_STEPS
+constexpr int RG = COSTAS_RING_STEPS;
+#else
+constexpr int RG = 16;
+#endif
+constexpr unsigned K0 = 64 / RG;      /* the run starts at chunk 1 */
 
 __global__ void __launch_bounds__(256) k(unsigned long long *cyc, float *sink, int groups, int nl, int real, int target)
 {
@@ -32,15 +39,15 @@ __global__ void __launch_bounds__(256) k(unsigned long long *cyc, float *sink, i
     float ph = loop < real ? 0.3f : 0.0f, fr = loop < real ? 0.1f : 0.0f;
     const float al = loop < real ? 0x1.4d0d4ap-3f : 0.0f, be = loop < real ? 0x1.d981e8p-7f : 0.0f;
     unsigned long long t0 = 0, t1 = 0, fl = 0;
-    unsigned kk = 4;
+    unsigned kk = K0;
     if (lane < nl) {
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0)::"memory");
 #ifdef PAIRED
         costas_asm_run_ring_pair(ph, fr, lds_addr(&dring[loop][0]), lds_addr(&zring[loop][0]), lds_addr(&flags[0]), lds_addr(&flags[1]), kk,
-                                 4u + (unsigned)groups, al, be, -1.0f, 1.0f, (lane & 1) != 0, fl);
+                                 K0 + (unsigned)groups, al, be, -1.0f, 1.0f, (lane & 1) != 0, fl);
 #else
         costas_asm_run_ring(ph, fr, lds_addr(&dring[lane][0]), lds_addr(&zring[lane][0]), lds_addr(&flags[0]), lds_addr(&flags[1]), kk,
-                            4u + (unsigned)groups, al, be, -1.0f, 1.0f, fl);
+                            K0 + (unsigned)groups, al, be, -1.0f, 1.0f, fl);
 #endif
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1)::"memory");
     }
@@ -58,7 +65,7 @@ int main(int argc, char **argv)
     float *sink;
     CHECK(hipMalloc(&cyc, 24));
     CHECK(hipMalloc(&sink, 4 * 192));
-    const int groups = 4096;       // 65536 steps
+    const int groups = 65536 / RG;       // 65536 steps
     printf("%-46s cycles/step for enabled lanes / real loops", argc > 1 ? argv[1] : "stream");
 #ifdef PAIRED
     const int cfg[8][3] = {{32, 16, 0}, {32, 16, 1}, {32, 16, 2}, {32, 16, 3}, {64, 16, 0}, {64, 32, 0}, {64, 32, 1}, {64, 32, 3}};      // enabled lanes, real loops, wave
@@ -72,7 +79,7 @@ int main(int argc, char **argv)
         hipLaunchKernelGGL(k, dim3(1), dim3(256), 0, 0, cyc, sink, groups, nl, real, target);
         CHECK(hipDeviceSynchronize());
         CHECK(hipMemcpy(h, cyc, 24, hipMemcpyDeviceToHost));
-        const double steps = 16.0 * (double)(h[1] - 4);
+        const double steps = (double)RG * (double)(h[1] - K0);
         printf("  %d/%d w%d: %5.1f%s", nl, real, target, (double)h[0] / steps, h[2] ? " (flag)" : "");
         if (c == 0) {      /* 16 real loops in every variant's first configuration */
             unsigned hs[192];

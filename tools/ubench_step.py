@@ -2,8 +2,9 @@
 """Builds tools/ubench_step.hip against variants of qpsk_amd/csrc/costas_asm.h (text substitutions on a copy: the
 product header is not touched) -> build_ubench/step/<variant>.bin; run them on the GPU box (this script there, hipcc is
 in the image: build_ubench/ is in .gpurunignore) with
-    python tools/ubench_step.py [--align] && for b in build_ubench/step/*.bin; do $b $(basename $b .bin); done
-What each variant removes from the serial wave's step tells what that piece costs the wave."""
+    python tools/ubench_step.py [--align] [--groups] && for b in build_ubench/step/*.bin; do $b $(basename $b .bin); done
+--groups builds the ring stream in groups of 16, 32 and 64 steps (COSTAS_RING_STEPS), with --align each at every placement of the group
+loop's head; --out DIR writes the binaries somewhere else.  What each variant removes from the serial wave's step tells what that piece costs the wave."""
 import os
 import re
 import subprocess
@@ -11,7 +12,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = open(os.path.join(ROOT, "qpsk_amd", "csrc", "costas_asm.h")).read()
-OUT = os.path.join(ROOT, "build_ubench", "step")
+OUT = os.path.abspath(sys.argv[sys.argv.index("--out") + 1]) if "--out" in sys.argv else os.path.join(ROOT, "build_ubench", "step")
 os.makedirs(OUT, exist_ok=True)
 
 
@@ -86,6 +87,8 @@ def split_step(n):
 
 
 PADS = (0, 1, 2, 3, 4, 5, 6, 7, 9, 11, 13, 15) if "--align" in sys.argv else ()
+GROUPS = (16, 32, 64) if "--groups" in sys.argv else ()
+GPADS = PADS or (None,)      # None: the placement the header ships
 # (name, header text, transformation, extra compiler flags)
 R05 = open(os.path.join(ROOT, "tools", "ref", "costas_asm_r05.h")).read()      # round 5's stream (28 VALU, magic-number rounding), for the comparison
 VARIANTS = [
@@ -95,6 +98,10 @@ VARIANTS = [
     *[("a%02d_one_lane" % k, SRC, aligned(k, "1"), []) for k in PADS],
     *[("b%02d_paired" % k, SRC, aligned(k, "P"), ["-DPAIRED"]) for k in PADS],
     *[("c%02d_paired_branch_%d_behind_the_test" % (k, k), SRC, split_step(k), ["-DPAIRED"]) for k in (5, 7, 9, 10, 11, 12, 13, 15)],
+    *[("g%d_a%s_one_lane" % (g, "%02d" % k if k is not None else "xx"), SRC, aligned(k, "1") if k is not None else (lambda s: s),
+       ["-DCOSTAS_RING_STEPS=%d" % g]) for g in GROUPS for k in GPADS],
+    *[("g%d_b%s_paired" % (g, "%02d" % k if k is not None else "xx"), SRC, aligned(k, "P") if k is not None else (lambda s: s),
+       ["-DPAIRED", "-DCOSTAS_RING_STEPS=%d" % g]) for g in GROUPS for k in GPADS],
     ("1_no_lds", SRC, no_lds, []),
     ("1p_paired_no_lds", SRC, no_lds, ["-DPAIRED"]),
     ("2_no_wrap_branch", SRC, no_branch, []),
