@@ -597,6 +597,60 @@ int qpsk_deframer_reset_coded_ilv(qpsk_ctx *ctx, int nstreams, const uint8_t *h_
                                   int max_packets, int mode, float scale, int period, uint32_t keep0, uint32_t keep1, int stride);
 
 /* -------------------------------------------------------------------------
+ * REED-SOLOMON: a byte-oriented outer code behind the convolutional code.  A Viterbi decoder that loses the path emits a run of wrong
+ * bytes; the outer code repairs up to nroots / 2 wrong bytes per codeword wherever they lie, or up to nroots bytes whose places are known
+ * (erasures), and says so per codeword when it cannot.  The library's own definition, integers only (the reference has no FEC; parity
+ * unpinned), restated in numpy by tests/test_rs_cpu.py and pinned there to a codebook decoder that enumerates every
+ * codeword of four small codes.  There is no tolerance anywhere.
+ *
+ * FIELD.  GF(256) modulo x^8 + x^4 + x^3 + x^2 + 1 (0x11D), alpha = 0x02.  Addition is xor.
+ * CODE (n, k), nroots = n - k:  1 <= k, 1 <= nroots <= 64, n <= 255.  A code shorter than 255 is the shortened code: the missing leading
+ *   bytes are zeros that are neither stored nor sent.
+ *       g(x) = prod_{i = 0}^{nroots - 1} (x - alpha^i)                                   (the first root is alpha^0)
+ *   With (204, 188) these are the field and generator polynomials ETSI EN 300 421 names for its outer code; conformity is by construction
+ *   (no outside test vector is pinned).
+ * ROW.  A codeword is n bytes, c(x) = sum_j row[j] x^(n - 1 - j).  row[0 .. k) is the data, unchanged (systematic); row[k .. n) is the
+ *   parity, (d(x) x^nroots) mod g(x) with d(x) = sum_{j < k} row[j] x^(k - 1 - j).  Hence c(alpha^i) = 0 for every i < nroots.
+ * DECODER, as a result.  Input: the received row r and, optionally, an erasure flag per byte (non-zero = erased); f = the number of
+ *   flagged positions.  For a codeword c let e = #{j not flagged : c[j] != r[j]}.
+ *       If f <= nroots and a codeword c with 2 e + f <= nroots exists, the output row is c.  Such a c is unique: the minimum distance is
+ *       nroots + 1.
+ *       Otherwise -- f > nroots included -- the output row is r, byte for byte, and the row's status is -1.
+ *   Consequence: a word beyond the radius of the codeword that was sent, but within the radius of ANOTHER codeword, decodes to that other
+ *   codeword, without a sign of it.  A caller who wants an end check puts a CRC of their own inside the data.
+ *   d_info [nrows][4] int32:
+ *       [0] the number of positions whose byte changed (flagged or not), or -1 on failure
+ *       [1] f
+ *       [2] e, or -1 on failure
+ *       [3] 1 if r as received already had all nroots syndromes r(alpha^i) zero, else 0
+ *   An erased position whose byte happens to be right counts in f and not in [0].
+ *
+ *   qpsk_rs_generator      host only, no context: the nroots + 1 coefficients of g into h_g, highest first, so h_g[0] = 1; nroots outside
+ *                1 .. 64, or h_g NULL, is QPSK_ERR_ARG
+ *   qpsk_rs_encode_batch   d_data [nrows][k] uint8, rows data_pitch bytes apart -> d_out [nrows][k + nroots], rows out_pitch bytes apart: the
+ *                data, then the parity.  d_out must not overlap d_data
+ *   qpsk_rs_decode_batch   d_in [nrows][n], rows in_pitch bytes apart; d_erase [nrows][n] uint8, tight, or NULL (nothing erased);
+ *                d_out [nrows][n], rows out_pitch bytes apart; d_info [nrows][4] int32, 4-byte aligned.  d_out or d_info may be NULL, not
+ *                both.  d_out may be exactly d_in with the same pitch (in place); any other overlap between d_out and d_in, and any
+ *                overlap of d_info or d_erase with an output, is QPSK_ERR_ARG
+ *   pitches      0 = tight (the row length); otherwise at least the row length; what lies between rows is never read or written
+ *   limits       nrows >= 1 and CODE's
+ * QPSK_ERR_ARG at the call for any bad argument, nothing launched.  Both batch calls are stream-ordered on the context's stream and touch
+ * neither the receive streams, the deframer, the histogram mode's guess nor the Viterbi scratch.  qpsk_ctx_last_kernel() names
+ * rs_encode_kernel / rs_decode_kernel.  A decode failure is a row's status: it is never a call error and never raises the context's status
+ * word.
+ * COMPOSITION.  in_pitch exists so that the d_bytes [nstreams][max_packets][nbytes + 2] of qpsk_deframer_push / _push_coded is decoded where
+ * it lies: n = nbytes, in_pitch = nbytes + 2, nrows = nstreams * max_packets.  The packet's CRC is then over the codeword.
+ * Not built: other field polynomials or first roots (CCSDS's dual-basis code among them), nroots > 64, a helper that interleaves
+ * codewords across packets, the outer code inside the deframer's own launch, qpsk_multi.  Usage: INTEGRATION.md 2.0.
+ * ------------------------------------------------------------------------- */
+int qpsk_rs_generator(int nroots, uint8_t *h_g);
+int qpsk_rs_encode_batch(qpsk_ctx *ctx, const uint8_t *d_data, long long data_pitch, int nrows, int k, int nroots, uint8_t *d_out,
+                         long long out_pitch);
+int qpsk_rs_decode_batch(qpsk_ctx *ctx, const uint8_t *d_in, long long in_pitch, int nrows, int n, int nroots, const uint8_t *d_erase,
+                         uint8_t *d_out, long long out_pitch, int32_t *d_info);
+
+/* -------------------------------------------------------------------------
  * The stages on their own (each is what the corresponding reference function
  * computes, batched).
  * ------------------------------------------------------------------------- */

@@ -2570,6 +2570,74 @@ int qpsk_frame_batch_ilv(qpsk_ctx *c, const uint8_t *d_payload, long long payloa
                       &stride, lead, gap, row_len, d_out, d_crc);
 }
 
+/* ------------------------------------------------------------ the Reed-Solomon outer code (REED-SOLOMON in include/qpsk_hip.h) */
+int qpsk_rs_generator(int nroots, uint8_t *h_g)
+{
+    if (!h_g) return fail(QPSK_ERR_ARG, "qpsk_rs_generator: null output");
+    if (nroots < 1 || nroots > RS_MAX_ROOTS) return fail(QPSK_ERR_ARG, "qpsk_rs_generator: nroots = %d outside 1..%d", nroots, RS_MAX_ROOTS);
+    rs_generator(nroots, h_g);
+    return QPSK_OK;
+}
+
+/* a pitch argument: 0 = tight, otherwise at least the row and small enough for nrows rows to stay inside 63 bits */
+static bool rs_pitch(long long pitch, int row, int nrows, size_t *out)
+{
+    if (pitch != 0 && (pitch < row || pitch > (LLONG_MAX >> 1) / nrows)) return false;
+    *out = pitch ? (size_t)pitch : (size_t)row;
+    return true;
+}
+
+static bool rs_overlap(uintptr_t a0, uintptr_t a1, uintptr_t b0, uintptr_t b1) { return a0 < b1 && b0 < a1; }
+
+int qpsk_rs_encode_batch(qpsk_ctx *c, const uint8_t *d_data, long long data_pitch, int nrows, int k, int nroots, uint8_t *d_out,
+                         long long out_pitch)
+{
+    if (!c || !d_data || !d_out) return fail(QPSK_ERR_ARG, "qpsk_rs_encode_batch: null context, data or output");
+    if (nrows < 1 || k < 1 || nroots < 1 || nroots > RS_MAX_ROOTS || k + nroots > 255)
+        return fail(QPSK_ERR_ARG, "qpsk_rs_encode_batch: nrows = %d, k = %d, nroots = %d (nrows >= 1, k >= 1, 1 <= nroots <= %d, k + nroots <= 255)",
+                    nrows, k, nroots, RS_MAX_ROOTS);
+    const int n = k + nroots;
+    size_t ip = 0, op = 0;
+    if (!rs_pitch(data_pitch, k, nrows, &ip) || !rs_pitch(out_pitch, n, nrows, &op))
+        return fail(QPSK_ERR_ARG, "qpsk_rs_encode_batch: data_pitch = %lld (0 or >= k = %d), out_pitch = %lld (0 or >= n = %d)", data_pitch, k,
+                    out_pitch, n);
+    const uintptr_t i0 = (uintptr_t)d_data, i1 = i0 + (size_t)(nrows - 1) * ip + (size_t)k;
+    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)(nrows - 1) * op + (size_t)n;
+    if (rs_overlap(i0, i1, o0, o1)) return fail(QPSK_ERR_ARG, "qpsk_rs_encode_batch: d_out overlaps d_data");
+    if (bind(c)) return QPSK_ERR_HIP;
+    KERNEL_TRY(launch_rs_encode(d_data, ip, nrows, k, nroots, d_out, op, c->stream));
+    c->last_kernel = "rs_encode_kernel";
+    return QPSK_OK;
+}
+
+int qpsk_rs_decode_batch(qpsk_ctx *c, const uint8_t *d_in, long long in_pitch, int nrows, int n, int nroots, const uint8_t *d_erase,
+                         uint8_t *d_out, long long out_pitch, int32_t *d_info)
+{
+    if (!c || !d_in) return fail(QPSK_ERR_ARG, "qpsk_rs_decode_batch: null context or input");
+    if (!d_out && !d_info) return fail(QPSK_ERR_ARG, "qpsk_rs_decode_batch: d_out and d_info are both NULL");
+    if (nrows < 1 || nroots < 1 || nroots > RS_MAX_ROOTS || n <= nroots || n > 255)
+        return fail(QPSK_ERR_ARG, "qpsk_rs_decode_batch: nrows = %d, n = %d, nroots = %d (nrows >= 1, 1 <= nroots <= %d, nroots < n <= 255)", nrows,
+                    n, nroots, RS_MAX_ROOTS);
+    size_t ip = 0, op = 0;
+    if (!rs_pitch(in_pitch, n, nrows, &ip) || !rs_pitch(out_pitch, n, nrows, &op))
+        return fail(QPSK_ERR_ARG, "qpsk_rs_decode_batch: in_pitch = %lld, out_pitch = %lld (each 0 or >= n = %d)", in_pitch, out_pitch, n);
+    const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (size_t)(nrows - 1) * ip + (size_t)n;
+    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)(nrows - 1) * op + (size_t)n;
+    const uintptr_t e0 = (uintptr_t)d_erase, e1 = e0 + (size_t)nrows * (size_t)n;
+    const uintptr_t f0 = (uintptr_t)d_info, f1 = f0 + 16 * (size_t)nrows;
+    /* in place: exactly the input rows, each wave reads its whole row before it writes it */
+    if (d_out && !(d_out == d_in && op == ip) && rs_overlap(i0, i1, o0, o1))
+        return fail(QPSK_ERR_ARG, "qpsk_rs_decode_batch: d_out overlaps d_in (allowed: d_out == d_in with the same pitch)");
+    if (d_out && d_erase && rs_overlap(e0, e1, o0, o1)) return fail(QPSK_ERR_ARG, "qpsk_rs_decode_batch: d_out overlaps d_erase");
+    if (d_info && (((uintptr_t)d_info & 3) || rs_overlap(f0, f1, i0, i1) || (d_out && rs_overlap(f0, f1, o0, o1)) ||
+                   (d_erase && rs_overlap(f0, f1, e0, e1))))
+        return fail(QPSK_ERR_ARG, "qpsk_rs_decode_batch: d_info is not 4-byte aligned, or overlaps d_in, d_out or d_erase");
+    if (bind(c)) return QPSK_ERR_HIP;
+    KERNEL_TRY(launch_rs_decode(d_in, ip, nrows, n, nroots, d_erase, d_out, op, d_info, c->stream));
+    c->last_kernel = "rs_decode_kernel";
+    return QPSK_OK;
+}
+
 /* test hook (tests/test_viterbi_chunks_gpu.py): host bookkeeping only */
 int qpsk_test_viterbi_launches(qpsk_ctx *c, int *out)
 {

@@ -407,6 +407,13 @@ struct FrameArgs {
 int launch_frame(const FrameArgs &a, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s);
 /* qpsk_frame_batch_ilv with a stride other than 1: frame_ilv_kernel, a.coded set, ilv.n = 2 a.nbody */
 int launch_frame_ilv(const FrameArgs &a, const Interleave &ilv, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s);
+/* rs.hip: the Reed-Solomon outer code (the definition: include/qpsk_hip.h, REED-SOLOMON).  One wave per codeword; pitches in bytes, never 0
+ * here; the caller has checked every bound and every overlap.  erase [nrows][n] or NULL; out or info may be NULL, not both */
+constexpr int RS_MAX_ROOTS = 64;
+void rs_generator(int nroots, uint8_t *g);      /* host: nroots + 1 coefficients, highest first; 1 <= nroots <= RS_MAX_ROOTS */
+int launch_rs_encode(const uint8_t *data, size_t data_pitch, int nrows, int k, int nroots, uint8_t *out, size_t out_pitch, hipStream_t s);
+int launch_rs_decode(const uint8_t *in, size_t in_pitch, int nrows, int n, int nroots, const uint8_t *erase, uint8_t *out, size_t out_pitch,
+                     int32_t *info, hipStream_t s);
 /* txchain.hip */
 int tx_history_symbols(void);          /* symbols of state per transmitter (uint8 each, 4 = none yet) */
 int launch_tx_shape(const uint8_t *sym, uint8_t *hist, const float *taps, float *sig, int nstreams, int nsym,

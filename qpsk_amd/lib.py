@@ -63,6 +63,7 @@ API_SYMBOLS = [
     "qpsk_test_viterbi_launches", "qpsk_test_deframer_advance",
     "qpsk_frame_len", "qpsk_frame_batch",
     "qpsk_ilv_stride", "qpsk_conv_encode_ilv_batch", "qpsk_viterbi_ilv_batch", "qpsk_frame_batch_ilv", "qpsk_deframer_reset_coded_ilv",
+    "qpsk_rs_generator", "qpsk_rs_encode_batch", "qpsk_rs_decode_batch",
 ]
 # the named puncturing patterns of include/qpsk_hip.h (QPSK_PUNCT_*): rate -> (period, keep0, keep1), bit r of a mask = step r of the period
 PUNCTURE = {"1/2": (1, 0x1, 0x1), "2/3": (2, 0x1, 0x3), "3/4": (3, 0x5, 0x3), "5/6": (5, 0x15, 0x0B), "7/8": (7, 0x51, 0x2F)}
@@ -152,6 +153,9 @@ def load():
     L.qpsk_viterbi_ilv_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, u32, u32, i32, vp, i32, vp, vp]
     L.qpsk_frame_batch_ilv.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, vp, i32, i32, i32, u32, u32, i32, i32, i32, i32, vp, vp]
     L.qpsk_deframer_reset_coded_ilv.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, f32, i32, u32, u32, i32]
+    L.qpsk_rs_generator.argtypes = [i32, vp]
+    L.qpsk_rs_encode_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, vp, C.c_longlong]
+    L.qpsk_rs_decode_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, vp, vp, C.c_longlong, vp]
     L.qpsk_rrc_fir_batch.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_rrc_fir_batch_fast.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_timing_hist_batch.argtypes = [vp, vp, i32, vp, vp]
@@ -229,6 +233,17 @@ def ilv_stride(nbits, want):
     if rc < 0:
         raise QpskError("libqpsk_hip error %d: %s" % (rc, L.qpsk_last_error().decode()))
     return rc
+
+
+def rs_generator(nroots):
+    """qpsk_rs_generator: the nroots + 1 coefficients of the Reed-Solomon generator polynomial prod (x - alpha^i), i < nroots, over GF(256)
+    modulo 0x11D, highest first, as a numpy uint8 array.  Host only, needs no GPU"""
+    L = load()
+    g = np.zeros(max(int(nroots), 0) + 1, np.uint8)
+    rc = L.qpsk_rs_generator(int(nroots), g.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise QpskError("libqpsk_hip error %d: %s" % (rc, L.qpsk_last_error().decode()))
+    return g
 
 
 def _interleaved(interleave):
@@ -804,6 +819,46 @@ class Modem:
                                                 *code, lead, gap, int(row_len), _ptr(o["dibits"]), _ptr(o["crc"])))
         o["_keep"] = (p,)      # the input stays alive until the caller is done with the outputs (stream order)
         return o
+
+    # ---- the Reed-Solomon outer code (qpsk_rs_*)
+    def rs_encode(self, data, nroots, pitch=0):
+        """qpsk_rs_encode_batch: data (R, k) uint8 -> (R, k + nroots) uint8, the data and then the parity of the (k + nroots, k) code over
+        GF(256).  pitch: the bytes between the OUTPUT's rows (0 = tight); the result is then a view of a (R, pitch) buffer, whose other
+        bytes are not written"""
+        t = self.torch
+        d = self._dev(data, t.uint8)
+        if d.dim() != 2:
+            raise ValueError("rs_encode() data must be (rows, k) uint8")
+        R, k = d.shape
+        n = k + int(nroots)
+        buf = self.empty((R, int(pitch) or n), t.uint8)
+        self._check(self.L.qpsk_rs_encode_batch(self.h, _ptr(d), 0, R, k, int(nroots), _ptr(buf), int(pitch)))
+        self._rs_keep = (d,)      # the input stays alive until the stream has run the call
+        return buf[:, :n]
+
+    def rs_decode(self, words, nroots, erasures=None, pitch=0, n=None, inplace=False):
+        """qpsk_rs_decode_batch: words (R, n) uint8, or with pitch (R, pitch) of which the first n bytes of each row are the codeword --
+        the deframers' bytes reshaped to (S * M, nbytes + 2) with pitch = nbytes + 2, n = nbytes.  erasures (R, n) uint8, non-zero =
+        that byte is erased, or None.  -> (words (R, n) uint8, info (R, 4) int32 = (bytes changed or -1, erasures, errors or -1, the
+        row came in with zero syndromes)).  A row that cannot be decoded comes back as it was with info[:, 0] = -1.  inplace: the
+        corrected rows are written over words (a device tensor) and the first result is a view of it"""
+        t = self.torch
+        w = self._dev(words, t.uint8)
+        if w.dim() != 2 or (pitch and w.shape[1] != pitch):
+            raise ValueError("rs_decode() words must be (rows, n or pitch) uint8")
+        R = w.shape[0]
+        n = int(n) if n is not None else w.shape[1]
+        e = None if erasures is None else self._dev(erasures, t.uint8)
+        if e is not None and tuple(e.shape) != (R, n):
+            raise ValueError("rs_decode() erasures must be (%d, %d) uint8" % (R, n))
+        if inplace and (not isinstance(words, t.Tensor) or w.data_ptr() != words.data_ptr()):
+            raise ValueError("rs_decode(inplace=True) needs a contiguous uint8 tensor on the modem's device")
+        out = w if inplace else self.empty((R, n), t.uint8)
+        info = self.empty((R, 4), t.int32)
+        self._check(self.L.qpsk_rs_decode_batch(self.h, _ptr(w), int(pitch), R, n, int(nroots), _ptr(e), _ptr(out), int(pitch) if inplace else 0,
+                                                _ptr(info)))
+        self._rs_keep = (w, e)
+        return out[:, :n], info
 
     def streams_loop_state(self):
         a = (C.c_float * (2 * self.nstreams))()

@@ -1,0 +1,377 @@
+"""qpsk_rs_encode_batch / qpsk_rs_decode_batch and Modem.rs_encode / rs_decode on the GPU, bit for bit against the numpy restatements of
+test_rs_cpu.py (REED-SOLOMON of include/qpsk_hip.h): every code and error pattern in one call per code, so that neighbouring waves leave by
+different exits; the call shapes (row counts, pitches with poison between the rows, in place, either output alone, guards); the encoder;
+the erasure identity; the error contract; and the link of the CPU test on the device, the deframer's bytes decoded where they lie.  There
+is no tolerance anywhere."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from test_deframe_coded_cpu import dibits_to_costas
+from test_punct_cpu import NAMED
+from test_rs_cpu import LINK, RS_CODES, link_result, rs_decode_ref, rs_encode_ref
+from test_viterbi_gpu import GUARD, modem, ptr
+
+pytestmark = pytest.mark.gpu
+
+QPSK_ERR_ARG = -2
+POISON, OUT_FILL, INFO_FILL = 0xA5, 0x55, 0x55555555
+
+
+# ------------------------------------------------------------------------------------------ the rows of one code, and their references
+def patterns(n, k):
+    """-> (words (R, n), flags (R, n), sent (R, n), names): codewords damaged in every way the issue lists, in an order that puts rows
+    with different exits next to each other"""
+    nroots, t = n - k, (n - k) // 2
+    rng = np.random.default_rng(1000 * n + k)
+    rows = []
+
+    def add(name, errors=0, erased=0, erased_right=0, at=None, word=None):
+        """a fresh codeword with `erased` flagged positions, of which `erased_right` keep their byte, and `errors` unflagged wrong bytes
+        (at the places `at` when given)"""
+        sent = rs_encode_ref(rng.integers(0, 256, (1, k), dtype=np.uint8), nroots)[0]
+        w, fl = sent.copy(), np.zeros(n, np.uint8)
+        if word is not None:
+            sent = w = np.asarray(word, np.uint8)
+        erased, errors = min(erased, n), min(errors, n - min(erased, n))
+        order = rng.permutation(n) if at is None else np.concatenate([at, np.setdiff1d(rng.permutation(n), at, assume_unique=True)])
+        err_at, era_at = order[:errors], order[errors:errors + erased]
+        fl[era_at] = 1
+        hit = np.concatenate([err_at, era_at[erased_right:]]).astype(np.int64)
+        w = w.copy()
+        w[hit] ^= rng.integers(1, 256, len(hit), dtype=np.uint8)
+        rows.append((name, w, fl, sent))
+
+    add("clean")
+    add("1 error", errors=1)
+    add("t errors", errors=t)
+    add("t + 1 errors", errors=t + 1)
+    add("clean, again")
+    add("error at j = 0", errors=1, at=np.array([0]))
+    add("f = nroots + 1", erased=nroots + 1)
+    add("error at j = n - 1", errors=1, at=np.array([n - 1]))
+    add("all zero", word=np.zeros(n, np.uint8))
+    add("error in the parity", errors=1, at=np.array([k + (nroots - 1) // 2]))
+    add("garbage", word=rng.integers(0, 256, n, dtype=np.uint8))
+    add("errors at both ends and in the parity", errors=min(3, max(t, 1)), at=np.array([0, n - 1, n - 2][:min(3, max(t, 1))]))
+    add("all 0xFF", word=np.full(n, 0xFF, np.uint8))
+    add("f = nroots, e = 0", erased=nroots)
+    e = max(1, t // 2)
+    add("2 e + f = nroots", errors=e, erased=max(nroots - 2 * e, 0))
+    add("2 e + f = nroots + 1", errors=e, erased=max(nroots + 1 - 2 * e, 0))
+    add("erased bytes that are right", erased=nroots, erased_right=(nroots + 1) // 2)
+    add("clean with erasures", erased=max(t, 1), erased_right=max(t, 1))
+    add("garbage with erasures", erased=t, word=rng.integers(0, 256, n, dtype=np.uint8))
+    add("t errors, again", errors=t)
+    return (np.stack([r[1] for r in rows]), np.stack([r[2] for r in rows]), np.stack([r[3] for r in rows]), [r[0] for r in rows])
+
+
+_CASES = {}
+
+
+def case(n, k):
+    """the rows of a code with both references, computed once and shared by every test; nobody changes them"""
+    if (n, k) not in _CASES:
+        words, flags, sent, names = patterns(n, k)
+        out_e, info_e = rs_decode_ref(words, n - k, flags)
+        out_0, info_0 = rs_decode_ref(words, n - k, None)
+        for a in (words, flags, sent, out_e, info_e, out_0, info_0):
+            a.setflags(write=False)
+        _CASES[(n, k)] = dict(words=words, flags=flags, sent=sent, names=names, erased=(out_e, info_e), plain=(out_0, info_0))
+    return _CASES[(n, k)]
+
+
+def tile(a, R):
+    return np.ascontiguousarray(np.resize(a, (R,) + a.shape[1:]))
+
+
+def decode(m, words, nroots, flags=None, in_pitch=0, out_pitch=0, inplace=False, want=("out", "info")):
+    """the raw call: pitched buffers filled with POISON between the rows, GUARD elements behind every output -> dict(out, info, kernel); an
+    output that was not asked for is passed as NULL"""
+    import torch
+    R, n = words.shape
+    ip, op = in_pitch or n, (in_pitch or n) if inplace else (out_pitch or n)
+    src = np.full((R, ip), POISON, np.uint8)
+    src[:, :n] = words
+    d_in = torch.from_numpy(np.concatenate([src.reshape(-1), np.full(GUARD, POISON, np.uint8)])).cuda()
+    d_er = None if flags is None else torch.from_numpy(np.array(flags, np.uint8)).cuda()
+    d_out = d_in if inplace else torch.full((R * op + GUARD,), OUT_FILL, dtype=torch.uint8, device="cuda")
+    d_info = torch.full((R * 4 + GUARD,), INFO_FILL, dtype=torch.int32, device="cuda")
+    m._check(m.L.qpsk_rs_decode_batch(m.h, ptr(d_in), in_pitch, R, n, nroots, ptr(d_er), ptr(d_out) if "out" in want else None,
+                                      in_pitch if inplace else out_pitch, ptr(d_info) if "info" in want else None))
+    kernel = m.last_kernel()
+    torch.cuda.synchronize()
+    ho, hi, hin = d_out.cpu().numpy(), d_info.cpu().numpy(), d_in.cpu().numpy()
+    fill = POISON if inplace else OUT_FILL
+    assert np.all(ho[R * op:] == fill) and np.all(hi[R * 4:] == INFO_FILL), "a guard behind an output was overwritten"
+    rows = ho[:R * op].reshape(R, op)
+    assert np.all(rows[:, n:] == fill), "bytes between the output's rows were written"
+    if "out" not in want:
+        assert np.all(ho == fill) or inplace
+    if "info" not in want:
+        assert np.all(hi == INFO_FILL)
+    if not inplace or "out" not in want:
+        assert np.array_equal(hin[:R * ip].reshape(R, ip), src), "the input was written"
+    return dict(out=rows[:, :n], info=hi[:R * 4].reshape(R, 4), kernel=kernel)
+
+
+def assert_rows(got, want, names, what):
+    out, info = want
+    for i in range(len(out)):
+        name = names[i % len(names)]
+        assert np.array_equal(got["info"][i], info[i]), (what, i, name, got["info"][i], info[i])
+        assert np.array_equal(got["out"][i], out[i]), (what, i, name)
+
+
+def case_checked(n, k):
+    """case(n, k), after the references themselves have said what the patterns were built for: rows within the radius come back as sent,
+    the others fail or come back as another codeword"""
+    c = case(n, k)
+    nroots, t = n - k, (n - k) // 2
+    names, (out, info) = c["names"], c["erased"]
+    for name in ("clean", "t errors", "f = nroots, e = 0", "2 e + f = nroots", "erased bytes that are right", "error at j = 0",
+                 "error at j = n - 1", "error in the parity")[:3 if nroots == 1 else None]:
+        i = names.index(name)
+        if name.startswith("error") and t == 0:
+            continue
+        assert info[i, 0] >= 0 and np.array_equal(out[i], c["sent"][i]), (name, info[i])
+    assert info[names.index("f = nroots + 1"), 0] == -1 and info[names.index("f = nroots + 1"), 1] == nroots + 1
+    i = names.index("erased bytes that are right")
+    assert 0 <= info[i, 0] < info[i, 1] == nroots
+    assert tuple(info[names.index("clean with erasures")]) == (0, max(t, 1), 0, 1)
+    i = names.index("t + 1 errors")
+    assert info[i, 0] == -1 or not np.array_equal(out[i], c["sent"][i])          # beyond the radius: failed, or another codeword
+    return c
+
+
+# ------------------------------------------------------------------------------------------ 1. every code, every pattern, one call
+@pytest.mark.parametrize("n,k", RS_CODES)
+def test_every_pattern_of_a_code_in_one_call_bit_for_bit(n, k):
+    c = case_checked(n, k)
+    nroots, names = n - k, c["names"]
+    m = modem()
+    got = decode(m, c["words"], nroots, c["flags"])
+    assert got["kernel"] == "rs_decode_kernel"
+    assert_rows(got, c["erased"], names, "erasures")
+    assert_rows(decode(m, c["words"], nroots, None), c["plain"], names, "d_erase NULL")
+    m.sync()
+    m.close()
+
+
+# ------------------------------------------------------------------------------------------ 2. the call shapes
+@pytest.mark.parametrize("n,k", [(60, 44), (21, 16), (255, 191)])
+@pytest.mark.parametrize("R", [1, 5, 70])
+def test_row_counts_pitches_in_place_and_either_output_alone(n, k, R):
+    c = case(n, k)
+    words, flags = tile(c["words"], R), tile(c["flags"], R)
+    want = (tile(c["erased"][0], R), tile(c["erased"][1], R))
+    m = modem()
+    for what, kw in (("tight", {}), ("pitched input", dict(in_pitch=n + 2)), ("pitched output", dict(out_pitch=n + 7)),
+                     ("both pitched", dict(in_pitch=n + 1, out_pitch=n + 3)), ("in place", dict(inplace=True)),
+                     ("in place, pitched", dict(inplace=True, in_pitch=n + 2))):
+        assert_rows(decode(m, words, n - k, flags, **kw), want, c["names"], what)
+    got = decode(m, words, n - k, flags, in_pitch=n + 2, want=("info",))
+    assert np.array_equal(got["info"], want[1])
+    got = decode(m, words, n - k, flags, out_pitch=n + 5, want=("out",))
+    assert np.array_equal(got["out"], want[0])
+    m.sync()
+    m.close()
+
+
+# ------------------------------------------------------------------------------------------ 3. the encoder
+def encode(m, data, nroots, data_pitch=0, out_pitch=0):
+    import torch
+    R, k = data.shape
+    n, ip, op = k + nroots, data_pitch or k, out_pitch or k + nroots
+    src = np.full((R, ip), POISON, np.uint8)
+    src[:, :k] = data
+    d_in = torch.from_numpy(src).cuda()
+    d_out = torch.full((R * op + GUARD,), OUT_FILL, dtype=torch.uint8, device="cuda")
+    m._check(m.L.qpsk_rs_encode_batch(m.h, ptr(d_in), data_pitch, R, k, nroots, ptr(d_out), out_pitch))
+    assert m.last_kernel() == "rs_encode_kernel"
+    torch.cuda.synchronize()
+    ho = d_out.cpu().numpy()
+    assert np.all(ho[R * op:] == OUT_FILL), "the guard behind the output was overwritten"
+    rows = ho[:R * op].reshape(R, op)
+    assert np.all(rows[:, n:] == OUT_FILL), "bytes between the output's rows were written"
+    assert np.array_equal(d_in.cpu().numpy(), src)
+    return rows[:, :n]
+
+
+@pytest.mark.parametrize("n,k", RS_CODES)
+def test_encoder_equals_the_restatement_for_every_row_count_and_pitch(n, k):
+    m = modem()
+    rng = np.random.default_rng(n * 300 + k)
+    for R in (1, 5, 70):
+        data = rng.integers(0, 256, (R, k), dtype=np.uint8)
+        data[0] = 0xFF
+        data[R // 2] = 0
+        want = rs_encode_ref(data, n - k)
+        for dp, op in ((0, 0), (k + 3, 0), (0, n + 2), (k + 1, n + 5)):
+            assert np.array_equal(encode(m, data, n - k, dp, op), want), (R, dp, op)
+    m.sync()
+    m.close()
+
+
+# ------------------------------------------------------------------------------------------ 4. encode, erase, decode
+@pytest.mark.parametrize("n,k", RS_CODES)
+def test_the_encoder_s_rows_come_back_from_random_erasures_of_up_to_nroots_positions(n, k):
+    import torch
+    m = modem()
+    nroots, R = n - k, 33
+    rng = np.random.default_rng(n + 7 * k)
+    data = torch.from_numpy(rng.integers(0, 256, (R, k), dtype=np.uint8)).cuda()
+    rows = m.rs_encode(data, nroots)
+    assert tuple(rows.shape) == (R, n)
+    sent = rows.cpu().numpy()
+    flags, hit = np.zeros((R, n), np.uint8), sent.copy()
+    for r in range(R):
+        f = nroots if r == 0 else int(rng.integers(0, nroots + 1))
+        at = rng.choice(n, f, replace=False)
+        flags[r, at] = 1
+        hit[r, at] = rng.integers(0, 256, f, dtype=np.uint8)                   # some erased bytes stay right by chance
+    out, info = m.rs_decode(hit, nroots, erasures=flags)
+    out, info = out.cpu().numpy(), info.cpu().numpy()
+    assert np.array_equal(out, sent)
+    assert np.array_equal(info[:, 0], (hit != sent).sum(axis=1)) and np.array_equal(info[:, 1], flags.sum(axis=1)) and not info[:, 2].any()
+    m.sync()
+    m.close()
+
+
+def test_python_front_end_pitch_n_and_inplace():
+    import torch
+    c = case(60, 44)
+    m = modem()
+    words, flags, (want_out, want_info) = c["words"].copy(), c["flags"].copy(), c["erased"]
+    out, info = m.rs_decode(words, 16, erasures=flags)
+    assert np.array_equal(out.cpu().numpy(), want_out) and np.array_equal(info.cpu().numpy(), want_info)
+    wide = np.full((len(words), 62), POISON, np.uint8)
+    wide[:, :60] = words
+    dev = torch.from_numpy(wide).cuda()
+    out, info = m.rs_decode(dev, 16, erasures=flags, pitch=62, n=60)
+    assert tuple(out.shape) == (len(words), 60) and np.array_equal(out.cpu().numpy(), want_out) and np.array_equal(dev.cpu().numpy(), wide)
+    out, info = m.rs_decode(dev, 16, erasures=flags, pitch=62, n=60, inplace=True)
+    assert out.data_ptr() == dev.data_ptr() and np.array_equal(info.cpu().numpy(), want_info)
+    back = dev.cpu().numpy()
+    assert np.array_equal(back[:, :60], want_out) and np.all(back[:, 60:] == POISON)
+    enc = m.rs_encode(c["sent"][:, :44], 16, pitch=62)
+    assert tuple(enc.shape) == (len(words), 60) and enc.stride(0) == 62
+    good = c["erased"][1][:, 0] >= 0
+    assert np.array_equal(enc.cpu().numpy()[good], want_out[good])              # every decoded row is a codeword: re-encoding its data gives it
+    with pytest.raises(ValueError):
+        m.rs_decode(words, 16, inplace=True)                                    # a numpy array cannot be decoded in place
+    m.sync()
+    m.close()
+
+
+# ------------------------------------------------------------------------------------------ 5. the error contract
+def test_every_bad_argument_is_refused_with_nothing_written_and_the_context_stays_usable():
+    import torch
+    import qpsk_amd
+    c = case(21, 16)
+    m = modem()
+    n, nroots, R = 21, 5, 8
+    words = tile(c["words"], R)
+    d_in = torch.from_numpy(words.copy()).cuda()
+    d_er = torch.zeros((R, n), dtype=torch.uint8, device="cuda")
+    d_out = torch.full((R * 64,), OUT_FILL, dtype=torch.uint8, device="cuda")
+    d_info = torch.full((R * 4 + 8,), INFO_FILL, dtype=torch.int32, device="cuda")
+    before = m.last_kernel()
+    L, h = m.L, m.h
+    at = lambda t, off: C.c_void_p(t.data_ptr() + off)      # noqa: E731
+    dec = [
+        ("null context", lambda: L.qpsk_rs_decode_batch(None, ptr(d_in), 0, R, n, nroots, None, ptr(d_out), 0, ptr(d_info))),
+        ("null input", lambda: L.qpsk_rs_decode_batch(h, None, 0, R, n, nroots, None, ptr(d_out), 0, ptr(d_info))),
+        ("both outputs null", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), 0, R, n, nroots, None, None, 0, None)),
+        ("nrows 0", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), 0, 0, n, nroots, None, ptr(d_out), 0, ptr(d_info))),
+        ("nrows negative", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), 0, -1, n, nroots, None, ptr(d_out), 0, ptr(d_info))),
+        ("nroots 0", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), 0, R, n, 0, None, ptr(d_out), 0, ptr(d_info))),
+        ("nroots 65", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), 0, 1, 130, 65, None, ptr(d_out), 0, ptr(d_info))),
+        ("k = 0", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), 0, R, 5, 5, None, ptr(d_out), 0, ptr(d_info))),
+        ("n = 256", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), 0, 1, 256, 32, None, ptr(d_out), 0, ptr(d_info))),
+        ("in_pitch below n", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), n - 1, R, n, nroots, None, ptr(d_out), 0, ptr(d_info))),
+        ("in_pitch negative", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), -n, R, n, nroots, None, ptr(d_out), 0, ptr(d_info))),
+        ("out_pitch below n", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), 0, R, n, nroots, None, ptr(d_out), n - 1, ptr(d_info))),
+        ("a pitch that leaves 64 bits", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), 0, R, n, nroots, None, ptr(d_out), 1 << 62, ptr(d_info))),
+        ("in place with another pitch", lambda: L.qpsk_rs_decode_batch(h, ptr(d_out), 0, R, n, nroots, None, ptr(d_out), n + 1, ptr(d_info))),
+        ("output one byte into the input", lambda: L.qpsk_rs_decode_batch(h, ptr(d_out), 0, R, n, nroots, None, at(d_out, 1), 0, ptr(d_info))),
+        ("output overlaps the input's tail", lambda: L.qpsk_rs_decode_batch(h, ptr(d_out), 0, R, n, nroots, None, at(d_out, R * n - 1), 0, ptr(d_info))),
+        ("info misaligned", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), 0, R, n, nroots, None, ptr(d_out), 0, at(d_info, 2))),
+        ("info inside the output", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), 0, R, n, nroots, None, ptr(d_out), 0, at(d_out, 16))),
+        ("info inside the input", lambda: L.qpsk_rs_decode_batch(h, ptr(d_out), 0, R, n, nroots, None, None, 0, at(d_out, 16))),
+        ("erasures inside the output", lambda: L.qpsk_rs_decode_batch(h, ptr(d_in), 0, R, n, nroots, at(d_out, 8), ptr(d_out), 0, ptr(d_info))),
+    ]
+    enc = [
+        ("null context", lambda: L.qpsk_rs_encode_batch(None, ptr(d_in), 0, R, 16, 5, ptr(d_out), 0)),
+        ("null data", lambda: L.qpsk_rs_encode_batch(h, None, 0, R, 16, 5, ptr(d_out), 0)),
+        ("null output", lambda: L.qpsk_rs_encode_batch(h, ptr(d_in), 0, R, 16, 5, None, 0)),
+        ("nrows 0", lambda: L.qpsk_rs_encode_batch(h, ptr(d_in), 0, 0, 16, 5, ptr(d_out), 0)),
+        ("k 0", lambda: L.qpsk_rs_encode_batch(h, ptr(d_in), 0, R, 0, 5, ptr(d_out), 0)),
+        ("nroots 0", lambda: L.qpsk_rs_encode_batch(h, ptr(d_in), 0, R, 16, 0, ptr(d_out), 0)),
+        ("nroots 65", lambda: L.qpsk_rs_encode_batch(h, ptr(d_in), 0, 1, 16, 65, ptr(d_out), 0)),
+        ("k + nroots = 256", lambda: L.qpsk_rs_encode_batch(h, ptr(d_in), 0, 1, 192, 64, ptr(d_out), 0)),
+        ("data_pitch below k", lambda: L.qpsk_rs_encode_batch(h, ptr(d_in), 15, R, 16, 5, ptr(d_out), 0)),
+        ("out_pitch below n", lambda: L.qpsk_rs_encode_batch(h, ptr(d_in), 0, R, 16, 5, ptr(d_out), 20)),
+        ("out_pitch negative", lambda: L.qpsk_rs_encode_batch(h, ptr(d_in), 0, R, 16, 5, ptr(d_out), -21)),
+        ("output over the data", lambda: L.qpsk_rs_encode_batch(h, ptr(d_out), 21, R, 16, 5, ptr(d_out), 21)),
+    ]
+    for who, calls in (("qpsk_rs_decode_batch", dec), ("qpsk_rs_encode_batch", enc)):
+        for what, call in calls:
+            assert call() == QPSK_ERR_ARG, (who, what)
+            assert who.encode() in L.qpsk_last_error(), (who, what)
+    torch.cuda.synchronize()
+    assert np.all(d_out.cpu().numpy() == OUT_FILL) and np.all(d_info.cpu().numpy() == INFO_FILL) and np.array_equal(d_in.cpu().numpy(), words)
+    assert m.last_kernel() == before                                            # nothing was launched
+    with pytest.raises(qpsk_amd.QpskError):
+        m.rs_encode(np.zeros((2, 200), np.uint8), 64)
+    m.sync()                                                                    # no call raised the context's status word
+    got = decode(m, c["words"], nroots, c["flags"])
+    assert_rows(got, c["erased"], c["names"], "after the refusals")
+    assert (c["erased"][1][:, 0] == -1).any()                                   # ... and failed rows do not raise it either
+    m.sync()
+    m.close()
+
+
+# ------------------------------------------------------------------------------------------ 6. the link of the CPU test, on the device
+def test_the_cpu_link_on_the_device_with_the_deframer_s_bytes_decoded_where_they_lie():
+    """Modem.rs_encode -> Modem.frame -> the CPU test's inverted run -> Modem.deframe_coded, then qpsk_rs_decode_batch straight on the
+    deframer's bytes (64 streams x 1 packet x 62 bytes) through in_pitch = nbytes + 2: crc_ok and the decoded data equal the CPU link
+    test's packet for packet"""
+    import torch
+    lk, r = LINK, link_result()
+    P, n, k = lk["packets"], lk["n"], lk["k"]
+    m = modem()
+    words = m.rs_encode(r["data"], n - k)
+    assert np.array_equal(words.cpu().numpy(), r["words"])
+    o = m.frame(words.contiguous(), r["sync"], coded=True, puncture=lk["rate"], per_row=1, lead=lk["lead"], gap=lk["gap"])
+    rows = o["dibits"].cpu().numpy()
+    assert np.array_equal(rows, r["rows"])
+    hit = rows.copy()
+    b0 = lk["lead"] + lk["nsync"] + lk["at"]
+    hit[:, b0:b0 + lk["run"]] ^= 3
+    assert np.array_equal(hit, r["hit"])
+    z = np.stack([dibits_to_costas(row, amp=lk["amp"]) for row in hit])
+    m.deframer_reset_coded(P, r["sync"], n, lk["min_score"], max_packets=1, puncture=NAMED[lk["rate"]])
+    gain = torch.full((P,), float(np.float32(64.0 / lk["amp"])), dtype=torch.float32, device="cuda")
+    d = m.deframe_coded(torch.from_numpy(z).cuda(), gain)
+    assert np.all(d["count"].cpu().numpy() == 1)
+    assert np.array_equal(d["crc_ok"].cpu().numpy()[:, 0] != 0, r["crc_ok"]) and not r["crc_ok"].any()
+    before = d["bytes"].cpu().numpy()
+    assert np.array_equal(before[:, 0], r["bytes"])
+    out = torch.full((P * n + GUARD,), OUT_FILL, dtype=torch.uint8, device="cuda")
+    info = torch.full((P * 4 + GUARD,), INFO_FILL, dtype=torch.int32, device="cuda")
+    m._check(m.L.qpsk_rs_decode_batch(m.h, ptr(d["bytes"]), n + 2, P, n, n - k, None, ptr(out), 0, ptr(info)))
+    m.sync()
+    want_out, want_info = rs_decode_ref(r["bytes"][:, :n], n - k)
+    ho, hi = out.cpu().numpy(), info.cpu().numpy()
+    assert np.all(ho[P * n:] == OUT_FILL) and np.all(hi[P * 4:] == INFO_FILL)
+    assert np.array_equal(ho[:P * n].reshape(P, n), want_out) and np.array_equal(hi[:P * 4].reshape(P, 4), want_info)
+    assert np.array_equal(ho[:P * n].reshape(P, n)[:, :k], r["data"])
+    assert np.array_equal(d["bytes"].cpu().numpy(), before)                     # the deframer's output was only read
+    # and in place, the CRC bytes between the codewords untouched
+    m._check(m.L.qpsk_rs_decode_batch(m.h, ptr(d["bytes"]), n + 2, P, n, n - k, None, ptr(d["bytes"]), n + 2, None))
+    m.sync()
+    after = d["bytes"].cpu().numpy()[:, 0]
+    assert np.array_equal(after[:, :n], want_out) and np.array_equal(after[:, n:], before[:, 0, n:])
+    m.close()
