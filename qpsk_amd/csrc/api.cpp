@@ -180,11 +180,8 @@ struct qpsk_ctx {
      * dibits [nsteps], then the CRC advance factors x^(8 m), m < nbytes, at DFC_ADV_OFFSET.  One deframer per context, in one mode */
     bool df_coded = false;
     int df_mode = 0, df_nsteps = 0;      /* df_nsteps: the trellis steps of a packet, 8 (nbytes + 2) + 6 */
-    int df_nbody = 0;             /* Nc: a body's dibits on air (df_nsteps; ntx(df_nsteps) after qpsk_deframer_reset_coded_punct) */
-    bool df_punct = false;        /* reset by qpsk_deframer_reset_coded_punct: the decode takes the punctured kernels, whatever the pattern */
-    Puncture df_pattern = {1, 1u, 1u, 2};
-    bool df_ilv = false;          /* reset by qpsk_deframer_reset_coded_ilv: the decode takes the interleaved kernels, whatever the stride */
-    Interleave df_ilv_stride = {2u, 1u, 1u};
+    int df_nbody = 0;             /* Nc: a body's dibits on air, coded_ndibits(df_layout, df_nsteps) */
+    CodedLayout df_layout;        /* the body's layout; its kind is the reset's (qpsk_deframer_reset_coded / _punct / _ilv), whatever the pattern and the stride */
     float df_scale = 0.f;
     unsigned df_crc_init = 0;
     DevBuf dfstage;               /* the soft rows of the packets a coded push completes, between the hunt and the decode */
@@ -440,8 +437,7 @@ static void free_deframer(qpsk_ctx *c)
     c->df_state = c->df_tables = nullptr;
     c->df_ready = false;
     c->df_coded = false;
-    c->df_punct = false;
-    c->df_ilv = false;
+    c->df_layout = CodedLayout{};
     c->df_nstreams = 0;
 }
 
@@ -1372,20 +1368,6 @@ int qpsk_soft_batch(qpsk_ctx *c, const float *d_costas, long long row_pitch, int
     return QPSK_OK;
 }
 
-/* the K = 7, rate-1/2 convolutional code (viterbi.hip; definition in include/qpsk_hip.h) */
-int qpsk_conv_encode_batch(qpsk_ctx *c, const uint8_t *d_bits, int nrows, int nbits, int flags, uint8_t *d_dibits)
-{
-    if (!c || !d_bits || !d_dibits) return fail(QPSK_ERR_ARG, "qpsk_conv_encode_batch: null argument");
-    if (flags & ~QPSK_CONV_TAIL) return fail(QPSK_ERR_ARG, "qpsk_conv_encode_batch: unknown flags 0x%x", flags);
-    const int tail = (flags & QPSK_CONV_TAIL) ? 6 : 0;
-    if (nrows <= 0 || nbits <= 0 || nbits > VITERBI_MAX_STEPS - tail)
-        return fail(QPSK_ERR_ARG, "qpsk_conv_encode_batch: nrows = %d, nbits = %d (1..%d)", nrows, nbits, VITERBI_MAX_STEPS - tail);
-    if (bind(c)) return QPSK_ERR_HIP;
-    KERNEL_TRY(launch_conv_encode(d_bits, nrows, nbits, nbits + tail, d_dibits, c->stream));
-    c->last_kernel = "conv_encode_kernel";
-    return QPSK_OK;
-}
-
 /* PUNCTURING (include/qpsk_hip.h): the pattern of a call, checked; who = the entry point's name */
 static int punct_make(const char *who, int period, uint32_t keep0, uint32_t keep1, Puncture *p)
 {
@@ -1394,31 +1376,6 @@ static int punct_make(const char *who, int period, uint32_t keep0, uint32_t keep
     if ((keep0 | keep1) & above) return fail(QPSK_ERR_ARG, "%s: keep0 = 0x%x / keep1 = 0x%x has a bit at or above period %d", who, keep0, keep1, period);
     if (!(keep0 | keep1)) return fail(QPSK_ERR_ARG, "%s: keep0 and keep1 are both 0: nothing would be sent", who);
     *p = Puncture{period, keep0, keep1, __builtin_popcount(keep0) + __builtin_popcount(keep1)};
-    return QPSK_OK;
-}
-
-int qpsk_punct_ntx(int nsteps, int period, uint32_t keep0, uint32_t keep1)
-{
-    Puncture p;
-    if (int rc = punct_make("qpsk_punct_ntx", period, keep0, keep1, &p)) return rc;
-    if (nsteps < 1 || nsteps > VITERBI_MAX_STEPS) return fail(QPSK_ERR_ARG, "qpsk_punct_ntx: nsteps = %d (1..%d)", nsteps, VITERBI_MAX_STEPS);
-    return (int)((punct_nsent(p, nsteps) + 1) / 2);
-}
-
-int qpsk_conv_encode_punct_batch(qpsk_ctx *c, const uint8_t *d_bits, int nrows, int nbits, int flags, int period, uint32_t keep0, uint32_t keep1,
-                                 uint8_t *d_dibits)
-{
-    if (!c || !d_bits || !d_dibits) return fail(QPSK_ERR_ARG, "qpsk_conv_encode_punct_batch: null argument");
-    if (flags & ~QPSK_CONV_TAIL) return fail(QPSK_ERR_ARG, "qpsk_conv_encode_punct_batch: unknown flags 0x%x", flags);
-    const int tail = (flags & QPSK_CONV_TAIL) ? 6 : 0;
-    if (nrows <= 0 || nbits <= 0 || nbits > VITERBI_MAX_STEPS - tail)
-        return fail(QPSK_ERR_ARG, "qpsk_conv_encode_punct_batch: nrows = %d, nbits = %d (1..%d)", nrows, nbits, VITERBI_MAX_STEPS - tail);
-    Puncture p;
-    if (int rc = punct_make("qpsk_conv_encode_punct_batch", period, keep0, keep1, &p)) return rc;
-    if (bind(c)) return QPSK_ERR_HIP;
-    if (punct_nsent(p, nbits + tail) == 0) return QPSK_OK;      /* every step of so short a row is deleted: nothing is sent */
-    KERNEL_TRY(launch_conv_encode_punct(d_bits, nrows, nbits, nbits + tail, p, d_dibits, c->stream));
-    c->last_kernel = "conv_encode_punct_kernel";
     return QPSK_OK;
 }
 
@@ -1433,6 +1390,47 @@ static int ilv_make(const char *who, long long ntx, int stride, Interleave *v)
     return QPSK_OK;
 }
 
+/* a pattern as the entry points take it */
+struct Pattern {
+    int period;
+    uint32_t keep0, keep1;
+};
+
+/* The layout of a call's rows (kernels.h, CodedLayout) is made layer by layer, each layer checked as it is added, and the kind follows the
+ * arguments the entry point has, never their values.  An entry point takes the two steps where its own checks have always had them: the
+ * pattern first, the stride once nsteps is known to be in range.  NULL adds nothing.
+ * layout_add_pattern: a plain *l becomes punctured */
+static int layout_add_pattern(const char *who, const Pattern *pattern, CodedLayout *l)
+{
+    if (!pattern) return QPSK_OK;
+    if (int rc = punct_make(who, pattern->period, pattern->keep0, pattern->keep1, &l->punct)) return rc;
+    l->kind = CODED_PUNCT;
+    return QPSK_OK;
+}
+/* layout_add_stride: *l becomes interleaved over the ntx dibits its nsteps steps have on air */
+static int layout_add_stride(const char *who, int nsteps, const int *stride, CodedLayout *l)
+{
+    if (!stride) return QPSK_OK;
+    if (int rc = ilv_make(who, coded_ndibits(*l, nsteps), *stride, &l->ilv)) return rc;
+    l->kind = CODED_ILV;
+    return QPSK_OK;
+}
+/* both at once, where nothing lies between them */
+static int coded_layout_make(const char *who, int nsteps, const Pattern *pattern, const int *stride, CodedLayout *l)
+{
+    if (int rc = layout_add_pattern(who, pattern, l)) return rc;
+    return layout_add_stride(who, nsteps, stride, l);
+}
+
+int qpsk_punct_ntx(int nsteps, int period, uint32_t keep0, uint32_t keep1)
+{
+    const Pattern pattern = {period, keep0, keep1};
+    CodedLayout l;
+    if (int rc = layout_add_pattern("qpsk_punct_ntx", &pattern, &l)) return rc;
+    if (nsteps < 1 || nsteps > VITERBI_MAX_STEPS) return fail(QPSK_ERR_ARG, "qpsk_punct_ntx: nsteps = %d (1..%d)", nsteps, VITERBI_MAX_STEPS);
+    return (int)coded_ndibits(l, nsteps);
+}
+
 int qpsk_ilv_stride(int nbits, int want)
 {
     if (nbits < 2 || want < 1) return fail(QPSK_ERR_ARG, "qpsk_ilv_stride: nbits = %d (>= 2), want = %d (>= 1)", nbits, want);
@@ -1441,22 +1439,43 @@ int qpsk_ilv_stride(int nbits, int want)
     return s;
 }
 
+/* the K = 7, rate-1/2 convolutional code (viterbi.hip; definition in include/qpsk_hip.h).  The three encoders: who = the entry point's name, the
+ * layout from what it takes.  A punctured row of which nothing is sent is no launch; behind a stride coded_layout_make has refused it */
+static int conv_encode_impl(qpsk_ctx *c, const char *who, const uint8_t *d_bits, int nrows, int nbits, int flags, const Pattern *pattern,
+                            const int *stride, uint8_t *d_dibits)
+{
+    static const char *const label[] = {"conv_encode_kernel", "conv_encode_punct_kernel", "conv_encode_ilv_kernel"};
+    if (!c || !d_bits || !d_dibits) return fail(QPSK_ERR_ARG, "%s: null argument", who);
+    if (flags & ~QPSK_CONV_TAIL) return fail(QPSK_ERR_ARG, "%s: unknown flags 0x%x", who, flags);
+    const int tail = (flags & QPSK_CONV_TAIL) ? 6 : 0;
+    if (nrows <= 0 || nbits <= 0 || nbits > VITERBI_MAX_STEPS - tail)
+        return fail(QPSK_ERR_ARG, "%s: nrows = %d, nbits = %d (1..%d)", who, nrows, nbits, VITERBI_MAX_STEPS - tail);
+    CodedLayout l;
+    if (int rc = coded_layout_make(who, nbits + tail, pattern, stride, &l)) return rc;
+    if (bind(c)) return QPSK_ERR_HIP;
+    if (coded_nsent(l, nbits + tail) == 0) return QPSK_OK;      /* every step of so short a row is deleted: nothing is sent */
+    KERNEL_TRY(launch_conv_encode(d_bits, nrows, nbits, nbits + tail, l, d_dibits, c->stream));
+    c->last_kernel = label[l.kind];
+    return QPSK_OK;
+}
+
+int qpsk_conv_encode_batch(qpsk_ctx *c, const uint8_t *d_bits, int nrows, int nbits, int flags, uint8_t *d_dibits)
+{
+    return conv_encode_impl(c, "qpsk_conv_encode_batch", d_bits, nrows, nbits, flags, nullptr, nullptr, d_dibits);
+}
+
+int qpsk_conv_encode_punct_batch(qpsk_ctx *c, const uint8_t *d_bits, int nrows, int nbits, int flags, int period, uint32_t keep0, uint32_t keep1,
+                                 uint8_t *d_dibits)
+{
+    const Pattern pattern = {period, keep0, keep1};
+    return conv_encode_impl(c, "qpsk_conv_encode_punct_batch", d_bits, nrows, nbits, flags, &pattern, nullptr, d_dibits);
+}
+
 int qpsk_conv_encode_ilv_batch(qpsk_ctx *c, const uint8_t *d_bits, int nrows, int nbits, int flags, int period, uint32_t keep0, uint32_t keep1,
                                int stride, uint8_t *d_dibits)
 {
-    if (!c || !d_bits || !d_dibits) return fail(QPSK_ERR_ARG, "qpsk_conv_encode_ilv_batch: null argument");
-    if (flags & ~QPSK_CONV_TAIL) return fail(QPSK_ERR_ARG, "qpsk_conv_encode_ilv_batch: unknown flags 0x%x", flags);
-    const int tail = (flags & QPSK_CONV_TAIL) ? 6 : 0;
-    if (nrows <= 0 || nbits <= 0 || nbits > VITERBI_MAX_STEPS - tail)
-        return fail(QPSK_ERR_ARG, "qpsk_conv_encode_ilv_batch: nrows = %d, nbits = %d (1..%d)", nrows, nbits, VITERBI_MAX_STEPS - tail);
-    Puncture p;
-    if (int rc = punct_make("qpsk_conv_encode_ilv_batch", period, keep0, keep1, &p)) return rc;
-    Interleave v;
-    if (int rc = ilv_make("qpsk_conv_encode_ilv_batch", (punct_nsent(p, nbits + tail) + 1) / 2, stride, &v)) return rc;
-    if (bind(c)) return QPSK_ERR_HIP;
-    KERNEL_TRY(launch_conv_encode_ilv(d_bits, nrows, nbits, nbits + tail, p, v, d_dibits, c->stream));
-    c->last_kernel = "conv_encode_ilv_kernel";
-    return QPSK_OK;
+    const Pattern pattern = {period, keep0, keep1};
+    return conv_encode_impl(c, "qpsk_conv_encode_ilv_batch", d_bits, nrows, nbits, flags, &pattern, &stride, d_dibits);
 }
 
 /* Where the decision words (8 bytes per step) wait for the trace-back: in LDS when a row's fit the launch limit and -- the library's own
@@ -1464,23 +1483,39 @@ int qpsk_conv_encode_ilv_batch(qpsk_ctx *c, const uint8_t *d_bits, int nrows, in
  * workgroups; otherwise in the context's scratch buffer, rows in chunks of at most VITERBI_SCRATCH_MAX bytes of it */
 static const size_t VITERBI_SCRATCH_MAX = (size_t)1 << 30;
 
-/* rows per launch: what VITERBI_SCRATCH_MAX allows (one row at least); on the scratch route (lds false) fewer where
- * QPSK_VITERBI_CHUNK_ROWS says so -- the key can only lower the cap, so the scratch buffer never grows by it */
-static size_t viterbi_chunk_rows(const qpsk_ctx *c, size_t rows, size_t per_row, bool lds)
+/* the rule for `rows` rows of nsteps steps, whatever their layout: per_row = the decision words' bytes; chunk_rows = rows per launch, what
+ * VITERBI_SCRATCH_MAX allows (one row at least), on the scratch route fewer where QPSK_VITERBI_CHUNK_ROWS says so -- the key can only lower
+ * the cap, so the scratch buffer never grows by it */
+struct ViterbiRoute {
+    size_t per_row;
+    bool lds;
+    size_t chunk_rows;
+};
+static ViterbiRoute viterbi_route(const qpsk_ctx *c, size_t rows, int nsteps)
 {
+    const size_t per_row = viterbi_scratch_bytes_per_row(nsteps);
+    const bool fits = per_row <= (size_t)VITERBI_LDS_MAX_BYTES;
+    const bool resident = fits && rows <= (size_t)c->ncu * (((size_t)160 << 10) / per_row);
+    const bool lds = fits && tuned(c->tune.viterbi_lds, resident ? 1 : 0) != 0;
     size_t cap = std::max<size_t>(1, VITERBI_SCRATCH_MAX / per_row);
     if (!lds && c->tune.viterbi_chunk_rows >= 1) cap = std::min<size_t>(cap, (size_t)c->tune.viterbi_chunk_rows);
-    return std::min<size_t>(rows, cap);
+    return ViterbiRoute{per_row, lds, std::min<size_t>(rows, cap)};
 }
 
-/* the decoders: who = the entry point's name; punct = NULL for rate 1/2, otherwise the checked pattern: the rows then hold the ntx
- * transmitted dibits of nsteps steps, and row_pitch and d_flip go by ntx.  The residency rule, the scratch and the chunks go by nsteps.
- * stride != NULL (with a pattern): qpsk_viterbi_ilv_batch; the stride is checked here, once nsteps is known to be in range */
-static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const Puncture *punct,
-                        const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info, const int *stride = nullptr)
+/* the three decoders: who = the entry point's name, the layout from what it takes.  Behind a pattern the rows hold the ntx transmitted dibits
+ * of nsteps steps, and row_pitch and d_flip go by ntx.  The pattern is checked first, as the entry points always have; the stride once nsteps
+ * is known to be in range */
+static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const Pattern *pattern,
+                        const int *stride, const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info)
 {
-    if (c) c->viterbi_launches = 0;      /* a refused call made none */
-    if (!c || !d_soft) return fail(QPSK_ERR_ARG, "%s: null context or input", who);
+    static const char *const label[][2] = {{"viterbi_kernel", "viterbi_lds_kernel"},
+                                           {"viterbi_punct_kernel", "viterbi_punct_lds_kernel"},
+                                           {"viterbi_ilv_kernel", "viterbi_ilv_lds_kernel"}};
+    if (!c) return fail(QPSK_ERR_ARG, "%s: null context or input", who);
+    c->viterbi_launches = 0;      /* a refused call made none */
+    CodedLayout l;
+    if (int rc = layout_add_pattern(who, pattern, &l)) return rc;
+    if (!d_soft) return fail(QPSK_ERR_ARG, "%s: null context or input", who);
     if (!d_bits && !d_info) return fail(QPSK_ERR_ARG, "%s: every output is NULL", who);
     if (nrows <= 0 || nsteps <= 0 || nsteps > VITERBI_MAX_STEPS)
         return fail(QPSK_ERR_ARG, "%s: nrows = %d, nsteps = %d (1..%d)", who, nrows, nsteps, VITERBI_MAX_STEPS);
@@ -1490,70 +1525,52 @@ static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long
     const int known = QPSK_VITERBI_OPEN_START | QPSK_VITERBI_OPEN_END;
 #endif
     if (flags & ~known) return fail(QPSK_ERR_ARG, "%s: unknown flags 0x%x", who, flags);
-    const long long nrow = punct ? (punct_nsent(*punct, nsteps) + 1) / 2 : nsteps;      /* the dibits of a row */
+    const long long nrow = coded_ndibits(l, nsteps);      /* the dibits of a row */
     if (row_pitch == 0) row_pitch = nrow;
-    if (row_pitch < nrow) return fail(QPSK_ERR_ARG, "%s: row_pitch = %lld (0, or >= %s %lld)", who, row_pitch, punct ? "ntx" : "nsteps", nrow);
+    if (row_pitch < nrow) return fail(QPSK_ERR_ARG, "%s: row_pitch = %lld (0, or >= %s %lld)", who, row_pitch, pattern ? "ntx" : "nsteps", nrow);
     if ((uintptr_t)d_soft % 2) return fail(QPSK_ERR_ARG, "%s: d_soft is not 2-byte aligned", who);
     if ((uintptr_t)d_info % 4) return fail(QPSK_ERR_ARG, "%s: d_info is not 4-byte aligned", who);
-    Interleave ilv = {2u, 1u, 1u};
-    if (stride)
-        if (int rc = ilv_make(who, nrow, *stride, &ilv)) return rc;
-    /* one launch of rows [r0, r0 + n) */
-    const auto launch = [&](size_t r0, int n, unsigned long long *scratch, bool lds, size_t nbytes) {
-        const int8_t *soft = d_soft + 2 * r0 * (size_t)row_pitch;
-        uint8_t *bits = d_bits ? d_bits + r0 * nbytes : nullptr;
-        int32_t *info = d_info ? d_info + 4 * r0 : nullptr;
-        return stride ? launch_viterbi_ilv(soft, (size_t)row_pitch, n, nsteps, *punct, ilv, d_flip, flags, scratch, lds, bits, info, c->stream)
-                      : launch_viterbi(soft, (size_t)row_pitch, n, nsteps, punct, d_flip, flags, scratch, lds, bits, info, c->stream);
-    };
+    if (int rc = layout_add_stride(who, nsteps, stride, &l)) return rc;
     static_assert(QPSK_VITERBI_OPEN_START == VITERBI_OPEN_START && QPSK_VITERBI_OPEN_END == VITERBI_OPEN_END, "the kernel takes the header's flag values");
     if (bind(c)) return QPSK_ERR_HIP;
-    const size_t per_row = viterbi_scratch_bytes_per_row(nsteps);
-    const bool fits = per_row <= (size_t)VITERBI_LDS_MAX_BYTES;
-    const bool resident = fits && (size_t)nrows <= (size_t)c->ncu * (((size_t)160 << 10) / per_row);
-    const bool lds = fits && tuned(c->tune.viterbi_lds, resident ? 1 : 0) != 0;
-    const size_t nbytes = ((size_t)nsteps + 7) / 8;
-    if (lds) {
-        KERNEL_TRY(launch(0, nrows, nullptr, true, nbytes));
+    const ViterbiRoute route = viterbi_route(c, (size_t)nrows, nsteps);
+    /* one launch of rows [r0, r0 + n) */
+    const auto launch = [&](size_t r0, int n, unsigned long long *scratch) {
+        return launch_viterbi(d_soft + 2 * r0 * (size_t)row_pitch, (size_t)row_pitch, n, nsteps, l, d_flip, flags, scratch, route.lds,
+                              d_bits ? d_bits + r0 * (((size_t)nsteps + 7) / 8) : nullptr, d_info ? d_info + 4 * r0 : nullptr, c->stream);
+    };
+    if (route.lds) {      /* nothing to chunk for: one launch */
+        KERNEL_TRY(launch(0, nrows, nullptr));
         c->viterbi_launches = 1;
-        c->last_kernel = stride ? "viterbi_ilv_lds_kernel" : punct ? "viterbi_punct_lds_kernel" : "viterbi_lds_kernel";
-        return QPSK_OK;
+    } else {
+        if (int rg = ensure(c, c->vitdec, route.chunk_rows * route.per_row)) return rg;
+        for (size_t r0 = 0; r0 < (size_t)nrows; r0 += route.chunk_rows) {      /* stream order: a chunk's trace-back is over before the next one's forward pass */
+            KERNEL_TRY(launch(r0, (int)std::min<size_t>(route.chunk_rows, (size_t)nrows - r0), (unsigned long long *)c->vitdec.p));
+            c->viterbi_launches++;
+        }
     }
-    const size_t chunk_rows = viterbi_chunk_rows(c, (size_t)nrows, per_row, false);
-    if (int rg = ensure(c, c->vitdec, chunk_rows * per_row)) return rg;
-    for (size_t r0 = 0; r0 < (size_t)nrows; r0 += chunk_rows) {      /* stream order: a chunk's trace-back is over before the next one's forward pass */
-        const int n = (int)std::min<size_t>(chunk_rows, (size_t)nrows - r0);
-        KERNEL_TRY(launch(r0, n, (unsigned long long *)c->vitdec.p, false, nbytes));
-        c->viterbi_launches++;
-    }
-    c->last_kernel = stride ? "viterbi_ilv_kernel" : punct ? "viterbi_punct_kernel" : "viterbi_kernel";
+    c->last_kernel = label[l.kind][route.lds];
     return QPSK_OK;
 }
 
 int qpsk_viterbi_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, const uint8_t *d_flip, int flags,
                        uint8_t *d_bits, int32_t *d_info)
 {
-    return viterbi_impl(c, "qpsk_viterbi_batch", d_soft, row_pitch, nrows, nsteps, nullptr, d_flip, flags, d_bits, d_info);
+    return viterbi_impl(c, "qpsk_viterbi_batch", d_soft, row_pitch, nrows, nsteps, nullptr, nullptr, d_flip, flags, d_bits, d_info);
 }
 
 int qpsk_viterbi_punct_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, int period, uint32_t keep0,
                              uint32_t keep1, const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info)
 {
-    Puncture p;
-    if (!c) return fail(QPSK_ERR_ARG, "qpsk_viterbi_punct_batch: null context or input");
-    c->viterbi_launches = 0;      /* a refused pattern made none */
-    if (int rc = punct_make("qpsk_viterbi_punct_batch", period, keep0, keep1, &p)) return rc;
-    return viterbi_impl(c, "qpsk_viterbi_punct_batch", d_soft, row_pitch, nrows, nsteps, &p, d_flip, flags, d_bits, d_info);
+    const Pattern pattern = {period, keep0, keep1};
+    return viterbi_impl(c, "qpsk_viterbi_punct_batch", d_soft, row_pitch, nrows, nsteps, &pattern, nullptr, d_flip, flags, d_bits, d_info);
 }
 
 int qpsk_viterbi_ilv_batch(qpsk_ctx *c, const int8_t *d_soft, long long row_pitch, int nrows, int nsteps, int period, uint32_t keep0,
                            uint32_t keep1, int stride, const uint8_t *d_flip, int flags, uint8_t *d_bits, int32_t *d_info)
 {
-    Puncture p;
-    if (!c) return fail(QPSK_ERR_ARG, "qpsk_viterbi_ilv_batch: null context or input");
-    c->viterbi_launches = 0;      /* a refused pattern made none */
-    if (int rc = punct_make("qpsk_viterbi_ilv_batch", period, keep0, keep1, &p)) return rc;
-    return viterbi_impl(c, "qpsk_viterbi_ilv_batch", d_soft, row_pitch, nrows, nsteps, &p, d_flip, flags, d_bits, d_info, &stride);
+    const Pattern pattern = {period, keep0, keep1};
+    return viterbi_impl(c, "qpsk_viterbi_ilv_batch", d_soft, row_pitch, nrows, nsteps, &pattern, &stride, d_flip, flags, d_bits, d_info);
 }
 
 int qpsk_costas_batch(qpsk_ctx *c, const float *d_symbols_in, int nframes, int nsym, float *d_state, uint8_t *d_sym,
@@ -2153,21 +2170,26 @@ int qpsk_scramble_batch(qpsk_ctx *c, uint8_t *d_sym, int npackets, int nsym)
 /* ---------------------------------------------------------------- deframer */
 static const int DF_ADV_OFFSET = 1040;      /* the tables: keystream bytes [0, nbytes + 2), then 64 uint16 */
 
-/* x^(8 k) mod the CRC-16 polynomial 0x1021: k zero bytes through crc16()'s register, starting from 1 */
-static uint16_t crc_advance(int k)
+/* r x^(8 k) mod the CRC-16 polynomial: k zero bytes through crc16()'s register, starting from r */
+static uint16_t crc_shift(unsigned r, int k)
 {
-    unsigned r = 1;
     for (int i = 0; i < 8 * k; i++) r = ((r << 1) ^ ((r & 0x8000u) ? 0x1021u : 0u)) & 0xFFFFu;
     return (uint16_t)r;
 }
+/* x^(8 k) */
+static uint16_t crc_advance(int k) { return crc_shift(1u, k); }
 
 static const int DFC_ADV_OFFSET = (DEFRAME_CODED_MAX_STEPS + 15) & ~15;      /* the coded mode's tables: keystream dibits [nsteps], then nbytes uint16 */
 
-/* both resets: who = the entry point's name; coded: the body is 8 (nbytes + 2) + 6 coded dibits held as int8 pairs */
+/* all four resets: who = the entry point's name; coded: the body is the coded dibits of 8 (nbytes + 2) + 6 trellis steps, held as int8 pairs, in the
+ * layout of what the entry point takes.  The pattern is checked first, as the entry points always have; the stride behind everything else */
 static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes,
-                               int max_packets, bool coded, int mode, float scale, const Puncture *punct = nullptr, const int *ilv_stride = nullptr)
+                               int max_packets, bool coded, int mode, float scale, const Pattern *pattern = nullptr, const int *stride = nullptr)
 {
-    if (!c || !h_sync) return fail(QPSK_ERR_ARG, "%s: null context or sync word", who);
+    if (!c) return fail(QPSK_ERR_ARG, "%s: null context or sync word", who);
+    CodedLayout l;
+    if (int rc = layout_add_pattern(who, pattern, &l)) return rc;
+    if (!h_sync) return fail(QPSK_ERR_ARG, "%s: null context or sync word", who);
     if (nstreams <= 0) return fail(QPSK_ERR_ARG, "%s: nstreams = %d", who, nstreams);
     if (nsync < 1 || nsync > SYNC_MAX_WORD) return fail(QPSK_ERR_ARG, "%s: nsync = %d outside 1..%d", who, nsync, SYNC_MAX_WORD);
     if (min_score < 1 || min_score > nsync) return fail(QPSK_ERR_ARG, "%s: min_score = %d outside 1..%d", who, min_score, nsync);
@@ -2181,36 +2203,27 @@ static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const
     const int nb = nbytes + 2, nsteps = 8 * nb + 6;
     /* dibits of a body: a punctured one is shorter than 8 nb + 6, so the pending buffer and the keystream table's bound hold as they are.
      * K >= 1 sent bit per period and nsteps > 32 >= period: at least one dibit */
-    const int N = !coded ? 4 * nb : punct ? (int)((punct_nsent(*punct, nsteps) + 1) / 2) : nsteps;
-    Interleave ilv = {2u, 1u, 1u};
-    if (ilv_stride)      /* a bad stride resets nothing */
-        if (int rc = ilv_make(who, N, *ilv_stride, &ilv)) return rc;
+    const int N = coded ? (int)coded_ndibits(l, nsteps) : 4 * nb;
+    if (int rc = layout_add_stride(who, nsteps, stride, &l)) return rc;      /* a bad stride resets nothing */
     if (bind(c)) return QPSK_ERR_HIP;
     /* refused until this call has completed */
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_deframer(c);
-    const size_t stride = (size_t)DEFRAME_PEND_OFFSET + (((size_t)N * (coded ? 2 : 1) + 15) & ~(size_t)15);
+    const size_t state_stride = (size_t)DEFRAME_PEND_OFFSET + (((size_t)N * (coded ? 2 : 1) + 15) & ~(size_t)15);
     const size_t tab_bytes = coded ? (size_t)DFC_ADV_OFFSET + 2 * (size_t)DEFRAME_MAX_BYTES : (size_t)DF_ADV_OFFSET + 128;
-    if (hipMalloc(&c->df_state, stride * (size_t)nstreams) != hipSuccess || hipMalloc(&c->df_tables, tab_bytes) != hipSuccess) {
+    if (hipMalloc(&c->df_state, state_stride * (size_t)nstreams) != hipSuccess || hipMalloc(&c->df_tables, tab_bytes) != hipSuccess) {
         free_deframer(c);
         (void)hipGetLastError();
-        return fail(QPSK_ERR_ALLOC, "%s: %d streams of %zu bytes of state", who, nstreams, stride);
+        return fail(QPSK_ERR_ALLOC, "%s: %d streams of %zu bytes of state", who, nstreams, state_stride);
     }
     std::vector<unsigned char> ks((size_t)N);
     qpsk_host_scramble_keystream(ks.data(), N);
     std::vector<uint8_t> tab(tab_bytes, 0);
     if (coded) {
         memcpy(tab.data(), ks.data(), (size_t)N);
-        unsigned adv = 1, init = 0xFFFFu;                               /* x^(8 m), and 0xFFFF x^(8 m), m = 0 .. nbytes */
-        for (int m = 0; m < nbytes; m++) {
-            const uint16_t v = (uint16_t)adv;
-            memcpy(&tab[DFC_ADV_OFFSET + 2 * m], &v, 2);
-            for (int i = 0; i < 8; i++) {
-                adv = ((adv << 1) ^ ((adv & 0x8000u) ? 0x1021u : 0u)) & 0xFFFFu;
-                init = ((init << 1) ^ ((init & 0x8000u) ? 0x1021u : 0u)) & 0xFFFFu;
-            }
-        }
-        c->df_crc_init = init;
+        uint16_t adv = 1;                                               /* x^(8 m), m = 0 .. nbytes - 1, a byte at a time */
+        for (int m = 0; m < nbytes; m++, adv = crc_shift(adv, 1)) memcpy(&tab[DFC_ADV_OFFSET + 2 * m], &adv, 2);
+        c->df_crc_init = crc_shift(0xFFFFu, nbytes);
     } else {
         for (int k = 0; k < nb; k++) tab[k] = (uint8_t)(ks[4 * k] | ks[4 * k + 1] << 2 | ks[4 * k + 2] << 4 | ks[4 * k + 3] << 6);
         const int per = (nb + 63) / 64;
@@ -2226,10 +2239,10 @@ static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const
         if (r & 1u) c->df_sync_lo[i >> 6] |= 1ull << (i & 63);
         if (r & 2u) c->df_sync_hi[i >> 6] |= 1ull << (i & 63);
     }
-    HIP_TRY(hipMemsetAsync(c->df_state, 0, stride * (size_t)nstreams, c->stream));
+    HIP_TRY(hipMemsetAsync(c->df_state, 0, state_stride * (size_t)nstreams, c->stream));
     HIP_TRY(hipMemcpyAsync(c->df_tables, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->df_stride = stride;
+    c->df_stride = state_stride;
     c->df_nstreams = nstreams;
     c->df_nsync = nsync;
     c->df_min_score = min_score;
@@ -2240,10 +2253,7 @@ static int deframer_reset_impl(qpsk_ctx *c, const char *who, int nstreams, const
     c->df_scale = scale;
     c->df_nsteps = coded ? nsteps : 0;
     c->df_nbody = coded ? N : 0;
-    c->df_punct = coded && punct;
-    c->df_pattern = punct ? *punct : Puncture{1, 1u, 1u, 2};
-    c->df_ilv = coded && punct && ilv_stride;
-    c->df_ilv_stride = ilv;
+    c->df_layout = l;
     c->df_ready = true;
     return QPSK_OK;
 }
@@ -2264,10 +2274,8 @@ int qpsk_deframer_reset_coded(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, 
 int qpsk_deframer_reset_coded_punct(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets,
                                     int mode, float scale, int period, uint32_t keep0, uint32_t keep1)
 {
-    Puncture p;
-    if (!c) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset_coded_punct: null context or sync word");
-    if (int rc = punct_make("qpsk_deframer_reset_coded_punct", period, keep0, keep1, &p)) return rc;
-    return deframer_reset_impl(c, "qpsk_deframer_reset_coded_punct", nstreams, h_sync, nsync, min_score, nbytes, max_packets, true, mode, scale, &p);
+    const Pattern pattern = {period, keep0, keep1};
+    return deframer_reset_impl(c, "qpsk_deframer_reset_coded_punct", nstreams, h_sync, nsync, min_score, nbytes, max_packets, true, mode, scale, &pattern);
 }
 
 /* the same behind a stride of INTERLEAVING as well: the body is as long, its bits lie at pi(k) on air, and qpsk_deframer_push_coded decodes
@@ -2275,11 +2283,9 @@ int qpsk_deframer_reset_coded_punct(qpsk_ctx *c, int nstreams, const uint8_t *h_
 int qpsk_deframer_reset_coded_ilv(qpsk_ctx *c, int nstreams, const uint8_t *h_sync, int nsync, int min_score, int nbytes, int max_packets,
                                   int mode, float scale, int period, uint32_t keep0, uint32_t keep1, int stride)
 {
-    Puncture p;
-    if (!c) return fail(QPSK_ERR_ARG, "qpsk_deframer_reset_coded_ilv: null context or sync word");
-    if (int rc = punct_make("qpsk_deframer_reset_coded_ilv", period, keep0, keep1, &p)) return rc;
-    return deframer_reset_impl(c, "qpsk_deframer_reset_coded_ilv", nstreams, h_sync, nsync, min_score, nbytes, max_packets, true, mode, scale, &p,
-                               &stride);
+    const Pattern pattern = {period, keep0, keep1};
+    return deframer_reset_impl(c, "qpsk_deframer_reset_coded_ilv", nstreams, h_sync, nsync, min_score, nbytes, max_packets, true, mode, scale,
+                               &pattern, &stride);
 }
 
 /* what both pushes do behind their own argument checks (who = the entry point's name): the state checks, no output (the caller's
@@ -2371,16 +2377,12 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
     const int per = std::min<long long>(c->df_max_packets, (long long)nsym / (c->df_nsync + Nc) + 1);
     const size_t rows = S * (size_t)per;
     const bool decode = d_bytes || d_crc_ok || d_info;
-    const size_t per_row = viterbi_scratch_bytes_per_row(c->df_nsteps);
-    const bool fits = per_row <= (size_t)VITERBI_LDS_MAX_BYTES;
-    const bool resident = fits && rows <= (size_t)c->ncu * (((size_t)160 << 10) / per_row);
-    const bool lds = fits && tuned(c->tune.viterbi_lds, resident ? 1 : 0) != 0;
-    const size_t chunk_rows = viterbi_chunk_rows(c, rows, per_row, lds);
+    const ViterbiRoute route = viterbi_route(c, rows, c->df_nsteps);
     if (int rg = ensure(c, c->dfstage, rows * 2 * (size_t)pitch)) return rg;
     if (!d_gain)
         if (int rg = ensure(c, c->softgain, sizeof(float) * S)) return rg;
-    if (decode && !lds)
-        if (int rg = ensure(c, c->vitdec, chunk_rows * per_row)) return rg;
+    if (decode && !route.lds)
+        if (int rg = ensure(c, c->vitdec, route.chunk_rows * route.per_row)) return rg;
 
     a.costas = reinterpret_cast<const float2 *>(d_costas);
     a.gain = d_gain ? d_gain : (const float *)c->softgain.p;
@@ -2405,53 +2407,48 @@ int qpsk_deframer_push_coded(qpsk_ctx *c, const float *d_costas, int nsym, const
     if (!d_gain)      /* nothing of the deframer's has run yet: a failure here leaves its state as it was */
         KERNEL_TRY(launch_soft_sums(d_costas, (size_t)nsym, c->df_nstreams, nsym, 0, c->df_mode, c->df_scale, (float *)c->softgain.p, nullptr, nullptr,
                                     c->d_status, c->stream));
-    const DeframeCodedBody body = {Nc, pitch, c->df_punct ? 1 : 0, c->df_pattern};
+    const DeframeCodedBody body = {Nc, pitch};      /* the decode's launch adds the layout */
     int e = launch_deframe_coded_hunt(a, body, c->stream);
-    for (size_t r0 = 0; e == 0 && decode && r0 < rows; r0 += chunk_rows) {      /* stream order: a chunk's trace-back is over before the next one's forward pass */
-        const int n = (int)std::min<size_t>(chunk_rows, rows - r0);
-        unsigned long long *scratch = lds ? nullptr : (unsigned long long *)c->vitdec.p;
-        e = c->df_ilv ? launch_deframe_coded_decode_ilv(a, body, c->df_ilv_stride, (int)r0, n, scratch, lds, c->stream)
-                      : launch_deframe_coded_decode(a, body, (int)r0, n, scratch, lds, c->stream);
+    for (size_t r0 = 0; e == 0 && decode && r0 < rows; r0 += route.chunk_rows) {      /* stream order: a chunk's trace-back is over before the next one's forward pass */
+        const int n = (int)std::min<size_t>(route.chunk_rows, rows - r0);
+        e = launch_deframe_coded_decode(a, body, c->df_layout, (int)r0, n, route.lds ? nullptr : (unsigned long long *)c->vitdec.p, route.lds, c->stream);
         if (e == 0) c->viterbi_launches++;
     }
     if (e != 0) {
         c->df_ready = false;
         return fail(QPSK_ERR_HIP, "qpsk_deframer_push_coded launch: %s", hipGetErrorString((hipError_t)e));
     }
-    c->last_kernel = !decode       ? "deframe_coded_hunt_kernel"
-                     : c->df_ilv   ? (lds ? "deframe_coded_hunt_kernel + deframe_coded_decode_ilv_kernel<lds>"
-                                          : "deframe_coded_hunt_kernel + deframe_coded_decode_ilv_kernel<global>")
-                     : c->df_punct ? (lds ? "deframe_coded_hunt_kernel + deframe_coded_decode_punct_kernel<lds>"
-                                          : "deframe_coded_hunt_kernel + deframe_coded_decode_punct_kernel<global>")
-                     : lds         ? "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<lds>"
-                                   : "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<global>";
+    static const char *const label[][2] = {
+        {"deframe_coded_hunt_kernel + deframe_coded_decode_kernel<global>", "deframe_coded_hunt_kernel + deframe_coded_decode_kernel<lds>"},
+        {"deframe_coded_hunt_kernel + deframe_coded_decode_punct_kernel<global>", "deframe_coded_hunt_kernel + deframe_coded_decode_punct_kernel<lds>"},
+        {"deframe_coded_hunt_kernel + deframe_coded_decode_ilv_kernel<global>", "deframe_coded_hunt_kernel + deframe_coded_decode_ilv_kernel<lds>"}};
+    c->last_kernel = decode ? label[c->df_layout.kind][route.lds] : "deframe_coded_hunt_kernel";
     return QPSK_OK;
 }
 
 
 /* ------------------------------------------------------------------ framer */
 /* FRAMER (include/qpsk_hip.h): the dibits of a body on air, B; who = the entry point's name.  The pattern is looked at only when coded */
-static int frame_body(const char *who, int nbytes, int coding, int period, uint32_t keep0, uint32_t keep1, Puncture *p, int *nbody)
+static int frame_body(const char *who, int nbytes, int coding, const Pattern &pattern, CodedLayout *l, int *nbody)
 {
     if (nbytes < 1 || nbytes > FRAME_MAX_BYTES) return fail(QPSK_ERR_ARG, "%s: nbytes = %d outside 1..%d", who, nbytes, FRAME_MAX_BYTES);
     if (coding != QPSK_FRAME_UNCODED && coding != QPSK_FRAME_CODED) return fail(QPSK_ERR_ARG, "%s: unknown coding %d", who, coding);
-    *p = Puncture{1, 1u, 1u, 2};
     if (coding == QPSK_FRAME_UNCODED) {
         *nbody = 4 * (nbytes + 2);
         return QPSK_OK;
     }
-    if (int rc = punct_make(who, period, keep0, keep1, p)) return rc;
+    if (int rc = layout_add_pattern(who, &pattern, l)) return rc;
     /* K >= 1 sent bit per period and 8 (nbytes + 2) + 6 > 32 >= period steps: at least one dibit */
-    *nbody = (int)((punct_nsent(*p, 8 * (nbytes + 2) + 6) + 1) / 2);
+    *nbody = (int)coded_ndibits(*l, 8 * (nbytes + 2) + 6);
     return QPSK_OK;
 }
 
 int qpsk_frame_len(int nsync, int nbytes, int coding, int period, uint32_t keep0, uint32_t keep1)
 {
     if (nsync < 1 || nsync > SYNC_MAX_WORD) return fail(QPSK_ERR_ARG, "qpsk_frame_len: nsync = %d outside 1..%d", nsync, SYNC_MAX_WORD);
-    Puncture p;
+    CodedLayout l;
     int nbody = 0;
-    if (int rc = frame_body("qpsk_frame_len", nbytes, coding, period, keep0, keep1, &p, &nbody)) return rc;
+    if (int rc = frame_body("qpsk_frame_len", nbytes, coding, Pattern{period, keep0, keep1}, &l, &nbody)) return rc;
     return nsync + nbody;
 }
 
@@ -2489,9 +2486,9 @@ static int frame_impl(qpsk_ctx *c, const char *who, const uint8_t *d_payload, lo
 {
     if (!c || !d_payload || !h_sync || !d_out) return fail(QPSK_ERR_ARG, "%s: null context, payload, sync word or output", who);
     if (nsync < 1 || nsync > SYNC_MAX_WORD) return fail(QPSK_ERR_ARG, "%s: nsync = %d outside 1..%d", who, nsync, SYNC_MAX_WORD);
-    Puncture p;
+    CodedLayout l;      /* coded: behind the pattern; the uncoded format has no layout */
     int nbody = 0;
-    if (int rc = frame_body(who, nbytes, coding, period, keep0, keep1, &p, &nbody)) return rc;
+    if (int rc = frame_body(who, nbytes, coding, Pattern{period, keep0, keep1}, &l, &nbody)) return rc;
     if (nrows < 1 || per_row < 1 || per_row > FRAME_MAX_PER_ROW || (long long)nrows * per_row > INT_MAX)
         return fail(QPSK_ERR_ARG, "%s: nrows = %d, per_row = %d (1..%d, nrows * per_row < 2^31)", who, nrows, per_row, FRAME_MAX_PER_ROW);
     if (payload_pitch != 0 && payload_pitch < nbytes)
@@ -2510,11 +2507,12 @@ static int frame_impl(qpsk_ctx *c, const char *who, const uint8_t *d_payload, lo
         if (((uintptr_t)d_crc & 1) || (r0 < i1 && i0 < r1) || (r0 < o1 && o0 < r1))
             return fail(QPSK_ERR_ARG, "%s: d_crc is not 2-byte aligned, or overlaps d_payload or d_out", who);
     }
-    /* the stride: 1 is no interleaving at all and takes frame_kernel; the uncoded format has none */
-    Interleave ilv = {2u, 1u, 1u};
+    /* the stride: the uncoded format has none; 1 is no interleaving at all and, here alone, takes the kernel of the layer below, frame_kernel<coded> */
     if (stride && coding == QPSK_FRAME_UNCODED && *stride != 1) return fail(QPSK_ERR_ARG, "%s: stride = %d with QPSK_FRAME_UNCODED (1 only)", who, *stride);
-    if (stride && coding == QPSK_FRAME_CODED)
-        if (int rc = ilv_make(who, nbody, *stride, &ilv)) return rc;
+    if (stride && coding == QPSK_FRAME_CODED) {
+        if (int rc = layout_add_stride(who, 8 * (nbytes + 2) + 6, stride, &l)) return rc;
+        if (l.ilv.s == 1) l.kind = CODED_PUNCT;
+    }
     if (bind(c)) return QPSK_ERR_HIP;
     if (int rc = frame_keystream(c, row_len > nbody ? row_len : nbody)) return rc;
     FrameArgs a{};
@@ -2533,24 +2531,15 @@ static int frame_impl(qpsk_ctx *c, const char *who, const uint8_t *d_payload, lo
     a.row_len = row_len;
     a.bytes_per_lane = (nbytes + 63) / 64;
     a.coded = coding == QPSK_FRAME_CODED;
-    a.nsent = a.coded ? (unsigned)punct_nsent(p, 8 * (nbytes + 2) + 6) : 0u;
-    a.punct = p;
     /* lane l's share of the CRC covers payload bytes [l c, min((l + 1) c, nbytes)): x^(8 k), k = the bytes behind them; then the init value's */
     uint16_t adv[65];
     for (int l = 0; l < 64; l++) {
         const int end = (l + 1) * a.bytes_per_lane < nbytes ? (l + 1) * a.bytes_per_lane : nbytes;
         adv[l] = crc_advance(nbytes - end);
     }
-    unsigned init = 0xFFFFu;
-    for (int i = 0; i < 8 * nbytes; i++) init = ((init << 1) ^ ((init & 0x8000u) ? 0x1021u : 0u)) & 0xFFFFu;
-    adv[64] = (uint16_t)init;
-    if (ilv.s != 1) {
-        KERNEL_TRY(launch_frame_ilv(a, ilv, h_sync, adv, c->stream));
-        c->last_kernel = "frame_kernel<coded,ilv>";
-        return QPSK_OK;
-    }
-    KERNEL_TRY(launch_frame(a, h_sync, adv, c->stream));
-    c->last_kernel = a.coded ? "frame_kernel<coded>" : "frame_kernel<uncoded>";
+    adv[64] = crc_shift(0xFFFFu, nbytes);
+    KERNEL_TRY(launch_frame(a, l, h_sync, adv, c->stream));
+    c->last_kernel = !a.coded ? "frame_kernel<uncoded>" : l.kind == CODED_ILV ? "frame_kernel<coded,ilv>" : "frame_kernel<coded>";
     return QPSK_OK;
 }
 

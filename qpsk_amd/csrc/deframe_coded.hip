@@ -18,12 +18,13 @@
  *                                 pass and trace-back with the keystream as flip and flags 0; the trace-back hands every 64 decoded bits
  *                                 to PacketSink: lanes 0..7 take one byte each, store it (bytes below nbytes + 2) and add its share of the
  *                                 CRC -- crc16() is linear, byte k of nbytes contributes crc_byte(b) x^(8 (nbytes - 1 - k)), the factors
- *                                 come from a table -- and a wave xor behind the trace-back sums the shares.  One template: <LDS, PUNCT>.
- *                                 PUNCT (qpsk_deframer_reset_coded_punct) takes viterbi_row.h's PunctLoader on the Nc staged dibits:
- *                                 nsteps = 8 (nbytes + 2) + 6 trellis steps, the keystream flips the transmitted dibits.
- *   deframe_coded_decode_ilv_kernel   the PUNCT instance behind viterbi_row.h's IlvLoader (qpsk_deframer_reset_coded_ilv): the staged row is
- *                                 the body as it was on air, and the loader reads sent bit k and its keystream bit at pi(k).  The hunt is
- *                                 the same: it only takes the body's length.
+ *                                 come from a table -- and a wave xor behind the trace-back sums the shares.  One template, <LDS, KIND>,
+ *                                 KIND = the kind of the deframer's CodedLayout (kernels.h), which picks viterbi_row.h's loader:
+ *                                 CODED_PUNCT (qpsk_deframer_reset_coded_punct) decodes the Nc staged dibits as nsteps = 8 (nbytes + 2) + 6
+ *                                 trellis steps, the keystream flipping the transmitted dibits; CODED_ILV (qpsk_deframer_reset_coded_ilv)
+ *                                 is the same behind the stride's position map: the staged row is the body as it was on air, and the
+ *                                 loader reads sent bit k and its keystream bit at pi(k).  The hunt is the same for all three: it only
+ *                                 takes the body's length.
  *
  * A staging row is addressed by (stream, slot), the packet's place in the outputs, so there is no list to append to and no atomic:
  * per_stream = min(max_packets, nsym / (nsync + Nc) + 1) bounds what one push can complete in a stream (packet ends lie nsync + Nc
@@ -124,13 +125,14 @@ struct PacketSink {
     }
 };
 
-/* one wave per staging row.  PUNCT = false, rate 1/2: the staged row is [nsteps] pairs (stage_pitch = nbody = nsteps, even); PUNCT = true,
- * behind a pattern: it holds the nbody transmitted dibits.  qpsk_ctx_last_kernel()'s label deframe_coded_decode_punct_kernel<x> names the
- * instance <x, PUNCT = true> of this template.  The body stays in the kernel: routed through a device function, all four instances come out
- * with two more scalar registers than DESIGN.md 4.4.7 / 4.4.8 record */
-template <bool LDS, bool PUNCT>
+/* one wave per staging row, behind the loader of the layout's kind (viterbi_row.h, coded_loader).  CODED_PLAIN, rate 1/2: the staged row is
+ * [nsteps] pairs (stage_pitch = nbody = nsteps, even); behind a pattern it holds the nbody transmitted dibits, as they were on air.
+ * qpsk_ctx_last_kernel()'s labels deframe_coded_decode_punct_kernel<x> and deframe_coded_decode_ilv_kernel<x> name the instances
+ * <x, CODED_PUNCT> and <x, CODED_ILV> of this template.  The body stays in the kernel: routed through a device function, the instances come
+ * out with two more scalar registers than DESIGN.md 4.4.7 / 4.4.8 record */
+template <bool LDS, int KIND>
 __global__ void __launch_bounds__(64)
-deframe_coded_decode_kernel(DeframeCodedArgs a, int row0, unsigned long long *scratch, DeframeCodedBody b)
+deframe_coded_decode_kernel(DeframeCodedArgs a, int row0, unsigned long long *scratch, DeframeCodedBody b, IlvMul pi)
 {
     const int lane = threadIdx.x;
     const int e = row0 + (int)blockIdx.x;
@@ -141,11 +143,12 @@ deframe_coded_decode_kernel(DeframeCodedArgs a, int row0, unsigned long long *sc
     PacketSink sink = {a.bytes ? a.bytes + r * (size_t)(a.nbytes + 2) : nullptr, a.crc_adv, a.nbytes, 0u};
     unsigned long long *gdec = LDS ? nullptr : scratch + (size_t)blockIdx.x * (nblk << 6);
     int32_t *info = a.info ? a.info + 4 * r : nullptr;
-    if constexpr (PUNCT) {
-        const PunctLoader ld = {a.stage + 2 * (size_t)e * (size_t)b.stage_pitch, a.flip, b.punct};
+    const int8_t *row = a.stage + 2 * (size_t)e * (size_t)(KIND == CODED_PLAIN ? a.nsteps : b.stage_pitch);
+    if constexpr (KIND == CODED_ILV) {      /* built here from the argument itself: through coded_loader pi's scalar loads move ahead of the return above */
+        const IlvLoader ld = {row, a.flip, b.punct, pi};
         viterbi_row<LDS>(ld, a.nsteps, 0, gdec, info, sink);
     } else {
-        const PairLoader ld = {a.stage + 2 * (size_t)e * (size_t)a.nsteps, a.flip};
+        const auto ld = coded_loader<KIND>(row, a.flip, b.punct, IlvMul{});      /* pi: CODED_ILV's, not looked at here */
         viterbi_row<LDS>(ld, a.nsteps, 0, gdec, info, sink);
     }
     unsigned share = sink.share;
@@ -154,26 +157,12 @@ deframe_coded_decode_kernel(DeframeCodedArgs a, int row0, unsigned long long *sc
     if (lane == 0 && a.crc_ok) a.crc_ok[r] = (uint8_t)(((share & 0xFFFFu) ^ a.crc_init) == (share >> 16));
 }
 
-/* deframe_coded_decode_kernel<LDS, true> with the stride: a kernel of its own, so that the four above keep their names and arguments */
-template <bool LDS>
-__global__ void __launch_bounds__(64)
-deframe_coded_decode_ilv_kernel(DeframeCodedArgs a, int row0, unsigned long long *scratch, DeframeCodedBody b, IlvMul pi)
+template <int KIND>
+static void launch_decode_kind(const DeframeCodedArgs &a, const DeframeCodedBody &b, const IlvMul &pi, int row0, int nrows, unsigned long long *scratch,
+                               bool lds, size_t bytes, hipStream_t s)
 {
-    const int lane = threadIdx.x;
-    const int e = row0 + (int)blockIdx.x;
-    const int stream = e / a.per_stream, slot = e - stream * a.per_stream;
-    if (slot >= a.count[stream]) return;
-    const size_t r = (size_t)stream * a.max_packets + slot;
-    const size_t nblk = ((size_t)a.nsteps + 63) >> 6;
-    PacketSink sink = {a.bytes ? a.bytes + r * (size_t)(a.nbytes + 2) : nullptr, a.crc_adv, a.nbytes, 0u};
-    unsigned long long *gdec = LDS ? nullptr : scratch + (size_t)blockIdx.x * (nblk << 6);
-    int32_t *info = a.info ? a.info + 4 * r : nullptr;
-    const IlvLoader ld = {a.stage + 2 * (size_t)e * (size_t)b.stage_pitch, a.flip, b.punct, pi};
-    viterbi_row<LDS>(ld, a.nsteps, 0, gdec, info, sink);
-    unsigned share = sink.share;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) share ^= (unsigned)__shfl_xor((int)share, o, 64);
-    if (lane == 0 && a.crc_ok) a.crc_ok[r] = (uint8_t)(((share & 0xFFFFu) ^ a.crc_init) == (share >> 16));
+    if (lds) hipLaunchKernelGGL((deframe_coded_decode_kernel<true, KIND>), dim3(nrows), dim3(64), bytes, s, a, row0, scratch, b, pi);
+    else hipLaunchKernelGGL((deframe_coded_decode_kernel<false, KIND>), dim3(nrows), dim3(64), 0, s, a, row0, scratch, b, pi);
 }
 
 } // namespace
@@ -188,39 +177,21 @@ int launch_deframe_coded_hunt(const DeframeCodedArgs &a, const DeframeCodedBody 
     return (int)hipGetLastError();
 }
 
-int launch_deframe_coded_decode(const DeframeCodedArgs &a, const DeframeCodedBody &b, int row0, int nrows, unsigned long long *scratch, bool lds,
-                                hipStream_t s)
+int launch_deframe_coded_decode(const DeframeCodedArgs &a, DeframeCodedBody b, const CodedLayout &l, int row0, int nrows, unsigned long long *scratch,
+                                bool lds, hipStream_t s)
 {
     if (row0 < 0 || nrows <= 0 || (long long)row0 + nrows > (long long)a.nstreams * a.per_stream || !a.stage || !a.count || !a.flip || !a.crc_adv)
         return (int)hipErrorInvalidValue;
-    if (b.punctured ? b.punct.period < 1 || b.punct.period > 32 || b.punct.K < 1 || 2LL * b.nbody < punct_nsent(b.punct, a.nsteps) || b.stage_pitch < b.nbody
-                    : b.nbody != a.nsteps || b.stage_pitch != a.nsteps)
+    if (!coded_layout_fits(l, a.nsteps) || b.nbody != coded_ndibits(l, a.nsteps) || (l.kind == CODED_PLAIN ? b.stage_pitch != b.nbody : b.stage_pitch < b.nbody))
         return (int)hipErrorInvalidValue;
     const size_t bytes = viterbi_scratch_bytes_per_row(a.nsteps);
     if (lds ? bytes > (size_t)VITERBI_LDS_MAX_BYTES : !scratch) return (int)hipErrorInvalidValue;
-    const dim3 grid(nrows), block(64);
-    if (b.punctured) {
-        if (lds) hipLaunchKernelGGL((deframe_coded_decode_kernel<true, true>), grid, block, bytes, s, a, row0, scratch, b);
-        else hipLaunchKernelGGL((deframe_coded_decode_kernel<false, true>), grid, block, 0, s, a, row0, scratch, b);
-    } else if (lds) hipLaunchKernelGGL((deframe_coded_decode_kernel<true, false>), grid, block, bytes, s, a, row0, scratch, b);
-    else hipLaunchKernelGGL((deframe_coded_decode_kernel<false, false>), grid, block, 0, s, a, row0, scratch, b);
-    return (int)hipGetLastError();
-}
-
-int launch_deframe_coded_decode_ilv(const DeframeCodedArgs &a, const DeframeCodedBody &b, const Interleave &ilv, int row0, int nrows,
-                                    unsigned long long *scratch, bool lds, hipStream_t s)
-{
-    if (row0 < 0 || nrows <= 0 || (long long)row0 + nrows > (long long)a.nstreams * a.per_stream || !a.stage || !a.count || !a.flip || !a.crc_adv)
-        return (int)hipErrorInvalidValue;
-    if (b.punct.period < 1 || b.punct.period > 32 || b.punct.K < 1 || 2LL * b.nbody != 2 * ((punct_nsent(b.punct, a.nsteps) + 1) / 2) ||
-        b.stage_pitch < b.nbody || ilv.n != 2u * (unsigned)b.nbody || ilv.s < 1 || ilv.s >= ilv.n)
-        return (int)hipErrorInvalidValue;
-    const size_t bytes = viterbi_scratch_bytes_per_row(a.nsteps);
-    if (lds ? bytes > (size_t)VITERBI_LDS_MAX_BYTES : !scratch) return (int)hipErrorInvalidValue;
-    const dim3 grid(nrows), block(64);
-    const IlvMul pi = ilv_mul(ilv.n, ilv.s);
-    if (lds) hipLaunchKernelGGL((deframe_coded_decode_ilv_kernel<true>), grid, block, bytes, s, a, row0, scratch, b, pi);
-    else hipLaunchKernelGGL((deframe_coded_decode_ilv_kernel<false>), grid, block, 0, s, a, row0, scratch, b, pi);
+    b.kind = l.kind;
+    b.punct = l.punct;
+    const IlvMul pi = ilv_mul(l.ilv.n, l.ilv.s);      /* CODED_ILV: sent bit k lies at pi.at(k); the other kinds do not read it */
+    if (l.kind == CODED_ILV) launch_decode_kind<CODED_ILV>(a, b, pi, row0, nrows, scratch, lds, bytes, s);
+    else if (l.kind == CODED_PUNCT) launch_decode_kind<CODED_PUNCT>(a, b, pi, row0, nrows, scratch, lds, bytes, s);
+    else launch_decode_kind<CODED_PLAIN>(a, b, pi, row0, nrows, scratch, lds, bytes, s);
     return (int)hipGetLastError();
 }
 

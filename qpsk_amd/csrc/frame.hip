@@ -17,16 +17,17 @@
  *           the gap otherwise), the packet, and for the row's last packet the columns behind it up to row_len -- the waves of a row
  *           tile it, nothing is written twice and nothing needs a second launch.  dibit_at(c) is the definition read column by column:
  *           idle ks[c]; the sync word from the kernel arguments; body dibit i = ks[i] ^ E[i].  E[i] uncoded: two bits of the packet.
- *           Coded: sent bits 2 i and 2 i + 1 map to (step t, generator) through punct_table.h's table -- conv_encode_punct_kernel's
- *           mapping -- and a coded bit is the parity of the encoder's register under the generator.  The register of step t is packet
+ *           Coded: punct_table.h's coded_dibit, the walk conv_encode_punct_kernel / conv_encode_ilv_kernel take from an on-air dibit to
+ *           its sent bits and their (step t, generator); here a coded bit comes from the staged packet.  The register of step t is packet
  *           bits t - 6 .. t, seven consecutive bits of the staged bytes: two LDS byte reads and a shift give them with bit t - 6 lowest,
  *           i.e. the register mirrored, so the generators are mirrored instead (171 -> 0x4F, 133 -> 0x6D; viterbi_row.h's re-encoder
  *           does the same).  The pad bit of an odd nsent stays 0 before the xor.
  *   stores  byte-wise up to the first 4-byte aligned ADDRESS of the range (d_out, row_len and the start column are arbitrary), then one
  *           dword of four dibits per lane, 256 contiguous bytes per wave instruction, then a byte-wise tail.
- * frame_ilv_kernel (qpsk_frame_batch_ilv, INTERLEAVING in include/qpsk_hip.h): the coded kernel with the gather turned round -- on-air bit
+ * frame_ilv_kernel (qpsk_frame_batch_ilv, INTERLEAVING in include/qpsk_hip.h): the coded kernel over the other position map -- on-air bit
  * 2 i + h of the body takes sent bit (2 i + h) s^-1 mod n, or 0 when that is at or beyond nsent (the pad's place) -- and everything else,
- * the stores included, as it is.  One body, frame_packet<CODED, ILV>, behind both kernel names.
+ * the stores included, as it is.  One body, frame_packet<CODED, ILV>, behind both kernel names, and one launch_frame that takes the body's
+ * CodedLayout (kernels.h) and picks the kernel by its kind.
  * No atomics, no scratch, no inter-wave traffic beyond the two barriers that order a wave's own LDS writes before its reads.
  */
 #include <hip/hip_runtime.h>
@@ -56,20 +57,15 @@ template <bool CODED, bool ILV>
 __device__ __forceinline__ unsigned body_dibit(const FrameArgs &a, const FrameTables &t, const IlvMul &inv, const uint8_t *slice, int i)
 {
     if (!CODED) return ((unsigned)slice[1 + (i >> 2)] >> (2 * (i & 3))) & 3u;
-    unsigned dibit = 0, at = ILV ? inv.at(2u * (unsigned)i) : 0u;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const unsigned k = ILV ? at : 2u * (unsigned)i + (unsigned)h;
-        if (ILV) at = inv.next(at);
-        if (k >= a.nsent) continue;
-        int step;
-        const unsigned j = punct_sent_step(k, a.punct.period, a.punct.K, t.punct, &step);
+    /* coded bit j of step `step` from the staged packet: the register mirrored, so the generators are */
+    const auto bit = [&](int step, unsigned j) {
         const int at = step + 2;                /* packet bit step - 6 in the slice: one zero byte in front */
         const unsigned two = (unsigned)slice[at >> 3] | (unsigned)slice[(at >> 3) + 1] << 8;
         const unsigned w = (two >> (at & 7)) & 127u;
-        dibit |= (unsigned)(__popc(w & (j ? 0x6Du : 0x4Fu)) & 1) << h;
-    }
-    return dibit;
+        return (unsigned)(__popc(w & (j ? 0x6Du : 0x4Fu)) & 1);
+    };
+    if (ILV) return coded_dibit((unsigned)i, a.nsent, a.punct, t.punct, inv, bit);
+    return coded_dibit((unsigned)i, a.nsent, a.punct, t.punct, FlatMap{}, bit);
 }
 
 template <bool CODED, bool ILV>
@@ -151,9 +147,9 @@ frame_ilv_kernel(FrameArgs a, FrameTables t, IlvMul inv)
 
 } // namespace
 
-/* ilv = NULL: frame_kernel<coded> / <uncoded> */
-static int launch_frame_impl(const FrameArgs &a, const Interleave *ilv, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s)
+int launch_frame(const FrameArgs &args, const CodedLayout &l, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s)
 {
+    FrameArgs a = args;
     if (!a.payload || !a.out || !a.ks || !h_sync || !h_crc_adv || a.npackets < 1 || a.per_row < 1 || a.nbytes < 1 || a.nbytes > FRAME_MAX_BYTES ||
         a.nsync < 1 || a.nsync > SYNC_MAX_WORD || a.nbody < 1 || a.lead < 0 || a.gap < 0 || a.bytes_per_lane * 64 < a.nbytes)
         return (int)hipErrorInvalidValue;
@@ -162,26 +158,19 @@ static int launch_frame_impl(const FrameArgs &a, const Interleave *ilv, const ui
     FrameTables t = {};
     for (int i = 0; i < a.nsync; i++) t.sync[i] = (uint8_t)(h_sync[i] & 3u);
     for (int i = 0; i < 65; i++) t.crc_adv[i] = h_crc_adv[i];
-    if (a.coded && !punct_table_make(a.punct, &t.punct)) return (int)hipErrorInvalidValue;
     const dim3 grid(((unsigned)a.npackets + FRAME_WAVES - 1) / FRAME_WAVES), block(64 * FRAME_WAVES);
-    if (ilv) {
-        if (!a.coded || ilv->n != 2u * (unsigned)a.nbody || a.nsent > ilv->n || ilv->sinv < 1 || ilv->sinv >= ilv->n) return (int)hipErrorInvalidValue;
-        hipLaunchKernelGGL(frame_ilv_kernel, grid, block, 0, s, a, t, ilv_mul(ilv->n, ilv->sinv));
-    } else if (a.coded)
-        hipLaunchKernelGGL(frame_kernel<true>, grid, block, 0, s, a, t);
-    else
+    if (!a.coded) {
         hipLaunchKernelGGL(frame_kernel<false>, grid, block, 0, s, a, t);
+        return (int)hipGetLastError();
+    }
+    const int nsteps = 8 * (a.nbytes + 2) + 6;
+    if (l.kind == CODED_PLAIN || !coded_layout_fits(l, nsteps) || a.nbody != coded_ndibits(l, nsteps) || !punct_table_make(l.punct, &t.punct))
+        return (int)hipErrorInvalidValue;
+    a.nsent = (unsigned)coded_nsent(l, nsteps);
+    a.punct = l.punct;
+    if (l.kind == CODED_ILV) hipLaunchKernelGGL(frame_ilv_kernel, grid, block, 0, s, a, t, ilv_mul(l.ilv.n, l.ilv.sinv));
+    else hipLaunchKernelGGL(frame_kernel<true>, grid, block, 0, s, a, t);
     return (int)hipGetLastError();
-}
-
-int launch_frame(const FrameArgs &a, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s)
-{
-    return launch_frame_impl(a, nullptr, h_sync, h_crc_adv, s);
-}
-
-int launch_frame_ilv(const FrameArgs &a, const Interleave &ilv, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s)
-{
-    return launch_frame_impl(a, &ilv, h_sync, h_crc_adv, s);
 }
 
 } // namespace qpsk

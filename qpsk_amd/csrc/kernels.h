@@ -289,21 +289,48 @@ struct IlvMul {
     __host__ __device__ __forceinline__ unsigned at(unsigned k) const { return ((k >> 9) * m9 + (k & 511u) * m) % n; }
     /* at(k + 1) from at(k): one conditional subtract */
     __host__ __device__ __forceinline__ unsigned next(unsigned a) const { return a + m >= n ? a + m - n : a + m; }
+    /* at(k + b) from at(k), b = 0 or 1 */
+    __host__ __device__ __forceinline__ unsigned ahead(unsigned a, unsigned b) const { return b ? next(a) : a; }
 };
 inline IlvMul ilv_mul(unsigned n, unsigned m) { return IlvMul{n, m, (unsigned)(((unsigned long long)m << 9) % n)}; }
-/* punct = NULL: rate 1/2, pitch in steps, flip [nsteps].  Otherwise the punctured kernels (viterbi_punct_kernel, viterbi_punct_lds_kernel):
- * pitch in transmitted dibits, flip [ntx]; the residency rule goes by nsteps either way */
-int launch_viterbi(const int8_t *soft, size_t pitch, int nrows, int nsteps, const Puncture *punct, const uint8_t *flip, int flags,
+/* the identity beside it: the position map of a row that is not interleaved.  ahead() is a sum here and a select there, which is why the maps
+ * say it themselves: written as a select over next() the punctured decoders cost scalar registers */
+struct FlatMap {
+    template <class Pos> __host__ __device__ __forceinline__ Pos at(Pos k) const { return k; }
+    template <class Pos> __host__ __device__ __forceinline__ Pos next(Pos a) const { return a + 1; }
+    template <class Pos> __host__ __device__ __forceinline__ Pos ahead(Pos a, unsigned b) const { return a + b; }
+};
+/* WHERE THE CODED BITS OF nsteps TRELLIS STEPS LIE IN THE TRANSMITTED ROW, said once for every stage of the coded path (the encoders, the
+ * decoders, the framer, the coded deframer).  Three kinds, each the one before behind one more layer:
+ *     CODED_PLAIN   rate 1/2: step t is dibit t of the row
+ *     CODED_PUNCT   behind a pattern: sent bit k is flat bit k of the row's ntx dibits
+ *     CODED_ILV     behind a pattern and a stride: sent bit k is flat bit pi(k)
+ * The kind is the ENTRY POINT's, not the values': the pattern (1, 1, 1) behind qpsk_viterbi_punct_batch is CODED_PUNCT and runs the punctured
+ * kernels.  Made and checked by the host (api.cpp, layout_add_pattern / layout_add_stride); the layers a kind does not have keep the values below */
+enum CodedKind { CODED_PLAIN = 0, CODED_PUNCT = 1, CODED_ILV = 2 };
+struct CodedLayout {
+    CodedKind kind = CODED_PLAIN;
+    Puncture punct = {1, 1u, 1u, 2};
+    Interleave ilv = {2u, 1u, 1u};
+};
+/* the sent bits of nsteps steps (2 nsteps at rate 1/2: the pattern a plain layout keeps says so), and their dibits on air, ntx */
+inline long long coded_nsent(const CodedLayout &l, int nsteps) { return punct_nsent(l.punct, nsteps); }
+inline long long coded_ndibits(const CodedLayout &l, int nsteps) { return (coded_nsent(l, nsteps) + 1) / 2; }
+/* what every launch below asks of a layout and its steps; that K counts the masks' bits, s is coprime to n and sinv its inverse is the host's */
+inline bool coded_layout_fits(const CodedLayout &l, int nsteps)
+{
+    if (nsteps < 1 || nsteps > VITERBI_MAX_STEPS || l.punct.period < 1 || l.punct.period > 32 || l.punct.K < 1 || l.punct.K > 64) return false;
+    if (l.kind != CODED_ILV) return true;
+    const long long ntx = coded_ndibits(l, nsteps);
+    return ntx >= 1 && l.ilv.n == 2u * (unsigned)ntx && l.ilv.s >= 1 && l.ilv.s < l.ilv.n && l.ilv.sinv >= 1 && l.ilv.sinv < l.ilv.n;
+}
+/* the six decode kernels, by the layout's kind and lds: viterbi_kernel / viterbi_punct_kernel / viterbi_ilv_kernel and their _lds_ twins.  pitch
+ * and flip go by the row's dibits on air (steps at rate 1/2, ntx otherwise); the residency rule goes by nsteps whatever the kind */
+int launch_viterbi(const int8_t *soft, size_t pitch, int nrows, int nsteps, const CodedLayout &layout, const uint8_t *flip, int flags,
                    unsigned long long *scratch, bool lds, uint8_t *bits, int32_t *info, hipStream_t s);
-/* viterbi_ilv_kernel / viterbi_ilv_lds_kernel: launch_viterbi behind a pattern and a stride (ilv.n = 2 ntx of the pattern) */
-int launch_viterbi_ilv(const int8_t *soft, size_t pitch, int nrows, int nsteps, const Puncture &punct, const Interleave &ilv, const uint8_t *flip,
-                       int flags, unsigned long long *scratch, bool lds, uint8_t *bits, int32_t *info, hipStream_t s);
-int launch_conv_encode(const uint8_t *bits, int nrows, int nbits, int nsteps, uint8_t *dibits, hipStream_t s);
-/* conv_encode_punct_kernel: one thread per transmitted dibit, dibits [nrows][ntx], ntx = ceil(punct_nsent / 2) >= 1 */
-int launch_conv_encode_punct(const uint8_t *bits, int nrows, int nbits, int nsteps, const Puncture &punct, uint8_t *dibits, hipStream_t s);
-/* conv_encode_ilv_kernel: the same thread per transmitted dibit; on-air bit a is sent bit a sinv mod n */
-int launch_conv_encode_ilv(const uint8_t *bits, int nrows, int nbits, int nsteps, const Puncture &punct, const Interleave &ilv, uint8_t *dibits,
-                           hipStream_t s);
+/* conv_encode_kernel (one thread per step), or one thread per transmitted dibit: conv_encode_punct_kernel / conv_encode_ilv_kernel, dibits
+ * [nrows][ntx], ntx >= 1 */
+int launch_conv_encode(const uint8_t *bits, int nrows, int nbits, int nsteps, const CodedLayout &layout, uint8_t *dibits, hipStream_t s);
 /* deframe.hip: qpsk_deframer_push.  Per stream, state_stride bytes of state: the header, the carried tail (the ring values of the last
  * min(len, nsync-1) dibits) at DEFRAME_TAIL_OFFSET, the pending packet's received payload (ring values) at DEFRAME_PEND_OFFSET */
 struct DeframeHeader {
@@ -370,22 +397,20 @@ struct DeframeCodedArgs : DeframeHuntArgs {
     int32_t *info;
     int *status;
 };
-/* what a puncturing pattern adds, a kernel argument of its own so that the rate-1/2 decode kernels keep their arguments as they were */
+/* the body on air and its layout as the decode kernels take it, a kernel argument of its own beside the hunt's */
 struct DeframeCodedBody {
-    int nbody;                    /* Nc, the dibits of a body on air: nsteps at rate 1/2, ntx(nsteps) of the pattern otherwise */
+    int nbody;                    /* Nc, the dibits of a body on air: coded_ndibits(layout, nsteps) */
     int stage_pitch;              /* dibits between staging rows: nbody rounded up to even, so that every row is 4-byte aligned */
-    int punctured;                /* qpsk_deframer_reset_coded_punct: the decode takes the punctured loader with punct */
-    Puncture punct;
+    int kind;                     /* PADDING that keeps punct where it was: its four words come with one aligned scalar load.  Holds the layout's
+                                   * CodedKind for a reader of a dump; no kernel reads it (they are instances by kind): do not branch on it */
+    Puncture punct;               /* CODED_PUNCT, CODED_ILV: the pattern */
+    /* the stride's IlvMul is the decode kernels' own trailing argument, not a field here: see deframe_coded_decode_kernel */
 };
 int launch_deframe_coded_hunt(const DeframeCodedArgs &a, const DeframeCodedBody &b, hipStream_t s);
-/* rows [row0, row0 + nrows) of the staging buffer; lds: the decision words in LDS (viterbi_scratch_bytes_per_row(nsteps) <=
- * VITERBI_LDS_MAX_BYTES), otherwise in scratch ([nrows] rows of that many bytes) */
-int launch_deframe_coded_decode(const DeframeCodedArgs &a, const DeframeCodedBody &b, int row0, int nrows, unsigned long long *scratch, bool lds,
-                                hipStream_t s);
-/* qpsk_deframer_reset_coded_ilv: the same rows through deframe_coded_decode_ilv_kernel<lds>; b as behind the pattern, ilv.n = 2 b.nbody.
- * The stride is an argument of these kernels alone, so that the others keep theirs as they were */
-int launch_deframe_coded_decode_ilv(const DeframeCodedArgs &a, const DeframeCodedBody &b, const Interleave &ilv, int row0, int nrows,
-                                    unsigned long long *scratch, bool lds, hipStream_t s);
+/* rows [row0, row0 + nrows) of the staging buffer through deframe_coded_decode_kernel<lds, kind>; lds: the decision words in LDS
+ * (viterbi_scratch_bytes_per_row(nsteps) <= VITERBI_LDS_MAX_BYTES), otherwise in scratch ([nrows] rows of that many bytes) */
+int launch_deframe_coded_decode(const DeframeCodedArgs &a, DeframeCodedBody b, const CodedLayout &layout, int row0, int nrows,
+                                unsigned long long *scratch, bool lds, hipStream_t s);
 /* frame.hip: qpsk_frame_batch (the definition: include/qpsk_hip.h, FRAMER).  One wave per packet; the caller has checked every bound */
 constexpr int FRAME_MAX_BYTES = DEFRAME_MAX_BYTES, FRAME_MAX_PER_ROW = 64, FRAME_MAX_ROW = DEFRAME_MAX_NSYM;
 struct FrameArgs {
@@ -398,15 +423,15 @@ struct FrameArgs {
     int nbody;                    /* B, the dibits of a body on air */
     int lead, gap, row_len;
     int bytes_per_lane;           /* ceil(nbytes / 64): the payload bytes one lane's CRC share covers */
-    int coded;                    /* frame_kernel<coded>: punct is the body's pattern and nsent its sent bits */
+    int coded;                    /* the body is convolutionally coded; nsent and punct are then the layout's, set by launch_frame */
     unsigned nsent;
     Puncture punct;
 };
 /* h_sync [nsync] dibits (taken & 3); h_crc_adv [65]: x^(8 k_l) mod the CRC-16 polynomial, k_l = the payload bytes behind lane l's chunk, then
  * the init value's share 0xFFFF x^(8 nbytes).  Both travel in the kernel arguments */
-int launch_frame(const FrameArgs &a, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s);
-/* qpsk_frame_batch_ilv with a stride other than 1: frame_ilv_kernel, a.coded set, ilv.n = 2 a.nbody */
-int launch_frame_ilv(const FrameArgs &a, const Interleave &ilv, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s);
+/* frame_kernel<uncoded> (a.coded = 0; the layout is not looked at), frame_kernel<coded> (CODED_PUNCT: the framer's coded body always lies behind a pattern,
+ * (1, 1, 1) included) or frame_ilv_kernel (CODED_ILV); a.nbody = coded_ndibits(layout, 8 (a.nbytes + 2) + 6) */
+int launch_frame(const FrameArgs &a, const CodedLayout &layout, const uint8_t *h_sync, const uint16_t *h_crc_adv, hipStream_t s);
 /* rs.hip: the Reed-Solomon outer code (the definition: include/qpsk_hip.h, REED-SOLOMON).  One wave per codeword; pitches in bytes, never 0
  * here; the caller has checked every bound and every overlap.  erase [nrows][n] or NULL; out or info may be NULL, not both */
 constexpr int RS_MAX_ROOTS = 64;

@@ -28,19 +28,20 @@
  *
  * conv_encode_kernel: one thread per coded dibit; a plain kernel so that a loopback stays on the device.
  *
- * PUNCTURED RATES (qpsk_viterbi_punct_batch, qpsk_conv_encode_punct_batch; PUNCTURING in include/qpsk_hip.h, restated by
- * tests/test_punct_cpu.py).  A punctured decode IS the decode of the zero-filled row, and a zero is an erasure the passes above need no
- * special case for, so viterbi_punct_kernel / viterbi_punct_lds_kernel are the same two kernels behind viterbi_row.h's PunctLoader: the
- * lane that loaded the pair of step 64 k + l now works out where the (up to) two sent bits of that step lie in the transmitted row -- one
- * division by the period and two popcounts per lane and 64 steps -- and loads them, and their flip bits, bytewise; unsent bits are 0.
- * That happens where the load sat, lane-parallel and a block ahead; the per-step chain is untouched.  conv_encode_punct_kernel: one
- * thread per transmitted dibit, its two sent bits mapped back to (step, generator) through a table of the period's K <= 64 sent bits.
- *
- * INTERLEAVING (qpsk_viterbi_ilv_batch, qpsk_conv_encode_ilv_batch; INTERLEAVING in include/qpsk_hip.h, restated by tests/test_ilv_cpu.py).
- * The coded bits of a row are spread over the row on air by pi(k) = k s mod n.  Both sides gather: viterbi_ilv_kernel /
- * viterbi_ilv_lds_kernel are the punctured kernels behind viterbi_row.h's IlvLoader, which reads sent bit k's soft value and flip bit at
- * pi(k); conv_encode_ilv_kernel is conv_encode_punct_kernel whose on-air bit a takes sent bit a s^-1 mod n.  No scatter, no atomics, no
- * pass of its own over memory, and nothing in the per-step chain.
+ * THE LAYERS.  Where the coded bits of a row lie on air is a CodedLayout (kernels.h): plain rate 1/2; behind a puncturing pattern
+ * (qpsk_*_punct_batch; PUNCTURING in include/qpsk_hip.h, restated by tests/test_punct_cpu.py); behind a pattern and an interleaver's stride
+ * (qpsk_*_ilv_batch; INTERLEAVING, tests/test_ilv_cpu.py).  Each is the one before behind one more map, and the code is written that way,
+ * as the numpy restatements are: one launch_viterbi and one launch_conv_encode take the layout, and its kind picks the kernel.
+ *   decode   A punctured decode IS the decode of the zero-filled row, and a zero is an erasure the passes above need no special case for, so
+ *            all six kernels are viterbi_batch_row behind the loader of their kind (viterbi_row.h, coded_loader).  Behind a pattern the lane
+ *            that loaded the pair of step 64 k + l works out where the (up to) two sent bits of that step lie in the transmitted row -- one
+ *            division by the period and two popcounts per lane and 64 steps -- and loads them, and their flip bits, bytewise; unsent bits
+ *            are 0.  Behind a stride as well, sent bit k and its flip bit are read at pi(k) = k s mod n: the same loader over another
+ *            position map.  That happens where the load sat, lane-parallel and a block ahead; the per-step chain is untouched.
+ *   encode   conv_encode_punct_kernel / conv_encode_ilv_kernel: one thread per transmitted dibit, punct_table.h's coded_dibit -- the dibit's
+ *            two sent bits (themselves, or sent bits a s^-1 mod n of on-air bits a) mapped back to (step, generator) through a table of the
+ *            period's K <= 64 sent bits -- over the same register-from-the-packed-row functor conv_encode_kernel uses.
+ * Both sides gather: no scatter, no atomics, no pass of its own over memory, and nothing in the per-step chain.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -61,197 +62,123 @@ struct VitArgs {
     unsigned long long *scratch;  /* [rows][nblk * 64] decision words (global route) */
     uint8_t *bits;
     int32_t *info;
-    Puncture punct;               /* the punctured kernels only */
+    Puncture punct;               /* the layout's pattern */
 };
 
-/* workgroup = wave = row blockIdx.x of the call (viterbi_row.h); PUNCT: the row is what was transmitted and PunctLoader finds the steps in it */
-template <bool LDS, bool PUNCT>
-__device__ __forceinline__ void viterbi_batch_row(const VitArgs &a)
+/* workgroup = wave = row blockIdx.x of the call (viterbi_row.h) behind the loader of the layout's kind; pi: the interleaved kernels' own argument */
+template <bool LDS, int KIND>
+__device__ __forceinline__ void viterbi_batch_row(const VitArgs &a, const IlvMul &pi)
 {
     const size_t row = blockIdx.x;
     const size_t nblk = ((size_t)a.nsteps + 63) >> 6;
     BitsSink sink = {a.bits ? a.bits + row * (((size_t)a.nsteps + 7) >> 3) : nullptr};
     unsigned long long *gdec = LDS ? nullptr : a.scratch + row * (nblk << 6);
     int32_t *info = a.info ? a.info + 4 * row : nullptr;
-    if (PUNCT) {
-        const PunctLoader ld = {a.soft + 2 * row * a.pitch, a.flip, a.punct};
-        viterbi_row<LDS>(ld, a.nsteps, a.flags, gdec, info, sink);
-    } else {
-        const PairLoader ld = {a.soft + 2 * row * a.pitch, a.flip};
-        viterbi_row<LDS>(ld, a.nsteps, a.flags, gdec, info, sink);
-    }
-}
-
-__global__ void __launch_bounds__(64) viterbi_kernel(VitArgs a) { viterbi_batch_row<false, false>(a); }
-__global__ void __launch_bounds__(64) viterbi_lds_kernel(VitArgs a) { viterbi_batch_row<true, false>(a); }
-__global__ void __launch_bounds__(64) viterbi_punct_kernel(VitArgs a) { viterbi_batch_row<false, true>(a); }
-__global__ void __launch_bounds__(64) viterbi_punct_lds_kernel(VitArgs a) { viterbi_batch_row<true, true>(a); }
-
-/* the same row behind IlvLoader; the stride is an argument of these two kernels alone */
-template <bool LDS>
-__device__ __forceinline__ void viterbi_ilv_row(const VitArgs &a, const IlvMul &pi)
-{
-    const size_t row = blockIdx.x;
-    const size_t nblk = ((size_t)a.nsteps + 63) >> 6;
-    BitsSink sink = {a.bits ? a.bits + row * (((size_t)a.nsteps + 7) >> 3) : nullptr};
-    unsigned long long *gdec = LDS ? nullptr : a.scratch + row * (nblk << 6);
-    int32_t *info = a.info ? a.info + 4 * row : nullptr;
-    const IlvLoader ld = {a.soft + 2 * row * a.pitch, a.flip, a.punct, pi};
+    const auto ld = coded_loader<KIND>(a.soft + 2 * row * a.pitch, a.flip, a.punct, pi);
     viterbi_row<LDS>(ld, a.nsteps, a.flags, gdec, info, sink);
 }
 
-__global__ void __launch_bounds__(64) viterbi_ilv_kernel(VitArgs a, IlvMul pi) { viterbi_ilv_row<false>(a, pi); }
-__global__ void __launch_bounds__(64) viterbi_ilv_lds_kernel(VitArgs a, IlvMul pi) { viterbi_ilv_row<true>(a, pi); }
+/* the six names stay one kernel each, so that a profile reads as the tables of DESIGN.md do.  IlvMul{} (n = 0) is a placeholder the plain and
+ * punctured loaders never look at (coded_loader): it must stay unused there */
+__global__ void __launch_bounds__(64) viterbi_kernel(VitArgs a) { viterbi_batch_row<false, CODED_PLAIN>(a, IlvMul{}); }
+__global__ void __launch_bounds__(64) viterbi_lds_kernel(VitArgs a) { viterbi_batch_row<true, CODED_PLAIN>(a, IlvMul{}); }
+__global__ void __launch_bounds__(64) viterbi_punct_kernel(VitArgs a) { viterbi_batch_row<false, CODED_PUNCT>(a, IlvMul{}); }
+__global__ void __launch_bounds__(64) viterbi_punct_lds_kernel(VitArgs a) { viterbi_batch_row<true, CODED_PUNCT>(a, IlvMul{}); }
+__global__ void __launch_bounds__(64) viterbi_ilv_kernel(VitArgs a, IlvMul pi) { viterbi_batch_row<false, CODED_ILV>(a, pi); }
+__global__ void __launch_bounds__(64) viterbi_ilv_lds_kernel(VitArgs a, IlvMul pi) { viterbi_batch_row<true, CODED_ILV>(a, pi); }
 
-/* one thread per coded dibit: register r of step t = bits t-6 .. t (bit t in bit 0), zeros before the row and in the tail */
+/* the encoder's register of step t from a row of packed bits: bits t-6 .. t (bit t in bit 0), zeros before the row and in the tail */
+struct RowRegister {
+    const uint8_t *__restrict__ src;
+    int nbits;
+    __device__ __forceinline__ unsigned operator()(int t) const
+    {
+        unsigned r = 0;
+#pragma unroll
+        for (int k = 0; k < 7; k++) {
+            const int p = t - k;
+            if (p >= 0 && p < nbits) r |= ((unsigned)(src[p >> 3] >> (p & 7)) & 1u) << k;
+        }
+        return r;
+    }
+};
+
+/* one thread per coded dibit */
 __global__ void __launch_bounds__(256)
 conv_encode_kernel(const uint8_t *__restrict__ in, size_t nrows, int nbits, int nsteps, uint8_t *__restrict__ out)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nrows * (size_t)nsteps) return;
     const size_t row = i / (size_t)nsteps;
-    const int t = (int)(i - row * (size_t)nsteps);
-    const uint8_t *src = in + row * (size_t)((nbits + 7) >> 3);
-    unsigned r = 0;
-#pragma unroll
-    for (int k = 0; k < 7; k++) {
-        const int p = t - k;
-        if (p >= 0 && p < nbits) r |= ((unsigned)(src[p >> 3] >> (p & 7)) & 1u) << k;
-    }
+    const RowRegister reg = {in + row * (size_t)((nbits + 7) >> 3), nbits};
+    const unsigned r = reg((int)(i - row * (size_t)nsteps));
     out[i] = (uint8_t)(parity(r & 0x79u) | (parity(r & 0x5Bu) << 1));
 }
 
-/* one thread per transmitted dibit: sent bits 2 d and 2 d + 1 of the row, each mapped back to (t, j) through the table (punct_table.h) and encoded as
- * conv_encode_kernel does; a sent bit at or beyond nsent -- the pad bit of an odd nsent -- is 0 */
-__global__ void __launch_bounds__(256)
-conv_encode_punct_kernel(const uint8_t *__restrict__ in, size_t nrows, int nbits, unsigned nsent, unsigned ntx, int period, int K, PunctTable tab,
-                         uint8_t *__restrict__ out)
+/* behind a pattern: one thread per transmitted dibit, punct_table.h's walk from the dibit to its (up to) two coded bits, each encoded as
+ * conv_encode_kernel does */
+struct EncodeArgs {
+    const uint8_t *in;
+    size_t nrows;
+    int nbits;
+    unsigned nsent, ntx;
+    Puncture punct;
+    PunctTable tab;
+    uint8_t *out;
+};
+
+template <class Map>
+__device__ __forceinline__ void conv_encode_sent(const EncodeArgs &a, const Map &map)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nrows * (size_t)ntx) return;
-    const size_t row = i / ntx;
-    const unsigned d = (unsigned)(i - row * ntx);
-    const uint8_t *src = in + row * (size_t)((nbits + 7) >> 3);
-    unsigned dibit = 0;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const unsigned k = 2 * d + h;
-        if (k >= nsent) continue;
-        int t;
-        const unsigned j = punct_sent_step(k, period, K, tab, &t);
-        unsigned r = 0;
-#pragma unroll
-        for (int b = 0; b < 7; b++) {
-            const int p = t - b;
-            if (p >= 0 && p < nbits) r |= ((unsigned)(src[p >> 3] >> (p & 7)) & 1u) << b;
-        }
-        dibit |= (unsigned)parity(r & (j ? 0x5Bu : 0x79u)) << h;
-    }
-    out[i] = (uint8_t)dibit;
+    if (i >= a.nrows * (size_t)a.ntx) return;
+    const size_t row = i / a.ntx;
+    const RowRegister reg = {a.in + row * (size_t)((a.nbits + 7) >> 3), a.nbits};
+    a.out[i] = (uint8_t)coded_dibit((unsigned)(i - row * a.ntx), a.nsent, a.punct, a.tab, map,
+                                    [&](int t, unsigned j) { return parity(reg(t) & (j ? 0x5Bu : 0x79u)); });
 }
 
-/* conv_encode_punct_kernel behind the permutation: on-air bits 2 d and 2 d + 1 take sent bits (2 d) s^-1 mod n and that + s^-1 (mod n); a sent
- * bit number at or beyond nsent is the pad of an odd nsent, 0 */
-__global__ void __launch_bounds__(256)
-conv_encode_ilv_kernel(const uint8_t *__restrict__ in, size_t nrows, int nbits, unsigned nsent, unsigned ntx, int period, int K, PunctTable tab,
-                       IlvMul inv, uint8_t *__restrict__ out)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nrows * (size_t)ntx) return;
-    const size_t row = i / ntx;
-    const unsigned d = (unsigned)(i - row * ntx);
-    const uint8_t *src = in + row * (size_t)((nbits + 7) >> 3);
-    unsigned dibit = 0, k = inv.at(2 * d);
-#pragma unroll
-    for (int h = 0; h < 2; h++, k = inv.next(k)) {
-        if (k >= nsent) continue;
-        int t;
-        const unsigned j = punct_sent_step(k, period, K, tab, &t);
-        unsigned r = 0;
-#pragma unroll
-        for (int b = 0; b < 7; b++) {
-            const int p = t - b;
-            if (p >= 0 && p < nbits) r |= ((unsigned)(src[p >> 3] >> (p & 7)) & 1u) << b;
-        }
-        dibit |= (unsigned)parity(r & (j ? 0x5Bu : 0x79u)) << h;
-    }
-    out[i] = (uint8_t)dibit;
-}
+__global__ void __launch_bounds__(256) conv_encode_punct_kernel(EncodeArgs a) { conv_encode_sent(a, FlatMap{}); }
+__global__ void __launch_bounds__(256) conv_encode_ilv_kernel(EncodeArgs a, IlvMul inv) { conv_encode_sent(a, inv); }
 
 } // namespace
 
 size_t viterbi_scratch_bytes_per_row(int nsteps) { return sizeof(unsigned long long) * (((size_t)nsteps + 63) & ~(size_t)63); }
 
-int launch_viterbi(const int8_t *soft, size_t pitch, int nrows, int nsteps, const Puncture *punct, const uint8_t *flip, int flags,
+int launch_viterbi(const int8_t *soft, size_t pitch, int nrows, int nsteps, const CodedLayout &l, const uint8_t *flip, int flags,
                    unsigned long long *scratch, bool lds, uint8_t *bits, int32_t *info, hipStream_t s)
 {
-    if (nrows <= 0 || nsteps <= 0 || nsteps > VITERBI_MAX_STEPS || !soft || (!bits && !info)) return (int)hipErrorInvalidValue;
-    if (punct && (punct->period < 1 || punct->period > 32 || punct->K < 1)) return (int)hipErrorInvalidValue;
+    if (nrows <= 0 || !soft || (!bits && !info) || !coded_layout_fits(l, nsteps)) return (int)hipErrorInvalidValue;
     const size_t bytes = viterbi_scratch_bytes_per_row(nsteps);
     if (lds ? bytes > (size_t)VITERBI_LDS_MAX_BYTES : !scratch) return (int)hipErrorInvalidValue;
-    const VitArgs a = {soft, pitch, nsteps, flags, flip, scratch, bits, info, punct ? *punct : Puncture{1, 1u, 1u, 2}};
-    if (lds) hipLaunchKernelGGL(punct ? viterbi_punct_lds_kernel : viterbi_lds_kernel, dim3(nrows), dim3(64), bytes, s, a);
-    else hipLaunchKernelGGL(punct ? viterbi_punct_kernel : viterbi_kernel, dim3(nrows), dim3(64), 0, s, a);
+    const VitArgs a = {soft, pitch, nsteps, flags, flip, scratch, bits, info, l.punct};
+    const dim3 grid(nrows), block(64);
+    const size_t shared = lds ? bytes : 0;
+    if (l.kind == CODED_ILV)
+        hipLaunchKernelGGL(lds ? viterbi_ilv_lds_kernel : viterbi_ilv_kernel, grid, block, shared, s, a, ilv_mul(l.ilv.n, l.ilv.s));
+    else if (l.kind == CODED_PUNCT)
+        hipLaunchKernelGGL(lds ? viterbi_punct_lds_kernel : viterbi_punct_kernel, grid, block, shared, s, a);
+    else
+        hipLaunchKernelGGL(lds ? viterbi_lds_kernel : viterbi_kernel, grid, block, shared, s, a);
     return (int)hipGetLastError();
 }
 
-/* n = 2 ntx of the pattern, 1 <= s < max(n, 2); that s is coprime to n and sinv its inverse is the caller's (api.cpp, ilv_make) */
-static bool ilv_fits(const Interleave &v, long long ntx)
+int launch_conv_encode(const uint8_t *bits, int nrows, int nbits, int nsteps, const CodedLayout &l, uint8_t *dibits, hipStream_t s)
 {
-    return ntx >= 1 && ntx <= (long long)VITERBI_MAX_STEPS && v.n == 2u * (unsigned)ntx && v.s >= 1 && v.s < v.n && v.sinv >= 1 && v.sinv < v.n;
-}
-
-int launch_viterbi_ilv(const int8_t *soft, size_t pitch, int nrows, int nsteps, const Puncture &punct, const Interleave &ilv, const uint8_t *flip,
-                       int flags, unsigned long long *scratch, bool lds, uint8_t *bits, int32_t *info, hipStream_t s)
-{
-    if (nrows <= 0 || nsteps <= 0 || nsteps > VITERBI_MAX_STEPS || !soft || (!bits && !info)) return (int)hipErrorInvalidValue;
-    if (punct.period < 1 || punct.period > 32 || punct.K < 1 || !ilv_fits(ilv, (punct_nsent(punct, nsteps) + 1) / 2)) return (int)hipErrorInvalidValue;
-    const size_t bytes = viterbi_scratch_bytes_per_row(nsteps);
-    if (lds ? bytes > (size_t)VITERBI_LDS_MAX_BYTES : !scratch) return (int)hipErrorInvalidValue;
-    const VitArgs a = {soft, pitch, nsteps, flags, flip, scratch, bits, info, punct};
-    const IlvMul pi = ilv_mul(ilv.n, ilv.s);
-    if (lds) hipLaunchKernelGGL(viterbi_ilv_lds_kernel, dim3(nrows), dim3(64), bytes, s, a, pi);
-    else hipLaunchKernelGGL(viterbi_ilv_kernel, dim3(nrows), dim3(64), 0, s, a, pi);
-    return (int)hipGetLastError();
-}
-
-int launch_conv_encode(const uint8_t *bits, int nrows, int nbits, int nsteps, uint8_t *dibits, hipStream_t s)
-{
-    if (nrows <= 0 || nbits <= 0 || nsteps < nbits || !bits || !dibits) return (int)hipErrorInvalidValue;
-    const size_t n = (size_t)nrows * (size_t)nsteps;
-    if ((n + 255) / 256 > 0x7fffffffull) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(conv_encode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bits, (size_t)nrows, nbits, nsteps, dibits);
-    return (int)hipGetLastError();
-}
-
-int launch_conv_encode_punct(const uint8_t *bits, int nrows, int nbits, int nsteps, const Puncture &p, uint8_t *dibits, hipStream_t s)
-{
-    if (nrows <= 0 || nbits <= 0 || nsteps < nbits || !bits || !dibits || p.period < 1 || p.period > 32 || p.K < 1 || p.K > 64)
-        return (int)hipErrorInvalidValue;
-    const long long nsent = punct_nsent(p, nsteps), ntx = (nsent + 1) / 2;
+    if (nrows <= 0 || nbits <= 0 || nsteps < nbits || !bits || !dibits || !coded_layout_fits(l, nsteps)) return (int)hipErrorInvalidValue;
+    const long long nsent = coded_nsent(l, nsteps), ntx = coded_ndibits(l, nsteps);
     if (ntx < 1) return (int)hipErrorInvalidValue;
-    PunctTable tab;
-    if (!punct_table_make(p, &tab)) return (int)hipErrorInvalidValue;
     const size_t n = (size_t)nrows * (size_t)ntx;
     if ((n + 255) / 256 > 0x7fffffffull) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(conv_encode_punct_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bits, (size_t)nrows, nbits, (unsigned)nsent,
-                       (unsigned)ntx, p.period, p.K, tab, dibits);
-    return (int)hipGetLastError();
-}
-
-int launch_conv_encode_ilv(const uint8_t *bits, int nrows, int nbits, int nsteps, const Puncture &p, const Interleave &ilv, uint8_t *dibits,
-                           hipStream_t s)
-{
-    if (nrows <= 0 || nbits <= 0 || nsteps < nbits || !bits || !dibits || p.period < 1 || p.period > 32 || p.K < 1 || p.K > 64)
-        return (int)hipErrorInvalidValue;
-    const long long nsent = punct_nsent(p, nsteps), ntx = (nsent + 1) / 2;
-    if (!ilv_fits(ilv, ntx)) return (int)hipErrorInvalidValue;
-    PunctTable tab;
-    if (!punct_table_make(p, &tab)) return (int)hipErrorInvalidValue;
-    const size_t n = (size_t)nrows * (size_t)ntx;
-    if ((n + 255) / 256 > 0x7fffffffull) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(conv_encode_ilv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bits, (size_t)nrows, nbits, (unsigned)nsent,
-                       (unsigned)ntx, p.period, p.K, tab, ilv_mul(ilv.n, ilv.sinv), dibits);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (l.kind == CODED_PLAIN) {
+        hipLaunchKernelGGL(conv_encode_kernel, grid, block, 0, s, bits, (size_t)nrows, nbits, nsteps, dibits);
+        return (int)hipGetLastError();
+    }
+    EncodeArgs a = {bits, (size_t)nrows, nbits, (unsigned)nsent, (unsigned)ntx, l.punct, {}, dibits};
+    if (!punct_table_make(l.punct, &a.tab)) return (int)hipErrorInvalidValue;
+    if (l.kind == CODED_ILV) hipLaunchKernelGGL(conv_encode_ilv_kernel, grid, block, 0, s, a, ilv_mul(l.ilv.n, l.ilv.sinv));
+    else hipLaunchKernelGGL(conv_encode_punct_kernel, grid, block, 0, s, a);
     return (int)hipGetLastError();
 }
 

@@ -1,8 +1,9 @@
 /*
  * viterbi_row.h -- one row of the K = 7, rate-1/2 Viterbi decoder by ONE WAVE (lane = new state): the forward pass, the trace-back and
  * the channel error count of qpsk_viterbi_batch (include/qpsk_hip.h), shared by viterbi.hip (rows of a caller's batch) and
- * deframe_coded.hip (the staged soft rows of packets found in a stream).  viterbi.hip's header describes the passes.  A punctured
- * rate (qpsk_viterbi_punct_batch) is the same passes behind another LOADER of the soft pairs, an interleaved row (qpsk_viterbi_ilv_batch) behind a third.
+ * deframe_coded.hip (the staged soft rows of packets found in a stream).  viterbi.hip's header describes the passes.  The three layouts of
+ * a row (kernels.h, CodedLayout) are the same passes behind a LOADER of the soft pairs: PairLoader at rate 1/2, and one loader behind a pattern
+ * whose position map is the identity (punctured) or the stride's (interleaved).
  *
  * The caller's kernel runs workgroups of exactly one wave (64 threads) and hands the row over as plain pointers; what happens to the
  * decoded bits is the caller's too: the trace-back gives every block of 64 steps to a SINK,
@@ -53,65 +54,65 @@ struct PairLoader {
     __device__ __forceinline__ void load(int t0, int nsteps, int lane, int &s0, int &s1) const { load_soft(row, flip, t0, nsteps, lane, s0, s1); }
 };
 
-/* PunctLoader (p: kernels.h): row = the flat int8 of the TRANSMITTED dibits, flip [ntx] over those dibits or NULL.  Sent bit (t, j) is flat number
- * idx(t, j); a lane works its two numbers out with one division and two popcounts per 64 steps and does byte loads; an unsent bit is 0,
- * the erasure the decoder needs no special case for.  idx < nsent for every sent bit of a step below nsteps, so the pad bit of an odd
- * nsent is never read */
-struct PunctLoader {
-    const int8_t *__restrict__ row;
-    const uint8_t *__restrict__ flip;
-    Puncture p;
-    __device__ __forceinline__ void load(int t0, int nsteps, int lane, int &s0, int &s1) const
-    {
-        const int t = t0 + lane;
-        s0 = s1 = 0;
-        if (t < nsteps) {
-            const unsigned q = (unsigned)t / (unsigned)p.period, r = (unsigned)t - q * (unsigned)p.period;
-            const unsigned low = (1u << r) - 1u;
-            const unsigned b0 = (p.keep0 >> r) & 1u, b1 = (p.keep1 >> r) & 1u;
-            const size_t k0 = (size_t)q * (unsigned)p.K + __popc(p.keep0 & low) + __popc(p.keep1 & low), k1 = k0 + b0;
-            if (b0) {
-                s0 = max((int)row[k0], -127);
-                if (flip && ((flip[k0 >> 1] >> (k0 & 1)) & 1u)) s0 = -s0;
-            }
-            if (b1) {
-                s1 = max((int)row[k1], -127);
-                if (flip && ((flip[k1 >> 1] >> (k1 & 1)) & 1u)) s1 = -s1;
-            }
-        }
-    }
+/* Behind a pattern (p: kernels.h) sent bit (t, j) is sent bit number idx(t, j) of the row: where step t's first sent bit lies and which of its
+ * two coded bits are sent -- one division by the period and two popcounts.  idx(t, 1) = idx(t, 0) + b0.  k0 < 2^18; it is 64-bit because the flat
+ * row is addressed with it as it is (IlvMul::at takes its low word) */
+struct SentStep {
+    size_t k0;
+    unsigned b0, b1;
 };
+__device__ __forceinline__ SentStep sent_step(const Puncture &p, unsigned t)
+{
+    const unsigned q = t / (unsigned)p.period, r = t - q * (unsigned)p.period;
+    const unsigned low = (1u << r) - 1u;
+    const unsigned b0 = (p.keep0 >> r) & 1u, b1 = (p.keep1 >> r) & 1u;
+    return SentStep{(size_t)q * (unsigned)p.K + __popc(p.keep0 & low) + __popc(p.keep1 & low), b0, b1};
+}
 
-/* IlvLoader (INTERLEAVING in include/qpsk_hip.h): PunctLoader's row behind the permutation pi(k) = k s mod n: sent bit k lies at flat
- * number pi(k) of the transmitted row and its flip bit at the same on-air position.  Per lane and 64 steps: PunctLoader's index, one
- * modular product (IlvMul: 32-bit, no 64-bit division) for the step's first sent bit, a conditional subtract for its second --
- * idx(t, 1) = idx(t, 0) + 1 when both are sent -- and the same byte loads, now s apart instead of adjacent.  Lane-parallel and a block
- * ahead like the others.  pi is a bijection and idx < nsent, so the pad position pi(nsent) of an odd nsent is never read */
-struct IlvLoader {
+/* SentLoader: row = the flat int8 of the TRANSMITTED dibits, flip [ntx] over those dibits or NULL; sent bit k lies at flat position map.at(k),
+ * its flip bit at the same on-air position.  A lane works out its step's sent_step and the position of its first sent bit once per 64 steps
+ * (map.ahead gives the second's) and does byte loads; an unsent bit is 0, the erasure the decoder needs no special case for.  idx < nsent for
+ * every sent bit of a step below nsteps and the map is a bijection, so the pad bit of an odd nsent is never read.  Lane-parallel and a block
+ * ahead like PairLoader.  The two maps (kernels.h):
+ *     PunctLoader   FlatMap, qpsk_viterbi_punct_batch: sent bit k is flat bit k, a step's two sent bits are adjacent bytes
+ *     IlvLoader     IlvMul, qpsk_viterbi_ilv_batch (INTERLEAVING in include/qpsk_hip.h): pi(k) = k s mod n, one modular product (32-bit, no
+ *                   64-bit division) for the step's first sent bit and a conditional subtract for its second, the bytes now s apart */
+template <class Map>
+struct SentLoader {
     const int8_t *__restrict__ row;
     const uint8_t *__restrict__ flip;
     Puncture p;
-    IlvMul pi;
-    __device__ __forceinline__ int value(unsigned a) const
+    Map map;
+    /* the soft value at flat position a after the -128 rule and d_flip */
+    template <class Pos>
+    __device__ __forceinline__ int value(Pos a) const
     {
         const int v = max((int)row[a], -127);
-        return (flip && ((flip[a >> 1] >> (a & 1u)) & 1u)) ? -v : v;
+        return (flip && ((flip[a >> 1] >> (a & 1)) & 1u)) ? -v : v;
     }
     __device__ __forceinline__ void load(int t0, int nsteps, int lane, int &s0, int &s1) const
     {
         const int t = t0 + lane;
         s0 = s1 = 0;
         if (t < nsteps) {
-            const unsigned q = (unsigned)t / (unsigned)p.period, r = (unsigned)t - q * (unsigned)p.period;
-            const unsigned low = (1u << r) - 1u;
-            const unsigned b0 = (p.keep0 >> r) & 1u, b1 = (p.keep1 >> r) & 1u;
-            const unsigned k0 = q * (unsigned)p.K + __popc(p.keep0 & low) + __popc(p.keep1 & low);
-            const unsigned a0 = pi.at(k0), a1 = b0 ? pi.next(a0) : a0;
-            if (b0) s0 = value(a0);
-            if (b1) s1 = value(a1);
+            const SentStep e = sent_step(p, (unsigned)t);
+            const auto a0 = map.at(e.k0), a1 = map.ahead(a0, e.b0);
+            if (e.b0) s0 = value(a0);
+            if (e.b1) s1 = value(a1);
         }
     }
 };
+using PunctLoader = SentLoader<FlatMap>;
+using IlvLoader = SentLoader<IlvMul>;
+
+/* the loader of a layout's kind (kernels.h, CodedKind) over one row; p and pi are looked at by the kinds that have them */
+template <int KIND>
+__device__ __forceinline__ auto coded_loader(const int8_t *row, const uint8_t *flip, const Puncture &p, const IlvMul &pi)
+{
+    if constexpr (KIND == CODED_PLAIN) return PairLoader{row, flip};
+    else if constexpr (KIND == CODED_PUNCT) return PunctLoader{row, flip, p, FlatMap{}};
+    else return IlvLoader{row, flip, p, pi};
+}
 
 /* the channel errors of block blk, lane-parallel: cur / prev = the decoded bits of blocks blk / blk - 1 (bit j = step 64 blk + j).
  * x = bits t-6 .. t of the row with bit t - 6 lowest, so the generators apply bit-reversed: 171 -> 0x4F, 133 -> 0x6D */
