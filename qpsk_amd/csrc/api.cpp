@@ -736,7 +736,7 @@ struct RxRoute {
     int G = 0;                        /* K_PIPE2, K_LEAN: frames per workgroup */
     int nf = 0;                       /* K_FUSED_PIPE: FIR waves per workgroup */
     unsigned long long layout = 0;    /* K_PIPE2, K_LEAN: units per hardware wave */
-    bool pipe_ok = false;             /* the shape the pipeline kernels (rx_fused.hip) are built for */
+    bool pipe_ok = false;             /* the shape the pipeline kernels (rx_pipe.h) are built for */
     bool fused_fft = false;           /* the FFT timing estimate runs inside the receive launch, not in a launch in front */
     bool need_pad = false;            /* the caller provides -- K_LEAN on a batch that is not whole workgroups: FusedArgs::sym_pad, G rows */
     bool data_rule = false;           /* qpsk_rx_batch_data: the kernel writes the data rule's decisions itself (FusedArgs::data_rule) */
@@ -841,7 +841,7 @@ static int rx_route(const qpsk_ctx *c, const FusedArgs &a, bool want_data, RxRou
     return QPSK_OK;
 }
 
-/* ---- histogram timing in ONE pass (round 6; rx_fused.hip, rx_hist_kernel): where the context has a guess -- the majority index of its
+/* ---- histogram timing in ONE pass (round 6; rx_hist.hip, rx_hist_kernel): where the context has a guess -- the majority index of its
  * previous histogram-mode batch -- the scan kernel's workgroup runs the receive path on that guess while it scans, the frames whose true
  * index differs are redone by a fall-back pass over their list (usually empty), and the batch's own majority becomes the next guess.
  * *taken = false and nothing launched: no guess yet, a shape the kernel does not serve, or a last batch that missed frames (the caller
@@ -1023,7 +1023,7 @@ static int rx_batch_common(qpsk_ctx *c, const float *d_in, long long frame_pitch
         c->hint_valid = true;
     }
     if (rt.kind == K_LEAN && (nframes & 1)) {
-        /* the last frame of an odd batch shares its two-frame unit with a pad frame: the unit's rows are pad rows (rx_fused.hip,
+        /* the last frame of an odd batch shares its two-frame unit with a pad frame: the unit's rows are pad rows (rx_lean.hip,
          * lean_unit_rows); its own row goes to its place behind the launch */
         const size_t last0 = (size_t)((nframes - 1) / rt.G) * (size_t)rt.G;      /* the last workgroup's first frame */
         HIP_TRY(hipMemcpyAsync(a.sym + (size_t)(nframes - 1) * (size_t)c->nsym, a.sym_pad + ((size_t)(nframes - 1) - last0) * (size_t)c->nsym,

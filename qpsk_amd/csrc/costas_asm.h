@@ -56,7 +56,7 @@
  * a squelched input, an all-zero frame -- where T is (+-0, +-0) whatever the phase: d = |T.y| - |T.x| = +0, the two updates add
  * +-0, and x + (+-0) = x for every x but -0, so the stream's step IS the reference's (phase + freq, wrap, clamp; state at rest
  * stays at rest) as long as neither phase nor freq is -0 -- which only loaded state can be, and the sum of two floats is -0 only if
- * both are.  The caller checks symbols and state (rx_fused.hip, zero_run) before it sets a lane's bit, per stretch of symbols.
+ * both are.  The caller checks symbols and state (rx_pipe.h, zero_run) before it sets a lane's bit, per stretch of symbols.
  *
  * Registers: v[100:143] are scratch owned by the block (clobbered; low enough for a kernel built for three
  * waves per SIMD, i.e. at most 168 VGPRs):
@@ -388,7 +388,7 @@ __device__ __forceinline__ unsigned costas_asm_run(float &phase, float &freq, un
 #undef QPSK_ZA
 
 /*
- * The same stream running THROUGH the chunk hand-overs of the pipeline kernels' rings (rx_fused.hip): symbol ring and
+ * The same stream running THROUGH the chunk hand-overs of the pipeline kernels' rings (rx_pipe.h): symbol ring and
  * record ring of 128 symbols per lane (two 64-symbol chunks) = 128 / G groups of G = COSTAS_RING_GROUP steps, group k at ring
  * position k % (128 / G).  G is 64: one group per chunk (the text macro also builds 16 and 32; tools/ubench_step.py --groups
  * measures all three; costas_asm_lo.h's copy for rx_hist_kernel keeps 16, COSTAS_RING_GROUP_LO).  What the serial wave did

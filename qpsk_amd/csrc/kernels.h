@@ -59,7 +59,7 @@ struct FusedArgs {
     const float2 *refill;
     float2 *refill_dst;     /* = dsrc, writable */
     int refill_planar;      /* refill rows are [cycles][nsym] planes (phase-major: what stream_scan_kernel leaves) instead of frame_size samples */
-    /* rx_fused_kernel as the fall-back pass of the one-pass histogram route (rx_hist_kernel, rx_fused.hip): the launch covers the frames
+    /* rx_fused_kernel as the fall-back pass of the one-pass histogram route (rx_hist_kernel, rx_hist.hip): the launch covers the frames
      * frame_list[0 .. *frame_list_count) instead of 0 .. nframes (both in device memory: the count is known only on the device; workgroups
      * beyond it retire at once); inputs, per-frame index and every output are addressed by the listed frame number.  NULL = off */
     const int32_t *frame_list, *frame_list_count;
@@ -93,44 +93,59 @@ struct FusedArgs {
 size_t fused_lds_bytes(int G, int S, int cycles, int nbw);
 int prepare_kernels(void);
 int launch_rx_fused(const FusedArgs &a, hipStream_t s);
-/* rx_fused.hip: the producer/consumer pipeline kernel (CYCLES = 8 only) */
+/* rx_fused_pipe.hip: the producer/consumer pipeline kernel (CYCLES = 8 only; the pipeline's shape: rx_pipe.h) */
 size_t pipe_lds_bytes(int NF, int nbw);
 int pipe_frames(int NF);               /* frames of a workgroup with NF FIR waves: 4 per wave */
 int pipe_cycles(void);
 int pipe_max_nf(void);                 /* FIR waves per workgroup: 4 (16 frames) */
-int prepare_pipe_kernel(void);
+int prepare_pipe_kernel(void);           /* every pipeline kernel: the four units' own prepare_*() below, the first error wins */
+#define QPSK_UNIT_LOCAL __attribute__((visibility("hidden")))      /* between the library's units only: not among its exported symbols */
+QPSK_UNIT_LOCAL int prepare_costas_pipe(void);
+QPSK_UNIT_LOCAL int prepare_rx_fused_pipe(void);
 int launch_rx_fused_pipe(const FusedArgs &a, int NF, int *status, hipStream_t s);
 int launch_costas_pipe(const FusedArgs &a, int NF, int *status, hipStream_t s);
-/* rx_fused.hip: the pipeline kernel for up to 32 frames per workgroup (two-frame units, per-wave windows) */
+/* rx_pipe2.hip: the pipeline kernel for up to 32 frames per workgroup (two-frame units, per-wave windows) */
 size_t pipe2_lds_bytes(int G, int nwin, int nbw);      /* nwin = FIR waves (one window each) */
 int pipe2_max_fir(void);
 int pipe2_max_frames(void);
 int pipe2_max_units_per_wave(void);
 int pipe2_max_hw_waves(void);
 unsigned long long pipe2_default_layout(int NU);        /* 4 bits per hardware wave: units it owns; 0 if NU does not fit */
-/* what a wave layout adds up to: the two-frame units of all its waves, and the waves that own any (one frame window each) */
-struct LayoutCount { int units, nwin; };
-inline LayoutCount layout_count(unsigned long long layout)
+/* THE decoder of a wave layout word on the host (the kernels deal their waves by the same word): what it adds up to -- the two-frame
+ * units of all its waves, the waves that own any (one frame window each), the hardware waves to launch (the last owner's number + 1),
+ * whether one sits beside the serial wave (hardware waves 4, 8) -- and whether it is one at all: nothing on wave 0 (the serial wave),
+ * at most max_per_wave units on a wave, no unit on a hardware wave the kernels do not have */
+struct LayoutCount {
+    int units, nwin, hw;
+    bool share_simd0, valid;
+};
+inline LayoutCount layout_count(unsigned long long layout, int max_per_wave = pipe2_max_units_per_wave())
 {
-    LayoutCount n = {0, 0};
+    LayoutCount n = {0, 0, 1, false, (layout & 15) == 0};
     for (int w = 1; w < 16; w++) {
         const int cw = (int)((layout >> (4 * w)) & 15);
+        if (cw > max_per_wave || (cw && w >= pipe2_max_hw_waves())) n.valid = false;
         n.units += cw;
         n.nwin += cw != 0;
+        if (cw) n.hw = w + 1;
+        if (cw && (w == 4 || w == 8)) n.share_simd0 = true;
     }
     return n;
 }
 int launch_rx_pipe2(const FusedArgs &a, int G, unsigned long long layout, int *status, hipStream_t s);
-/* rx_fused.hip: the same pipeline with the FIR waves' chunk loop as one hand-written stream (fir_lean_asm.h) */
+QPSK_UNIT_LOCAL int prepare_rx_pipe2(void);
+/* rx_lean.hip: the same pipeline with the FIR waves' chunk loop as one hand-written stream (fir_lean_asm.h) */
 size_t lean_lds_bytes(int G, int nwin);
 unsigned long long lean_default_layout(int NU);         /* rx_lean_kernel: 1, 5, 5, 5 units on SIMDs 0-3 for a full workgroup */
 bool lean_shape_ok(const FusedArgs &a, int G);          /* one loop per frame, whole chunks, an even workgroup size, ... */
 int launch_rx_lean(const FusedArgs &a, int G, unsigned long long layout, int *status, hipStream_t s);
+QPSK_UNIT_LOCAL int prepare_rx_lean(void);
 bool lean_est_ok(const FusedArgs &a, int G, unsigned long long layout);   /* the FFT timing estimate inside rx_lean_kernel's launch fits this geometry */
-/* rx_fused.hip: the reference's histogram timing mode in ONE pass (timing scan + receive path on a guessed index, verified per frame) */
+/* rx_hist.hip: the reference's histogram timing mode in ONE pass (timing scan + receive path on a guessed index, verified per frame) */
 bool rx_hist_shape_ok(const FusedArgs &a);
 int launch_rx_hist(const FusedArgs &a, int32_t *index_true, const int32_t *hint, int32_t *mis_list, int32_t *mis_count, int *status, hipStream_t s);
 int launch_index_majority(const int32_t *index, int nframes, int32_t *hint, int32_t *mis_count, int32_t *h_stats, hipStream_t s);
+QPSK_UNIT_LOCAL int prepare_rx_hist(void);
 int launch_rrc_fir(const float *x, const float *memory, float *y, const float *taps, int nframes, int length,
                    hipStream_t s, size_t in_pitch = 0);      /* in_pitch: samples between input frames (0 = length) */
 /* firstream.hip: the same filter as the generated stream fir_full8s_asm.h (SYMMETRIC taps only: the caller checks) */

@@ -224,7 +224,7 @@ rrc_fir_kernel(const float2 *__restrict__ x, const float2 *__restrict__ memory, 
     const float2 *rd = xs + 9 * tid;
     const float4 *taps4 = reinterpret_cast<const float4 *>(taps);
     /* Left to itself the compiler emits each multiply-add as v_pk_mul, s_nop, dependent v_pk_add (357 s_nops and
-     * as many stalls in 2032 packed operations).  As in rx_fused.hip the order inside a window position is pinned
+     * as many stalls in 2032 packed operations).  As in rx_fused_pipe.hip the order inside a window position is pinned
      * with empty asm statements: the up to 8 products of the position, then the 8 adds, so that a product is 8
      * instructions ahead of its add and an accumulator's adds are 16 apart.  Window values and tap groups are
      * fetched one block of 8 positions ahead (three tap groups live: a position's 8 outputs reach back into the

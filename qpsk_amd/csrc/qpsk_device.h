@@ -26,7 +26,7 @@ constexpr double TAU = 2.0 * 3.14159265358979323846; /* qpsk.h:29 */
 constexpr float TAU_F = 0x1.921fb6p+2f; /* the float just above TAU: "phase > TAU" <=> phase >= TAU_F */
 constexpr float ROT45 = 0x1.6a09e6p-1f; /* cosf((float)(M_PI/4)) == sinf(same), qpsk.h:30, qpsk.c:75 */
 
-/* tools of the hand-ordered FIR loops (rx_fused.hip, rrc_fir_kernel) */
+/* tools of the hand-ordered FIR loops (rx_fused_pipe.hip, rx_pipe2.hip, rrc_fir_kernel) */
 typedef float v2f __attribute__((ext_vector_type(2)));   /* one VGPR pair: operand type of the packed fp32 ops */
 
 template <int I>

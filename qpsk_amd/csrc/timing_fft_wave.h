@@ -1,6 +1,6 @@
 /*
  * timing_fft_wave.h -- the FFT timing estimate of ONE frame by ONE wave (definition and method: timing_fft.hip's header),
- * shared by timing_fft_kernel and by the estimate that runs inside rx_fused_pipe_kernel's prologue (rx_fused.hip).
+ * shared by timing_fft_kernel and by the estimate that runs inside rx_fused_pipe_kernel's and rx_lean_kernel's prologue (rx_fused_pipe.hip, rx_lean.hip).
  */
 #ifndef QPSK_TIMING_FFT_WAVE_H
 #define QPSK_TIMING_FFT_WAVE_H

@@ -1788,7 +1788,7 @@ def test_timing_scan_fused(oracle, L, F):
 def test_streams_stretches_of_zero_symbols(oracle, block):
     """Symbols that are exactly (+0, +0) -- every stream's first block after qpsk_streams_reset(), a squelched input from its third
     silent block on -- trip the Costas instruction stream's exact-zero test in every group; the lanes concerned are excused from it
-    for the stretch of zeros they have ahead (costas_asm.h `ign`, rx_fused.hip costas_wave, streamblock.hip) instead of sending the
+    for the stretch of zeros they have ahead (costas_asm.h `ign`, rx_pipe.h costas_wave, streamblock.hip) instead of sending the
     whole workgroup through the C++ step.  Loop states that meet such a stretch: zeros of both signs in phase and frequency (where
     signed zeros decide: those stay with the C++ step), phases in every quadrant at rest, moving loops that wrap, a frequency at its
     limit, denormal frequencies; then squelch and signal again.  Every block of every stream against the oracle's modem; block = 1:

@@ -22,7 +22,7 @@ Arithmetic: symbol 0 of the lane sums window position t times tap t, symbol 1 po
 tap order 0..126 into its own packed (re, im) accumulator, multiply and add unfused (the reference is built without
 contraction): exactly the C++ step it replaces; the parity tests compare every output bit with the oracle.
 
-Window image (rx_fused.hip, namespace pipe2): position p at float2 slot p + 2*(p/16) from the lane's base, so that
+Window image (rx_pipe2_geom.h, namespace pipe2): position p at float2 slot p + 2*(p/16) from the lane's base, so that
 positions (t, t+1), t even, are one aligned 16-byte word; taps as 128 floats in LDS (tap 127 = 0, never used).
 """
 import sys

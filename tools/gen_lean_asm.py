@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generator of qpsk_amd/csrc/fir_lean_asm.h: the WHOLE chunk loop of a FIR wave of rx_lean_kernel (rx_fused.hip) as
+"""Generator of qpsk_amd/csrc/fir_lean_asm.h: the WHOLE chunk loop of a FIR wave of rx_lean_kernel (rx_lean.hip) as
 one gfx950 instruction stream per wave shape (1 or 2 two-frame units per wave).
 
     python tools/gen_lean_asm.py > qpsk_amd/csrc/fir_lean_asm.h
@@ -58,8 +58,8 @@ SRC = 10            # s10..s17   source pointers unit ui, frame ff -> SRC + 4 ui
 SYMB = 18           # s18..s21   symbol store bases per unit
 SC, SN, SPR, SSPIN, ST0, ST1, ST2, ST3, SIX, SFL, SCONS = 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 35
 SPIN_LIMIT = 1 << 24
-CTL_READY, CTL_CONSUMED = 0, 64        # lean::Ctl (rx_fused.hip): ready[16], consumed, abort flag
-WS_SLOTS = 712                         # slots per frame window (rx_fused.hip, lean::WS): positions 0..633; a lane never reads past 630
+CTL_READY, CTL_CONSUMED = 0, 64        # lean::Ctl (rx_pipe2_geom.h): ready[16], consumed, abort flag
+WS_SLOTS = 712                         # slots per frame window (rx_lean.hip, lean::WS): positions 0..633; a lane never reads past 630
 # measurement variant (--profile -> fir_lean_prof_asm.h, only compiled into the -DQPSK_PIPE_PROFILE library): shader cycles per
 # phase of a unit, accumulated in v160..v165 (v166 scratch, v167 the last stamp) and handed back through six outputs
 PROFILE = False
@@ -482,7 +482,7 @@ def flush(e, ui):
 def unit(e, ui, nuw, packed=True):
     last = ui == nuw - 1
     nx = (ui + 1) % nuw
-    # ---- priority by need: the fewer chunks this wave is ahead of the loop, the higher (rx_fused.hip, rx_pipe2_kernel)
+    # ---- priority by need: the fewer chunks this wave is ahead of the loop, the higher (rx_pipe2.hip, rx_pipe2_kernel)
     pr_done, pr1, pr2 = e.label("pr"), e.label("pr"), e.label("pr")
     e("ds_read_b32 v%d, %%[smem] offset:%d", TMP + 1, CTL_CONSUMED)
     e("s_waitcnt lgkmcnt(0)")
@@ -741,7 +741,7 @@ def main():
     print('''/*
  * fir_lean_asm.h -- GENERATED by tools/gen_lean_asm.py; do not edit.
  *
- * The chunk loop of a FIR wave of rx_lean_kernel (rx_fused.hip): stage, prefetch, filter, gain, flush, hand-over of
+ * The chunk loop of a FIR wave of rx_lean_kernel (rx_lean.hip): stage, prefetch, filter, gain, flush, hand-over of
  * one or two two-frame units per 64-symbol chunk, as one instruction stream (see the generator's docstring).
  *
  * Contract with the kernel:
