@@ -1,5 +1,5 @@
 /*
- * carrier.h -- the streams' carrier while it is ONE carrier for all of them (streamscan.hip MODE 2; api.cpp carrier_shared).
+ * carrier.h -- the streams' carrier while it is ONE carrier for all of them (streamscan.hip MODE 2; api_streams.cpp, Streams::carrier_shared).
  *
  * fbb_rx_phase *= fbb_rx_rect per sample (qpsk.c:115) is a strictly serial complex recurrence: 16384 dependent steps per 16384-sample
  * block, ~50 cycles each for a wave alone on its SIMD and ~100 beside three busy ones.  It does not depend on the data, and

@@ -19,7 +19,7 @@
 
 #define TAU_D (2.0 * 3.14159265358979323846) /* qpsk.h:29 */
 
-/* internal extras of api.cpp */
+/* internal extras of api_streams.cpp */
 int qpsk_streams_set_loop_state(qpsk_ctx *ctx, const float *h_state);
 int qpsk_streams_get_loop_state(qpsk_ctx *ctx, float *h_state);
 

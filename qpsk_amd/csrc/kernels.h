@@ -1,4 +1,4 @@
-/* kernels.h -- launch interface between the C-ABI layer (api.cpp) and kernels.hip */
+/* kernels.h -- launch interface between the C-ABI layer (api_*.cpp) and kernels.hip */
 #ifndef QPSK_KERNELS_H
 #define QPSK_KERNELS_H
 
@@ -12,7 +12,7 @@ constexpr int LOOKBACK = 128;  /* >= 126 samples of FIR history, kept 16-byte fr
 constexpr int LOOKAHEAD = 8;   /* the decimation offset can reach 7 (qpsk.c:173-180) */
 constexpr int MAX_LDS_BYTES = 160 * 1024;
 constexpr int MAX_INDEX = 7;
-/* values a kernel stores in the context's status word (FusedArgs::status; api.cpp check_status) */
+/* values a kernel stores in the context's status word (FusedArgs::status; api_ctx.cpp check_status) */
 constexpr int STATUS_PIPE_TIMEOUT = 1;   /* the in-LDS producer/consumer pipeline exhausted its bounded spins */
 constexpr int STATUS_PHASE_RANGE = 2;    /* a loop phase beyond the bounded 2 pi wrap (qpsk_device.h, phase_wrap) */
 constexpr int STATUS_NONFINITE = 3;      /* a loop ended on a NaN / Inf phase or frequency: the input held a non-finite sample */
@@ -33,10 +33,10 @@ struct FusedArgs {
     int share_simd0;        /* rx_pipe2_kernel, set by its launcher: a FIR wave sits beside the serial wave (priorities, see there) */
     const int32_t *index;   /* [nframes] or NULL -> fixed_index */
     int fixed_index;
-    /* rx_fused_pipe_kernel, full 16-frame workgroups only (set by api.cpp when the shape allows it): the FFT timing estimate
+    /* rx_fused_pipe_kernel, full 16-frame workgroups only (set by api_rx.cpp when the shape allows it): the FFT timing estimate
      * runs INSIDE the launch -- every hardware wave estimates two of the workgroup's frames before the pipeline starts
      * (timing_fft_wave.h) -- instead of in a launch of its own in front.  est_tw: size-512 twiddle table, est_cs: the CYCLES
-     * candidate phases (both host-built, api.cpp); index_out [nframes] or NULL receives the indices.  NULL = off */
+     * candidate phases (both host-built, api_rx.cpp); index_out [nframes] or NULL receives the indices.  NULL = off */
     const double2 *est_tw, *est_cs;
     int32_t *index_out;
     int lean_twowin;        /* rx_lean_kernel, set by launch_rx_lean when the LDS allows it (workgroups of up to 16 frames): every two-frame unit has
@@ -48,7 +48,7 @@ struct FusedArgs {
                                (costas_asm.h, QPSK_BODY_P): 1 = in workgroups of up to 16 frames, 2 = up to 32, 3 = up to 24 (the library's rule), 0 = never; launch_rx_lean turns the wish into 0 / 1.  Same bits ("QPSK_LEAN_PAIR") */
     int dbg;                /* layout variants of the pipeline kernel, all bit-exact (qpsk_ctx_set_tuning "QPSK_PIPE_DBG"):
                                4 no spare waves, 8 C++ Costas step, 16 serial wave chunk by chunk (no stream across the ring hand-overs), 64 FIR waves that share a SIMD keep their hardware order (16-frame kernel), 128 one lane mapping for all FIR waves (the plain
-                               layout).  Measurement build only (-DQPSK_PIPE_PROFILE; masked off by api.cpp otherwise):
+                               layout).  Measurement build only (-DQPSK_PIPE_PROFILE; masked off by api_rx.cpp otherwise):
                                1 skip FIR arithmetic, 2 skip the Costas recurrence (both change the result), 32 print the
                                cycle accounting of workgroup 0's FIR waves */
     const float2 *dsrc;     /* costas_pipe_kernel only: decimated symbols, rows dstride symbols apart */
@@ -278,7 +278,7 @@ constexpr int VITERBI_MAX_STEPS = 131072;
 constexpr int VITERBI_LDS_MAX_BYTES = 65536;
 constexpr int VITERBI_OPEN_START = 1, VITERBI_OPEN_END = 2, VITERBI_PROFILE_FORWARD_ONLY = 0x100, VITERBI_PROFILE_CYCLES = 0x200;
 size_t viterbi_scratch_bytes_per_row(int nsteps);
-/* a pattern of PUNCTURING (include/qpsk_hip.h), checked by the host (api.cpp, punct_make): 1 <= period <= 32, no mask bit at or above
+/* a pattern of PUNCTURING (include/qpsk_hip.h), checked by the host (api_coded.cpp, punct_make): 1 <= period <= 32, no mask bit at or above
  * period, K = popc(keep0) + popc(keep1) > 0 = the sent bits of a period */
 struct Puncture {
     int period;
@@ -291,7 +291,7 @@ inline long long punct_nsent(const Puncture &p, int nsteps)
     const unsigned r = (unsigned)(nsteps % p.period), low = (1u << r) - 1u;
     return (long long)(nsteps / p.period) * p.K + __builtin_popcount(p.keep0 & low) + __builtin_popcount(p.keep1 & low);
 }
-/* a stride of INTERLEAVING (include/qpsk_hip.h), checked by the host (api.cpp, ilv_make): n = 2 ntx bits on air, 1 <= s < max(n, 2),
+/* a stride of INTERLEAVING (include/qpsk_hip.h), checked by the host (api_coded.cpp, ilv_make): n = 2 ntx bits on air, 1 <= s < max(n, 2),
  * gcd(s, n) = 1, s sinv = 1 mod n.  pi(k) = k s mod n is where sent bit k lies on air; on-air bit a is sent bit a sinv mod n */
 struct Interleave {
     unsigned n, s, sinv;
@@ -321,7 +321,7 @@ struct FlatMap {
  *     CODED_PUNCT   behind a pattern: sent bit k is flat bit k of the row's ntx dibits
  *     CODED_ILV     behind a pattern and a stride: sent bit k is flat bit pi(k)
  * The kind is the ENTRY POINT's, not the values': the pattern (1, 1, 1) behind qpsk_viterbi_punct_batch is CODED_PUNCT and runs the punctured
- * kernels.  Made and checked by the host (api.cpp, layout_add_pattern / layout_add_stride); the layers a kind does not have keep the values below */
+ * kernels.  Made and checked by the host (api_coded.cpp, layout_add_pattern / layout_add_stride); the layers a kind does not have keep the values below */
 enum CodedKind { CODED_PLAIN = 0, CODED_PUNCT = 1, CODED_ILV = 2 };
 struct CodedLayout {
     CodedKind kind = CODED_PLAIN;
@@ -356,7 +356,7 @@ struct DeframeHeader {
 };
 constexpr int DEFRAME_TAIL_OFFSET = 64, DEFRAME_PEND_OFFSET = 192;
 constexpr int DEFRAME_MAX_BYTES = 1024, DEFRAME_MAX_PACKETS = 64, DEFRAME_MAX_NSYM = 1 << 21;
-/* what the one hunt (deframe_hunt.h) reads, the base of both pushes' arguments (api.cpp, deframer_hunt_args) */
+/* what the one hunt (deframe_hunt.h) reads, the base of both pushes' arguments (api_packets.cpp, deframer_push_begin) */
 struct DeframeHuntArgs {
     int nstreams, nsym;
     int nsync, min_score;

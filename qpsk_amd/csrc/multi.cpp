@@ -31,7 +31,7 @@
 
 #include "../../include/qpsk_hip.h"
 
-extern "C" int qpsk_set_error(int code, const char *msg);      /* api.cpp: the thread's last error text */
+extern "C" int qpsk_set_error(int code, const char *msg);      /* api_ctx.cpp: the thread's last error text */
 
 namespace {
 

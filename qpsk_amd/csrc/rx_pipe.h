@@ -67,7 +67,7 @@ constexpr int SPIN_LIMIT = 1 << 24;
  *                workgroup; the serial wave has a SIMD of its own (spare waves retire at once) and three SIMDs
  *                filter.  Lane mappings of its FIR waves: (frame of 4) x (q of 16) with 4 symbols per lane, or
  *                (frame of 2) x (q of 32) with 2 symbols per lane -- both in one workgroup when it is full (see
- *                the kernel).  Batches above 16 frames per CU go to rx_pipe2_kernel (api.cpp).
+ *                the kernel).  Batches above 16 frames per CU go to rx_pipe2_kernel (api_rx.cpp).
  */
 template <int QL_, int R_, int MAX_NF_, int SPARE_, bool PINNED_>
 struct Geom {
@@ -131,7 +131,7 @@ __device__ __forceinline__ void st_release(int *p, int v)
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-/* the context's status word lives in pinned host memory (api.cpp): the host reads it after any synchronisation */
+/* the context's status word lives in pinned host memory (api_ctx.cpp): the host reads it after any synchronisation */
 __device__ __forceinline__ void report_status(int *status, int what)
 {
     __hip_atomic_store(status, what, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -5,7 +5,7 @@
  * The product build is the first half of this file: every probe is an empty always-inline body, so a call site costs the shipped kernels
  * nothing, and nothing but this header changes between the two builds.  The measurement build is the second half: cycle accounting of the
  * serial wave and of the FIR waves (FusedArgs::dbg bit 5 = 32, bits 11 and 12 with it), result-changing ablations (bits 0, 1 and the lean
- * streams' 14-20), frame-source overrides (bits 21, 22) and the wall-clock timeline of one rx_lean_kernel launch (bit 23).  api.cpp masks
+ * streams' 14-20), frame-source overrides (bits 21, 22) and the wall-clock timeline of one rx_lean_kernel launch (bit 23).  api_rx.cpp masks
  * those bits off in the product (PIPE_VARIANT_MASK), which therefore computes the reference's result whatever the environment says.
  *
  * The units are built without relocatable device code, so a __device__ variable cannot be shared between them: each unit that includes

@@ -1,5 +1,5 @@
 """Differential fuzzing of the HIP path against the CPU oracle: randomly drawn configurations and inputs through the library's OWN
-dispatch (no tuning keys set, so whichever kernel api.cpp picks for the shape is the one compared), every output bit for bit.
+dispatch (no tuning keys set, so whichever kernel the host layer (api_rx.cpp, api_streams.cpp) picks for the shape is the one compared), every output bit for bit.
 
 Used by tests/test_gpu_fuzz.py (a fixed handful of seeds in the suite) and tools/fuzz.py (long runs on the GPU box, log kept under
 profiles/).  The oracle is the checker here, as everywhere under tests/ (oracle/ header: test infrastructure, never a product path).

@@ -1,6 +1,6 @@
 """Which kernel serves which receive call: a table from (entry point, batch size, timing mode, tuning keys) to the exact string
 qpsk_ctx_last_kernel() gives afterwards.  No result is compared here -- every route's bits are held against the oracle by
-test_gpu_parity.py, test_rx_ext_gpu.py and test_rx_data_gpu.py -- this file pins the ROUTING of rx_batch_common (api.cpp), so that a
+test_gpu_parity.py, test_rx_ext_gpu.py and test_rx_data_gpu.py -- this file pins the ROUTING of rx_batch_common (api_rx.cpp), so that a
 change to the host code that moves a shape to another kernel, or to another error text, shows as a changed string.
 
 The expected strings are a record: they were taken from the library as it stood before the routing was rewritten as a side-effect-free

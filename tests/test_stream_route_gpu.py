@@ -1,7 +1,7 @@
 """Which kernel serves which block of the running streams: a table from (entry point, rates, frame_size, stream count, timing mode, tuning
 keys, pointer alignment) to the exact string qpsk_ctx_last_kernel() gives after one call.  No result is compared here -- every route's
 bits are held against the oracle by test_gpu_parity.py and test_abi.py, which force the routes with tuning keys -- this file pins the
-ROUTING of the three stream entries (stream_route() in api.cpp) at the library's OWN thresholds: 1.4 M, 3.5 M and 0.4 M samples per block
+ROUTING of the three stream entries (stream_route() in api_streams.cpp) at the library's OWN thresholds: 1.4 M, 3.5 M and 0.4 M samples per block
 of all streams, 1024, 2560 and 3584 streams, a row on either side of each.  The thresholds are constants; none depends on the CU count.
 
 The expected strings are a record: they were taken from the library as it stood before the routing was rewritten as a side-effect-free
