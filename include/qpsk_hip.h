@@ -658,7 +658,8 @@ int qpsk_rs_decode_batch(qpsk_ctx *ctx, const uint8_t *d_in, long long in_pitch,
 /* rrc_fir() (rrc_fir.c:17-30) on nframes independent delay lines.
  *   d_memory [nframes][127] complex float  in/out (may be NULL: zero history, not written back)
  *   d_in, d_out [nframes][length] complex float; d_out may equal d_in only if nframes*length
- *   fits the library's staging (it copies first); prefer separate buffers. */
+ *   fits the library's staging (it copies first); prefer separate buffers.
+ *   qpsk_ctx_last_kernel() names the filter kernel afterwards: rrc_fir_stream_kernel (symmetric taps) or rrc_fir_kernel. */
 int qpsk_rrc_fir_batch(qpsk_ctx *ctx, float *d_memory, const float *d_in, float *d_out, int nframes, int length);
 
 /* The same filter by overlap-save with 512-point FFTs (algorithms/fft.h:44) -- FAST, NOT EXACT: the
@@ -886,6 +887,11 @@ int qpsk_test_inject_status(qpsk_ctx *ctx, int code);
 /* Test hook (the one-pass histogram route): synchronises, then out[5] = {the guess the next histogram-mode call will take (-1: none), frames
  * the last one-pass call's guess missed, and the statistics the host steers by: majority index, frames, frames off the majority or missed by the guess} */
 int qpsk_test_hist_state(qpsk_ctx *ctx, int32_t *out);
+/* Test hook (the full-rate filter's multi-tile runs, tests/test_fir_runs_gpu.py): out[3] = {ntiles, parts, tpp} -- how rrc_fir_stream_kernel, the
+ * kernel behind qpsk_rrc_fir_batch for a symmetric filter, would cut nframes delay lines of `length` samples on this context's device: a frame
+ * is ntiles 512-output tiles in parts runs of tpp consecutive tiles, one wave per run.  Host arithmetic only: no device work, and
+ * qpsk_ctx_last_kernel() stays.  QPSK_ERR_ARG for a NULL pointer, nframes < 1 or length < 1. */
+int qpsk_test_fir_runs(qpsk_ctx *ctx, int nframes, int length, int32_t out[3]);
 /* Test hook (the chunk loops of the decoder's scratch route): *out = the decode launches of the context's last qpsk_viterbi_batch,
  * qpsk_viterbi_punct_batch, qpsk_viterbi_ilv_batch or qpsk_deframer_push_coded call -- 1 with the decision words in LDS, 0 for a push whose bytes, crc_ok and
  * info were all NULL, or for a call that was refused.  Host bookkeeping only: no synchronisation, no device work. */

@@ -187,7 +187,7 @@ struct qpsk_ctx {
     int device = 0;
     qpsk::Tuning tune;
     int ncu = 256;                /* compute units of the device (256 on MI355X) */
-    const char *last_kernel = ""; /* the receive kernel the last rx batch launched (qpsk_ctx_last_kernel) */
+    const char *last_kernel = ""; /* the kernel the last rx batch (or qpsk_rrc_fir_batch, ...) launched (qpsk_ctx_last_kernel) */
     int viterbi_launches = 0;     /* decode launches of the last qpsk_viterbi_batch / _punct_batch / _ilv_batch / qpsk_deframer_push_coded (qpsk_test_viterbi_launches) */
     bool taps_symmetric = false;  /* taps[k] == taps[126 - k] bit for bit: rx_lean_kernel keeps the 64 distinct ones in SGPRs */
     hipStream_t stream = nullptr; /* caller's stream; nullptr = default stream */

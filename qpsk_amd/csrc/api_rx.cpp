@@ -33,6 +33,17 @@ int qpsk_test_hist_state(qpsk_ctx *c, int32_t *out)
     return QPSK_OK;
 }
 
+/* test hook: the runs launch_rrc_fir_stream cuts nframes delay lines of `length` samples into on this context's device -- out = {ntiles,
+ * parts, tpp} (kernels.h, FirRuns).  Host arithmetic only: nothing is launched, last_kernel stays */
+int qpsk_test_fir_runs(qpsk_ctx *c, int nframes, int length, int32_t out[3])
+{
+    if (!c || !out) return fail(QPSK_ERR_ARG, "qpsk_test_fir_runs: null argument");
+    if (nframes < 1 || length < 1) return fail(QPSK_ERR_ARG, "qpsk_test_fir_runs: nframes %d length %d", nframes, length);
+    const FirRuns r = rrc_fir_stream_runs(nframes, length, c->ncu);
+    out[0] = r.ntiles; out[1] = r.parts; out[2] = r.tpp;
+    return QPSK_OK;
+}
+
 void HistGuess::release()
 {
     if (d_hint) hipFree(d_hint);
@@ -43,9 +54,11 @@ void HistGuess::release()
 /* ---------------------------------------------------------------- tiling */
 /* full-rate rrc_fir() of a batch of delay lines (rrc_fir.c:17-30): the generated stream with the taps in SGPRs when the
  * filter is symmetric (firstream.hip), the compiler-scheduled kernel for any other tap set (kernels.hip) */
+static bool fir_takes_stream(const qpsk_ctx *c) { return c->taps_symmetric && tuned(c->tune.fir_generic, 0) == 0; }
+
 int qpsk::fir_full_rate(qpsk_ctx *c, const float *x, const float *memory, float *y, int nframes, int length, size_t in_pitch)
 {
-    if (c->taps_symmetric && tuned(c->tune.fir_generic, 0) == 0)
+    if (fir_takes_stream(c))
         return launch_rrc_fir_stream(x, memory, y, c->d_taps, nframes, length, c->stream, in_pitch, c->ncu);
     return launch_rrc_fir(x, memory, y, c->d_taps, nframes, length, c->stream, in_pitch);
 }
@@ -658,6 +671,7 @@ int qpsk_rrc_fir_batch(qpsk_ctx *c, float *d_memory, const float *d_in, float *d
         src = (const float *)c->mixed.p;
     }
     KERNEL_TRY(fir_full_rate(c, src, d_memory, d_out, nframes, length));
+    c->last_kernel = fir_takes_stream(c) ? "rrc_fir_stream_kernel" : "rrc_fir_kernel";
     if (d_memory) KERNEL_TRY(launch_delay_line(src, d_memory, nframes, length, c->stream));
     return QPSK_OK;
 }

@@ -135,21 +135,31 @@ rrc_fir_stream_kernel(const float2 *__restrict__ x, const float2 *__restrict__ m
     }
 }
 
-/* symmetric taps only (the caller checks).  ncu: compute units of the device */
+/* how a batch is cut into runs.  ncu: compute units of the device */
+FirRuns rrc_fir_stream_runs(int nframes, int length, int ncu)
+{
+    using namespace firs;
+    if (ncu < 1) ncu = 256;
+    FirRuns r;
+    r.ntiles = (length + TILE - 1) / TILE;
+    /* runs per frame: enough to give every wave slot of the chip a run when the batch has few delay lines */
+    const long long slots = (long long)ncu * 4 * WAVES_PER_SIMD;
+    r.parts = (int)((slots + nframes - 1) / nframes);
+    if (r.parts > r.ntiles) r.parts = r.ntiles;
+    if (r.parts < 1) r.parts = 1;
+    r.tpp = (r.ntiles + r.parts - 1) / r.parts;
+    r.parts = (r.ntiles + r.tpp - 1) / r.tpp;
+    return r;
+}
+
+/* symmetric taps only (the caller checks) */
 int launch_rrc_fir_stream(const float *x, const float *memory, float *y, const float *taps, int nframes, int length,
                           hipStream_t s, size_t in_pitch, int ncu)
 {
     using namespace firs;
     if (in_pitch == 0) in_pitch = (size_t)length;
-    if (ncu < 1) ncu = 256;
-    const int ntiles = (length + TILE - 1) / TILE;
-    /* runs per frame: enough to give every wave slot of the chip a run when the batch has few delay lines */
-    const long long slots = (long long)ncu * 4 * WAVES_PER_SIMD;
-    int parts = (int)((slots + nframes - 1) / nframes);
-    if (parts > ntiles) parts = ntiles;
-    if (parts < 1) parts = 1;
-    const int tpp = (ntiles + parts - 1) / parts;
-    parts = (ntiles + tpp - 1) / tpp;
+    const FirRuns runs = rrc_fir_stream_runs(nframes, length, ncu);
+    const int parts = runs.parts, tpp = runs.tpp;
     const int aligned = (reinterpret_cast<uintptr_t>(x) % 16) == 0 && (reinterpret_cast<uintptr_t>(y) % 16) == 0 && (in_pitch % 2) == 0;
     const long long units = (long long)nframes * parts;
     hipLaunchKernelGGL(rrc_fir_stream_kernel, dim3((unsigned)((units + WAVES - 1) / WAVES)), dim3(64 * WAVES), 0, s,

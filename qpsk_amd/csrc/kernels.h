@@ -151,6 +151,10 @@ int launch_rrc_fir(const float *x, const float *memory, float *y, const float *t
 /* firstream.hip: the same filter as the generated stream fir_full8s_asm.h (SYMMETRIC taps only: the caller checks) */
 int launch_rrc_fir_stream(const float *x, const float *memory, float *y, const float *taps, int nframes, int length,
                           hipStream_t s, size_t in_pitch = 0, int ncu = 0);
+/* its run geometry: a frame is ntiles 512-output tiles, cut into parts runs of tpp consecutive tiles (the last may be shorter), one
+ * wave per run; ncu: compute units of the device (qpsk_test_fir_runs reports it) */
+struct FirRuns { int ntiles, parts, tpp; };
+FirRuns rrc_fir_stream_runs(int nframes, int length, int ncu);
 int launch_delay_line(const float *x, float *memory, int nframes, int length, hipStream_t s);
 /* firfast.hip: overlap-save FIR, 512-point fp32 FFTs (not a parity path); H, tw: [512][2] floats from qpsk_host_fir_fast_tables */
 int launch_rrc_fir_fast(const float *x, const float *memory, float *y, const float *H, const float *tw, int nframes, int length,

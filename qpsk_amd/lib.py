@@ -60,7 +60,7 @@ API_SYMBOLS = [
     "qpsk_deframer_reset_coded", "qpsk_deframer_push_coded",
     "qpsk_soft_batch", "qpsk_conv_encode_batch", "qpsk_viterbi_batch",
     "qpsk_punct_ntx", "qpsk_conv_encode_punct_batch", "qpsk_viterbi_punct_batch", "qpsk_deframer_reset_coded_punct",
-    "qpsk_test_viterbi_launches", "qpsk_test_deframer_advance",
+    "qpsk_test_viterbi_launches", "qpsk_test_deframer_advance", "qpsk_test_fir_runs",
     "qpsk_frame_len", "qpsk_frame_batch",
     "qpsk_ilv_stride", "qpsk_conv_encode_ilv_batch", "qpsk_viterbi_ilv_batch", "qpsk_frame_batch_ilv", "qpsk_deframer_reset_coded_ilv",
     "qpsk_rs_generator", "qpsk_rs_encode_batch", "qpsk_rs_decode_batch",
@@ -176,6 +176,7 @@ def load():
     L.qpsk_test_hist_state.argtypes = [vp, C.POINTER(i32)]
     L.qpsk_test_viterbi_launches.argtypes = [vp, C.POINTER(i32)]
     L.qpsk_test_deframer_advance.argtypes = [vp, C.c_longlong]
+    L.qpsk_test_fir_runs.argtypes = [vp, i32, i32, C.POINTER(i32)]
     L.qpsk_multi_create.argtypes = [C.POINTER(vp), C.POINTER(i32), i32, C.POINTER(Params)]
     L.qpsk_multi_destroy.argtypes = [vp]
     L.qpsk_multi_destroy.restype = None
@@ -306,7 +307,7 @@ class Modem:
         return self._sync_search(data, sync, lag_min, lag_max, nout)
 
     def last_kernel(self):
-        """Name of the receive kernel the last rx_batch*() call launched (which geometry served that shape)."""
+        """Name of the kernel the last rx_batch*() (or rrc_fir(), ...) call launched (which geometry served that shape)."""
         return self.L.qpsk_ctx_last_kernel(self.h).decode()
 
     def tune(self, **kw):
@@ -324,6 +325,13 @@ class Modem:
     def deframer_advance(self, delta):
         """Test hook: move both deframers' stream positions on by delta dibits (qpsk_test_deframer_advance)."""
         self._check(self.L.qpsk_test_deframer_advance(self.h, int(delta)))
+
+    def fir_runs(self, nframes, length):
+        """Test hook: (ntiles, parts, tpp) -- the runs of 512-output tiles rrc_fir_stream_kernel cuts this batch into on this device
+        (qpsk_test_fir_runs); nothing is launched."""
+        out = (C.c_int * 3)()
+        self._check(self.L.qpsk_test_fir_runs(self.h, int(nframes), int(length), out))
+        return tuple(out)
 
     def set_stream(self, stream):
         """Enqueue this context's work on another HIP stream (a torch.cuda.Stream or a raw handle; None = default)."""

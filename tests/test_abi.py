@@ -216,6 +216,13 @@ def test_no_gpu_means_error_not_fallback(qpsk_lib):
     assert qpsk_lib.qpsk_unpack_symbols_host(pk, 1, 5, out) == 0 and list(out) == [0, 1, 2, 3, 2]      # plain host code: runs anywhere
 
 
+def test_fir_runs_hook_refuses_a_null_context(qpsk_lib):
+    """qpsk_test_fir_runs is host arithmetic behind an argument check: without a context it is QPSK_ERR_ARG and out[] stays"""
+    out = (C.c_int * 3)(-7, -7, -7)
+    assert qpsk_lib.qpsk_test_fir_runs(None, 5, 4097, out) == -2 and list(out) == [-7, -7, -7]
+    assert b"qpsk_test_fir_runs" in qpsk_lib.qpsk_last_error()
+
+
 def test_bad_arguments_are_rejected(qpsk_lib):
     # argument validation happens before any device work only when a device exists; without one the
     # device error wins -- either way nothing is computed
