@@ -651,6 +651,74 @@ int qpsk_rs_decode_batch(qpsk_ctx *ctx, const uint8_t *d_in, long long in_pitch,
                          uint8_t *d_out, long long out_pitch, int32_t *d_info);
 
 /* -------------------------------------------------------------------------
+ * VITERBI STREAM: the decoder of CONVOLUTIONAL CODE for a code that runs continuously -- no packets, no tails, no row that ends (the inner
+ * code of DVB-S behind REED-SOLOMON's (204, 188) is one).  It carries its path metrics and a ring of decision words from call to call and
+ * emits every bit once it is `depth` steps old.  The library's own definition, integers only, no tolerance anywhere (parity unpinned,
+ * DESIGN.md 4.4.13), restated in numpy by tests/test_viterbi_stream_cpu.py (viterbi_stream_ref, conv_encode_stream_ref).  Code, branch
+ * metric, step, the tie rule (A TIE KEEPS p0), the -128 -> -127 rule and the erasure 0 are word for word qpsk_viterbi_batch's.
+ *
+ * RESET (nstreams, depth D, window W, pattern).  nstreams >= 1; D and W multiples of 64, both >= 64, D + W <= 8192; (period, keep0, keep1) a
+ *   pattern under PUNCTURING's rules, (1, 1, 1) = rate 1/2, K = popc(keep0) + popc(keep1).
+ * PUSH.  Every stream gets the same number ntx of transmitted dibits, rows row_pitch dibits apart in the layout qpsk_soft_batch writes
+ *   (0 = ntx; otherwise >= ntx; what lies between rows is never read).  A push carries WHOLE PATTERN PERIODS: 2 ntx must be a multiple of K,
+ *   and the push holds n = (2 ntx / K) period trellis steps, 1 <= n <= 131072; anything else is QPSK_ERR_ARG with nothing launched and the
+ *   state untouched.  At rate 1/2 every ntx >= 1 is legal; for the four named patterns every multiple of 12 dibits is.  So the pattern's
+ *   phase is 0 at a push's first step, and within a push the sent bits are numbered as PUNCTURING does with nsteps = n:
+ *       s_j of the push's step u = sent(u, j) ? v(idx(u, j)) : 0          (after the -128 rule)
+ * FORWARD.  t = the step's absolute number since the reset (or the last flush), 64-bit, the same for every stream.
+ *   start: pm[0] = 0, the 63 others NEG = -2^30.
+ *   NORMALISATION: before every step with t % 64 == 0, max(pm) is subtracted from all 64 metrics.  (At t = 0 that is 0.  Every state is
+ *   reachable by t = 6, so from t = 64 on max - min <= 3048 and the int32 metrics stay bounded for ever; a common offset changes no
+ *   decision and no argmax.)  The step itself is qpsk_viterbi_batch's.
+ * DECISION POINTS: at every T = k W, k >= 1, after step T - 1:
+ *       st = the state of the largest pm, TIES TO THE LOWEST STATE NUMBER
+ *       for t = T-1 down to max(0, T-D-W):   bit[t] = st & 1;   st = (st >> 1) | (d[t][st] << 5)
+ *   Bits t in [T-D-W, T-D) with t >= 0 are FINAL and emitted, in ascending order; if T <= D nothing is.  Emitted counts are therefore
+ *   multiples of 64 bits.  NOTHING DEPENDS ON HOW THE STEPS WERE CUT INTO PUSHES: any partition of the same steps gives the same
+ *   concatenated bits, the same summed counts and the same state and spread at every decision point.
+ *   A decision walks D + W steps to emit W: that cost is part of the definition and the caller's choice of W against latency.
+ * FLUSH (flags).  With `total` steps in: st = 0 with QPSK_VITERBI_STREAM_TERMINATED, otherwise the argmax as above (the reported spread is
+ *   the metrics' either way); trace back from total - 1 down to e = max(0, floor(total / W) W - D), e = 0 while total < W -- the first bit
+ *   not yet emitted -- and emit [e, total): fewer than D + W bits.  Afterwards the streams are as after a reset with the same parameters.
+ * CHANNEL ERRORS.  The emitted bit sequence of a stream is re-encoded (register fed by all earlier emitted bits, zeros before bit 0); for
+ *   every emitted step, a non-zero soft value whose sign disagrees with the re-encoded bit is an error (qpsk_viterbi_batch's rule).
+ * OUTPUTS of a push or a flush:
+ *   d_bits [nstreams][bits_pitch bytes] uint8: bit j of THIS CALL's emitted bits in byte j >> 3 at position j & 7; bytes beyond
+ *       ceil(nbits / 8) are not written.  bits_pitch 0 = ceil(nbits / 8); one too small for this call's bits is QPSK_ERR_ARG, nothing launched
+ *   *h_nbits (may be NULL) = the bits each stream emits in this call: host arithmetic on total, D and W, handed back without a
+ *       synchronisation.  qpsk_viterbi_stream_emits(ntx) = what a push of ntx would emit now (< 0: an error code), to size d_bits by
+ *   d_info [nstreams][4] int32, for this call = { channel errors among the emitted steps, non-zero soft values among the emitted steps,
+ *       the state the call's last decision traced from (a flush: its st) or -1 if it had none, max(pm) - min(pm) at that decision or 0 }
+ *   Either output may be NULL, not both.
+ * Hence, and tested:  (1) partition independence, above;  (2) if floor(N / W) W <= D nothing is emitted before the flush, whose bits equal
+ *   qpsk_viterbi_batch / _punct_batch on the N-step row with QPSK_VITERBI_OPEN_END (flags 0 with TERMINATED) and whose error count is that
+ *   call's d_info[3];  (3) on noise-free input (+-64, any named pattern, D = W = 64) the output is the data.
+ *
+ *   qpsk_viterbi_stream_reset   one decoder per context; a refused reset leaves an armed one as it was, a failed allocation
+ *                (QPSK_ERR_ALLOC) the context usable
+ *   qpsk_viterbi_stream_push / _flush   QPSK_ERR_STATE before a reset; d_soft 2-byte, d_info 4-byte aligned
+ *   qpsk_conv_encode_stream_batch   the transmit twin: qpsk_conv_encode_punct_batch without a tail over a register that is carried.  The six
+ *                bits before the row come from d_state_in[row] (uint8, bit k = the bit of step -1 - k; NULL = 0), the register's low six
+ *                bits after the row go to d_state_out[row] (may be NULL; must not overlap d_state_in).  nbits covers whole periods that send
+ *                whole dibits (nbits % period == 0, an even number of sent bits); d_dibits [nrows][nbits / period * K / 2]
+ * The calls are stream-ordered on the context's stream and touch neither the deframer, the receive streams, the histogram mode's guess
+ * nor the Viterbi scratch buffer: qpsk_viterbi_batch may be called between pushes.  qpsk_ctx_last_kernel() names viterbi_stream_kernel,
+ * viterbi_stream_punct_kernel (any pattern but (1, 1, 1)), viterbi_stream_flush_kernel, viterbi_stream_init_kernel or
+ * conv_encode_stream_kernel.
+ * Not built: d_flip (a descrambler on the soft values) and an interleaver in front of the stream decoder; streams pushed with different
+ * step counts; resolving the quarter-turn and pattern-phase ambiguity of a continuous link (the caller does, with d_info[0] / d_info[1] as
+ * the handle: INTEGRATION.md 2.0); qpsk_multi.
+ * ------------------------------------------------------------------------- */
+enum { QPSK_VITERBI_STREAM_TERMINATED = 1 };
+int qpsk_viterbi_stream_reset(qpsk_ctx *ctx, int nstreams, int depth, int window, int period, uint32_t keep0, uint32_t keep1);
+int qpsk_viterbi_stream_emits(qpsk_ctx *ctx, int ntx);
+int qpsk_viterbi_stream_push(qpsk_ctx *ctx, const int8_t *d_soft, long long row_pitch, int ntx, uint8_t *d_bits, long long bits_pitch,
+                             int32_t *d_info, int *h_nbits);
+int qpsk_viterbi_stream_flush(qpsk_ctx *ctx, int flags, uint8_t *d_bits, long long bits_pitch, int32_t *d_info, int *h_nbits);
+int qpsk_conv_encode_stream_batch(qpsk_ctx *ctx, const uint8_t *d_bits, int nrows, int nbits, int period, uint32_t keep0, uint32_t keep1,
+                                  const uint8_t *d_state_in, uint8_t *d_state_out, uint8_t *d_dibits);
+
+/* -------------------------------------------------------------------------
  * The stages on their own (each is what the corresponding reference function
  * computes, batched).
  * ------------------------------------------------------------------------- */
@@ -902,6 +970,10 @@ int qpsk_test_viterbi_launches(qpsk_ctx *ctx, int *out);
  * call.  QPSK_ERR_ARG for delta < 0 or delta > 2^62; QPSK_ERR_STATE before a reset, after a failed push, or while a stream has seen fewer
  * than nsync - 1 dibits. */
 int qpsk_test_deframer_advance(qpsk_ctx *ctx, long long delta);
+/* Test hook (stream positions beyond 32 bits, VITERBI STREAM): synchronises the context's stream, then adds delta to the streaming decoder's
+ * position counters; metrics, pending pairs and the ring stay.  Everything after it comes out as without the call.  QPSK_ERR_ARG for
+ * delta < 0, delta > 2^62 or a delta that is no multiple of the window; QPSK_ERR_STATE before a reset or while total < depth + window. */
+int qpsk_test_viterbi_stream_advance(qpsk_ctx *ctx, long long delta);
 
 #ifdef __cplusplus
 }

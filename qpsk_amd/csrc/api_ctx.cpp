@@ -256,6 +256,7 @@ void qpsk_ctx_destroy(qpsk_ctx *c)
     c->tx.release();
     c->df.release();
     c->framer.release();
+    c->vs.release();
     delete c;
 }
 

@@ -7,6 +7,7 @@
  *   api_streams.cpp  the running streams and the transmit side
  *   api_coded.cpp    soft decisions, the convolutional code, Reed-Solomon
  *   api_packets.cpp  bit stages, the deframers, the framer
+ *   api_vstream.cpp  the streaming Viterbi decoder and the encoder that carries its register
  *
  * OWNERSHIP: each nested group of qpsk_ctx below names the one unit that reads and writes it; the members outside a group
  * (configuration, scratch buffers) are every unit's.  DESIGN.md, "The host layer", lists the few places that reach across.
@@ -181,6 +182,19 @@ struct QPSK_UNIT_LOCAL Framer {
     void release();
 };
 
+/* api_vstream.cpp.  The streaming Viterbi decoder (qpsk_viterbi_stream_*): per-stream state on the device (viterbi_stream.hip: metrics, pending
+ * pairs, the last emitted word, the ring of decision and ballot words); the positions are the same for every stream and are the host's */
+struct QPSK_UNIT_LOCAL ViterbiStream {
+    uint8_t *state = nullptr;
+    size_t stride = 0;
+    int nstreams = 0, depth = 0, window = 0;
+    Puncture punct = {1, 1u, 1u, 2};
+    bool punctured = false;       /* any pattern but (1, 1, 1): viterbi_stream_punct_kernel */
+    long long total = 0;          /* trellis steps since the reset or the last flush, qpsk_test_viterbi_stream_advance's delta included */
+    long long advanced = 0;       /* the sum of those deltas: the ring is indexed by (total - advanced) / 64 */
+    void release();               /* leaves the group value-initialised: no decoder.  Behind a synchronisation of the context's stream */
+};
+
 } // namespace qpsk
 
 struct qpsk_ctx {
@@ -217,6 +231,7 @@ struct qpsk_ctx {
     qpsk::Transmitters tx;
     qpsk::Deframer df;
     qpsk::Framer framer;
+    qpsk::ViterbiStream vs;
 };
 
 namespace qpsk {

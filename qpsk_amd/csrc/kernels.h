@@ -350,6 +350,38 @@ int launch_viterbi(const int8_t *soft, size_t pitch, int nrows, int nsteps, cons
 /* conv_encode_kernel (one thread per step), or one thread per transmitted dibit: conv_encode_punct_kernel / conv_encode_ilv_kernel, dibits
  * [nrows][ntx], ntx >= 1 */
 int launch_conv_encode(const uint8_t *bits, int nrows, int nbits, int nsteps, const CodedLayout &layout, uint8_t *dibits, hipStream_t s);
+/* viterbi_stream.hip: the streaming decoder (VITERBI STREAM in include/qpsk_hip.h).  One wave per stream over state_stride bytes of state each
+ * (vstream_state_stride(nring); the layout is that file's).  The host keeps the positions and hands a launch small numbers only:
+ *     nring, dblk, wblk   (D + W) / 64, D / 64, W / 64
+ *     pc                  pending steps the state holds, total % 64
+ *     slot                push: the ring slot of the first block it completes; flush: the slot of the newest block (the partial one if pc > 0)
+ *     have                push: the blocks the ring holds, min(total / 64, nring); flush: the blocks it walks, all of them emitted
+ *     wphase              push: whole blocks since the last decision point, (total / 64) % wblk
+ *     n, soft, pitch      push: the trellis steps of the call, and every stream's row of transmitted dibits, pitch dibits apart
+ * bits rows bits_pitch bytes apart, info [nstreams][4]; one of the two may be NULL */
+constexpr int VSTREAM_MAX_SPAN = 8192;      /* D + W at most */
+constexpr int VSTREAM_TERMINATED = 1;
+struct VStreamArgs {
+    const int8_t *soft;
+    size_t pitch;
+    int n, pc, slot, have, wphase;
+    int nring, dblk, wblk;
+    int flags;                    /* flush: VSTREAM_TERMINATED */
+    uint8_t *state;
+    size_t state_stride;
+    uint8_t *bits;
+    size_t bits_pitch;
+    int32_t *info;
+    Puncture punct;
+};
+size_t vstream_state_stride(int nring);
+int launch_vstream_init(const VStreamArgs &a, int nstreams, hipStream_t s);
+/* viterbi_stream_kernel, or punctured = true viterbi_stream_punct_kernel */
+int launch_vstream_push(const VStreamArgs &a, int nstreams, bool punctured, hipStream_t s);
+int launch_vstream_flush(const VStreamArgs &a, int nstreams, hipStream_t s);
+/* conv_encode_stream_kernel: nbits whole periods with an even number of sent bits; state_in / state_out [nrows] or NULL */
+int launch_conv_encode_stream(const uint8_t *bits, int nrows, int nbits, const Puncture &p, const uint8_t *state_in, uint8_t *state_out,
+                              uint8_t *dibits, hipStream_t s);
 /* deframe.hip: qpsk_deframer_push.  Per stream, state_stride bytes of state: the header, the carried tail (the ring values of the last
  * min(len, nsync-1) dibits) at DEFRAME_TAIL_OFFSET, the pending packet's received payload (ring values) at DEFRAME_PEND_OFFSET */
 struct DeframeHeader {

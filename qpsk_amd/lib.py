@@ -64,6 +64,8 @@ API_SYMBOLS = [
     "qpsk_frame_len", "qpsk_frame_batch",
     "qpsk_ilv_stride", "qpsk_conv_encode_ilv_batch", "qpsk_viterbi_ilv_batch", "qpsk_frame_batch_ilv", "qpsk_deframer_reset_coded_ilv",
     "qpsk_rs_generator", "qpsk_rs_encode_batch", "qpsk_rs_decode_batch",
+    "qpsk_viterbi_stream_reset", "qpsk_viterbi_stream_emits", "qpsk_viterbi_stream_push", "qpsk_viterbi_stream_flush",
+    "qpsk_conv_encode_stream_batch", "qpsk_test_viterbi_stream_advance",
 ]
 # the named puncturing patterns of include/qpsk_hip.h (QPSK_PUNCT_*): rate -> (period, keep0, keep1), bit r of a mask = step r of the period
 PUNCTURE = {"1/2": (1, 0x1, 0x1), "2/3": (2, 0x1, 0x3), "3/4": (3, 0x5, 0x3), "5/6": (5, 0x15, 0x0B), "7/8": (7, 0x51, 0x2F)}
@@ -176,6 +178,12 @@ def load():
     L.qpsk_test_hist_state.argtypes = [vp, C.POINTER(i32)]
     L.qpsk_test_viterbi_launches.argtypes = [vp, C.POINTER(i32)]
     L.qpsk_test_deframer_advance.argtypes = [vp, C.c_longlong]
+    L.qpsk_viterbi_stream_reset.argtypes = [vp, i32, i32, i32, i32, u32, u32]
+    L.qpsk_viterbi_stream_emits.argtypes = [vp, i32]
+    L.qpsk_viterbi_stream_push.argtypes = [vp, vp, C.c_longlong, i32, vp, C.c_longlong, vp, C.POINTER(i32)]
+    L.qpsk_viterbi_stream_flush.argtypes = [vp, i32, vp, C.c_longlong, vp, C.POINTER(i32)]
+    L.qpsk_conv_encode_stream_batch.argtypes = [vp, vp, i32, i32, i32, u32, u32, vp, vp, vp]
+    L.qpsk_test_viterbi_stream_advance.argtypes = [vp, C.c_longlong]
     L.qpsk_test_fir_runs.argtypes = [vp, i32, i32, C.POINTER(i32)]
     L.qpsk_multi_create.argtypes = [C.POINTER(vp), C.POINTER(i32), i32, C.POINTER(Params)]
     L.qpsk_multi_destroy.argtypes = [vp]
@@ -282,6 +290,7 @@ class Modem:
         self.nsym = self.L.qpsk_ctx_nsym(h)
         self.frame_size = frame_size
         self.nstreams = 0
+        self._vs_streams = 0      # streams of the streaming Viterbi decoder (viterbi_stream_reset)
 
     def _check(self, rc):
         if rc != 0:
@@ -622,6 +631,82 @@ class Modem:
                                               _ptr(o["bits"]), _ptr(o["info"])))
         o["_keep"] = (q, f)      # the inputs stay alive until the caller is done with the outputs (stream order)
         return o
+
+    # ---- the streaming decoder (VITERBI STREAM in include/qpsk_hip.h)
+    def viterbi_stream_reset(self, nstreams, depth=128, window=256, puncture=None):
+        """qpsk_viterbi_stream_reset: nstreams decoders that carry their path from call to call and emit every bit once it is depth steps
+        old, `window` bits per decision (both multiples of 64, depth + window <= 8192).  puncture: a key of PUNCTURE or a (period, keep0,
+        keep1) tuple; None = rate 1/2."""
+        pat = _pattern("1/2" if puncture is None else puncture)
+        self._check(self.L.qpsk_viterbi_stream_reset(self.h, int(nstreams), int(depth), int(window), *pat))
+        self._vs_streams = int(nstreams)
+
+    def viterbi_stream_emits(self, ntx):
+        """qpsk_viterbi_stream_emits: the bits per stream a viterbi_stream() of ntx transmitted dibits would emit now; host only"""
+        rc = self.L.qpsk_viterbi_stream_emits(self.h, int(ntx))
+        self._check(min(rc, 0))
+        return rc
+
+    def _viterbi_stream_out(self, nbits):
+        t = self.torch
+        return dict(bits=self.empty((self._vs_streams, (nbits + 7) // 8), t.uint8), info=self.empty((self._vs_streams, 4), t.int32))
+
+    def viterbi_stream(self, soft, pitch=0, ntx=None):
+        """qpsk_viterbi_stream_push: soft (S, ntx, 2) int8, the TRANSMITTED symbols of every stream (whole periods of the pattern) -- or,
+        with pitch, (S, pitch, 2) of which the first ntx dibits of each row are pushed.  Dict of torch tensors bits (S, nbits / 8) uint8
+        (this call's emitted bits, low bits first), nbits, info (S, 4) int32 = (channel errors, non-zero soft values, the state the last
+        decision traced from or -1, the metric spread there)."""
+        t = self.torch
+        if isinstance(soft, dict):
+            soft = soft["soft"]
+        if not self._vs_streams:
+            raise QpskError("viterbi_stream() before viterbi_stream_reset()")
+        q = self._dev(soft, t.int8)
+        if q.dim() != 3 or q.shape[0] != self._vs_streams or q.shape[2] != 2 or (pitch and q.shape[1] != pitch):
+            raise ValueError("viterbi_stream() input must be (streams = %d, ntx or pitch, 2) int8" % self._vs_streams)
+        ntx = q.shape[1] if ntx is None else int(ntx)
+        o = self._viterbi_stream_out(self.viterbi_stream_emits(ntx))
+        n = C.c_int32(-1)
+        self._check(self.L.qpsk_viterbi_stream_push(self.h, _ptr(q), int(pitch), ntx, _ptr(o["bits"]), o["bits"].shape[1], _ptr(o["info"]),
+                                                    C.byref(n)))
+        o["nbits"] = n.value
+        o["_keep"] = (q,)      # the input stays alive until the caller is done with the outputs (stream order)
+        return o
+
+    def viterbi_stream_flush(self, terminated=False):
+        """qpsk_viterbi_stream_flush: the bits not yet emitted, traced from state 0 (terminated) or from the best state; the streams are
+        then as after viterbi_stream_reset().  Dict as viterbi_stream()."""
+        if not self._vs_streams:
+            raise QpskError("viterbi_stream_flush() before viterbi_stream_reset()")
+        o = self._viterbi_stream_out(8192)      # a flush emits fewer than depth + window <= 8192 bits
+        n = C.c_int32(-1)
+        self._check(self.L.qpsk_viterbi_stream_flush(self.h, 1 if terminated else 0, _ptr(o["bits"]), o["bits"].shape[1], _ptr(o["info"]),
+                                                     C.byref(n)))
+        o["nbits"] = n.value
+        o["bits"] = o["bits"][:, :(n.value + 7) // 8]
+        return o
+
+    def viterbi_stream_advance(self, delta):
+        """Test hook: move the streaming decoder's position counters on by delta steps (qpsk_test_viterbi_stream_advance)."""
+        self._check(self.L.qpsk_test_viterbi_stream_advance(self.h, int(delta)))
+
+    def conv_encode_stream(self, bits_packed, nbits, state=None, puncture=None):
+        """qpsk_conv_encode_stream_batch: conv_encode() without a tail over a register that is carried: bits_packed (R, ceil(nbits / 8)),
+        state (R,) uint8 = the register's low six bits before the row (None = 0) -> (dibits (R, ntx) uint8, state (R,) uint8 behind the
+        row).  nbits covers whole periods of the pattern that send whole dibits."""
+        t = self.torch
+        b = self._dev(bits_packed, t.uint8)
+        if b.dim() != 2 or b.shape[1] != (int(nbits) + 7) // 8:
+            raise ValueError("conv_encode_stream() input must be (rows, ceil(nbits / 8)) uint8")
+        pat = _pattern("1/2" if puncture is None else puncture)
+        K = bin(pat[1]).count("1") + bin(pat[2]).count("1")
+        st = None if state is None else self._dev(state, t.uint8)
+        if st is not None and tuple(st.shape) != (b.shape[0],):
+            raise ValueError("conv_encode_stream() state must be (rows,) uint8")
+        out = self.empty((b.shape[0], max(int(nbits) // pat[0] * K // 2, 1)), t.uint8)
+        nxt = self.empty((b.shape[0],), t.uint8)
+        self._check(self.L.qpsk_conv_encode_stream_batch(self.h, _ptr(b), b.shape[0], int(nbits), *pat, _ptr(st), _ptr(nxt), _ptr(out)))
+        return out, nxt
 
     # ---- stages
     def rrc_fir(self, x, memory=None, fast=False):
