@@ -324,6 +324,8 @@ class Reference:
                   "set_frequency", "set_phase", "set_max_freq", "set_min_freq"):
             getattr(L, n).argtypes = [C.c_float]
         L.create_control_loop.argtypes = [C.c_float, C.c_float, C.c_float]
+        for n in ("set_max_freq", "set_min_freq", "update_gains"):
+            getattr(L, n).restype = None
 
     def reset(self, loop_bw=np.float32(TAU / 100.0), min_freq=-1.0, max_freq=1.0, rrc_alpha=0.35, tx_hz=1550.0,
               rx_hz=1500.0):

@@ -220,3 +220,64 @@ def test_zero_symbols_and_signed_zero_states_match_reference(oracle, reference, 
                 d = ref.decimated
                 d[2 * ref.nsym - 1] = m.decimated[2 * ref.nsym - 1]
                 ref.set_decimated(d)
+
+
+# ------------------------------------------------------------------ the loop's control surface (tests/loopsched.py)
+@pytest.mark.parametrize("name", ["shipped", "c1small"])
+def test_loop_edits_between_blocks_match_reference(oracle, reference, name):
+    """costas_loop.h setters, create_control_loop() and a host-side loop step between rx_frame() calls (loopsched.SCHEDULE): the
+    reference's file statics against the oracle's modem with the same edits on m.s.loop.  The drop-in's rx_frame() is tested
+    against this oracle on the GPU (tests/test_dropin_gpu.py); this pins the oracle there."""
+    from loopsched import NBLOCKS, SCHEDULE, apply_lib, apply_oracle, state_of, stimulus
+    ref = reference(name)
+    ref.reset(BW, -1.0, 1.0, .35, 1550.0, 1500.0)
+    L = ref.frame_size
+    pcm = stimulus(oracle, ref.fs, ref.rs, L, 1500.0)
+    m = oracle.modem(ref.fs, ref.rs, L, loop_bw=BW)
+    m.set_mixer(ref.mixer)
+    for k in range(NBLOCKS):
+        if k:
+            apply_lib(ref.lib, SCHEDULE[k - 1])
+            apply_oracle(oracle, m.s.loop, SCHEDULE[k - 1])
+            assert bits_equal(ref.costas_state, state_of(m.s.loop)), ("edits", k)
+        blk = pcm[k * L:(k + 1) * L]
+        ref.rx_pcm(blk)
+        m.rx_pcm(blk)
+        assert bits_equal(ref.symbols, m.symbols) and bits_equal(ref.costas_frame, m.costas_frame), k
+        assert ref.phase.tobytes() == m.phase.tobytes() and ref.freq.tobytes() == m.freq.tobytes(), k
+        assert ref.offset_hz.tobytes() == m.offset_hz.tobytes(), k
+        assert bits_equal(ref.costas_state, state_of(m.s.loop)), k
+        if ref.cycles < 8:      # SURVEY Q5, as in test_streaming_pcm_matches_reference: the reference's last pick may lie past its array
+            d = ref.decimated
+            d[2 * ref.nsym - 1] = m.decimated[2 * ref.nsym - 1]
+            ref.set_decimated(d)
+
+
+def test_costas_scalar_calls_left_out_match_reference(oracle, reference):
+    """What test_costas_scalar_api_matches_reference leaves out (loopsched.SETTER_LIST): limits moved and a frequency beyond either,
+    set_phase() at +-float32(2 pi), signed zeros and +-1e6, update_gains() on its own after set_alpha().  Oracle side: the qo_
+    functions as loopsched.apply_oracle() uses them, create_control_loop() as the reference's setter sequence on the existing struct."""
+    from loopsched import SETTER_LIST, TRIPLES, apply_lib, apply_oracle, state_of
+    from oracle.pyoracle import Costas
+    ref = reference("shipped")
+    ref.reset()
+    c = Costas(*[float(v) for v in ref.costas_state])
+    assert bits_equal(ref.costas_state, state_of(c))
+    for bw, lo, hi in TRIPLES:
+        for op in [("create_control_loop", bw, lo, hi)] + SETTER_LIST:
+            apply_lib(ref.lib, [op])
+            apply_oracle(oracle, c, [op])
+            assert bits_equal(ref.costas_state, state_of(c)), op
+
+
+def test_detector_and_slicer_grid_match_reference(oracle, reference):
+    """phase_detector() (costas_loop.c:44-59) and qpsk_demod() (qpsk.c:74-79) on loopsched.detector_grid(): signed zeros, denormals,
+    +-FLT_MAX, NaN, the diagonals where the slicer's difference is an exact zero.  NaN results compare as NaN where NaN."""
+    from loopsched import detector_grid, oracle_detector, same_with_nans
+    ref = reference("shipped")
+    grid = detector_grid()
+    e, s = oracle_detector(oracle, grid)
+    re_ = np.array([ref.phase_detector(float(a), float(b)) for a, b in grid], np.float32)
+    rs_ = np.array([ref.demod(float(a), float(b)) for a, b in grid], np.uint8)
+    assert same_with_nans(re_, e)
+    assert bits_equal(rs_, s)
