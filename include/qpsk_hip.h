@@ -706,8 +706,9 @@ int qpsk_rs_decode_batch(qpsk_ctx *ctx, const uint8_t *d_in, long long in_pitch,
  * viterbi_stream_punct_kernel (any pattern but (1, 1, 1)), viterbi_stream_flush_kernel, viterbi_stream_init_kernel or
  * conv_encode_stream_kernel.
  * Not built: d_flip (a descrambler on the soft values) and an interleaver in front of the stream decoder; streams pushed with different
- * step counts; resolving the quarter-turn and pattern-phase ambiguity of a continuous link (the caller does, with d_info[0] / d_info[1] as
- * the handle: INTEGRATION.md 2.0); qpsk_multi.
+ * step counts; resolving the quarter-turn (90 degrees) and pattern-phase ambiguity of a continuous link (the caller does, with d_info[0] /
+ * d_info[1] as the handle: INTEGRATION.md 2.0 -- the half turn alone is resolved behind the decoder, by OUTER LINK's word sync, and the
+ * byte interleaver of a continuous link is OUTER LINK's too); qpsk_multi.
  * ------------------------------------------------------------------------- */
 enum { QPSK_VITERBI_STREAM_TERMINATED = 1 };
 int qpsk_viterbi_stream_reset(qpsk_ctx *ctx, int nstreams, int depth, int window, int period, uint32_t keep0, uint32_t keep1);
@@ -717,6 +718,68 @@ int qpsk_viterbi_stream_push(qpsk_ctx *ctx, const int8_t *d_soft, long long row_
 int qpsk_viterbi_stream_flush(qpsk_ctx *ctx, int flags, uint8_t *d_bits, long long bits_pitch, int32_t *d_info, int *h_nbits);
 int qpsk_conv_encode_stream_batch(qpsk_ctx *ctx, const uint8_t *d_bits, int nrows, int nbits, int period, uint32_t keep0, uint32_t keep1,
                                   const uint8_t *d_state_in, uint8_t *d_state_out, uint8_t *d_dibits);
+
+/* -------------------------------------------------------------------------
+ * OUTER LINK: what stands between VITERBI STREAM and REED-SOLOMON on a continuously coded link -- word sync with carried state, polarity
+ * (half-turn) resolution, a convolutional (Forney) byte deinterleaver, and aligned words out, ready for qpsk_rs_decode_batch through a
+ * pitch; and the interleaver that is its transmit twin.  The library's own definition, integers only, no tolerance anywhere (parity
+ * unpinned: the reference has no FEC), restated in numpy by tests/test_outer_cpu.py (outer_ref, outer_interleave_ref).
+ *
+ * RESET (nstreams >= 1; n = 2..255 bytes a word; branches I = 1..32 with n % I == 0, the cell is M = n / I so that M I = n, as in DVB-S:
+ *   204 = 12 * 17; sync = one byte value; lock L = 1..16; drop = 0..16, 0 = never drop; flags of QPSK_OUTER_POLARITY | QPSK_OUTER_MSB_FIRST).
+ * BYTES.  For one stream let B be the concatenation of every bit pushed since the reset.
+ *       V(u) = sum_{i<8} B[u+i] << i          the first bit in bit 0: the packing of qpsk_viterbi_stream_push's d_bits and qpsk_pack_symbols
+ *       with MSB_FIRST                << (7-i)   DVB's order
+ *       m(u) = +1 if V(u) == sync;  -1 if POLARITY is set and V(u) == sync ^ 0xFF;  0 otherwise
+ * HUNT, from h (0 after a reset):  u* = the smallest u >= h with m(u) != 0 and m(u + 8 n i) == m(u) for every i < L.  The lock is declared by
+ *   the push that delivers bit u* + 8 n (L-1) + 7; every smaller candidate is decidable by then.  After it: u0 = u*, s = m(u*), c = 0, run = 0.
+ * LOCKED.  Raw word c is the bits [u0 + 8 n c, u0 + 8 n (c+1));  Y[c][q] = V(u0 + 8 (n c + q)) ^ (s < 0 ? 0xFF : 0).  Words are handled in
+ *   order of c, each by the push that delivers its last bit:
+ *     1. miss = (Y[c][0] != sync);  run = miss ? run + 1 : 0
+ *     2. if drop > 0 and run == drop: the lock is lost, nothing is emitted for c, HUNT resumes at h = u0 + 8 n c + 1, the words in flight
+ *        are gone
+ *     3. otherwise, if c >= I - 1, one word is emitted:  Z[q] = Y[c - (I - 1 - q mod I)][q], q < n, with pos = u0 + 8 n c (int64, counted
+ *        from the reset) and flags: bit 0 = (Z[0] != sync), bit 1 = (s < 0)
+ *     4. c += 1
+ *   The state machine runs as far as the bits that have arrived allow and no further; nothing is pending at an end: a word whose last bit
+ *   never comes is not emitted, and there is no flush.  THE RESULT DEPENDS ONLY ON B, NOT ON HOW B WAS CUT INTO PUSHES, except for which push
+ *   reports a word.
+ * WORD BOUND.  A push of nbits emits at most L + ceil(nbits / 8 n) words per stream; qpsk_outer_max_words(nbits) returns that by host
+ *   arithmetic (< 0: an error code).  (The tightest push -- one that completes a lock with L - 1 whole words behind it -- emits one word
+ *   fewer: emitted words end at least 8 n bits apart, and only a lock declared in the push adds words that ended before it, L - 1 of them.)
+ * PUSH.  Every stream gets the same nbits, 1..2^20, any value, not only multiples of 8.
+ *   d_bits [nstreams][bits_pitch bytes]: bit j of this call in byte j >> 3 at position j & 7 -- exactly what qpsk_viterbi_stream_push /
+ *       _flush write.  bits_pitch 0 = ceil(nbits / 8), otherwise >= that; what lies beyond a row's bits is never read
+ *   d_count [nstreams] int32, required: the true number of words of this call, also beyond max_words
+ *   d_words [nstreams][max_words][word_pitch]: word_pitch 0 = n, otherwise >= n; bytes between words are never written.  It is then
+ *       qpsk_rs_decode_batch's d_in with in_pitch = word_pitch and nrows = nstreams * max_words
+ *   d_pos [nstreams][max_words] int64, d_flags [nstreams][max_words] uint8: as above.  Each of these three may be NULL; only the first
+ *       min(count, max_words) entries of a stream are written
+ *   d_info [nstreams][4] int32 (may be NULL) = { 1 if locked after the call else 0, s or 0, locks declared in this call, locks lost in
+ *       this call }
+ *   No output may share a byte with the input or another output.  d_count and d_info 4-byte, d_pos 8-byte aligned.
+ * THE TRANSMIT TWIN.  qpsk_outer_interleave_batch:  Y[c][q] = X[c - q mod I][q] over d_words / d_out [nrows][nwords][n].  The I - 1 source
+ *   words before the call come from d_hist_in [nrows][I-1][n], the last I - 1 source words, oldest first (NULL = zeros); the last I - 1
+ *   source words after the call go to d_hist_out (may be NULL; must not overlap any input, nor may d_out).  This is Forney's interleaver with
+ *   I branches of j M cells, the sync byte on the undelayed branch, and the receiver's Z is then X delayed by I - 1 words.  A caller puts
+ *   `sync` into byte 0 of every word BEFORE RS-encoding it: the sync byte is data of the codeword, as in DVB.
+ *
+ *   qpsk_outer_reset   one link per context; a refused reset leaves an armed one as it was, a failed allocation (QPSK_ERR_ALLOC) the
+ *                context usable
+ *   qpsk_outer_push / _max_words   QPSK_ERR_STATE before a reset; anything outside the rules above is QPSK_ERR_ARG with nothing launched
+ *                and the state untouched
+ * The calls are stream-ordered on the context's stream and touch no other state of the context.  qpsk_ctx_last_kernel() names
+ * outer_push_kernel, outer_init_kernel or outer_interleave_kernel.
+ * Not built: DVB's inverted sync byte in every eighth word and its energy dispersal; cells other than n / I; streams pushed with different
+ * lengths; the quarter-turn (90 degrees) search, which stays with the error ratio; qpsk_multi.
+ * ------------------------------------------------------------------------- */
+enum { QPSK_OUTER_POLARITY = 1, QPSK_OUTER_MSB_FIRST = 2 };
+int qpsk_outer_reset(qpsk_ctx *ctx, int nstreams, int n, int branches, int sync, int lock, int drop, int flags);
+int qpsk_outer_max_words(qpsk_ctx *ctx, int nbits);
+int qpsk_outer_push(qpsk_ctx *ctx, const uint8_t *d_bits, long long bits_pitch, int nbits, int max_words, int32_t *d_count, uint8_t *d_words,
+                    long long word_pitch, long long *d_pos, uint8_t *d_flags, int32_t *d_info);
+int qpsk_outer_interleave_batch(qpsk_ctx *ctx, const uint8_t *d_words, int nrows, int nwords, int n, int branches, const uint8_t *d_hist_in,
+                                uint8_t *d_hist_out, uint8_t *d_out);
 
 /* -------------------------------------------------------------------------
  * The stages on their own (each is what the corresponding reference function
@@ -974,6 +1037,10 @@ int qpsk_test_deframer_advance(qpsk_ctx *ctx, long long delta);
  * position counters; metrics, pending pairs and the ring stay.  Everything after it comes out as without the call.  QPSK_ERR_ARG for
  * delta < 0, delta > 2^62 or a delta that is no multiple of the window; QPSK_ERR_STATE before a reset or while total < depth + window. */
 int qpsk_test_viterbi_stream_advance(qpsk_ctx *ctx, long long delta);
+/* Test hook (positions beyond 32 bits, OUTER LINK): synchronises the context's stream, then moves the outer link's position counter on by
+ * delta; the lock, the words in flight and the ring stay.  Later words are reported with pos + delta, everything else as without the call.
+ * QPSK_ERR_ARG for delta < 0, delta > 2^62 or a delta that is no multiple of 8; QPSK_ERR_STATE before a reset. */
+int qpsk_test_outer_advance(qpsk_ctx *ctx, long long delta);
 
 #ifdef __cplusplus
 }

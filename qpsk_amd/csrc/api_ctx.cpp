@@ -257,6 +257,7 @@ void qpsk_ctx_destroy(qpsk_ctx *c)
     c->df.release();
     c->framer.release();
     c->vs.release();
+    c->outer.release();
     delete c;
 }
 

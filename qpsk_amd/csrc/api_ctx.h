@@ -8,6 +8,7 @@
  *   api_coded.cpp    soft decisions, the convolutional code, Reed-Solomon
  *   api_packets.cpp  bit stages, the deframers, the framer
  *   api_vstream.cpp  the streaming Viterbi decoder and the encoder that carries its register
+ *   api_outer.cpp    the outer link behind it: word sync, the byte deinterleaver and the interleaver
  *
  * OWNERSHIP: each nested group of qpsk_ctx below names the one unit that reads and writes it; the members outside a group
  * (configuration, scratch buffers) are every unit's.  DESIGN.md, "The host layer", lists the few places that reach across.
@@ -195,6 +196,16 @@ struct QPSK_UNIT_LOCAL ViterbiStream {
     void release();               /* leaves the group value-initialised: no decoder.  Behind a synchronisation of the context's stream */
 };
 
+/* api_outer.cpp.  The outer link of a continuous stream (qpsk_outer_*): per-stream state on the device (outer.hip: a header and the ring of raw
+ * received bits); every stream is pushed with the same bits, so the bits since the reset are the host's number */
+struct QPSK_UNIT_LOCAL OuterLink {
+    uint8_t *state = nullptr;
+    size_t stride = 0;
+    int nstreams = 0, n = 0, branches = 0, sync = 0, lock = 0, drop = 0, flags = 0;
+    long long total = 0;          /* bits since the reset, qpsk_test_outer_advance's deltas included */
+    void release();               /* leaves the group value-initialised: no link.  Behind a synchronisation of the context's stream */
+};
+
 } // namespace qpsk
 
 struct qpsk_ctx {
@@ -232,6 +243,7 @@ struct qpsk_ctx {
     qpsk::Deframer df;
     qpsk::Framer framer;
     qpsk::ViterbiStream vs;
+    qpsk::OuterLink outer;
 };
 
 namespace qpsk {

@@ -379,6 +379,34 @@ int launch_vstream_init(const VStreamArgs &a, int nstreams, hipStream_t s);
 /* viterbi_stream_kernel, or punctured = true viterbi_stream_punct_kernel */
 int launch_vstream_push(const VStreamArgs &a, int nstreams, bool punctured, hipStream_t s);
 int launch_vstream_flush(const VStreamArgs &a, int nstreams, hipStream_t s);
+/* outer.hip: the outer link of a continuous stream (OUTER LINK in include/qpsk_hip.h).  One wave per stream over state_stride bytes of state
+ * each (outer_state_stride(n, branches, lock); the layout is that file's).  The host keeps the bits since the reset and hands a launch `total`
+ * (what the streams had before this push: a wave adds a relative position to it for the `pos` it stores, and takes its bit phase total & 7
+ * from it) and the call's buffers: bits rows bits_pitch bytes apart; words [nstreams][max_words][word_pitch], pos and wflags
+ * [nstreams][max_words], info [nstreams][4], each of these four or NULL; count [nstreams] */
+constexpr int OUTER_POLARITY = 1, OUTER_MSB_FIRST = 2;
+constexpr int OUTER_MAX_BITS = 1 << 20;
+struct OuterArgs {
+    int n, branches, sync, lock, drop, flags;
+    uint8_t *state;
+    size_t state_stride;
+    long long total;
+    const uint8_t *bits;
+    size_t bits_pitch;
+    int nbits, max_words;
+    int32_t *count;
+    uint8_t *words;
+    size_t word_pitch;
+    long long *pos;
+    uint8_t *wflags;
+    int32_t *info;
+};
+size_t outer_state_stride(int n, int branches, int lock);
+int launch_outer_init(const OuterArgs &a, int nstreams, hipStream_t s);
+int launch_outer_push(const OuterArgs &a, int nstreams, hipStream_t s);
+/* outer_interleave_kernel: words / out [nrows][nwords][n]; hist_in / hist_out [nrows][branches - 1][n] or NULL */
+int launch_outer_interleave(const uint8_t *words, int nrows, int nwords, int n, int branches, const uint8_t *hist_in, uint8_t *hist_out,
+                            uint8_t *out, hipStream_t s);
 /* conv_encode_stream_kernel: nbits whole periods with an even number of sent bits; state_in / state_out [nrows] or NULL */
 int launch_conv_encode_stream(const uint8_t *bits, int nrows, int nbits, const Puncture &p, const uint8_t *state_in, uint8_t *state_out,
                               uint8_t *dibits, hipStream_t s);

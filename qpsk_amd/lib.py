@@ -11,6 +11,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 TAU = 2.0 * 3.14159265358979323846
 TIMING_HIST, TIMING_FIXED, TIMING_FFT = 0, 1, 2
+OUTER_POLARITY, OUTER_MSB_FIRST = 1, 2      # qpsk_outer_reset's flags
 NTAPS = 127
 
 
@@ -66,6 +67,7 @@ API_SYMBOLS = [
     "qpsk_rs_generator", "qpsk_rs_encode_batch", "qpsk_rs_decode_batch",
     "qpsk_viterbi_stream_reset", "qpsk_viterbi_stream_emits", "qpsk_viterbi_stream_push", "qpsk_viterbi_stream_flush",
     "qpsk_conv_encode_stream_batch", "qpsk_test_viterbi_stream_advance",
+    "qpsk_outer_reset", "qpsk_outer_max_words", "qpsk_outer_push", "qpsk_outer_interleave_batch", "qpsk_test_outer_advance",
 ]
 # the named puncturing patterns of include/qpsk_hip.h (QPSK_PUNCT_*): rate -> (period, keep0, keep1), bit r of a mask = step r of the period
 PUNCTURE = {"1/2": (1, 0x1, 0x1), "2/3": (2, 0x1, 0x3), "3/4": (3, 0x5, 0x3), "5/6": (5, 0x15, 0x0B), "7/8": (7, 0x51, 0x2F)}
@@ -184,6 +186,11 @@ def load():
     L.qpsk_viterbi_stream_flush.argtypes = [vp, i32, vp, C.c_longlong, vp, C.POINTER(i32)]
     L.qpsk_conv_encode_stream_batch.argtypes = [vp, vp, i32, i32, i32, u32, u32, vp, vp, vp]
     L.qpsk_test_viterbi_stream_advance.argtypes = [vp, C.c_longlong]
+    L.qpsk_outer_reset.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32]
+    L.qpsk_outer_max_words.argtypes = [vp, i32]
+    L.qpsk_outer_push.argtypes = [vp, vp, C.c_longlong, i32, i32, vp, vp, C.c_longlong, vp, vp, vp]
+    L.qpsk_outer_interleave_batch.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.qpsk_test_outer_advance.argtypes = [vp, C.c_longlong]
     L.qpsk_test_fir_runs.argtypes = [vp, i32, i32, C.POINTER(i32)]
     L.qpsk_multi_create.argtypes = [C.POINTER(vp), C.POINTER(i32), i32, C.POINTER(Params)]
     L.qpsk_multi_destroy.argtypes = [vp]
@@ -291,6 +298,7 @@ class Modem:
         self.frame_size = frame_size
         self.nstreams = 0
         self._vs_streams = 0      # streams of the streaming Viterbi decoder (viterbi_stream_reset)
+        self._outer = None        # (streams, n) of the outer link (outer_reset)
 
     def _check(self, rc):
         if rc != 0:
@@ -707,6 +715,68 @@ class Modem:
         nxt = self.empty((b.shape[0],), t.uint8)
         self._check(self.L.qpsk_conv_encode_stream_batch(self.h, _ptr(b), b.shape[0], int(nbits), *pat, _ptr(st), _ptr(nxt), _ptr(out)))
         return out, nxt
+
+    # ---- the outer link of a continuous stream
+    def outer_reset(self, nstreams, n, branches=1, sync=0x47, lock=2, drop=3, polarity=True, msb_first=False):
+        """qpsk_outer_reset: nstreams receivers of words of n bytes behind viterbi_stream(): word sync on the byte `sync` (declared after
+        `lock` words in a row, lost after `drop` misses in a row, 0 = never), polarity resolution, and a Forney deinterleaver of
+        `branches` branches (a divisor of n).  msb_first: a byte's first bit is its bit 7 (DVB's order)."""
+        flags = (OUTER_POLARITY if polarity else 0) | (OUTER_MSB_FIRST if msb_first else 0)
+        self._check(self.L.qpsk_outer_reset(self.h, int(nstreams), int(n), int(branches), int(sync), int(lock), int(drop), flags))
+        self._outer = (int(nstreams), int(n))
+
+    def outer_max_words(self, nbits):
+        """qpsk_outer_max_words: the most words per stream an outer() of nbits can emit; host only"""
+        rc = self.L.qpsk_outer_max_words(self.h, int(nbits))
+        self._check(min(rc, 0))
+        return rc
+
+    def outer(self, bits, nbits=None, pitch=0, max_words=None):
+        """qpsk_outer_push: bits (S, ceil(nbits / 8)) uint8, low bits first -- the `bits` of viterbi_stream() as it is (or its dict) -- or,
+        with pitch, (S, pitch) of which the first nbits bits of each row are pushed; nbits None = every bit of a row.  Dict of torch
+        tensors count (S,) int32 (the true number of words, also beyond max_words), words (S, max_words, n) uint8, pos (S, max_words)
+        int64, flags (S, max_words) uint8 (bit 0: the sync byte is wrong, bit 1: the stream is inverted), info (S, 4) int32 = (locked, s,
+        locks declared, locks lost); only the first min(count, max_words) entries of a stream are written."""
+        t = self.torch
+        if isinstance(bits, dict):
+            bits, nbits = bits["bits"], (bits["nbits"] if nbits is None else nbits)
+        if self._outer is None:
+            raise QpskError("outer() before outer_reset()")
+        S, n = self._outer
+        b = self._dev(bits, t.uint8)
+        if b.dim() != 2 or b.shape[0] != S or (pitch and b.shape[1] != pitch):
+            raise ValueError("outer() input must be (streams = %d, ceil(nbits / 8) or pitch) uint8" % S)
+        nbits = 8 * b.shape[1] if nbits is None else int(nbits)
+        mw = self.outer_max_words(nbits) if max_words is None else int(max_words)
+        o = dict(count=self.empty((S,), t.int32), words=self.empty((S, mw, n), t.uint8), pos=self.empty((S, mw), t.int64),
+                 flags=self.empty((S, mw), t.uint8), info=self.empty((S, 4), t.int32))
+        self._check(self.L.qpsk_outer_push(self.h, _ptr(b), b.shape[1], nbits, mw, _ptr(o["count"]), _ptr(o["words"]), n, _ptr(o["pos"]),
+                                           _ptr(o["flags"]), _ptr(o["info"])))
+        o["_keep"] = (b,)      # the input stays alive until the caller is done with the outputs (stream order)
+        return o
+
+    def outer_interleave(self, words, branches, history=None):
+        """qpsk_outer_interleave_batch: words (R, nwords, n) uint8 -> (out (R, nwords, n), history (R, branches - 1, n)): out[c][q] =
+        words[c - q % branches][q]; history = the last branches - 1 source words before the call, oldest first (None = zeros), and after
+        it."""
+        t = self.torch
+        w = self._dev(words, t.uint8)
+        if w.dim() != 3:
+            raise ValueError("outer_interleave() input must be (rows, nwords, n) uint8")
+        R, nw, n = w.shape
+        I = int(branches)
+        h = None if history is None else self._dev(history, t.uint8)
+        if h is not None and tuple(h.shape) != (R, I - 1, n):
+            raise ValueError("outer_interleave() history must be (rows, branches - 1, n) uint8")
+        out = self.empty((R, nw, n), t.uint8)
+        nxt = self.empty((R, max(I - 1, 0), n), t.uint8)
+        self._check(self.L.qpsk_outer_interleave_batch(self.h, _ptr(w), R, nw, n, I, _ptr(h) if I > 1 else None, _ptr(nxt) if I > 1 else None,
+                                                       _ptr(out)))
+        return out, nxt
+
+    def outer_advance(self, delta):
+        """Test hook: move the outer link's position counter on by delta bits, a multiple of 8 (qpsk_test_outer_advance)."""
+        self._check(self.L.qpsk_test_outer_advance(self.h, int(delta)))
 
     # ---- stages
     def rrc_fir(self, x, memory=None, fast=False):
