@@ -706,9 +706,9 @@ int qpsk_rs_decode_batch(qpsk_ctx *ctx, const uint8_t *d_in, long long in_pitch,
  * viterbi_stream_punct_kernel (any pattern but (1, 1, 1)), viterbi_stream_flush_kernel, viterbi_stream_init_kernel or
  * conv_encode_stream_kernel.
  * Not built: d_flip (a descrambler on the soft values) and an interleaver in front of the stream decoder; streams pushed with different
- * step counts; resolving the quarter-turn (90 degrees) and pattern-phase ambiguity of a continuous link (the caller does, with d_info[0] /
- * d_info[1] as the handle: INTEGRATION.md 2.0 -- the half turn alone is resolved behind the decoder, by OUTER LINK's word sync, and the
- * byte interleaver of a continuous link is OUTER LINK's too); qpsk_multi.
+ * step counts; qpsk_multi.  The quarter-turn (90 degrees) and pattern-phase ambiguity of a continuous link is resolved in front of the
+ * decoder by NODE SYNC, which reads this call's d_info[0] / d_info[1] on the device; the half turn is resolved behind the decoder, by OUTER
+ * LINK's word sync, and the byte interleaver of a continuous link is OUTER LINK's too.
  * ------------------------------------------------------------------------- */
 enum { QPSK_VITERBI_STREAM_TERMINATED = 1 };
 int qpsk_viterbi_stream_reset(qpsk_ctx *ctx, int nstreams, int depth, int window, int period, uint32_t keep0, uint32_t keep1);
@@ -771,7 +771,7 @@ int qpsk_conv_encode_stream_batch(qpsk_ctx *ctx, const uint8_t *d_bits, int nrow
  * The calls are stream-ordered on the context's stream and touch no other state of the context.  qpsk_ctx_last_kernel() names
  * outer_push_kernel, outer_init_kernel or outer_interleave_kernel.
  * Not built: DVB's inverted sync byte in every eighth word and its energy dispersal; cells other than n / I; streams pushed with different
- * lengths; the quarter-turn (90 degrees) search, which stays with the error ratio; qpsk_multi.
+ * lengths; qpsk_multi.  The quarter-turn (90 degrees) search is NODE SYNC's, in front of the decoder.
  * ------------------------------------------------------------------------- */
 enum { QPSK_OUTER_POLARITY = 1, QPSK_OUTER_MSB_FIRST = 2 };
 int qpsk_outer_reset(qpsk_ctx *ctx, int nstreams, int n, int branches, int sync, int lock, int drop, int flags);
@@ -780,6 +780,78 @@ int qpsk_outer_push(qpsk_ctx *ctx, const uint8_t *d_bits, long long bits_pitch, 
                     long long word_pitch, long long *d_pos, uint8_t *d_flags, int32_t *d_info);
 int qpsk_outer_interleave_batch(qpsk_ctx *ctx, const uint8_t *d_words, int nrows, int nwords, int n, int branches, const uint8_t *d_hist_in,
                                 uint8_t *d_hist_out, uint8_t *d_out);
+
+/* -------------------------------------------------------------------------
+ * NODE SYNC: what stands between qpsk_soft_batch and VITERBI STREAM on a continuously coded link -- the quarter turn the Costas loop may
+ * have locked on and the phase of the puncturing pattern are unknown, and a loop that slips changes both mid-stream.  Per link a CANDIDATE
+ * (quarter turn r, delay h in dibits) is applied to the soft rows, and a MONITOR judges it by the error count the stream decoder reported for
+ * the previous block and moves to the next candidate when it is bad; one launch per block does both, with no host synchronisation and no
+ * decoder reset.  The library's own definition, integers only, no tolerance anywhere (parity unpinned: the reference has no FEC), restated
+ * in numpy by tests/test_nodesync_cpu.py (nodesync_ref).  The code is transparent to the half turn (r and r + 2 decode alike, the data
+ * inverted), so two rotation candidates, r = 0 and r = 1, suffice and the half turn stays OUTER LINK's.
+ *
+ * RESET (nlinks >= 1; nrot in {1, 2, 4}; nshift = 1..32; span = 1..2^24; settle = 0..2^24; thr_num = 0..65535; thr_den = 1..65535; drop =
+ *   1..16).  There are C = nrot nshift candidates; candidate c means r = c mod nrot, h = c div nrot: nrot = 2 tries r = 0 and r = 1, one of
+ *   which is right or the half-turn twin of the right one; nrot = 4 tries all four and locks on the first of {r, r + 2} it meets.  After a reset
+ *   every link has c = 0, locked = 0, run = 0, err = cnt = 0, settle_left = 0, switches = 0 and no input history.
+ *   qpsk_nodesync_shifts(period, keep0, keep1) = the delays a pattern needs, by host arithmetic: K / 2 for even K, K for odd K, K =
+ *   popc(keep0) + popc(keep1) (a delay of h dibits moves the pattern by 2 h sent bits); < 0: the error code of a bad pattern (PUNCTURING's
+ *   rules).  1 for (1, 1, 1), 3 for 2/3, 2 for 3/4, 3 for 5/6, 4 for 7/8.
+ * INPUT.  For one link X is the concatenation of every soft pair pushed since the reset, in qpsk_soft_batch's layout; -128 IS TAKEN AS -127
+ *   BEFORE ANYTHING ELSE, so every negation is exact and -128 never appears in the output.  turn_r is qpsk_soft_batch's rule, same signs:
+ *       r=0 (a, b)   r=1 (b, -a)   r=2 (-a, -b)   r=3 (-b, a)
+ * PUSH (ntx dibits for every link, max(1, nshift - 1) <= ntx <= 2^20) does two things, in this order:
+ *   1. TICK, only if d_vinfo is not NULL.  d_vinfo [nlinks][4] int32 = what qpsk_viterbi_stream_push wrote into its d_info for this link's
+ *      previous block; e = word 0 (channel errors), n = word 1 (non-zero soft values).
+ *          verdict = 0
+ *          if n > 0:
+ *              if settle_left > 0:   settle_left = max(0, settle_left - n);  verdict = 3
+ *              else:
+ *                  err += e;  cnt += n
+ *                  if cnt >= span:
+ *                      bad = (int64) err * thr_den > (int64) thr_num * cnt;   err = cnt = 0
+ *                      if not bad:   run = 0;  locked = 1;  verdict = 1
+ *                      else:
+ *                          verdict = 2;  run += 1
+ *                          if not locked or run >= drop:
+ *                              c = (c + 1) mod C;  locked = 0;  run = 0;  settle_left = settle;  switches += 1
+ *      All accumulators fit int32 (cnt < span + 2^19 on a decoder's counts).  A hunting link moves on after ONE bad span; a locked one after
+ *      `drop` bad spans in a row.  settle covers the decoder's latency: the counts of the first depth + window steps behind a switch still
+ *      belong to the old candidate.
+ *   2. TRANSFORM with the candidate now in force.  With `total` = the dibits pushed before this call, for j < ntx and i = total + j:
+ *          out[j] = turn_r(X[i - h])   if i - h >= 0
+ *          out[j] = (0, 0)             otherwise (an erasure)
+ *      The state keeps the last nshift - 1 input dibits of a link, so any h is available at the next push whatever the candidate was.
+ *      Every link gets ntx dibits in and ntx out, so a push of whole pattern periods stays one and d_soft_out goes into
+ *      qpsk_viterbi_stream_push as it is.  WITH d_vinfo NULL IN EVERY PUSH NOTHING DEPENDS ON HOW THE DIBITS WERE CUT INTO PUSHES.
+ * OUTPUTS.
+ *   d_soft_out [nlinks][out_pitch dibits][2] int8, required; the span of its rows must not share a byte with the span of the input's
+ *   d_info [nlinks][8] int32 (may be NULL) = { r, h, locked, switches since the reset, verdict of this call, run, err, cnt }, after the call
+ *   in_pitch / out_pitch: 0 = ntx, otherwise >= ntx; what lies between rows is neither read nor written.  Both soft pointers are 2-byte
+ *   aligned and nothing more, any pitch is legal; d_vinfo and d_info 4-byte aligned.
+ * SET.  qpsk_nodesync_set(d_cand): d_cand [nlinks] int32 on the device, NULL = all zero; c = d_cand[l] as an unsigned number mod C; err =
+ *   cnt = run = 0, locked = 0, settle_left = settle; the history and `switches` stay.  Stream-ordered, no synchronisation: how a caller who
+ *   searched the candidates in parallel hands over the winner.
+ * Hence, and tested:  (1) with nrot = nshift = 1 the output is the input after the -128 rule;  (2) partition independence, above;  (3)
+ *   turn_r equals qpsk_soft_batch with d_rot = r on the same costas_frame[] rows wherever both are defined;  (4) with d_vinfo given the state
+ *   after each push is a function of the old state and (e, n) alone.
+ *
+ *   qpsk_nodesync_reset   one node sync per context; a refused reset leaves an armed one as it was, a failed allocation (QPSK_ERR_ALLOC)
+ *                the context usable
+ *   qpsk_nodesync_push / _set   QPSK_ERR_STATE before a reset; anything outside the rules above is QPSK_ERR_ARG with nothing launched and the
+ *                state untouched
+ * The calls are stream-ordered on the context's stream and touch no other state of the context: the decoder's d_info is only ever a pointer
+ * handed in.  qpsk_ctx_last_kernel() names nodesync_push_kernel or nodesync_init_kernel (a reset, a set).  How to choose thr and span from
+ * the measured error ratios of right and wrong candidates: INTEGRATION.md 2.0.  No test hook: the only position the definition uses is
+ * min(total, nshift - 1).
+ * Not built: fan-out of all candidates into rows of one launch; a per-link ntx; qpsk_multi; a monitor fed by anything but the decoder's
+ * error count, such as metric growth; a transform fused into the stream decoder's loader.
+ * ------------------------------------------------------------------------- */
+int qpsk_nodesync_reset(qpsk_ctx *ctx, int nlinks, int nrot, int nshift, int span, int settle, int thr_num, int thr_den, int drop);
+int qpsk_nodesync_shifts(int period, uint32_t keep0, uint32_t keep1);
+int qpsk_nodesync_push(qpsk_ctx *ctx, const int8_t *d_soft_in, long long in_pitch, int ntx, const int32_t *d_vinfo, int8_t *d_soft_out,
+                       long long out_pitch, int32_t *d_info);
+int qpsk_nodesync_set(qpsk_ctx *ctx, const int32_t *d_cand);
 
 /* -------------------------------------------------------------------------
  * The stages on their own (each is what the corresponding reference function

@@ -258,6 +258,7 @@ void qpsk_ctx_destroy(qpsk_ctx *c)
     c->framer.release();
     c->vs.release();
     c->outer.release();
+    c->nodesync.release();
     delete c;
 }
 

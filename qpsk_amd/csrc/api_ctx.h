@@ -9,6 +9,7 @@
  *   api_packets.cpp  bit stages, the deframers, the framer
  *   api_vstream.cpp  the streaming Viterbi decoder and the encoder that carries its register
  *   api_outer.cpp    the outer link behind it: word sync, the byte deinterleaver and the interleaver
+ *   api_nodesync.cpp the node sync in front of it: the candidate transform and the monitor on the decoder's error count
  *
  * OWNERSHIP: each nested group of qpsk_ctx below names the one unit that reads and writes it; the members outside a group
  * (configuration, scratch buffers) are every unit's.  DESIGN.md, "The host layer", lists the few places that reach across.
@@ -206,6 +207,16 @@ struct QPSK_UNIT_LOCAL OuterLink {
     void release();               /* leaves the group value-initialised: no link.  Behind a synchronisation of the context's stream */
 };
 
+/* api_nodesync.cpp.  The node sync in front of the streaming decoder (qpsk_nodesync_*): per-link state on the device (nodesync.hip: the
+ * candidate, the monitor's counters and the last nshift - 1 input dibits); every link is pushed with the same dibits, so how many of those
+ * history dibits are real is the host's number */
+struct QPSK_UNIT_LOCAL NodeSync {
+    uint8_t *state = nullptr;
+    int nlinks = 0, nrot = 0, nshift = 0, span = 0, settle = 0, thr_num = 0, thr_den = 0, drop = 0;
+    int have = 0;                 /* min(dibits since the reset, nshift - 1) */
+    void release();               /* leaves the group value-initialised: no node sync.  Behind a synchronisation of the context's stream */
+};
+
 } // namespace qpsk
 
 struct qpsk_ctx {
@@ -244,6 +255,7 @@ struct qpsk_ctx {
     qpsk::Framer framer;
     qpsk::ViterbiStream vs;
     qpsk::OuterLink outer;
+    qpsk::NodeSync nodesync;
 };
 
 namespace qpsk {

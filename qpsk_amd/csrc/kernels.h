@@ -407,6 +407,28 @@ int launch_outer_push(const OuterArgs &a, int nstreams, hipStream_t s);
 /* outer_interleave_kernel: words / out [nrows][nwords][n]; hist_in / hist_out [nrows][branches - 1][n] or NULL */
 int launch_outer_interleave(const uint8_t *words, int nrows, int nwords, int n, int branches, const uint8_t *hist_in, uint8_t *hist_out,
                             uint8_t *out, hipStream_t s);
+/* nodesync.hip: the node sync in front of the streaming decoder (NODE SYNC in include/qpsk_hip.h).  One wave per link over NODESYNC_STRIDE bytes
+ * of state each (the layout is that file's).  The host keeps the dibits since the reset and hands a launch `have` = min(total, nshift - 1), the
+ * dibits of history that are real.  soft_in / soft_out rows in_pitch / out_pitch dibits apart; vinfo [nlinks][4] or NULL (no tick); info
+ * [nlinks][8] or NULL */
+constexpr int NODESYNC_MAX_SHIFT = 32;
+constexpr int NODESYNC_MAX_NTX = 1 << 20;
+constexpr size_t NODESYNC_STRIDE = 96;
+struct NodeSyncArgs {
+    int nrot, nshift, span, settle, thr_num, thr_den, drop;
+    uint8_t *state;
+    int have;
+    const int8_t *soft_in;
+    size_t in_pitch;
+    int ntx;
+    const int32_t *vinfo;
+    int8_t *soft_out;
+    size_t out_pitch;
+    int32_t *info;
+};
+/* nodesync_init_kernel: a reset's state (keep = false), or qpsk_nodesync_set (keep = true: the history and `switches` stay); cand [nlinks] or NULL */
+int launch_nodesync_init(const NodeSyncArgs &a, int nlinks, const int32_t *cand, bool keep, hipStream_t s);
+int launch_nodesync_push(const NodeSyncArgs &a, int nlinks, hipStream_t s);
 /* conv_encode_stream_kernel: nbits whole periods with an even number of sent bits; state_in / state_out [nrows] or NULL */
 int launch_conv_encode_stream(const uint8_t *bits, int nrows, int nbits, const Puncture &p, const uint8_t *state_in, uint8_t *state_out,
                               uint8_t *dibits, hipStream_t s);

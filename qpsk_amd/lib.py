@@ -68,6 +68,7 @@ API_SYMBOLS = [
     "qpsk_viterbi_stream_reset", "qpsk_viterbi_stream_emits", "qpsk_viterbi_stream_push", "qpsk_viterbi_stream_flush",
     "qpsk_conv_encode_stream_batch", "qpsk_test_viterbi_stream_advance",
     "qpsk_outer_reset", "qpsk_outer_max_words", "qpsk_outer_push", "qpsk_outer_interleave_batch", "qpsk_test_outer_advance",
+    "qpsk_nodesync_reset", "qpsk_nodesync_shifts", "qpsk_nodesync_push", "qpsk_nodesync_set",
 ]
 # the named puncturing patterns of include/qpsk_hip.h (QPSK_PUNCT_*): rate -> (period, keep0, keep1), bit r of a mask = step r of the period
 PUNCTURE = {"1/2": (1, 0x1, 0x1), "2/3": (2, 0x1, 0x3), "3/4": (3, 0x5, 0x3), "5/6": (5, 0x15, 0x0B), "7/8": (7, 0x51, 0x2F)}
@@ -191,6 +192,10 @@ def load():
     L.qpsk_outer_push.argtypes = [vp, vp, C.c_longlong, i32, i32, vp, vp, C.c_longlong, vp, vp, vp]
     L.qpsk_outer_interleave_batch.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.qpsk_test_outer_advance.argtypes = [vp, C.c_longlong]
+    L.qpsk_nodesync_reset.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32]
+    L.qpsk_nodesync_shifts.argtypes = [i32, u32, u32]
+    L.qpsk_nodesync_push.argtypes = [vp, vp, C.c_longlong, i32, vp, vp, C.c_longlong, vp]
+    L.qpsk_nodesync_set.argtypes = [vp, vp]
     L.qpsk_test_fir_runs.argtypes = [vp, i32, i32, C.POINTER(i32)]
     L.qpsk_multi_create.argtypes = [C.POINTER(vp), C.POINTER(i32), i32, C.POINTER(Params)]
     L.qpsk_multi_destroy.argtypes = [vp]
@@ -262,6 +267,16 @@ def rs_generator(nroots):
     return g
 
 
+def nodesync_shifts(puncture):
+    """qpsk_nodesync_shifts: the delays (in dibits) a node sync has to try for a pattern, a key of PUNCTURE or a (period, keep0, keep1)
+    tuple: nodesync_reset()'s nshift.  Host only, needs no GPU"""
+    L = load()
+    rc = L.qpsk_nodesync_shifts(*_pattern(puncture))
+    if rc < 0:
+        raise QpskError("libqpsk_hip error %d: %s" % (rc, L.qpsk_last_error().decode()))
+    return rc
+
+
 def _interleaved(interleave):
     """interleave= of the Modem calls: None or 1 is off (the existing entry points are called), an integer stride takes the ilv ones"""
     return interleave is not None and int(interleave) != 1
@@ -299,6 +314,7 @@ class Modem:
         self.nstreams = 0
         self._vs_streams = 0      # streams of the streaming Viterbi decoder (viterbi_stream_reset)
         self._outer = None        # (streams, n) of the outer link (outer_reset)
+        self._ns_links = 0        # links of the node sync (nodesync_reset)
 
     def _check(self, rc):
         if rc != 0:
@@ -777,6 +793,51 @@ class Modem:
     def outer_advance(self, delta):
         """Test hook: move the outer link's position counter on by delta bits, a multiple of 8 (qpsk_test_outer_advance)."""
         self._check(self.L.qpsk_test_outer_advance(self.h, int(delta)))
+
+    # ---- the node sync in front of the streaming decoder (NODE SYNC in include/qpsk_hip.h)
+    def nodesync_reset(self, nlinks, nrot=2, nshift=1, span=4096, settle=1024, threshold=(1, 32), drop=2):
+        """qpsk_nodesync_reset: nlinks node syncs in front of viterbi_stream(): nrot (1, 2 or 4) quarter-turn candidates times nshift
+        (nodesync_shifts(puncture)) delays; a candidate is judged over `span` counted soft values, bad when errors / counted > threshold =
+        (num, den); `settle` counted values are skipped behind a switch (the decoder's latency: the soft values of depth + window
+        steps); a locked link moves on after `drop` bad spans in a row."""
+        num, den = threshold
+        self._check(self.L.qpsk_nodesync_reset(self.h, int(nlinks), int(nrot), int(nshift), int(span), int(settle), int(num), int(den), int(drop)))
+        self._ns_links = int(nlinks)
+
+    def nodesync(self, soft, vinfo=None, pitch=0, ntx=None):
+        """qpsk_nodesync_push: soft (S, ntx, 2) int8 as soft() writes it -- or, with pitch, (S, pitch, 2) of which the first ntx dibits of
+        each row are pushed; vinfo (S, 4) int32 = the info of the previous viterbi_stream() (or its dict; it stays on the device), None = no
+        tick.  Dict of torch tensors soft (S, ntx, 2) int8, which goes into viterbi_stream() as it is, and info (S, 8) int32 = (r, h, locked,
+        switches, verdict, run, err, cnt)."""
+        t = self.torch
+        if isinstance(soft, dict):
+            soft = soft["soft"]
+        if isinstance(vinfo, dict):
+            vinfo = vinfo["info"]
+        if not self._ns_links:
+            raise QpskError("nodesync() before nodesync_reset()")
+        S = self._ns_links
+        q = self._dev(soft, t.int8)
+        if q.dim() != 3 or q.shape[0] != S or q.shape[2] != 2 or (pitch and q.shape[1] != pitch):
+            raise ValueError("nodesync() input must be (links = %d, ntx or pitch, 2) int8" % S)
+        v = None if vinfo is None else self._dev(vinfo, t.int32)
+        if v is not None and tuple(v.shape) != (S, 4):
+            raise ValueError("nodesync() vinfo must be (links = %d, 4) int32" % S)
+        ntx = q.shape[1] if ntx is None else int(ntx)
+        o = dict(soft=self.empty((S, max(ntx, 0), 2), t.int8), info=self.empty((S, 8), t.int32))
+        self._check(self.L.qpsk_nodesync_push(self.h, _ptr(q), int(pitch), ntx, _ptr(v), _ptr(o["soft"]), 0, _ptr(o["info"])))
+        o["_keep"] = (q, v)      # the inputs stay alive until the caller is done with the outputs (stream order)
+        return o
+
+    def nodesync_set(self, cand=None):
+        """qpsk_nodesync_set: put every link on candidate cand[l] (mod nrot * nshift; None = 0) with a fresh monitor; the carried history
+        and the switch count stay."""
+        if not self._ns_links:
+            raise QpskError("nodesync_set() before nodesync_reset()")
+        d = None if cand is None else self._dev(cand, self.torch.int32)
+        if d is not None and tuple(d.shape) != (self._ns_links,):
+            raise ValueError("nodesync_set() cand must be (links = %d,) int32" % self._ns_links)
+        self._check(self.L.qpsk_nodesync_set(self.h, _ptr(d)))
 
     # ---- stages
     def rrc_fir(self, x, memory=None, fast=False):
