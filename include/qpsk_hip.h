@@ -764,22 +764,71 @@ int qpsk_conv_encode_stream_batch(qpsk_ctx *ctx, const uint8_t *d_bits, int nrow
  *   I branches of j M cells, the sync byte on the undelayed branch, and the receiver's Z is then X delayed by I - 1 words.  A caller puts
  *   `sync` into byte 0 of every word BEFORE RS-encoding it: the sync byte is data of the codeword, as in DVB.
  *
- *   qpsk_outer_reset   one link per context; a refused reset leaves an armed one as it was, a failed allocation (QPSK_ERR_ALLOC) the
- *                context usable
+ * GROUP SYNC.  qpsk_outer_reset_group(..., group): group = 0 is qpsk_outer_reset.  Otherwise every G-th word, G = group = 3..16, carries the
+ *   complement of the sync byte (DVB: G = 8, 0xB8 for 0x47), and lock L = G..16: a look-ahead over one whole group determines the polarity
+ *   and the group phase uniquely (by enumeration for every such G and L); with L < G - 1, or with G = 2, two (s, g) share a sign pattern,
+ *   and L = G - 1 would take L sync bytes with no complement among them for a lock.  Anything else is QPSK_ERR_ARG.  With  e(k) = -1 if k = 0, else +1  and  m(u) = +1 if V(u) == sync, -1 if V(u) == sync ^ 0xFF, 0 otherwise  (both signs
+ *   are always formed in group mode, whatever POLARITY says):
+ *   HUNT, from h:  u* = the smallest u >= h with m(u + 8 n i) != 0 for every i < L, for which there are an s in {+1, -1} (s = +1 only, if
+ *     POLARITY is not set) and a g in 0..G-1 with m(u + 8 n i) = s e((i + g) mod G) for every i < L.  A candidate whose L bytes all match but
+ *     whose signs fit no (s, g) is not a lock.  The lock is declared by the push that delivers bit u* + 8 n (L-1) + 7, as above.  After it:
+ *     u0 = u*, s and g as found, c = 0, run = 0.
+ *   LOCKED.  Raw word c has the group index k(c) = (g + c) mod G and the expected first byte E(c) = sync ^ (k(c) == 0 ? 0xFF : 0).  Steps 1
+ *     to 4 as above, except:  miss = (Y[c][0] != E(c));  the emitted word Z is as above, bytes as received -- the sync byte is data of the
+ *     codeword, 0xB8 stays 0xB8 --;  flags bit 0 = (Z[0] != E(c - (I - 1))), bit 1 = (s < 0), bits 4..7 = k(c - (I - 1)), bits 2 and 3 zero;
+ *     a lost lock forgets g, and HUNT resumes at u0 + 8 n c + 1.
+ *   The word bound, qpsk_outer_max_words, d_info, d_pos and THE RESULT DEPENDS ONLY ON B hold as above.  d_flags is then the d_flags of
+ *   qpsk_dispersal_batch (DVB TRANSPORT).  Restated in numpy by tests/test_dvb_cpu.py (outer_group_ref).
+ *
+ *   qpsk_outer_reset / _reset_group   one link per context; a refused reset leaves an armed one as it was, a failed allocation
+ *                (QPSK_ERR_ALLOC) the context usable.  qpsk_outer_reset knows no flag beyond the two below
  *   qpsk_outer_push / _max_words   QPSK_ERR_STATE before a reset; anything outside the rules above is QPSK_ERR_ARG with nothing launched
  *                and the state untouched
  * The calls are stream-ordered on the context's stream and touch no other state of the context.  qpsk_ctx_last_kernel() names
  * outer_push_kernel, outer_init_kernel or outer_interleave_kernel.
- * Not built: DVB's inverted sync byte in every eighth word and its energy dispersal; cells other than n / I; streams pushed with different
+ * Built since: DVB's inverted sync byte in every eighth word is GROUP SYNC above, and its energy dispersal is DVB TRANSPORT below.
+ * Not built: cells other than n / I; streams pushed with different
  * lengths; qpsk_multi.  The quarter-turn (90 degrees) search is NODE SYNC's, in front of the decoder.
  * ------------------------------------------------------------------------- */
 enum { QPSK_OUTER_POLARITY = 1, QPSK_OUTER_MSB_FIRST = 2 };
 int qpsk_outer_reset(qpsk_ctx *ctx, int nstreams, int n, int branches, int sync, int lock, int drop, int flags);
+int qpsk_outer_reset_group(qpsk_ctx *ctx, int nstreams, int n, int branches, int sync, int lock, int drop, int flags, int group);
 int qpsk_outer_max_words(qpsk_ctx *ctx, int nbits);
 int qpsk_outer_push(qpsk_ctx *ctx, const uint8_t *d_bits, long long bits_pitch, int nbits, int max_words, int32_t *d_count, uint8_t *d_words,
                     long long word_pitch, long long *d_pos, uint8_t *d_flags, int32_t *d_info);
 int qpsk_outer_interleave_batch(qpsk_ctx *ctx, const uint8_t *d_words, int nrows, int nwords, int n, int branches, const uint8_t *d_hist_in,
                                 uint8_t *d_hist_out, uint8_t *d_out);
+
+/* -------------------------------------------------------------------------
+ * DVB TRANSPORT: the energy dispersal of ETSI EN 300 421 over groups of G transport packets, the stage behind REED-SOLOMON on the way in and
+ * in front of it on the way out.  The library's own definition, integers only, on a keystream that is pinned: K[j], j >= 0, are the bits
+ * scramble() (bit-scramble.c:57-68) xors onto successive input bits from SEED 0x4A80 -- the generator 1 + x^14 + x^15 loaded with
+ * 100101010000000 -- so dibit d of qpsk_scramble_batch's keystream is K[2 d] | K[2 d + 1] << 1.  Restated in numpy by tests/test_dvb_cpu.py
+ * (dispersal_ref).
+ *       PR[t] = sum_{i<8} K[8 t + i] << i,  t = 0 .. G len - 2;  with QPSK_DISPERSAL_MSB_FIRST  << (7 - i), DVB's order: PR = 03 F6 08 34 30
+ *               B8 A3 93 ..., the sequence the standard prints; G = 8, len = 188 gives its period of 1503 bytes
+ *       a row of len bytes with group index k:   out[0] = in[0] ^ (k == 0 ? 0xFF : 0);   out[q] = in[q] ^ PR[k len + q - 1], 1 <= q < len
+ * The generator runs through the sync bytes of packets 1 .. G-1 and is not applied to them.  The map is an involution: the same call
+ * randomises on the way out and de-randomises on the way in.
+ *   qpsk_dispersal_batch     nrows >= 1 rows of len = 2..255 bytes, group = 1..16, flags 0 or QPSK_DISPERSAL_MSB_FIRST; d_in / d_out rows
+ *                in_pitch / out_pitch bytes apart, 0 = len, otherwise >= len; bytes between rows are neither read nor written.
+ *                d_flags == NULL: row r has the index (first + r) mod group, first = 0..group-1 -- the transmitter's case.  Otherwise the
+ *                index of row r is d_flags[r] >> 4, exactly the array qpsk_outer_push writes under GROUP SYNC, and first must be 0; a row
+ *                whose index is >= group is copied unchanged (rows beyond a stream's d_count hold whatever was in memory; their index is
+ *                never used as an address).  d_out == d_in with equal pitches is allowed (in place); otherwise no two of d_in, d_out and
+ *                d_flags may overlap, a pitched buffer counting from its first row's first byte to its last row's last.  The table of a
+ *                (len, group, flags) is built on the host and kept in the context; a call that names another triple waits for the
+ *                context's stream once and replaces it
+ *   qpsk_dispersal_sequence  host only, no context, no device: writes PR[0 .. group len - 2] to out and returns group len - 1, or < 0: an
+ *                error code
+ * QPSK_ERR_ARG at the call for a bad argument, decided before the context is looked at, nothing launched.  qpsk_dispersal_batch is
+ * stream-ordered on the context's stream and touches no other state of the context; qpsk_ctx_last_kernel() names dispersal_kernel.
+ * Not built: a fused RS-decode + dispersal; qpsk_multi; DVB's I/Q mapping of the punctured code.  Usage: INTEGRATION.md 2.0.
+ * ------------------------------------------------------------------------- */
+enum { QPSK_DISPERSAL_MSB_FIRST = 1 };
+int qpsk_dispersal_batch(qpsk_ctx *ctx, const uint8_t *d_in, long long in_pitch, int nrows, int len, int group, int flags, const uint8_t *d_flags,
+                         int first, uint8_t *d_out, long long out_pitch);
+int qpsk_dispersal_sequence(int len, int group, int flags, uint8_t *out);
 
 /* -------------------------------------------------------------------------
  * NODE SYNC: what stands between qpsk_soft_batch and VITERBI STREAM on a continuously coded link -- the quarter turn the Costas loop may

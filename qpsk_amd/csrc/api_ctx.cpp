@@ -259,6 +259,7 @@ void qpsk_ctx_destroy(qpsk_ctx *c)
     c->vs.release();
     c->outer.release();
     c->nodesync.release();
+    c->dispersal.release();
     delete c;
 }
 

@@ -9,6 +9,7 @@
  *   api_packets.cpp  bit stages, the deframers, the framer
  *   api_vstream.cpp  the streaming Viterbi decoder and the encoder that carries its register
  *   api_outer.cpp    the outer link behind it: word sync, the byte deinterleaver and the interleaver
+ *   api_dispersal.cpp DVB's energy dispersal behind the Reed-Solomon decoder
  *   api_nodesync.cpp the node sync in front of it: the candidate transform and the monitor on the decoder's error count
  *
  * OWNERSHIP: each nested group of qpsk_ctx below names the one unit that reads and writes it; the members outside a group
@@ -203,6 +204,7 @@ struct QPSK_UNIT_LOCAL OuterLink {
     uint8_t *state = nullptr;
     size_t stride = 0;
     int nstreams = 0, n = 0, branches = 0, sync = 0, lock = 0, drop = 0, flags = 0;
+    int group = 0;                /* qpsk_outer_reset_group's G, 0 = no group sync */
     long long total = 0;          /* bits since the reset, qpsk_test_outer_advance's deltas included */
     void release();               /* leaves the group value-initialised: no link.  Behind a synchronisation of the context's stream */
 };
@@ -215,6 +217,14 @@ struct QPSK_UNIT_LOCAL NodeSync {
     int nlinks = 0, nrot = 0, nshift = 0, span = 0, settle = 0, thr_num = 0, thr_den = 0, drop = 0;
     int have = 0;                 /* min(dibits since the reset, nshift - 1) */
     void release();               /* leaves the group value-initialised: no node sync.  Behind a synchronisation of the context's stream */
+};
+
+/* api_dispersal.cpp.  Energy dispersal (qpsk_dispersal_batch): the table of the last (len, group, flags), group rows of
+ * dispersal_table_pitch(len) bytes; rebuilt, behind a synchronisation of the context's stream, when a call names another triple */
+struct QPSK_UNIT_LOCAL Dispersal {
+    uint8_t *table = nullptr;     /* DISPERSAL_MAX_GROUP * 256 bytes: every triple fits */
+    int len = 0, group = 0, flags = 0;
+    void release();               /* leaves the group value-initialised: no table.  Behind a synchronisation of the context's stream */
 };
 
 } // namespace qpsk
@@ -256,6 +266,7 @@ struct qpsk_ctx {
     qpsk::ViterbiStream vs;
     qpsk::OuterLink outer;
     qpsk::NodeSync nodesync;
+    qpsk::Dispersal dispersal;
 };
 
 namespace qpsk {

@@ -35,12 +35,13 @@ static OuterArgs outer_args(const OuterLink &o)
     a.state = o.state;
     a.state_stride = o.stride;
     a.total = o.total;
+    a.group = o.group;
     return a;
 }
 
-int qpsk_outer_reset(qpsk_ctx *c, int nstreams, int n, int branches, int sync, int lock, int drop, int flags)
+/* both resets: group = 0 is the ungrouped link */
+static int outer_reset(const char *who, qpsk_ctx *c, int nstreams, int n, int branches, int sync, int lock, int drop, int flags, int group)
 {
-    static const char *const who = "qpsk_outer_reset";
     static_assert(QPSK_OUTER_POLARITY == OUTER_POLARITY && QPSK_OUTER_MSB_FIRST == OUTER_MSB_FIRST, "the kernel takes the header's flag values");
     /* what the arguments alone decide comes first: it needs neither a context nor a device */
     if (nstreams < 1) return fail(QPSK_ERR_ARG, "%s: nstreams = %d", who, nstreams);
@@ -49,6 +50,8 @@ int qpsk_outer_reset(qpsk_ctx *c, int nstreams, int n, int branches, int sync, i
     if (lock < 1 || lock > 16) return fail(QPSK_ERR_ARG, "%s: lock = %d outside 1..16", who, lock);
     if (drop < 0 || drop > 16) return fail(QPSK_ERR_ARG, "%s: drop = %d outside 0..16", who, drop);
     if (flags & ~(QPSK_OUTER_POLARITY | QPSK_OUTER_MSB_FIRST)) return fail(QPSK_ERR_ARG, "%s: unknown flags 0x%x", who, flags);
+    if (group && (group < 3 || group > 16)) return fail(QPSK_ERR_ARG, "%s: group = %d (0, or 3..16)", who, group);
+    if (group && lock < group) return fail(QPSK_ERR_ARG, "%s: lock = %d below group = %d (a look-ahead shorter than a group leaves its phase open)", who, lock, group);
     if (!c) return fail(QPSK_ERR_ARG, "%s: null context", who);
     if (bind(c)) return QPSK_ERR_HIP;
     OuterLink o;
@@ -59,6 +62,7 @@ int qpsk_outer_reset(qpsk_ctx *c, int nstreams, int n, int branches, int sync, i
     o.lock = lock;
     o.drop = drop;
     o.flags = flags;
+    o.group = group;
     o.stride = outer_state_stride(n, branches, lock);
     /* the new state first: a failed allocation leaves the context, and a link it has, as they were */
     if (o.stride > SIZE_MAX / (size_t)nstreams || hipMalloc(&o.state, o.stride * (size_t)nstreams) != hipSuccess) {
@@ -75,6 +79,16 @@ int qpsk_outer_reset(qpsk_ctx *c, int nstreams, int n, int branches, int sync, i
     KERNEL_TRY(launch_outer_init(outer_args(c->outer), nstreams, c->stream));
     c->last_kernel = "outer_init_kernel";
     return QPSK_OK;
+}
+
+int qpsk_outer_reset(qpsk_ctx *c, int nstreams, int n, int branches, int sync, int lock, int drop, int flags)
+{
+    return outer_reset("qpsk_outer_reset", c, nstreams, n, branches, sync, lock, drop, flags, 0);
+}
+
+int qpsk_outer_reset_group(qpsk_ctx *c, int nstreams, int n, int branches, int sync, int lock, int drop, int flags, int group)
+{
+    return outer_reset("qpsk_outer_reset_group", c, nstreams, n, branches, sync, lock, drop, flags, group);
 }
 
 int qpsk_outer_max_words(qpsk_ctx *c, int nbits)

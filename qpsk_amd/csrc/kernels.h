@@ -400,6 +400,7 @@ struct OuterArgs {
     long long *pos;
     uint8_t *wflags;
     int32_t *info;
+    int group;                    /* 0, or G = 3..16: group sync (qpsk_outer_reset_group); behind the fields the ungrouped kernel reads */
 };
 size_t outer_state_stride(int n, int branches, int lock);
 int launch_outer_init(const OuterArgs &a, int nstreams, hipStream_t s);
@@ -407,6 +408,15 @@ int launch_outer_push(const OuterArgs &a, int nstreams, hipStream_t s);
 /* outer_interleave_kernel: words / out [nrows][nwords][n]; hist_in / hist_out [nrows][branches - 1][n] or NULL */
 int launch_outer_interleave(const uint8_t *words, int nrows, int nwords, int n, int branches, const uint8_t *hist_in, uint8_t *hist_out,
                             uint8_t *out, hipStream_t s);
+/* dispersal.hip: DVB's energy dispersal over rows of len bytes (DVB TRANSPORT in include/qpsk_hip.h).  table [group][table_pitch]: what is
+ * xored onto byte q of a row of group index k, table_pitch = dispersal_table_pitch(len) a multiple of 4 so that every table row is dword
+ * aligned (api_dispersal.cpp builds it on the host); wflags [nrows] (the index of row r is wflags[r] >> 4, a row with an index >= group is
+ * copied) or NULL (the index is (first + r) mod group).  Pitches in bytes, never 0 */
+constexpr int DISPERSAL_MSB_FIRST = 1;
+constexpr int DISPERSAL_MAX_GROUP = 16;
+constexpr int dispersal_table_pitch(int len) { return (len + 3) & ~3; }
+int launch_dispersal(const uint8_t *in, size_t in_pitch, int nrows, int len, int group, const uint8_t *table, const uint8_t *wflags, int first,
+                     uint8_t *out, size_t out_pitch, hipStream_t s);
 /* nodesync.hip: the node sync in front of the streaming decoder (NODE SYNC in include/qpsk_hip.h).  One wave per link over NODESYNC_STRIDE bytes
  * of state each (the layout is that file's).  The host keeps the dibits since the reset and hands a launch `have` = min(total, nshift - 1), the
  * dibits of history that are real.  soft_in / soft_out rows in_pitch / out_pitch dibits apart; vinfo [nlinks][4] or NULL (no tick); info

@@ -17,8 +17,9 @@
  * push: at most max(I, L) n + 2 bytes (LOCKED: the I - 1 words in flight and a word not yet whole; HUNT: the look-ahead of the first
  * undecided candidate).
  *
- * STATE per stream, state_stride bytes (outer_state_stride): 8 int32 { locked, p, s, c, run, kbits, 0, 0 } and the ring at byte 32.  p is h, or
- * the first bit of raw word c, counted from the ring's first bit; c is capped at I - 1; kbits is what the ring holds.  Every word of the state
+ * STATE per stream, state_stride bytes (outer_state_stride): 8 int32 { locked, p, s, c, run, kbits, gk, 0 } and the ring at byte 32.  p is h, or
+ * the first bit of raw word c, counted from the ring's first bit; c is capped at I - 1; kbits is what the ring holds; gk is the group index of
+ * raw word c under group sync (c is capped, so k(c) is carried) and 0 without it.  Every word of the state
  * is written with ordinary vector stores at the end of a launch and read at the start of the next; inside a launch the window lives in the
  * LDS, where a wave's accesses are in order, so nothing a launch wrote to memory is read back by it.
  *
@@ -64,16 +65,26 @@ __device__ __forceinline__ int window_match(const uint8_t *w, int u, unsigned sy
     return v == sync ? 1 : (polarity && v == (sync ^ 255u)) ? -1 : 0;
 }
 
-template <bool MSB>
+/* GROUP: group sync (qpsk_outer_reset_group), a variant at compile time so that the ungrouped instantiations keep their code.  What it adds is
+ * gk = k(c), the group index of the raw word at p (header slot 6), and in HUNT a lane's mask of the signs of its L bytes, bit i = (m(u + 8 n i)
+ * < 0).  The legal masks of s = +1 are the G shifts of ONE wave-uniform mask, p0 = the bits i = 0, G, 2 G, ... (formed once per launch): P_g =
+ * (p0 << f) & lmask with f = (G - g) mod G the place of its first set bit, and f < G because L >= G; those of s = -1 are their complements in
+ * lmask.  So a lane compares its mask x (or its complement) with the one legal mask that has x's first set bit, instead of with all G. */
+template <bool MSB, bool GROUP>
 __device__ __forceinline__ void outer_push(const OuterArgs &a, uint8_t *w, int stream, int lane)
 {
     const int n = a.n, I = a.branches, L = a.lock;
     const int wordbits = 8 * n, span = wordbits * (L - 1) + 8;      /* HUNT: the bits a candidate needs from its own first bit on */
     const unsigned sync = (unsigned)a.sync;
     const bool polarity = (a.flags & OUTER_POLARITY) != 0;
+    const int G = GROUP ? a.group : 1;
+    const unsigned lmask = (1u << L) - 1u;
+    unsigned p0 = 0;
+    if (GROUP)
+        for (int i = 0; i < L; i += G) p0 |= 1u << i;
     uint8_t *state = a.state + (size_t)stream * a.state_stride;
     int *hdr = reinterpret_cast<int *>(state);
-    int locked, p, s, c, run, avail;
+    int locked, p, s, c, run, avail, gk = 0;
     {
         const int h = lane < 8 ? hdr[lane] : 0;
         locked = __builtin_amdgcn_readlane(h, 0);
@@ -82,6 +93,7 @@ __device__ __forceinline__ void outer_push(const OuterArgs &a, uint8_t *w, int s
         c = __builtin_amdgcn_readlane(h, 3);
         run = __builtin_amdgcn_readlane(h, 4);
         avail = __builtin_amdgcn_readlane(h, 5);
+        if (GROUP) gk = __builtin_amdgcn_readlane(h, 6);
     }
     {
         const unsigned *ring = reinterpret_cast<const unsigned *>(state + OUTER_HDR);
@@ -127,14 +139,35 @@ __device__ __forceinline__ void outer_push(const OuterArgs &a, uint8_t *w, int s
                 if (nv <= 0) break;
                 const int u = p + lane;
                 int m = 0;
-                if (lane < nv) m = window_match<MSB>(w, u, sync, polarity);
+                if (lane < nv) m = window_match<MSB>(w, u, sync, GROUP || polarity);
                 bool hit = m != 0;
+                unsigned x = m < 0 ? 1u : 0u;      /* GROUP: the signs of the L bytes */
                 for (int i = 1; i < L && __ballot(hit); i++)      /* the look-ahead, as long as a candidate is left */
-                    if (hit) hit = window_match<MSB>(w, u + i * wordbits, sync, polarity) == m;
+                    if (hit) {
+                        const int mi = window_match<MSB>(w, u + i * wordbits, sync, GROUP || polarity);
+                        if (GROUP) {
+                            hit = mi != 0;
+                            x |= (mi < 0 ? 1u : 0u) << i;
+                        } else
+                            hit = mi == m;
+                    }
+                int sg = 0;      /* GROUP: g, and 16 where s < 0 */
+                if (GROUP && hit) {
+                    const unsigned y = ~x & lmask;
+                    const int fx = __ffs((int)x) - 1, fy = __ffs((int)y) - 1;
+                    if (x && fx < G && x == ((p0 << fx) & lmask)) sg = (G - fx) % G;
+                    else if (polarity && y && fy < G && y == ((p0 << fy) & lmask)) sg = 16 | (G - fy) % G;
+                    else hit = false;      /* L sync bytes in a sign pattern no (s, g) gives: not a lock */
+                }
                 const unsigned long long hits = __ballot(hit);
                 if (hits) {
                     const int first = __ffsll((long long)hits) - 1;
-                    s = (__ballot(hit && m > 0) >> first) & 1ull ? 1 : -1;
+                    if (GROUP) {
+                        sg = __builtin_amdgcn_readlane(sg, first);
+                        s = sg & 16 ? -1 : 1;
+                        gk = sg & 15;
+                    } else
+                        s = (__ballot(hit && m > 0) >> first) & 1ull ? 1 : -1;
                     p += first;
                     locked = 1;
                     c = run = 0;
@@ -146,12 +179,13 @@ __device__ __forceinline__ void outer_push(const OuterArgs &a, uint8_t *w, int s
             } else {
                 if (p + wordbits > avail) break;
                 const unsigned inv = s < 0 ? 255u : 0u;
-                const bool miss = (window_byte<MSB>(w, p) ^ inv) != sync;
+                const bool miss = (window_byte<MSB>(w, p) ^ inv) != (GROUP && gk == 0 ? sync ^ 255u : sync);      /* E(c) */
                 run = miss ? run + 1 : 0;
                 if (a.drop > 0 && run == a.drop) {
                     locked = 0;
                     p += 1;
                     nlost++;
+                    if (GROUP) gk = 0;      /* g is forgotten */
                     continue;
                 }
                 if (c >= I - 1) {
@@ -168,12 +202,18 @@ __device__ __forceinline__ void outer_push(const OuterArgs &a, uint8_t *w, int s
                         if (lane == 0) {
                             const size_t at = (size_t)stream * (size_t)a.max_words + (size_t)count;
                             if (a.pos) a.pos[at] = pos0 + p;
-                            if (a.wflags) a.wflags[at] = (uint8_t)(((window_byte<MSB>(w, first) ^ inv) != sync ? 1u : 0u) | (s < 0 ? 2u : 0u));
+                            if (GROUP) {
+                                const unsigned kz = (unsigned)((gk - (I - 1) % G + G) % G);      /* k(c - (I - 1)) */
+                                const unsigned ez = kz == 0 ? sync ^ 255u : sync;
+                                if (a.wflags) a.wflags[at] = (uint8_t)(((window_byte<MSB>(w, first) ^ inv) != ez ? 1u : 0u) | (s < 0 ? 2u : 0u) | kz << 4);
+                            } else if (a.wflags)
+                                a.wflags[at] = (uint8_t)(((window_byte<MSB>(w, first) ^ inv) != sync ? 1u : 0u) | (s < 0 ? 2u : 0u));
                         }
                     }
                     count++;
                 }
                 c = min(c + 1, I - 1);
+                if (GROUP) gk = gk + 1 == G ? 0 : gk + 1;
                 p += wordbits;
             }
         }
@@ -203,12 +243,16 @@ __device__ __forceinline__ void outer_push(const OuterArgs &a, uint8_t *w, int s
         unsigned *ring = reinterpret_cast<unsigned *>(state + OUTER_HDR);
         const unsigned *w4 = reinterpret_cast<const unsigned *>(w);
         for (int i = lane; i < nd; i += 64) ring[i] = w4[i];
-        if (lane < 6) hdr[lane] = lane == 0 ? locked : lane == 1 ? p : lane == 2 ? s : lane == 3 ? c : lane == 4 ? run : avail;
+        if (GROUP) {
+            if (lane < 7) hdr[lane] = lane == 0 ? locked : lane == 1 ? p : lane == 2 ? s : lane == 3 ? c : lane == 4 ? run : lane == 5 ? avail : gk;
+        } else if (lane < 6)
+            hdr[lane] = lane == 0 ? locked : lane == 1 ? p : lane == 2 ? s : lane == 3 ? c : lane == 4 ? run : avail;
     }
     if (lane == 0) a.count[stream] = count;
     if (a.info && lane < 4) a.info[4 * (size_t)stream + lane] = lane == 0 ? locked : lane == 1 ? (locked ? s : 0) : lane == 2 ? nlock : nlost;
 }
 
+template <bool GROUP>
 __global__ void __launch_bounds__(64 * OUTER_WAVES) outer_push_kernel(OuterArgs a, int nstreams)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t outer_lds[];
@@ -216,8 +260,8 @@ __global__ void __launch_bounds__(64 * OUTER_WAVES) outer_push_kernel(OuterArgs 
     const int stream = blockIdx.x * OUTER_WAVES + wave;
     if (stream >= nstreams) return;      /* a whole wave: nothing below waits for another */
     uint8_t *w = outer_lds + (size_t)wave * outer_slice_bytes(a.n, a.branches, a.lock);
-    if (a.flags & OUTER_MSB_FIRST) outer_push<true>(a, w, stream, lane);
-    else outer_push<false>(a, w, stream, lane);
+    if (a.flags & OUTER_MSB_FIRST) outer_push<true, GROUP>(a, w, stream, lane);
+    else outer_push<false, GROUP>(a, w, stream, lane);
 }
 
 /* a reset's state: HUNT from bit 0 over an empty ring */
@@ -266,7 +310,8 @@ static bool outer_geometry_fits(const OuterArgs &a, int nstreams)
 {
     return nstreams >= 1 && a.state && a.n >= 2 && a.n <= 255 && a.branches >= 1 && a.branches <= 32 && a.n % a.branches == 0 && a.sync >= 0 &&
            a.sync <= 255 && a.lock >= 1 && a.lock <= 16 && a.drop >= 0 && a.drop <= 16 && !(a.flags & ~(OUTER_POLARITY | OUTER_MSB_FIRST)) &&
-           a.state_stride >= outer_state_stride(a.n, a.branches, a.lock) && a.state_stride % 4 == 0;
+           a.state_stride >= outer_state_stride(a.n, a.branches, a.lock) && a.state_stride % 4 == 0 &&
+           (a.group == 0 || (a.group >= 3 && a.group <= 16 && a.lock >= a.group));
 }
 
 int launch_outer_init(const OuterArgs &a, int nstreams, hipStream_t s)
@@ -282,7 +327,9 @@ int launch_outer_push(const OuterArgs &a, int nstreams, hipStream_t s)
         a.bits_pitch < (size_t)((a.nbits + 7) >> 3) || (a.words && a.word_pitch < (size_t)a.n))
         return (int)hipErrorInvalidValue;
     const size_t lds = (size_t)OUTER_WAVES * outer_slice_bytes(a.n, a.branches, a.lock);
-    hipLaunchKernelGGL(outer_push_kernel, dim3((unsigned)((nstreams + OUTER_WAVES - 1) / OUTER_WAVES)), dim3(64 * OUTER_WAVES), lds, s, a, nstreams);
+    const dim3 grid((unsigned)((nstreams + OUTER_WAVES - 1) / OUTER_WAVES));
+    if (a.group) hipLaunchKernelGGL(outer_push_kernel<true>, grid, dim3(64 * OUTER_WAVES), lds, s, a, nstreams);
+    else hipLaunchKernelGGL(outer_push_kernel<false>, grid, dim3(64 * OUTER_WAVES), lds, s, a, nstreams);
     return (int)hipGetLastError();
 }
 

@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 TAU = 2.0 * 3.14159265358979323846
 TIMING_HIST, TIMING_FIXED, TIMING_FFT = 0, 1, 2
 OUTER_POLARITY, OUTER_MSB_FIRST = 1, 2      # qpsk_outer_reset's flags
+DISPERSAL_MSB_FIRST = 1                     # qpsk_dispersal_batch's
 NTAPS = 127
 
 
@@ -69,6 +70,7 @@ API_SYMBOLS = [
     "qpsk_conv_encode_stream_batch", "qpsk_test_viterbi_stream_advance",
     "qpsk_outer_reset", "qpsk_outer_max_words", "qpsk_outer_push", "qpsk_outer_interleave_batch", "qpsk_test_outer_advance",
     "qpsk_nodesync_reset", "qpsk_nodesync_shifts", "qpsk_nodesync_push", "qpsk_nodesync_set",
+    "qpsk_outer_reset_group", "qpsk_dispersal_batch", "qpsk_dispersal_sequence",
 ]
 # the named puncturing patterns of include/qpsk_hip.h (QPSK_PUNCT_*): rate -> (period, keep0, keep1), bit r of a mask = step r of the period
 PUNCTURE = {"1/2": (1, 0x1, 0x1), "2/3": (2, 0x1, 0x3), "3/4": (3, 0x5, 0x3), "5/6": (5, 0x15, 0x0B), "7/8": (7, 0x51, 0x2F)}
@@ -188,6 +190,9 @@ def load():
     L.qpsk_conv_encode_stream_batch.argtypes = [vp, vp, i32, i32, i32, u32, u32, vp, vp, vp]
     L.qpsk_test_viterbi_stream_advance.argtypes = [vp, C.c_longlong]
     L.qpsk_outer_reset.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32]
+    L.qpsk_outer_reset_group.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32]
+    L.qpsk_dispersal_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, i32, vp, i32, vp, C.c_longlong]
+    L.qpsk_dispersal_sequence.argtypes = [i32, i32, i32, vp]
     L.qpsk_outer_max_words.argtypes = [vp, i32]
     L.qpsk_outer_push.argtypes = [vp, vp, C.c_longlong, i32, i32, vp, vp, C.c_longlong, vp, vp, vp]
     L.qpsk_outer_interleave_batch.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
@@ -265,6 +270,17 @@ def rs_generator(nroots):
     if rc < 0:
         raise QpskError("libqpsk_hip error %d: %s" % (rc, L.qpsk_last_error().decode()))
     return g
+
+
+def dispersal_sequence(len=188, group=8, msb_first=False):      # noqa: A002 (the header's name)
+    """qpsk_dispersal_sequence: the group * len - 1 bytes PR of DVB's energy dispersal (DVB TRANSPORT in include/qpsk_hip.h), as bytes;
+    msb_first: a byte's first bit is its bit 7 (DVB's order: 03 F6 08 34 ...).  Host only, needs no GPU"""
+    L = load()
+    out = np.zeros(max(int(group) * int(len), 1), np.uint8)
+    rc = L.qpsk_dispersal_sequence(int(len), int(group), DISPERSAL_MSB_FIRST if msb_first else 0, out.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise QpskError("libqpsk_hip error %d: %s" % (rc, L.qpsk_last_error().decode()))
+    return out[:rc].tobytes()
 
 
 def nodesync_shifts(puncture):
@@ -733,12 +749,17 @@ class Modem:
         return out, nxt
 
     # ---- the outer link of a continuous stream
-    def outer_reset(self, nstreams, n, branches=1, sync=0x47, lock=2, drop=3, polarity=True, msb_first=False):
+    def outer_reset(self, nstreams, n, branches=1, sync=0x47, lock=2, drop=3, polarity=True, msb_first=False, group=0):
         """qpsk_outer_reset: nstreams receivers of words of n bytes behind viterbi_stream(): word sync on the byte `sync` (declared after
         `lock` words in a row, lost after `drop` misses in a row, 0 = never), polarity resolution, and a Forney deinterleaver of
-        `branches` branches (a divisor of n).  msb_first: a byte's first bit is its bit 7 (DVB's order)."""
+        `branches` branches (a divisor of n).  msb_first: a byte's first bit is its bit 7 (DVB's order).  group: 0, or 3..16 with lock >=
+        group = qpsk_outer_reset_group: every group-th word carries the complement of `sync` (DVB: 8), and outer()'s flags >> 4 is a
+        word's place in its group."""
         flags = (OUTER_POLARITY if polarity else 0) | (OUTER_MSB_FIRST if msb_first else 0)
-        self._check(self.L.qpsk_outer_reset(self.h, int(nstreams), int(n), int(branches), int(sync), int(lock), int(drop), flags))
+        if group:
+            self._check(self.L.qpsk_outer_reset_group(self.h, int(nstreams), int(n), int(branches), int(sync), int(lock), int(drop), flags, int(group)))
+        else:
+            self._check(self.L.qpsk_outer_reset(self.h, int(nstreams), int(n), int(branches), int(sync), int(lock), int(drop), flags))
         self._outer = (int(nstreams), int(n))
 
     def outer_max_words(self, nbits):
@@ -793,6 +814,29 @@ class Modem:
     def outer_advance(self, delta):
         """Test hook: move the outer link's position counter on by delta bits, a multiple of 8 (qpsk_test_outer_advance)."""
         self._check(self.L.qpsk_test_outer_advance(self.h, int(delta)))
+
+    # ---- DVB's energy dispersal (DVB TRANSPORT in include/qpsk_hip.h)
+    def dispersal(self, rows, group=8, flags=None, first=0, msb_first=False, pitch=0):
+        """qpsk_dispersal_batch: rows (R, len) uint8 -- a view with its rows further apart is taken as it lies -- -> (R, len) uint8, every
+        row xored with its part of the dispersal sequence, the first byte of a row of group index 0 inverted.  flags None: row r has
+        the index (first + r) % group (the transmitter); otherwise flags holds R bytes, outer()'s `flags` over the same rows, and a
+        row's index is flags >> 4 (a row whose index is >= group is copied).  pitch: the bytes between the OUTPUT's rows (0 = tight);
+        the result is then a view of a (R, pitch) buffer, whose other bytes are not written"""
+        t = self.torch
+        d = rows if isinstance(rows, t.Tensor) and rows.dtype == t.uint8 and rows.is_cuda else self._dev(rows, t.uint8)
+        if d.dim() != 2:
+            raise ValueError("dispersal() rows must be (rows, len) uint8")
+        R, n = d.shape
+        if d.stride(1) != 1 or (R > 1 and d.stride(0) < n):
+            d = d.contiguous()
+        f = None if flags is None else self._dev(flags, t.uint8).reshape(-1)
+        if f is not None and f.numel() != R:
+            raise ValueError("dispersal() flags must hold one byte per row (%d)" % R)
+        buf = self.empty((R, int(pitch) or n), t.uint8)
+        self._check(self.L.qpsk_dispersal_batch(self.h, _ptr(d), d.stride(0) if R > 1 else n, R, n, int(group), DISPERSAL_MSB_FIRST if msb_first else 0,
+                                                _ptr(f), int(first), _ptr(buf), int(pitch)))
+        self._dispersal_keep = (d, f)      # the inputs stay alive until the stream has run the call
+        return buf[:, :n]
 
     # ---- the node sync in front of the streaming decoder (NODE SYNC in include/qpsk_hip.h)
     def nodesync_reset(self, nlinks, nrot=2, nshift=1, span=4096, settle=1024, threshold=(1, 32), drop=2):
