@@ -14,8 +14,8 @@ import os
 import numpy as np
 import pytest
 
-from test_outer_cpu import (CASES, MSB_FIRST, POLARITY, bytes_to_bits, cut, damaged_stream, outer_interleave_ref, outer_ref, run_outer,
-                            split_sizes, word_bound)
+from test_outer_cpu import (CASES, MSB_FIRST, POLARITY, bytes_to_bits, cut, damaged_stream, input_set, outer_interleave_ref, outer_ref,
+                            run_outer, split_sizes, word_bound)
 from test_punct_cpu import NAMED
 from test_rs_cpu import rs_decode_ref, rs_encode_ref
 from test_rx_ext_cpu import declared
@@ -188,6 +188,122 @@ def group_stream(rng, n, I, G, L, nwords, lead=0, phase=0, kind="clean", invert=
     start = sum(len(p) for p in parts)
     b = np.concatenate(parts + [body])
     return (b ^ 1 if invert else b), x, start
+
+
+# ------------------------------------------------------------------- what the GPU tests push
+# As in test_outer_cpu.py: every input test_dvb_gpu.py feeds qpsk_outer_push under group sync is built here, so that the scalar port of the
+# kernel (outer_port.py, test_outer_port_cpu.py) runs over literally the same bits.
+STREAMS = (("clean", False, 5, 1), ("clean", True, 18, -1), ("decoy", False, 0, 2), ("slip", True, 43, 0), ("decoy+slip", False, 62, 3))
+GPU_GROUPS = ((6, 3, 3, 3), (20, 1, 8, 9), (204, 12, 8, 8), (255, 5, 16, 16))      # n, I, G, L
+GPU_FLAGS = (POLARITY, POLARITY | MSB_FIRST, 0, MSB_FIRST)
+GPU_DROP = 2
+
+
+def reference_of(s):
+    """the restatement of the header for an input set: outer_ref, or outer_group_ref where the set has a group"""
+    return outer_group_ref(**s["reset"])
+
+
+def reference_outputs(s):
+    """what the reference returns for every push of an input set"""
+    ref, wants = reference_of(s), []
+    for step in s["steps"]:
+        if step[0] == "advance":
+            ref.advance(step[1])
+        else:
+            wants.append(ref.push(step[1]))
+    return wants
+
+
+def group_streams(rng, n, I, G, L, msb_first):
+    """five streams (not a multiple of a workgroup's four waves): kind, inverted or not, lead-in and group phase all differ; random bodies,
+    false sync bytes and all.  -> bits (5, N)"""
+    nwords = 3 * L + 2 * I + 3 * G
+    made = [group_stream(rng, n, I, G, L, nwords, lead, phase % G, kind, inv, msb_first)[0] for kind, inv, lead, phase in STREAMS]
+    N = min(len(b) for b in made)
+    return np.stack([b[:N] for b in made])
+
+
+def random_cuts(rng, N, step):
+    """pushes of 1 bit seven times over (so that every bit phase total & 7 begins a push), then 7, 8191 and random lengths"""
+    sizes = [1] * 7 + [7, 8191] + [int(v) for v in rng.integers(1, 4 * step, 64)]
+    spans = cut(N, tuple(sizes))
+    assert {a & 7 for a, _ in spans} == set(range(8)) or N < 8
+    return spans
+
+
+def group_sync_inputs(n, I, G, L, flags):
+    rng = np.random.default_rng(n * 1000 + I * 100 + G * 10 + L + flags)
+    bits = group_streams(rng, n, I, G, L, bool(flags & MSB_FIRST))
+    return bits, random_cuts(rng, bits.shape[1], 8 * n)
+
+
+# b. a look-ahead longer than two groups (p0 has bits from 2 G on), the longest look-ahead with the shortest group, and I = 32 under group sync
+LONG_LOCKS = ((6, 3, 3, 7), (6, 2, 3, 16), (8, 4, 5, 16), (96, 32, 16, 16))      # n, I, G, L
+LONG_FLAGS = (POLARITY, 0)
+
+
+def long_lock_set(n, I, G, L, flags):
+    bits, spans = group_sync_inputs(n, I, G, L, flags)
+
+    def check(wants):
+        groups = np.concatenate([f >> 4 for w in wants for f in w["flags"]])
+        assert set(groups.tolist()) == set(range(G)), sorted(set(groups.tolist()))
+        emitted = sum(w["count"].astype(np.int64) for w in wants)
+        assert (emitted > 0).all() if flags & POLARITY else (emitted[0] > 0 and emitted[1] == 0 and emitted[3] == 0)
+    return input_set("long look-ahead %s flags %d" % ((n, I, G, L), flags), n, I, L, GPU_DROP, bits, spans, flags=flags, group=G, check=check)
+
+
+# d. the late decoy: L sync-like bytes whose first complement comes a whole group late -- complements at G, 2 G, ..., none at 0.  Every
+# legal mask has its first set bit below G, so the pattern is no (s, g)'s; a hunt that compared it with p0 shifted by G would take it
+LATE_DECOYS = ((6, 3, 3, 7), (6, 1, 3, 4), (20, 1, 8, 9), (6, 2, 8, 16))       # n, I, G, L
+LATE_STREAMS = ((False, 0, 1), (True, 3, 0), (False, 13, 2), (True, 6, 1))      # inverted, lead-in of zero bits, group phase
+
+
+def late_decoy_stream(rng, n, I, G, L, invert, lead, phase, sync=0x47):
+    """-> (bits, the bit the stream behind the decoy begins at)"""
+    d = rng.integers(0, 256, (L, n), dtype=np.uint8)
+    d[(d == sync) | (d == sync ^ 0xFF)] = 0
+    d[:, 0] = sync
+    d[G::G, 0] = sync ^ 0xFF
+    behind, _, start = group_stream(rng, n, I, G, L, L + I + G + 3, 0, phase, "clean", False, False, sync, plain_body=True)
+    assert start == 0
+    front = np.concatenate([np.zeros(lead, np.uint8), bytes_to_bits(d.reshape(-1)), rng.integers(0, 2, DECOY_GAP, dtype=np.uint8)])
+    b = np.concatenate([front, behind])
+    return (b ^ 1 if invert else b), len(front)
+
+
+def late_decoy_set(n, I, G, L):
+    rng = np.random.default_rng(n * 1000 + I * 100 + G * 10 + L + 7)
+    made = [late_decoy_stream(rng, n, I, G, L, inv, lead, phase) for inv, lead, phase in LATE_STREAMS]
+    N = min(len(b) for b, _ in made)
+    bits = np.stack([b[:N] for b, _ in made])
+
+    def check(wants):
+        for i, (_, start) in enumerate(made):
+            pos = np.concatenate([w["pos"][i] for w in wants])
+            info = sum(w["info"][i, 2:].astype(np.int64) for w in wants)
+            # one lock, never lost, on the first word behind the decoy: nothing was declared while the decoy passed
+            assert tuple(info) == (1, 0) and len(pos) > 0 and pos[0] == start + 8 * n * (I - 1), (i, info, pos[:2], start)
+            assert wants[-1]["info"][i, 1] == (-1 if LATE_STREAMS[i][0] else 1)
+    return input_set("late decoy %s" % ((n, I, G, L),), n, I, L, GPU_DROP, bits, [(0, N // 3 + 5), (N // 3 + 5, N)], group=G, check=check)
+
+
+def dvb_gpu_sets(new=True):
+    """every link test_dvb_gpu.py pushes through the device under group sync (new=False: without the cases b and d above).  Its test of
+    the old reset pushes test_outer_cpu's partition inputs, which outer_gpu_sets() holds"""
+    sets = []
+    if new:
+        sets += [late_decoy_set(*case) for case in LATE_DECOYS]
+        sets += [long_lock_set(*case, flags) for case in LONG_LOCKS for flags in LONG_FLAGS]
+    for n, I, G, L in GPU_GROUPS:
+        for flags in GPU_FLAGS:
+            bits, spans = group_sync_inputs(n, I, G, L, flags)
+            sets.append(input_set("group sync %s flags %d" % ((n, I, G, L), flags), n, I, L, GPU_DROP, bits, spans, flags=flags, group=G))
+    p = DVB
+    pushes = [unpack_bits(c["bits"], c["nbits"]) for c in dvb_link_result()["vcalls"] if c["nbits"]]
+    sets.append(input_set("the DVB link", p["n"], p["I"], p["L"], p["drop"], steps=[("push", b, None) for b in pushes], flags=p["flags"], group=p["G"]))
+    return sets
 
 
 # ------------------------------------------------------------------- 1. ABI (fails without the feature)

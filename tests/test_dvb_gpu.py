@@ -7,47 +7,29 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_dvb_cpu import DVB, dispersal_ref, dvb_link_result, group_stream, outer_group_ref
-from test_outer_cpu import MSB_FIRST, POLARITY, bytes_to_bits, cut, outer_ref, split_sizes
-from test_outer_gpu import run_both, streams_of
+from test_dvb_cpu import (DVB, GPU_DROP, GPU_FLAGS, GPU_GROUPS, LATE_DECOYS, LONG_FLAGS, LONG_LOCKS, dispersal_ref, dvb_link_result,
+                          group_sync_inputs, late_decoy_set, long_lock_set, outer_group_ref)
+from test_outer_cpu import MSB_FIRST, POLARITY, bytes_to_bits, cut, outer_ref, partition_inputs, split_sizes
+from test_outer_gpu import run_both, run_set
 from test_viterbi_cpu import pack_bits
 from test_viterbi_gpu import modem, ptr
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 64
-STREAMS = (("clean", False, 5, 1), ("clean", True, 18, -1), ("decoy", False, 0, 2), ("slip", True, 43, 0), ("decoy+slip", False, 62, 3))
-
-
-def group_streams(rng, n, I, G, L, msb_first):
-    """five streams (not a multiple of a workgroup's four waves): kind, inverted or not, lead-in and group phase all differ; random bodies,
-    false sync bytes and all.  -> bits (5, N)"""
-    nwords = 3 * L + 2 * I + 3 * G
-    made = [group_stream(rng, n, I, G, L, nwords, lead, phase % G, kind, inv, msb_first)[0] for kind, inv, lead, phase in STREAMS]
-    N = min(len(b) for b in made)
-    return np.stack([b[:N] for b in made])
-
-
-def random_cuts(rng, N, step):
-    """pushes of 1 bit seven times over (so that every bit phase total & 7 begins a push), then 7, 8191 and random lengths"""
-    sizes = [1] * 7 + [7, 8191] + [int(v) for v in rng.integers(1, 4 * step, 64)]
-    spans = cut(N, tuple(sizes))
-    assert {a & 7 for a, _ in spans} == set(range(8)) or N < 8
-    return spans
 
 
 # ------------------------------------------------------------------------------------------ 1. group sync
-@pytest.mark.parametrize("n,I,G,L", [(6, 3, 3, 3), (20, 1, 8, 9), (204, 12, 8, 8), (255, 5, 16, 16)])
-@pytest.mark.parametrize("flags", [POLARITY, POLARITY | MSB_FIRST, 0, MSB_FIRST])
+@pytest.mark.parametrize("n,I,G,L", GPU_GROUPS)
+@pytest.mark.parametrize("flags", GPU_FLAGS)
 def test_group_sync_at_every_geometry_bit_order_polarity_and_bit_phase(n, I, G, L, flags):
-    rng = np.random.default_rng(n * 1000 + I * 100 + G * 10 + L + flags)
-    bits = group_streams(rng, n, I, G, L, bool(flags & MSB_FIRST))
+    bits, spans = group_sync_inputs(n, I, G, L, flags)        # five streams; every bit phase begins a push
     S, N = bits.shape
-    drop = 2
+    drop = GPU_DROP
     m = modem()
     m.outer_reset(S, n, I, 0x47, L, drop, polarity=bool(flags & POLARITY), msb_first=bool(flags & MSB_FIRST), group=G)
     assert m.last_kernel() == "outer_init_kernel"
-    calls = run_both(m, outer_group_ref(S, n, I, 0x47, L, drop, flags, G), n, bits, random_cuts(rng, N, 8 * n))
+    calls = run_both(m, outer_group_ref(S, n, I, 0x47, L, drop, flags, G), n, bits, spans)
     emitted = sum(c["count"].astype(np.int64) for c in calls)
     info = sum(c["info"][:, 2:].astype(np.int64) for c in calls)
     if flags & POLARITY:
@@ -61,13 +43,34 @@ def test_group_sync_at_every_geometry_bit_order_polarity_and_bit_phase(n, I, G, 
     m.close()
 
 
+# The inputs of the next two are input sets of test_dvb_cpu.py; test_outer_port_cpu.py shows on the scalar port of the kernel what each is
+# there to catch (p0's bits from 2 G on, I = 32 under group sync; a legal-mask test that forgets fx < G or fy < G).
+@pytest.mark.parametrize("n,I,G,L", LONG_LOCKS)
+@pytest.mark.parametrize("flags", LONG_FLAGS)
+def test_group_sync_with_a_look_ahead_longer_than_two_groups_and_with_32_branches(n, I, G, L, flags):
+    m = modem()
+    run_set(m, long_lock_set(n, I, G, L, flags))             # every group index appears in the flags: asserted on the reference
+    m.sync()
+    m.close()
+
+
+@pytest.mark.parametrize("n,I,G,L", LATE_DECOYS)
+def test_a_decoy_whose_first_complement_comes_a_whole_group_late_is_not_a_lock(n, I, G, L):
+    """L sync-like bytes with complements at G, 2 G, ... and none at 0, upright and inverted: no lock while they pass, one lock on the first
+    word of the stream behind them (asserted on the reference)"""
+    m = modem()
+    calls = run_set(m, late_decoy_set(n, I, G, L))
+    assert np.array_equal(sum(c["info"][:, 2:] for c in calls), [[1, 0]] * 4) and all(c["info"][:, 0].all() for c in calls[-1:])
+    m.sync()
+    m.close()
+
+
 # ------------------------------------------------------------------------------------------ 2. the old reset
 @pytest.mark.parametrize("n,I,L,drop", [(6, 3, 3, 1), (204, 12, 2, 3)])
 def test_the_old_reset_is_unchanged(n, I, L, drop):
     """test_outer_gpu's partition cases through qpsk_outer_reset, and through qpsk_outer_reset_group with group 0: outer_ref's outputs, bits
     4..7 of the flags zero"""
-    rng = np.random.default_rng(n)
-    bits, _ = streams_of(rng, n, I, 2 * I + 14 if n > 100 else 70, ("delete", "clean", "insert+invert"))
+    bits = partition_inputs(n, I)
     S, N = bits.shape
     m = modem()
     for group_zero in (False, True):

@@ -8,6 +8,9 @@ all u with array operations and the state machine loops over events only (a lock
 What the arguments of qpsk_outer_reset, qpsk_outer_max_words and qpsk_outer_interleave_batch decide by themselves is decided before the
 context is looked at, so every such QPSK_ERR_ARG is pinned here, by its error text, without a device; test_outer_gpu.py repeats them on a
 context, with the refusals of the push.
+
+The bits test_outer_gpu.py pushes through the device are built here too (outer_gpu_sets and the functions it calls), so that
+test_outer_port_cpu.py can run the scalar port of the kernel over the same inputs and say what they would and would not notice.
 """
 import ctypes as C
 import inspect
@@ -202,6 +205,244 @@ def damaged_stream(rng, n, I, nwords, lead, kind, sync=0x47):
         else:
             assert k == "clean"
     return b, x[0]
+
+
+# ------------------------------------------------------------------- what the GPU tests push
+# Every input test_outer_gpu.py feeds the device is built here, so that test_outer_port_cpu.py runs the scalar port of the kernel
+# (outer_port.py) over literally the same bits: the GPU tests call these functions, and outer_gpu_sets() calls them over the same parameter
+# lists.  An input set is one link: the reset's arguments and its steps, ("push", bits (S, nbits), max_words or None) or ("advance", delta);
+# "check", where a set has one, asserts on the reference's outputs alone what the case is there for.
+LEADS = (0, 9, 18, 27, 36, 45, 54, 63)      # one lead-in per stream: every value of u0 & 7
+GPU_GEOMETRIES = ((4, 1), (4, 2), (4, 4), (6, 3), (255, 1), (204, 12))
+GPU_LOCKS = ((1, 0), (2, 1), (3, 2), (1, 2), (3, 0))
+GPU_FLAGS = (POLARITY, 0, POLARITY | MSB_FIRST, MSB_FIRST)
+GPU_SLIPS = ((4, 2), (6, 3))
+GPU_PARTITIONS = ((4, 2, 2, 2), (6, 3, 3, 1), (204, 12, 2, 3))
+
+
+def streams_of(rng, n, I, nwords, kinds, leads=LEADS, msb_first=False, sync=0x47):
+    """one damaged_stream per lead-in, cut to a common length: (bits (S, N), the source words)"""
+    made = [damaged_stream(rng, n, I, nwords, lead, kinds[i % len(kinds)], sync) for i, lead in enumerate(leads)]
+    if msb_first:      # the same bytes sent high bit first: every byte of the bit stream is reversed in place
+        made = [(np.concatenate([b[:lead], b[lead:lead + (len(b) - lead) // 8 * 8].reshape(-1, 8)[:, ::-1].reshape(-1)]), x)
+                for (b, x), lead in zip(made, leads)]
+    N = min(len(b) for b, _ in made)
+    return np.stack([b[:N] for b, _ in made]), [x for _, x in made]
+
+
+def input_set(what, n, I, L, drop, bits=None, spans=None, steps=None, flags=POLARITY, group=0, sync=0x47, check=None):
+    if steps is None:
+        steps = [("push", bits[:, a:b], None) for a, b in spans]
+    S = next(x[1] for x in steps if x[0] == "push").shape[0]
+    return dict(what=what, reset=dict(nstreams=S, n=n, branches=I, sync=sync, lock=L, drop=drop, flags=flags, group=group), steps=steps, check=check)
+
+
+def geometry_inputs(n, I, L, drop):
+    rng = np.random.default_rng(n * 1000 + I * 100 + L * 10 + drop)
+    bits, _ = streams_of(rng, n, I, 2 * I + L + 8, ("clean", "delete", "insert"))
+    N = bits.shape[1]
+    return bits, [(0, N // 3 + 5), (N // 3 + 5, N)]
+
+
+def polarity_inputs(flags):
+    rng = np.random.default_rng(flags + 5)
+    bits, x = streams_of(rng, 6, 3, 40, ("clean",), msb_first=bool(flags & MSB_FIRST), sync=0x47)
+    bits[1::2] ^= 1                                           # every other stream inverted
+    N = bits.shape[1]
+    return bits, x, [(0, N // 2 + 3), (N // 2 + 3, N)]
+
+
+def slip_inputs(n, I, across):
+    rng = np.random.default_rng(n + I + across)
+    bits, _ = streams_of(rng, n, I, 90, ("delete+invert", "insert+invert", "invert", "delete"))
+    N = bits.shape[1]
+    # the slips sit near N / 2, the inversion at 2 N / 3: inside one push, or with a push boundary on each
+    return bits, [(0, N // 2), (N // 2, N * 2 // 3 + 30), (N * 2 // 3 + 30, N)] if across else [(0, N)]
+
+
+def partition_inputs(n, I):
+    rng = np.random.default_rng(n)
+    return streams_of(rng, n, I, 2 * I + 14 if n > 100 else 70, ("delete", "clean", "insert+invert"))[0]
+
+
+def big16_inputs():
+    rng = np.random.default_rng(16)
+    return streams_of(rng, 4, 2, (1 << 16) // 32 + 80, ("clean", "delete"), leads=(0, 13, 70))[0]
+
+
+def big20_inputs():
+    rng = np.random.default_rng(20)
+    return streams_of(rng, 204, 12, (1 << 20) // 1632 + 2, ("clean", "delete+invert"), leads=(5, 62))[0][:, :1 << 20]
+
+
+def layout_inputs():
+    rng = np.random.default_rng(6)
+    bits, _ = streams_of(rng, 6, 3, 60, ("clean", "insert"))
+    return bits, cut(bits.shape[1], (301, 299, 403, 211, 97))
+
+
+def positions_inputs():
+    rng = np.random.default_rng(31)
+    return streams_of(rng, 6, 3, 90, ("delete+invert", "insert"))[0]
+
+
+def refusal_inputs():
+    rng = np.random.default_rng(8)
+    return streams_of(rng, 6, 3, 60, ("clean", "delete"))[0]
+
+
+def replaced_link_inputs():
+    rng = np.random.default_rng(88)
+    bits, _ = streams_of(rng, 4, 2, 40, ("clean",))
+    other, _ = streams_of(rng, 6, 3, 30, ("clean",), leads=LEADS[:3])
+    return bits, other
+
+
+def totals(wants):
+    """per stream: words emitted, locks declared, locks lost, over all the calls of a link"""
+    return (sum(w["count"].astype(np.int64) for w in wants), sum(w["info"][:, 2].astype(np.int64) for w in wants),
+            sum(w["info"][:, 3].astype(np.int64) for w in wants))
+
+
+# a. the limits of the geometry: I = 32 (the gather's lanes 32 .. 63 wrap twice), the longest word I = 32 allows, L = 16 and drop = 16
+LIMITS = ((64, 32, 2, 3, False), (32, 32, 3, 2, True), (224, 32, 2, 3, False), (6, 3, 16, 16, False), (4, 1, 16, 3, True))      # n, I, L, drop, split
+LIMIT_KINDS = ("clean", "delete", "insert")
+
+
+def limit_inputs(n, I, L, drop, split):
+    """eight streams at the eight lead-ins; a slip sits in the middle, so either half holds the words of a lock, of a drop and of I - 1
+    words in flight with some to spare"""
+    rng = np.random.default_rng(n * 1000 + I * 100 + L * 10 + drop)
+    bits, _ = streams_of(rng, n, I, 2 * (I + L + drop) + 16, LIMIT_KINDS)
+    N = bits.shape[1]
+    return bits, cut(N, split_sizes(n)) if split else [(0, N // 3 + 5), (N // 3 + 5, N)]
+
+
+def limit_set(n, I, L, drop, split):
+    def check(wants):
+        emitted, nlock, nlost = totals(wants)
+        assert (emitted > 0).all(), emitted
+        if drop == 16:                                        # the streams with a slip lose the lock sixteen misses later and find it again
+            slipped = np.array([LIMIT_KINDS[i % 3] != "clean" for i in range(len(LEADS))])
+            assert (nlost[slipped] >= 1).all() and (nlock[slipped] >= 2).all(), (nlock, nlost)
+    bits, spans = limit_inputs(n, I, L, drop, split)
+    return input_set("limits %s" % ((n, I, L, drop),), n, I, L, drop, bits, spans, check=check)
+
+
+# c. the look-ahead edge: the push that ends on the last bit of a candidate's look-ahead declares the lock, the one a bit shorter does not
+EDGES = ((4, 1, 3), (6, 3, 2))              # n, I, L
+EDGE_LEADS = range(10)
+
+
+def edge_stream(n, L, I, lead):
+    """`lead` zero bits, then words of a sync byte and a zero body: no candidate but the true one"""
+    x = np.zeros((L + I + 3, n), np.uint8)
+    x[:, 0] = 0x47
+    return np.concatenate([np.zeros(lead, np.uint8), bytes_to_bits(x.reshape(-1))])
+
+
+def edge_sets(n, I, L):
+    """HUNT: every lead-in of 0 .. 9 bits against a cut at lead + span - 2 .. lead + span + 2, the streams whose cut is the same bit
+    sharing a link.  LOCKED: the cut on the last bit of raw word L + I - 1 and one bit before it"""
+    span, step = 8 * n * (L - 1) + 8, 8 * n
+    N = len(edge_stream(n, L, I, 0))
+    sets = []
+    for k in range(-2, 12):                                   # the cut at span + k: the leads within 2 of k
+        leads = [l for l in EDGE_LEADS if abs(k - l) <= 2]
+        bits = np.stack([edge_stream(n, L, I, l)[:N] for l in leads])
+
+        def check(wants, leads=leads, k=k):
+            for i, l in enumerate(leads):
+                assert wants[0]["info"][i, 2] == (1 if k >= l else 0), (k, l, wants[0]["info"][i])
+                assert wants[0]["info"][i, 2] + wants[1]["info"][i, 2] == 1 and wants[1]["count"][i] > 0
+        sets.append(input_set("hunt edge %s cut at span + %d" % ((n, I, L), k), n, I, L, 3, bits, [(0, span + k), (span + k, N)], check=check))
+    words = L + I                                             # raw words whole in the first push: emitted from word I - 1 on
+    for j in range(-1, 10):                                   # the cut at step * words + j: on a stream's last bit (lead = j), or one before
+        leads = [l for l in EDGE_LEADS if l - j in (0, 1)]
+        bits = np.stack([edge_stream(n, L, I, l)[:N] for l in leads])
+
+        def check(wants, leads=leads, j=j):
+            for i, l in enumerate(leads):
+                assert wants[0]["count"][i] == words - (I - 1) - (l - j), (j, l, wants[0]["count"])
+                assert wants[0]["count"][i] + wants[1]["count"][i] == (N - l) // step - (I - 1)
+        sets.append(input_set("word edge %s cut at %d words + %d" % ((n, I, L), words, j), n, I, L, 3, bits,
+                              [(0, step * words + j), (step * words + j, N)], check=check))
+    return sets
+
+
+# e. hunting through chunks: at (255, 1) and L = 16 a candidate's look-ahead spans 30 608 bits, so four chunks of 8192 bits arrive before
+# the first candidate is whole, and the window holds the most a hunt ever keeps
+NOISE = dict(n=255, I=1, L=16, drop=3, nbits=6 * 8192, leads=(0, 5))
+
+
+def noise_set(phase):
+    """noise in one push (preceded by a push of `phase` bits, so that it is appended at that bit phase), then a clean stream"""
+    p = NOISE
+    rng = np.random.default_rng(255 + phase)
+    noise = rng.integers(0, 2, (2, phase + p["nbits"]), dtype=np.uint8)
+    clean, _ = streams_of(rng, p["n"], p["I"], p["L"] + 4, ("clean",), leads=p["leads"])
+    steps = ([("push", noise[:, :phase], None)] if phase else []) + [("push", noise[:, phase:], None), ("push", clean, None)]
+
+    def check(wants):
+        for w in wants[:-1]:
+            assert not w["count"].any() and not w["info"].any()
+        last = wants[-1]
+        assert np.array_equal(last["info"], [[1, 1, 1, 0]] * 2) and (last["count"] > 0).all()
+        assert [int(x[0]) for x in last["pos"]] == [phase + p["nbits"] + lead for lead in p["leads"]]      # counted from the reset
+    return input_set("noise at bit phase %d" % phase, p["n"], p["I"], p["L"], p["drop"], steps=steps, check=check)
+
+
+# f. max_words = 0: the count is the true count and nothing else is written
+def no_slots_set():
+    bits, _ = streams_of(np.random.default_rng(60), 6, 3, 40, ("clean", "insert"))
+    N = bits.shape[1]
+    steps = [("push", bits[:, :N // 3], None), ("push", bits[:, N // 3:2 * N // 3], 0), ("push", bits[:, 2 * N // 3:], None)]
+
+    def check(wants):
+        assert (wants[1]["count"] > 0).all() and (wants[2]["count"] > 0).all()
+    return input_set("max_words = 0", 6, 3, 2, 2, steps=steps, check=check)
+
+
+def outer_gpu_sets(new=True):
+    """every link test_outer_gpu.py pushes through the device (new=False: without the cases a and c above)"""
+    sets = []
+    if new:
+        sets += [s for n, I, L in EDGES for s in edge_sets(n, I, L)]
+        sets += [limit_set(*case) for case in LIMITS]
+    sets += [no_slots_set(), noise_set(0), noise_set(3)]
+    for n, I in GPU_GEOMETRIES:
+        for L, drop in GPU_LOCKS:
+            sets.append(input_set("geometry %s" % ((n, I, L, drop),), n, I, L, drop, *geometry_inputs(n, I, L, drop)))
+    for flags in GPU_FLAGS:
+        bits, _, spans = polarity_inputs(flags)
+        sets.append(input_set("polarity and bit order %d" % flags, 6, 3, 2, 2, bits, spans, flags=flags))
+    for n, I in GPU_SLIPS:
+        for across in (False, True):
+            sets.append(input_set("slips %s" % ((n, I, across),), n, I, 2, 2, *slip_inputs(n, I, across)))
+    for n, I, L, drop in GPU_PARTITIONS:
+        bits = partition_inputs(n, I)
+        N = bits.shape[1]
+        sets.append(input_set("the repeating split %s" % ((n, I, L, drop),), n, I, L, drop, bits, cut(N, split_sizes(n))))
+        sets.append(input_set("one push %s" % ((n, I, L, drop),), n, I, L, drop, bits, [(0, N)]))
+    bits = big16_inputs()
+    sets.append(input_set("2^16 bits into three slots", 4, 2, 2, 2, steps=[("push", bits[:, :1 << 16], 3), ("push", bits[:, 1 << 16:], None)]))
+    bits = big20_inputs()
+    sets.append(input_set("2^20 bits", 204, 12, 2, 3, bits, [(0, 1 << 20)]))
+    sets.append(input_set("layout", 6, 3, 2, 2, *layout_inputs()))
+    bits = positions_inputs()
+    N = bits.shape[1]
+    for delta in (1 << 31, 1 << 40):
+        sets.append(input_set("positions past %d" % delta, 6, 3, 2, 2, steps=[("push", bits[:, :N // 4], None), ("advance", delta),
+                                                                                ("push", bits[:, N // 4:N // 2 + 9], None), ("push", bits[:, N // 2 + 9:], None)]))
+    bits = refusal_inputs()
+    sets.append(input_set("around the refused calls", 6, 3, 2, 2, bits, [(0, 400), (400, 901), (901, bits.shape[1])]))
+    bits, other = replaced_link_inputs()
+    sets.append(input_set("the link a reset replaces", 4, 2, 2, 2, bits, [(0, bits.shape[1] // 2)]))
+    sets.append(input_set("the link that replaces it", 6, 3, 1, 0, other, [(0, other.shape[1])], flags=0, sync=0xB8))
+    for I in (1, 12):
+        pushes = [unpack_bits(c["bits"], c["nbits"]) for c in link_result()[I]["vcalls"] if c["nbits"]]
+        sets.append(input_set("the link at I = %d" % I, LINK["n"], I, LINK["lock"], LINK["drop"], steps=[("push", b, None) for b in pushes], sync=LINK["sync"]))
+    return sets
 
 
 # ------------------------------------------------------------------- 1. ABI (fails without the feature)

@@ -8,8 +8,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_outer_cpu import (LINK, MSB_FIRST, POLARITY, bytes_to_bits, cut, damaged_stream, link_result, outer_interleave_ref, outer_ref,
-                            split_sizes, sync_words, word_bound)
+from test_dvb_cpu import reference_of
+from test_outer_cpu import (EDGES, GPU_FLAGS, GPU_GEOMETRIES, GPU_LOCKS, GPU_PARTITIONS, GPU_SLIPS, LIMITS, LINK, MSB_FIRST, POLARITY,
+                            big16_inputs, big20_inputs, cut, edge_sets, geometry_inputs, layout_inputs, limit_set, link_result, no_slots_set,
+                            noise_set, outer_interleave_ref, outer_ref, partition_inputs, polarity_inputs, positions_inputs, refusal_inputs,
+                            replaced_link_inputs, slip_inputs, split_sizes, word_bound)
 from test_viterbi_cpu import pack_bits
 from test_viterbi_gpu import modem, ptr
 
@@ -18,7 +21,6 @@ pytestmark = pytest.mark.gpu
 QPSK_ERR_ARG, QPSK_ERR_STATE = -2, -5
 GUARD = 64
 ALL = ("words", "pos", "flags", "info")
-LEADS = (0, 9, 18, 27, 36, 45, 54, 63)      # one lead-in per stream: every value of u0 & 7
 
 
 def device_bits(bits, pitch=0):
@@ -98,45 +100,54 @@ def run_both(m, ref, n, bits, spans, what="", **kw):
     return calls
 
 
-def streams_of(rng, n, I, nwords, kinds, leads=LEADS, msb_first=False, sync=0x47):
-    """one damaged_stream per lead-in, cut to a common length: (bits (S, N), the source words)"""
-    made = [damaged_stream(rng, n, I, nwords, lead, kinds[i % len(kinds)], sync) for i, lead in enumerate(leads)]
-    if msb_first:      # the same bytes sent high bit first: every byte of the bit stream is reversed in place
-        made = [(np.concatenate([b[:lead], b[lead:lead + (len(b) - lead) // 8 * 8].reshape(-1, 8)[:, ::-1].reshape(-1)]), x)
-                for (b, x), lead in zip(made, leads)]
-    N = min(len(b) for b, _ in made)
-    return np.stack([b[:N] for b, _ in made]), [x for _, x in made]
+def run_set(m, s, **kw):
+    """one input set of test_outer_cpu / test_dvb_cpu -- the sets the scalar port of the kernel is held to in test_outer_port_cpu.py --
+    through the device and the restatement, every call compared; what the set asserts on the reference alone is asserted here too
+    -> the device's calls"""
+    r = s["reset"]
+    m.outer_reset(r["nstreams"], r["n"], r["branches"], r["sync"], r["lock"], r["drop"], polarity=bool(r["flags"] & POLARITY),
+                  msb_first=bool(r["flags"] & MSB_FIRST), group=r["group"])
+    ref, calls, wants = reference_of(s), [], []
+    for step in s["steps"]:
+        if step[0] == "advance":
+            m.outer_advance(step[1])
+            ref.advance(step[1])
+            continue
+        got = push(m, r["nstreams"], r["n"], step[1], max_words=step[2], **kw)
+        wants.append(ref.push(step[1]))
+        same(got, wants[-1], (s["what"], "push", len(calls)))
+        calls.append(got)
+    if s["check"]:
+        s["check"](wants)
+    return calls
 
 
 # ------------------------------------------------------------------------------------------ 1. geometry
-@pytest.mark.parametrize("n,I", [(4, 1), (4, 2), (4, 4), (6, 3), (255, 1), (204, 12)])
-@pytest.mark.parametrize("L,drop", [(1, 0), (2, 1), (3, 2), (1, 2), (3, 0)])
+@pytest.mark.parametrize("n,I", GPU_GEOMETRIES)
+@pytest.mark.parametrize("L,drop", GPU_LOCKS)
 def test_every_geometry_locks_at_every_bit_phase_and_emits_the_reference_s_words(n, I, L, drop):
-    rng = np.random.default_rng(n * 1000 + I * 100 + L * 10 + drop)
-    bits, _ = streams_of(rng, n, I, 2 * I + L + 8, ("clean", "delete", "insert"))
+    bits, spans = geometry_inputs(n, I, L, drop)
     S, N = bits.shape
     m = modem()
     m.outer_reset(S, n, I, 0x47, L, drop)
     assert m.last_kernel() == "outer_init_kernel"
     assert m.outer_max_words(N) == word_bound(L, n, N)
-    calls = run_both(m, outer_ref(S, n, I, 0x47, L, drop), n, bits, [(0, N // 3 + 5), (N // 3 + 5, N)])
+    calls = run_both(m, outer_ref(S, n, I, 0x47, L, drop), n, bits, spans)
     assert sum(int(c["count"].sum()) for c in calls) >= S
     m.sync()
     m.close()
 
 
 # ------------------------------------------------------------------------------------------ 2. polarity and bit order
-@pytest.mark.parametrize("flags", [POLARITY, 0, POLARITY | MSB_FIRST, MSB_FIRST])
+@pytest.mark.parametrize("flags", GPU_FLAGS)
 def test_inverted_streams_lock_with_s_minus_one_only_with_polarity_and_msb_first_reverses_the_bytes(flags):
-    rng = np.random.default_rng(flags + 5)
     n, I, L, drop = 6, 3, 2, 2
-    bits, x = streams_of(rng, n, I, 40, ("clean",), msb_first=bool(flags & MSB_FIRST), sync=0x47)
-    bits[1::2] ^= 1                                           # every other stream inverted
+    bits, x, spans = polarity_inputs(flags)                   # every other stream inverted
     S, N = bits.shape
     m = modem()
     m.outer_reset(S, n, I, 0x47, L, drop, polarity=bool(flags & POLARITY), msb_first=bool(flags & MSB_FIRST))
     ref = outer_ref(S, n, I, 0x47, L, drop, flags)
-    calls = run_both(m, ref, n, bits, [(0, N // 2 + 3), (N // 2 + 3, N)])
+    calls = run_both(m, ref, n, bits, spans)
     last = calls[-1]
     assert (last["info"][0::2, 1] == 1).all()
     if flags & POLARITY:
@@ -150,16 +161,13 @@ def test_inverted_streams_lock_with_s_minus_one_only_with_polarity_and_msb_first
 
 # ------------------------------------------------------------------------------------------ 3. slips
 @pytest.mark.parametrize("across", [False, True])
-@pytest.mark.parametrize("n,I", [(4, 2), (6, 3)])
+@pytest.mark.parametrize("n,I", GPU_SLIPS)
 def test_a_deleted_bit_an_inserted_bit_and_an_inversion_drop_the_lock_and_relock(n, I, across):
-    rng = np.random.default_rng(n + I + across)
-    bits, _ = streams_of(rng, n, I, 90, ("delete+invert", "insert+invert", "invert", "delete"))
+    bits, spans = slip_inputs(n, I, across)      # the slips near N / 2, the inversion at 2 N / 3: inside one push, or a push boundary on each
     S, N = bits.shape
     m = modem()
     m.outer_reset(S, n, I, 0x47, 2, 2)
     ref = outer_ref(S, n, I, 0x47, 2, 2)
-    # the slips sit near N / 2, the inversion at 2 N / 3: inside one push, or with a push boundary on each
-    spans = [(0, N // 2), (N // 2, N * 2 // 3 + 30), (N * 2 // 3 + 30, N)] if across else [(0, N)]
     calls = run_both(m, ref, n, bits, spans)
     info = sum(c["info"][:, 2:].astype(np.int64) for c in calls)
     assert (info[:, 0] >= 2).all() and (info[:, 1] >= 1).all()      # every stream lost its lock and found another
@@ -168,10 +176,9 @@ def test_a_deleted_bit_an_inserted_bit_and_an_inversion_drop_the_lock_and_relock
 
 
 # ------------------------------------------------------------------------------------------ 4. partition independence
-@pytest.mark.parametrize("n,I,L,drop", [(4, 2, 2, 2), (6, 3, 3, 1), (204, 12, 2, 3)])
+@pytest.mark.parametrize("n,I,L,drop", GPU_PARTITIONS)
 def test_the_same_bits_in_one_push_and_in_the_repeating_split(n, I, L, drop):
-    rng = np.random.default_rng(n)
-    bits, _ = streams_of(rng, n, I, 2 * I + 14 if n > 100 else 70, ("delete", "clean", "insert+invert"))
+    bits = partition_inputs(n, I)
     S, N = bits.shape
     m = modem()
     m.outer_reset(S, n, I, 0x47, L, drop)
@@ -187,9 +194,8 @@ def test_the_same_bits_in_one_push_and_in_the_repeating_split(n, I, L, drop):
 
 # ------------------------------------------------------------------------------------------ 5. large pushes
 def test_a_push_of_65536_bits_into_three_slots_counts_every_word_and_the_state_goes_on():
-    rng = np.random.default_rng(16)
     n, I, L, drop = 4, 2, 2, 2
-    bits, _ = streams_of(rng, n, I, (1 << 16) // 32 + 80, ("clean", "delete"), leads=(0, 13, 70))
+    bits = big16_inputs()
     S = bits.shape[0]
     m = modem()
     m.outer_reset(S, n, I, 0x47, L, drop)
@@ -205,10 +211,8 @@ def test_a_push_of_65536_bits_into_three_slots_counts_every_word_and_the_state_g
 
 
 def test_one_push_of_2_to_the_20_bits_at_204_12():
-    rng = np.random.default_rng(20)
     n, I = 204, 12
-    bits, _ = streams_of(rng, n, I, (1 << 20) // 1632 + 2, ("clean", "delete+invert"), leads=(5, 62))
-    bits = bits[:, :1 << 20]
+    bits = big20_inputs()
     m = modem()
     m.outer_reset(2, n, I)
     got = push(m, 2, n, bits)
@@ -219,14 +223,12 @@ def test_one_push_of_2_to_the_20_bits_at_204_12():
 
 # ------------------------------------------------------------------------------------------ 6. layout
 def test_pitched_rows_pitched_words_and_each_optional_output_null_in_turn():
-    rng = np.random.default_rng(6)
     n, I, L, drop = 6, 3, 2, 2
-    bits, _ = streams_of(rng, n, I, 60, ("clean", "insert"))
+    bits, spans = layout_inputs()
     S, N = bits.shape
     m = modem()
     m.outer_reset(S, n, I, 0x47, L, drop)
     ref = outer_ref(S, n, I, 0x47, L, drop)
-    spans = cut(N, (301, 299, 403, 211, 97))
     wants = [ALL, ("pos", "flags", "info"), ("words", "flags", "info"), ("words", "pos", "info"), ("words", "pos", "flags"), ()]
     for k, (a, b) in enumerate(spans):
         got = push(m, S, n, bits[:, a:b], want=wants[k % len(wants)], word_pitch=(0, 11, n)[k % 3], bits_pitch=(b - a + 7) // 8 + (0, 3, 17)[k % 3])
@@ -237,9 +239,8 @@ def test_pitched_rows_pitched_words_and_each_optional_output_null_in_turn():
 # ------------------------------------------------------------------------------------------ 7. positions
 @pytest.mark.parametrize("delta", [1 << 31, 1 << 40])
 def test_positions_past_32_bits_are_exact(delta):
-    rng = np.random.default_rng(31)
     n, I, L, drop = 6, 3, 2, 2
-    bits, _ = streams_of(rng, n, I, 90, ("delete+invert", "insert"))
+    bits = positions_inputs()
     S, N = bits.shape
     m = modem()
     m.outer_reset(S, n, I, 0x47, L, drop)
@@ -258,9 +259,8 @@ def test_positions_past_32_bits_are_exact(delta):
 # ------------------------------------------------------------------------------------------ 8. state and refusals
 def test_refused_calls_launch_nothing_and_leave_the_state_untouched():
     import torch
-    rng = np.random.default_rng(8)
     n, I, L, drop = 6, 3, 2, 2
-    bits, _ = streams_of(rng, n, I, 60, ("clean", "delete"))
+    bits = refusal_inputs()
     S, N = bits.shape
     m = modem()
     d_bits, bp = device_bits(bits[:, :400])
@@ -314,16 +314,54 @@ def test_refused_calls_launch_nothing_and_leave_the_state_untouched():
 
 
 def test_a_reset_over_an_armed_link_replaces_it():
-    rng = np.random.default_rng(88)
-    bits, _ = streams_of(rng, 4, 2, 40, ("clean",))
+    bits, other = replaced_link_inputs()
     S, N = bits.shape
     m = modem()
     m.outer_reset(S, 4, 2, 0x47, 2, 2)
     run_both(m, outer_ref(S, 4, 2, 0x47, 2, 2), 4, bits, [(0, N // 2)])
-    other, _ = streams_of(rng, 6, 3, 30, ("clean",), leads=LEADS[:3])
     m.outer_reset(3, 6, 3, 0xB8, 1, 0, polarity=False)
     calls = run_both(m, outer_ref(3, 6, 3, 0xB8, 1, 0, 0), 6, other, [(0, other.shape[1])])
     assert (calls[0]["pos"][0] < N // 2).any()                # positions count from the new reset
+    m.close()
+
+
+# ------------------------------------------------------------------------------------------ 8a. limits, edges and chunks
+# The inputs are input sets of test_outer_cpu.py; test_outer_port_cpu.py shows on the scalar port of the kernel what each is there to catch.
+@pytest.mark.parametrize("n,I,L,drop,split", LIMITS)
+def test_the_limits_of_the_geometry_32_branches_a_lock_of_16_and_a_drop_of_16(n, I, L, drop, split):
+    m = modem()
+    run_set(m, limit_set(n, I, L, drop, split))
+    m.sync()
+    m.close()
+
+
+@pytest.mark.parametrize("n,I,L", EDGES)
+def test_a_push_that_ends_on_the_last_bit_of_a_look_ahead_or_of_a_word_and_one_that_ends_a_bit_sooner(n, I, L):
+    """the lock is declared by the push that brings the last bit of the candidate's look-ahead, a word is emitted by the push that brings
+    its last bit: lead-ins of 0 .. 9 bits, cuts from two bits before to two bits behind (the sets assert that on the reference)"""
+    m = modem()
+    sets = edge_sets(n, I, L)
+    assert len(sets) == 14 + 11
+    for s in sets:
+        run_set(m, s)
+    m.sync()
+    m.close()
+
+
+@pytest.mark.parametrize("phase", [0, 3])
+def test_a_hunt_whose_look_ahead_spans_four_chunks_finds_nothing_in_noise_and_then_the_stream(phase):
+    m = modem()
+    calls = run_set(m, noise_set(phase))
+    assert not calls[-2]["count"].any() and not calls[-2]["info"].any() and (calls[-1]["info"][:, 0] == 1).all()
+    m.close()
+
+
+def test_a_push_with_no_slots_writes_the_true_count_and_nothing_else_and_the_link_goes_on():
+    """max_words = 0 with all four outputs given: push() finds its poison in every byte of d_words, d_pos and d_flags"""
+    m = modem()
+    calls = run_set(m, no_slots_set())
+    assert calls[1]["max_words"] == 0 and (calls[1]["count"] > 0).all() and all(len(w) == 0 for w in calls[1]["words"])
+    assert set(calls[1]) >= {"words", "pos", "flags", "info"}
     m.close()
 
 
