@@ -7,7 +7,7 @@ import pytest
 
 from test_deframe_coded_cpu import (LINK, coded_link_pcm, coded_steps, cut, deframe_coded_ref, dibits_to_costas, link_rows,
                                     make_coded_packet)
-from test_deframe_cpu import deframe_ref, keystream, turn
+from test_deframe_cpu import HUNT_CODED_SET_NAMES, HUNT_S, coded_reference, deframe_ref, hunt_coded_sets, keystream, turn
 from test_rx_data_cpu import data_rule
 
 pytestmark = pytest.mark.gpu
@@ -239,6 +239,47 @@ def test_overflow_counts_everything_and_writes_only_max_packets():
     for k in KEYS:
         assert (o[k][S * M:] == canary[k]).all(), k                      # and the guard behind the whole block
     m.close()
+
+
+# ------------------------------------------------------------------- 4b. the hunt where candidates are dense, and at the per-push bound
+def hunt_set_on_the_device(s):
+    """one set of test_deframe_cpu.hunt_coded_sets (any kind: the reset follows the set's) under each of its cuttings, push by push through
+    raw_push's guarded buffers: count, and pos, rot, score, bytes, crc_ok, info of every row a push writes against the set's reference,
+    with the push; the rows of a stream beyond min(count, max_packets) and the guard rows come back as they went in"""
+    M, nbytes = s["max_packets"], s["nbytes"]
+    canary = dict(bytes=0xA5, pos=-7, rot=-7, score=-7, crc_ok=0xA5, info=-7)
+    refs = [coded_reference(s, cuts) for cuts in s["cuttings"]]
+    s["check"](s, refs)
+    m = modem()
+    for cuts, ref in zip(s["cuttings"], refs):
+        m.deframer_reset_coded(HUNT_S, s["sync"], nbytes, s["min_score"], max_packets=M, puncture=None if s["kind"] == "plain" else s["pattern"],
+                               interleave=s["stride"])
+        at = 0
+        for k, c in enumerate(cuts):
+            o = raw_push(m, s["z"][:, at:at + c], s["gain"], M, nbytes)
+            at += c
+            for j in range(HUNT_S):
+                want = ref[j][k]
+                assert o["count"][j] == len(want), (s["what"], cuts[:2], k, j)
+                w = min(len(want), M)
+                for q in range(w):
+                    assert o["crc_ok"][j * M + q] in (0, 1)
+                    assert rec(k, {key: o[key][j * M + q] for key in KEYS}) == rec(k, want[q]), (s["what"], cuts[:2], k, j, q)
+                for key in KEYS:
+                    assert (o[key][j * M + w:(j + 1) * M] == canary[key]).all(), (s["what"], k, j, key)
+            for key in KEYS:
+                assert (o[key][HUNT_S * M:] == canary[key]).all(), (s["what"], k, key)
+        word = {"plain": "deframe_coded_decode_kernel", "punct": "deframe_coded_decode_punct_kernel", "ilv": "deframe_coded_decode_ilv_kernel"}[s["kind"]]
+        assert word in m.last_kernel(), m.last_kernel()
+    m.close()
+
+
+@pytest.mark.parametrize("what", HUNT_CODED_SET_NAMES["plain"])
+def test_the_hunt_on_dense_candidates_and_at_the_per_push_bound(what):
+    """rate 1/2.  Dense noise: every completion is a Viterbi decode of garbage, compared bit for bit all the same.  Back to back: a push of
+    k (nsync + Nc) + 1 symbols that begins with the last symbol of a pending body completes k + 1 packets, per_stream's nsym term at
+    equality; at max_packets = k the cap bites (count k + 1, k rows written)"""
+    hunt_set_on_the_device(next(s for s in hunt_coded_sets("plain") if s["what"] == what))
 
 
 def test_each_output_alone_equals_all_together_and_null_outputs_are_never_written():

@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 
 from test_deframe_coded_cpu import dibits_to_costas
-from test_deframe_coded_gpu import modem, push_all, rec, rows_of
-from test_deframe_cpu import turn
+from test_deframe_coded_gpu import hunt_set_on_the_device, modem, push_all, rec, rows_of
+from test_deframe_cpu import HUNT_CODED_SET_NAMES, hunt_coded_sets, turn
 from test_punct_cpu import NAMED, coded_punct_steps, deframe_coded_punct_ref, make_coded_punct_packet, punct_nsent, punct_ntx
 
 pytestmark = pytest.mark.gpu
@@ -81,6 +81,13 @@ def test_punctured_packets_bit_for_bit_for_random_cuts(nbytes, name, with_gain):
     good = [[r for r in g if r[5]] for g in seen[0]]
     assert all(len(g) >= 5 for g in good) and any(not r[5] for g in seen[0] for r in g)      # the payloads come back; the bad CRC shows
     m.close()
+
+
+@pytest.mark.parametrize("what", HUNT_CODED_SET_NAMES["punct"])
+def test_the_hunt_on_dense_candidates_and_at_the_per_push_bound_behind_the_pattern_2_3(what):
+    """test_deframe_coded_gpu's cases behind a pattern: the back-to-back sets have nbytes = 5, so Nc = 47 is odd, the staging rows lie
+    stage_pitch = 48 dibits apart, and the pending body is copied with an odd and an even number of pairs"""
+    hunt_set_on_the_device(next(s for s in hunt_coded_sets("punct") if s["what"] == what))
 
 
 @pytest.mark.parametrize("route", [0, 1])

@@ -4,7 +4,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_deframe_cpu import deframe_ref, keystream, link_pcm, make_packet, turn
+from test_deframe_cpu import (COSTAS_CASE_CUTS, EDGE_CUTTINGS, HUNT_SET_NAMES, costas_case, cuttings_of_test_1, deframe_ref, edge_case, hunt_sets,
+                              link_pcm, overflow_set, planted_streams, want_of, written)
 from test_rx_data_cpu import data_rule
 
 pytestmark = pytest.mark.gpu
@@ -33,34 +34,6 @@ def push_all(m, rows, costas=False):
     return got
 
 
-def want_of(D, cuts, sync, min_score, nbytes):
-    """deframe_ref over the concatenation, each packet tagged with the push that completes it"""
-    ends = np.cumsum(cuts)
-    out = []
-    for p in deframe_ref(D, sync, min_score, nbytes):
-        k = int(np.searchsorted(ends, p["end"]))            # the first push whose cumulative length reaches the packet's end
-        out.append((k, p["pos"], p["rot"], p["score"], p["bytes"].tobytes(), p["crc_ok"]))
-    return out
-
-
-def planted_streams(rng, S, total, sync, nbytes, max_err=3):
-    """S rows of random dibits with packets at random gaps and rotations, 0..max_err dibit errors in each word"""
-    ks = keystream(4 * (nbytes + 2))
-    D = rng.integers(0, 4, (S, total), dtype=np.uint8)
-    for s in range(S):
-        t = int(rng.integers(0, 300))
-        while True:
-            pkt, _ = make_packet(rng, sync, nbytes, ks, corrupt=bool(rng.integers(0, 8) == 0))
-            pkt = turn(pkt, int(rng.integers(0, 4)))
-            for i in rng.choice(len(sync), int(rng.integers(0, max_err + 1)), replace=False):
-                pkt[i] = (pkt[i] + 1 + rng.integers(0, 3)) & 3
-            if t + len(pkt) > total:
-                break
-            D[s, t:t + len(pkt)] = pkt
-            t += len(pkt) + int(rng.integers(0, 400))
-    return D
-
-
 # ------------------------------------------------------------------- 1. planted words, bit for bit, any cuts
 @pytest.mark.parametrize("nsync,nbytes", [(32, 16), (64, 64), (100, 5)])
 def test_planted_words_bit_for_bit_for_every_cut(nsync, nbytes):
@@ -70,15 +43,8 @@ def test_planted_words_bit_for_bit_for_every_cut(nsync, nbytes):
     min_score = nsync - 3
     D = planted_streams(rng, S, total, sync, nbytes)
     m = modem()
-    mixed = []
-    while sum(mixed) < total:
-        mixed.append(int(rng.choice([1, 7, 128, 2048, int(rng.integers(1, 700))])))
-    mixed[-1] -= sum(mixed) - total
-    mixed = [c for c in mixed if c > 0]
     lists = []
-    for cuts in ([1] * 300 + [total - 300], [7] * (total // 7) + [total % 7], [128] * (total // 128) + [total % 128],
-                 [2048, 2048, total - 4096], mixed):
-        cuts = [c for c in cuts if c > 0]
+    for cuts in cuttings_of_test_1(rng, total):
         m.deframer_reset(S, sync, nbytes, min_score, max_packets=64)
         rows, at = [], 0
         for c in cuts:
@@ -95,26 +61,6 @@ def test_planted_words_bit_for_bit_for_every_cut(nsync, nbytes):
 
 
 # ------------------------------------------------------------------- 1b. one and two plane words, on both inputs
-EDGE_CUTTINGS = ([1] * 200 + [1300], [97] * 15 + [45])
-
-
-def edge_case(nsync, nbytes):
-    """6 streams of 1500 dibits for a word of nsync dibits, and per cutting the reference's records.  The seed is chosen so that the
-    reference, before anything is compared with it, shows two packets in every stream and, under either cutting, a packet that ends in
-    a later push than the one that completed its sync word"""
-    rng = np.random.default_rng(101 + nsync)
-    sync = rng.integers(0, 4, nsync, dtype=np.uint8)
-    D = planted_streams(rng, 6, 1500, sync, nbytes, max_err=1)
-    wants = []
-    for cuts in EDGE_CUTTINGS:
-        ends = np.cumsum(cuts)
-        want = [want_of(D[s], cuts, sync, nsync - 1, nbytes) for s in range(6)]
-        assert all(len(w) >= 2 for w in want), [len(w) for w in want]
-        assert any(r[0] > np.searchsorted(ends, r[1] + nsync) for w in want for r in w)
-        wants.append(want)
-    return sync, D, wants
-
-
 @pytest.mark.parametrize("nsync,nbytes", [(7, 1), (65, 2), (128, 5)])
 def test_words_of_7_65_and_128_dibits_on_data_rows_and_on_costas_input(nsync, nbytes):
     sync, D, wants = edge_case(nsync, nbytes)
@@ -132,20 +78,12 @@ def test_words_of_7_65_and_128_dibits_on_data_rows_and_on_costas_input(nsync, nb
 
 # ------------------------------------------------------------------- 2. costas input = its data rule
 def test_costas_input_equals_its_data_rule():
-    rng = np.random.default_rng(11)
-    S, total, nsync, nbytes = 64, 3000, 40, 12
-    sync = rng.integers(0, 4, nsync, dtype=np.uint8)
-    D = planted_streams(rng, S, total, sync, nbytes, max_err=2)
-    # complex values whose data rule is D, with -0.0, +0.0 and NaN components sprinkled in
-    re = np.where(D & 1, -1.0, 1.0).astype(np.float32) * rng.uniform(0.1, 2.0, D.shape).astype(np.float32)
-    im = np.where(D & 2, -1.0, 1.0).astype(np.float32) * rng.uniform(0.1, 2.0, D.shape).astype(np.float32)
-    z = np.stack([re, im], axis=-1)
-    special = np.array([-0.0, 0.0, np.nan, -np.nan], np.float32)
-    sel = rng.random(z.shape) < 0.05
-    z[sel] = special[rng.integers(0, 4, int(sel.sum()))]
-    data = data_rule(z)
+    # complex values with -0.0, +0.0 and NaN components sprinkled in (test_deframe_cpu.costas_case: the port's CPU test runs `data` too)
+    sync, nbytes, min_score, z, data = costas_case()
+    S, nsync = z.shape[0], len(sync)
+    assert min_score == nsync - 2
     m = modem()
-    cuts = [100, 1, 900, 1999]
+    cuts = COSTAS_CASE_CUTS
     rows_z, rows_d, at = [], [], 0
     for c in cuts:
         rows_z.append(np.ascontiguousarray(z[:, at:at + c]))
@@ -164,12 +102,9 @@ def test_costas_input_equals_its_data_rule():
 # ------------------------------------------------------------------- 3. overflow
 def test_overflow_counts_everything_and_writes_only_max_packets():
     import torch
-    rng = np.random.default_rng(12)
-    S, nsync, nbytes, M = 5, 16, 2, 3
-    sync = rng.integers(0, 4, nsync, dtype=np.uint8)
-    ks = keystream(4 * (nbytes + 2))
-    D = np.concatenate([make_packet(rng, sync, nbytes, ks)[0] for _ in range(10)] + [np.zeros(5, np.uint8)])
-    D = np.tile(D, (S, 1))
+    t3 = overflow_set()
+    sync, nsync, nbytes, M, D = t3["sync"], t3["nsync"], t3["nbytes"], t3["max_packets"], t3["D"]
+    S = D.shape[0]
     m = modem()
     m.deframer_reset(S, sync, nbytes, nsync, max_packets=M)
     d = torch.from_numpy(D).cuda()
@@ -196,6 +131,71 @@ def test_overflow_counts_everything_and_writes_only_max_packets():
             assert (fp[s * M + j], fr[s * M + j], fs_[s * M + j], fo[s * M + j]) == (want[j]["pos"], want[j]["rot"], want[j]["score"], 1)
     assert (fb[n_b:] == 0xA5).all() and (fp[n_p:] == -7).all() and (fr[n_p:] == -7).all() and (fs_[n_p:] == -7).all()
     assert (fo[n_p:] == 0xA5).all()
+    m.close()
+
+
+# ------------------------------------------------------------------- 3b. the hunt where candidates are dense and rotations tie
+def push_guarded(m, x, cuts, M, nbytes, costas=False):
+    """the C call push by push over x (S, total[, 2]), every output poisoned before each push and one canary row per stream behind the
+    [S][M] block (test 3's layout) -> per stream (count per push, the records written: push, pos, rot, score, bytes, crc_ok).  The rows of
+    a stream beyond min(count, M) and the canary rows must come back as they went in"""
+    import torch
+    S = x.shape[0]
+    xs = torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    cnt = torch.empty((S,), dtype=torch.int32, device="cuda")
+    by = torch.empty((S * (M + 1), nbytes + 2), dtype=torch.uint8, device="cuda")
+    pos = torch.empty((S * (M + 1),), dtype=torch.int64, device="cuda")
+    rot, sc = torch.empty_like(pos, dtype=torch.int32), torch.empty_like(pos, dtype=torch.int32)
+    ok = torch.empty_like(pos, dtype=torch.uint8)
+    P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    counts, got, at = [[] for _ in range(S)], [[] for _ in range(S)], 0
+    for k, c in enumerate(cuts):
+        row = xs[:, at:at + c].contiguous()
+        at += c
+        cnt.fill_(-1)
+        for t, v in ((by, 0xA5), (pos, -7), (rot, -7), (sc, -7), (ok, 0xA5)):
+            t.fill_(v)
+        rc = m.L.qpsk_deframer_push(m.h, P(row) if costas else None, None if costas else P(row), c, P(cnt), P(by), P(pos), P(rot), P(sc), P(ok))
+        assert rc == 0, m.L.qpsk_last_error()
+        m.sync()
+        hc, hb, hp, hr, hs, ho = [t.cpu().numpy() for t in (cnt, by, pos, rot, sc, ok)]
+        if not hc.any():
+            assert (hb == 0xA5).all() and (hp == -7).all() and (hr == -7).all() and (hs == -7).all() and (ho == 0xA5).all(), k
+            for s in range(S):
+                counts[s].append(0)
+            continue
+        for s in range(S):
+            w = min(int(hc[s]), M)
+            counts[s].append(int(hc[s]))
+            got[s] += [(k, int(hp[s * M + j]), int(hr[s * M + j]), int(hs[s * M + j]), hb[s * M + j].tobytes(), bool(ho[s * M + j])) for j in range(w)]
+            assert all(int(ho[s * M + j]) in (0, 1) for j in range(w))
+            idle = slice(s * M + w, (s + 1) * M)
+            assert (hb[idle] == 0xA5).all() and (hp[idle] == -7).all() and (hr[idle] == -7).all() and (hs[idle] == -7).all() and (ho[idle] == 0xA5).all(), (k, s)
+        assert (hb[S * M:] == 0xA5).all() and (hp[S * M:] == -7).all() and (hr[S * M:] == -7).all() and (hs[S * M:] == -7).all() and (ho[S * M:] == 0xA5).all(), k
+    return [(counts[s], got[s]) for s in range(S)]
+
+
+@pytest.mark.parametrize("what", HUNT_SET_NAMES)
+def test_the_hunt_on_dense_candidates_tied_rotations_and_the_per_push_bound(what):
+    """test_deframe_cpu.hunt_sets: low thresholds on noise (every step holds candidates, hx lands inside a step, the [1500] push of the
+    short words overflows max_packets), constant words against alternating and period-4 ring values (two and four rotations tie: the
+    smallest wins), packets back to back with a push of k periods + 1 dibits at max_packets = k + 1, k and 64.  test_hunt_port_cpu.py has
+    run the same bytes through the scalar port of the hunt; here the kernel, on data rows and on costas input: count, pos, rot, score,
+    bytes, crc_ok and the push, bit for bit"""
+    s = next(t for t in hunt_sets() if t["what"] == what)
+    s["check"](s)
+    D = s["D"]
+    z = np.stack([np.where(D & 1, -1.0, 1.0), np.where(D & 2, -0.5, 0.5)], axis=-1).astype(np.float32)
+    assert np.array_equal(data_rule(z), D)
+    m = modem()
+    for cuts in s["cuttings"]:
+        want = [written(want_of(D[k], cuts, s["sync"], s["min_score"], s["nbytes"]), len(cuts), s["max_packets"]) for k in range(D.shape[0])]
+        for costas, x in ((False, D), (True, z)):
+            m.deframer_reset(D.shape[0], s["sync"], s["nbytes"], s["min_score"], max_packets=s["max_packets"])
+            got = push_guarded(m, x, cuts, s["max_packets"], s["nbytes"], costas=costas)
+            for k in range(D.shape[0]):
+                assert got[k][0] == want[k][0], (what, cuts[:2], costas, k, "count")
+                assert got[k][1] == want[k][1], (what, cuts[:2], costas, k)
     m.close()
 
 

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 from test_deframe_coded_cpu import dibits_to_costas
-from test_deframe_coded_gpu import push_all, rec, rows_of
+from test_deframe_coded_gpu import hunt_set_on_the_device, push_all, rec, rows_of
+from test_deframe_cpu import hunt_coded_sets
 from test_frame_cpu import HALF, body_len, frame_ref, starts
 from test_ilv_cpu import (deframe_coded_ilv_ref, frame_ilv_ref, gather_ref, ilv_stream, ilv_stride, interleave_ref, strides_for,
                           viterbi_ilv_ref)
@@ -392,6 +393,14 @@ def test_deframer_bit_for_bit_for_several_cuts_and_stride_one_equals_the_punctur
     b = push_all(m, rows, gains)
     assert "ilv" in ka and "punct" in m.last_kernel() and a == b and sum(len(x) for x in a) == 6
     m.close()
+
+
+def test_packets_back_to_back_at_the_per_push_bound_through_a_stride():
+    """test_deframe_coded_gpu's back-to-back sets behind the pattern 3/4 and a stride: max_packets = k + 1, k and 64"""
+    sets = hunt_coded_sets("ilv")
+    assert len(sets) == 3 and all(s["stride"] > 1 for s in sets)
+    for s in sets:
+        hunt_set_on_the_device(s)
 
 
 def test_a_refused_reset_leaves_the_deframer_working_and_the_uncoded_push_is_refused():
