@@ -641,14 +641,65 @@ int qpsk_deframer_reset_coded_ilv(qpsk_ctx *ctx, int nstreams, const uint8_t *h_
  * word.
  * COMPOSITION.  in_pitch exists so that the d_bytes [nstreams][max_packets][nbytes + 2] of qpsk_deframer_push / _push_coded is decoded where
  * it lies: n = nbytes, in_pitch = nbytes + 2, nrows = nstreams * max_packets.  The packet's CRC is then over the codeword.
- * Not built: other field polynomials or first roots (CCSDS's dual-basis code among them), nroots > 64, a helper that interleaves
- * codewords across packets, the outer code inside the deframer's own launch, qpsk_multi.  Usage: INTEGRATION.md 2.0.
+ * Not built: other field polynomials or first roots (CCSDS's dual-basis code among them), nroots > 64, the outer code inside the deframer's own launch, qpsk_multi.  Usage: INTEGRATION.md 2.0.
  * ------------------------------------------------------------------------- */
 int qpsk_rs_generator(int nroots, uint8_t *h_g);
 int qpsk_rs_encode_batch(qpsk_ctx *ctx, const uint8_t *d_data, long long data_pitch, int nrows, int k, int nroots, uint8_t *d_out,
                          long long out_pitch);
 int qpsk_rs_decode_batch(qpsk_ctx *ctx, const uint8_t *d_in, long long in_pitch, int nrows, int n, int nroots, const uint8_t *d_erase,
                          uint8_t *d_out, long long out_pitch, int32_t *d_info);
+
+/* -------------------------------------------------------------------------
+ * PACKET ERASURE CODE: REED-SOLOMON's code laid across the packets of a group, against packets that are lost whole -- a sync word that was
+ * not found, a fade longer than a codeword's radius, a body whose CRC fails behind every decoder.  The code is REED-SOLOMON's (field, g,
+ * limits, c(x) = sum_p w[p] x^(n - 1 - p)) and nothing new; the library's own definition, integers only, no tolerance anywhere (parity
+ * unpinned), restated in numpy by tests/test_cross_cpu.py (cross_encode_ref, cross_decode_ref, cross_place_ref).
+ *
+ * GROUP.  n = k + nroots packets of len bytes, pitch bytes apart (0 = len; otherwise >= len); ngroups groups lie n pitch bytes apart.
+ *   Packets 0 .. k-1 are data, k .. n-1 parity.  The first skip bytes (0 <= skip < len) of EVERY packet are the caller's header -- the
+ *   place of a sequence number, which a parity packet needs too: never coded, never changed.  For every column j in [skip, len) the word
+ *   W_j[p] = byte j of packet p is one REED-SOLOMON word of (n, k).
+ *   qpsk_rs_cross_encode_batch   in place on d_group [ngroups][n][pitch]: reads bytes [skip, len) of packets 0 .. k-1 and writes bytes
+ *                [skip, len) of packets k .. n-1 so that every column is a codeword.  Nothing else is touched: not a header byte, not a
+ *                byte between packets.  With payload_pitch = pitch the buffer is qpsk_frame_batch's d_payload of ngroups n packets as it lies.
+ * DECODER, as a result.  d_have [ngroups][n] uint8: zero = packet p is missing and its bytes mean nothing; f = the zeros of a group.  Per
+ *   column:  if f <= nroots and a codeword c exists that equals the column in every place that is NOT missing, the output column is c
+ *   (unique, since f <= nroots < the minimum distance);  otherwise the output column is the input column byte for byte and the column has
+ *   FAILED.  This is REED-SOLOMON's DECODER restricted to e = 0: where that decoder, on the column with the same flags, reports e = 0, the
+ *   outputs are equal; where it reports e > 0 or fails, the column fails here.  So a wrong byte in a PRESENT packet is detected while
+ *   f < nroots (through the nroots - f spare syndromes) and is invisible at f = nroots, where any k bytes determine a codeword.  A caller
+ *   who wants such columns corrected gathers them and runs qpsk_rs_decode_batch on them.
+ *   A missing packet's bytes decide nothing and never reach an output of a decoded column; they are read only to count [2] below and to
+ *   copy a failed column.  Header bytes [0, skip) of every packet are copied to d_out as they are.
+ *   qpsk_rs_cross_decode_batch   d_group as above (read only unless d_out is d_group); d_out [ngroups][n][out_pitch] may be exactly d_group
+ *                with the same pitch (in place: only bytes that change are written), otherwise it must not overlap d_group; bytes between
+ *                packets are never written
+ *       d_info   [ngroups][4] int32, 4-byte aligned = { columns failed, f, places where the output differs from the input (all columns),
+ *                1 if no column failed else 0 }
+ *       d_colfail  [ngroups][len - skip] uint8, 1 = that column failed; may be NULL
+ *                d_out or d_info may be NULL, not both.  A failed column is a group's result: never a call error, never the status word
+ * PLACE: the bookkeeping between qpsk_deframer_push / _push_coded and the decoder.  Byte 0 of a packet is its sequence number q (so
+ *   len >= 1, and the coding above uses skip >= 1).  Per stream the window is the ngroups n <= 256 numbers from d_base[stream] & 255 on
+ *   (d_base int32 [nstreams], NULL = 0).  The packets i < min(d_count[stream], max_packets) are taken in index order: d = (q - base) & 255;
+ *   a packet with d_crc_ok == 0 or d >= ngroups n is ignored; otherwise its len bytes go to d_group[stream][d / n][d % n] and
+ *   d_have[stream][d] becomes 1.  Of two packets with the same d the later index wins.  The call never clears d_have and writes no slot
+ *   it does not fill: a caller accumulates over as many pushes as a window spans and clears between windows.  Deterministic.
+ *   qpsk_rs_cross_place_batch    d_bytes [nstreams][max_packets][byte_pitch] (0 = len; the deframers': nbytes + 2), d_count [nstreams]
+ *                int32 and d_crc_ok [nstreams][max_packets] as the push left them -> d_group [nstreams][ngroups][n][pitch],
+ *                d_have [nstreams][ngroups n]; no output may overlap an input or the other output
+ * QPSK_ERR_ARG at the call, nothing launched, for: a bad (n, k, nroots), len < 1, skip outside [0, len), a pitch below len, ngroups < 1,
+ * ngroups n > 256 or n > 255 in place, max_packets or nstreams < 1, overlapping buffers, NULL where a pointer is required, a misaligned int32
+ * array.  The three calls are stream-ordered on the context's stream and touch no other state of the context.  qpsk_ctx_last_kernel() names
+ * rs_cross_encode_kernel, rs_cross_decode_kernel or rs_cross_place_kernel.
+ * Not built: errors and erasures per column (qpsk_rs_decode_batch on the failed columns is the way), a stateful collector that carries
+ * windows across pushes, sequence numbers wider than a byte, qpsk_multi.  Usage: INTEGRATION.md 2.0.
+ * ------------------------------------------------------------------------- */
+int qpsk_rs_cross_encode_batch(qpsk_ctx *ctx, uint8_t *d_group, long long pitch, int ngroups, int k, int nroots, int len, int skip);
+int qpsk_rs_cross_decode_batch(qpsk_ctx *ctx, const uint8_t *d_group, long long pitch, int ngroups, int n, int nroots, int len, int skip,
+                               const uint8_t *d_have, uint8_t *d_out, long long out_pitch, int32_t *d_info, uint8_t *d_colfail);
+int qpsk_rs_cross_place_batch(qpsk_ctx *ctx, const uint8_t *d_bytes, long long byte_pitch, const int32_t *d_count, const uint8_t *d_crc_ok,
+                              int nstreams, int max_packets, int len, int n, int ngroups, const int32_t *d_base, uint8_t *d_group,
+                              long long pitch, uint8_t *d_have);
 
 /* -------------------------------------------------------------------------
  * VITERBI STREAM: the decoder of CONVOLUTIONAL CODE for a code that runs continuously -- no packets, no tails, no row that ends (the inner

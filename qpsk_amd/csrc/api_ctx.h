@@ -11,6 +11,7 @@
  *   api_outer.cpp    the outer link behind it: word sync, the byte deinterleaver and the interleaver
  *   api_dispersal.cpp DVB's energy dispersal behind the Reed-Solomon decoder
  *   api_nodesync.cpp the node sync in front of it: the candidate transform and the monitor on the decoder's error count
+ *   api_cross.cpp    the packet erasure code: Reed-Solomon across the packets of a group, and the place call in front of it
  *
  * OWNERSHIP: each nested group of qpsk_ctx below names the one unit that reads and writes it; the members outside a group
  * (configuration, scratch buffers) are every unit's.  DESIGN.md, "The host layer", lists the few places that reach across.

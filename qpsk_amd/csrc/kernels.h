@@ -550,8 +550,16 @@ void rs_generator(int nroots, uint8_t *g);      /* host: nroots + 1 coefficients
 int launch_rs_encode(const uint8_t *data, size_t data_pitch, int nrows, int k, int nroots, uint8_t *out, size_t out_pitch, hipStream_t s);
 int launch_rs_decode(const uint8_t *in, size_t in_pitch, int nrows, int n, int nroots, const uint8_t *erase, uint8_t *out, size_t out_pitch,
                      int32_t *info, hipStream_t s);
+/* rs_cross.hip: the packet erasure code (the definition: include/qpsk_hip.h, PACKET ERASURE CODE).  One workgroup per group, a lane per byte
+ * column; pitches in bytes, never 0 here; the caller has checked every bound and every overlap.  out or info may be NULL, not both; out may
+ * be `in` with the same pitch; colfail and base may be NULL */
+int launch_rs_cross_encode(uint8_t *group, size_t pitch, int ngroups, int k, int nroots, int len, int skip, hipStream_t s);
+int launch_rs_cross_decode(const uint8_t *in, size_t pitch, int ngroups, int n, int nroots, int len, int skip, const uint8_t *have,
+                           uint8_t *out, size_t out_pitch, int32_t *info, uint8_t *colfail, hipStream_t s);
+int launch_rs_cross_place(const uint8_t *bytes, size_t byte_pitch, const int32_t *count, const uint8_t *crc_ok, int nstreams, int max_packets,
+                          int len, int n, int ngroups, const int32_t *base, uint8_t *group, size_t pitch, uint8_t *have, hipStream_t s);
 /* txchain.hip */
-int tx_history_symbols(void);          /* symbols of state per transmitter (uint8 each, 4 = none yet) */
+int tx_history_symbols(void);         /* symbols of state per transmitter (uint8 each, 4 = none yet) */
 int launch_tx_shape(const uint8_t *sym, uint8_t *hist, const float *taps, float *sig, int nstreams, int nsym,
                     int cycles, hipStream_t s);   /* shaped baseband of nsym symbols per transmitter; updates hist */
 int launch_tx_upmix(const float *sig, int16_t *pcm, float *state, int nstreams, int length, hipStream_t s);

@@ -66,6 +66,7 @@ API_SYMBOLS = [
     "qpsk_frame_len", "qpsk_frame_batch",
     "qpsk_ilv_stride", "qpsk_conv_encode_ilv_batch", "qpsk_viterbi_ilv_batch", "qpsk_frame_batch_ilv", "qpsk_deframer_reset_coded_ilv",
     "qpsk_rs_generator", "qpsk_rs_encode_batch", "qpsk_rs_decode_batch",
+    "qpsk_rs_cross_encode_batch", "qpsk_rs_cross_decode_batch", "qpsk_rs_cross_place_batch",
     "qpsk_viterbi_stream_reset", "qpsk_viterbi_stream_emits", "qpsk_viterbi_stream_push", "qpsk_viterbi_stream_flush",
     "qpsk_conv_encode_stream_batch", "qpsk_test_viterbi_stream_advance",
     "qpsk_outer_reset", "qpsk_outer_max_words", "qpsk_outer_push", "qpsk_outer_interleave_batch", "qpsk_test_outer_advance",
@@ -163,6 +164,9 @@ def load():
     L.qpsk_rs_generator.argtypes = [i32, vp]
     L.qpsk_rs_encode_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, vp, C.c_longlong]
     L.qpsk_rs_decode_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, vp, vp, C.c_longlong, vp]
+    L.qpsk_rs_cross_encode_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, i32, i32]
+    L.qpsk_rs_cross_decode_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, i32, i32, vp, vp, C.c_longlong, vp, vp]
+    L.qpsk_rs_cross_place_batch.argtypes = [vp, vp, C.c_longlong, vp, vp, i32, i32, i32, i32, i32, vp, vp, C.c_longlong, vp]
     L.qpsk_rrc_fir_batch.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_rrc_fir_batch_fast.argtypes = [vp, vp, vp, vp, i32, i32]
     L.qpsk_timing_hist_batch.argtypes = [vp, vp, i32, vp, vp]
@@ -1127,6 +1131,73 @@ class Modem:
                                                 _ptr(info)))
         self._rs_keep = (w, e)
         return out[:, :n], info
+
+    # ---- the packet erasure code (qpsk_rs_cross_*): Reed-Solomon across the packets of a group
+    def rs_cross_encode(self, groups, nroots, skip=0):
+        """qpsk_rs_cross_encode_batch: groups (G, n, len) uint8, n = k + nroots packets each -- the k data packets filled in, the first
+        skip bytes of every packet the caller's header.  The parity packets' bytes [skip, len) are written IN PLACE so that every byte
+        column is a codeword of the (n, k) code; -> the device tensor (groups itself when it is a contiguous uint8 tensor on the modem's
+        device).  groups.reshape(G * n, len) is then frame()'s payloads"""
+        t = self.torch
+        g = self._dev(groups, t.uint8)
+        if g.dim() != 3:
+            raise ValueError("rs_cross_encode() groups must be (G, n, len) uint8")
+        G, n, ln = g.shape
+        self._check(self.L.qpsk_rs_cross_encode_batch(self.h, _ptr(g), 0, G, n - int(nroots), int(nroots), ln, int(skip)))
+        return g
+
+    def rs_cross_decode(self, groups, have, nroots, skip=0, inplace=False):
+        """qpsk_rs_cross_decode_batch: groups (G, n, len) uint8, have (G, n) uint8 (zero = that packet is missing) -> (groups (G, n, len)
+        uint8, info (G, 4) int32 = (columns failed, missing packets, bytes changed, 1 if no column failed)).  A column that cannot be
+        completed comes back as it was.  inplace: the result is written over groups (a device tensor) and the first result is groups"""
+        t = self.torch
+        g = self._dev(groups, t.uint8)
+        if g.dim() != 3:
+            raise ValueError("rs_cross_decode() groups must be (G, n, len) uint8")
+        G, n, ln = g.shape
+        h = self._dev(have, t.uint8)
+        if tuple(h.shape) != (G, n):
+            raise ValueError("rs_cross_decode() have must be (%d, %d) uint8" % (G, n))
+        if inplace and (not isinstance(groups, t.Tensor) or g.data_ptr() != groups.data_ptr()):
+            raise ValueError("rs_cross_decode(inplace=True) needs a contiguous uint8 tensor on the modem's device")
+        out = g if inplace else self.empty((G, n, ln), t.uint8)
+        info = self.empty((G, 4), t.int32)
+        self._check(self.L.qpsk_rs_cross_decode_batch(self.h, _ptr(g), 0, G, n, int(nroots), ln, int(skip), _ptr(h), _ptr(out), 0, _ptr(info),
+                                                      None))
+        self._rs_keep = (g, h)
+        return out, info
+
+    def rs_cross_place(self, bytes, count, crc_ok, n, ngroups, base=None, groups=None, have=None):      # noqa: A002 (the header's name)
+        """qpsk_rs_cross_place_batch: bytes (S, M, row) uint8, count (S,) int32 and crc_ok (S, M) uint8 as deframe() / deframe_coded()
+        return them; byte 0 of a packet is its sequence number q.  A packet with crc_ok set and d = (q - base[s]) & 255 < ngroups * n goes to
+        groups[s, d // n, d % n] and sets have[s, d]; the later of two with one d wins.  base (S,) int32 or None = 0.  groups (S, ngroups,
+        n, len) and have (S, ngroups * n) are device tensors to accumulate into -- the first len <= row bytes of a packet are taken, so
+        len = nbytes leaves the deframers' two CRC bytes behind -- or None: zeroed buffers with len = row.  -> (groups, have)"""
+        t = self.torch
+        b = self._dev(bytes, t.uint8)
+        if b.dim() != 3:
+            raise ValueError("rs_cross_place() bytes must be (S, max_packets, row) uint8")
+        S, M, row = b.shape
+        n, ngroups = int(n), int(ngroups)
+        cnt, ok = self._dev(count, t.int32), self._dev(crc_ok, t.uint8)
+        if tuple(cnt.shape) != (S,) or tuple(ok.shape) != (S, M):
+            raise ValueError("rs_cross_place() count must be (%d,) int32 and crc_ok (%d, %d) uint8" % (S, S, M))
+        bs = None if base is None else self._dev(base, t.int32)
+        if bs is not None and tuple(bs.shape) != (S,):
+            raise ValueError("rs_cross_place() base must be (%d,) int32" % S)
+        if groups is None:
+            groups = t.zeros((S, max(ngroups, 0), max(n, 0), row), dtype=t.uint8, device=self.dev)
+        if have is None:
+            have = t.zeros((S, max(ngroups * n, 0)), dtype=t.uint8, device=self.dev)
+        for name, x, shape in (("groups", groups, (S, ngroups, n)), ("have", have, (S, ngroups * n))):
+            if not isinstance(x, t.Tensor) or x.dtype != t.uint8 or not x.is_contiguous() or x.device != self.dev or tuple(x.shape[:len(shape)]) != shape:
+                raise ValueError("rs_cross_place() %s must be a contiguous uint8 tensor %s on the modem's device" % (name, shape))
+        if groups.dim() != 4 or groups.shape[3] > row:
+            raise ValueError("rs_cross_place() groups must be (S, ngroups, n, len) with len <= %d" % row)
+        self._check(self.L.qpsk_rs_cross_place_batch(self.h, _ptr(b), row, _ptr(cnt), _ptr(ok), S, M, groups.shape[3], n, ngroups, _ptr(bs),
+                                                     _ptr(groups), 0, _ptr(have)))
+        self._rs_keep = (b, cnt, ok, bs)
+        return groups, have
 
     def streams_loop_state(self):
         a = (C.c_float * (2 * self.nstreams))()
