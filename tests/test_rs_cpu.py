@@ -324,6 +324,80 @@ def test_qpsk_rs_generator_equals_the_numpy_product_and_refuses_out_of_range(qps
 RS_CODES = ((3, 1), (6, 2), (7, 5), (15, 11), (34, 32), (60, 44), (204, 188), (255, 223), (255, 254), (65, 1), (255, 191), (21, 16))
 
 
+def patterns(n, k):
+    """-> (words (R, n), flags (R, n), sent (R, n), names): codewords damaged in every way the issue lists, in an order that puts rows
+    with different exits next to each other"""
+    nroots, t = n - k, (n - k) // 2
+    rng = np.random.default_rng(1000 * n + k)
+    rows = []
+
+    def add(name, errors=0, erased=0, erased_right=0, at=None, word=None):
+        """a fresh codeword with `erased` flagged positions, of which `erased_right` keep their byte, and `errors` unflagged wrong bytes
+        (at the places `at` when given)"""
+        sent = rs_encode_ref(rng.integers(0, 256, (1, k), dtype=np.uint8), nroots)[0]
+        w, fl = sent.copy(), np.zeros(n, np.uint8)
+        if word is not None:
+            sent = w = np.asarray(word, np.uint8)
+        erased, errors = min(erased, n), min(errors, n - min(erased, n))
+        order = rng.permutation(n) if at is None else np.concatenate([at, np.setdiff1d(rng.permutation(n), at, assume_unique=True)])
+        err_at, era_at = order[:errors], order[errors:errors + erased]
+        fl[era_at] = 1
+        hit = np.concatenate([err_at, era_at[erased_right:]]).astype(np.int64)
+        w = w.copy()
+        w[hit] ^= rng.integers(1, 256, len(hit), dtype=np.uint8)
+        rows.append((name, w, fl, sent))
+
+    add("clean")
+    add("1 error", errors=1)
+    add("t errors", errors=t)
+    add("t + 1 errors", errors=t + 1)
+    add("clean, again")
+    add("error at j = 0", errors=1, at=np.array([0]))
+    add("f = nroots + 1", erased=nroots + 1)
+    add("error at j = n - 1", errors=1, at=np.array([n - 1]))
+    add("all zero", word=np.zeros(n, np.uint8))
+    add("error in the parity", errors=1, at=np.array([k + (nroots - 1) // 2]))
+    add("garbage", word=rng.integers(0, 256, n, dtype=np.uint8))
+    add("errors at both ends and in the parity", errors=min(3, max(t, 1)), at=np.array([0, n - 1, n - 2][:min(3, max(t, 1))]))
+    add("all 0xFF", word=np.full(n, 0xFF, np.uint8))
+    add("f = nroots, e = 0", erased=nroots)
+    e = max(1, t // 2)
+    add("2 e + f = nroots", errors=e, erased=max(nroots - 2 * e, 0))
+    add("2 e + f = nroots + 1", errors=e, erased=max(nroots + 1 - 2 * e, 0))
+    add("erased bytes that are right", erased=nroots, erased_right=(nroots + 1) // 2)
+    add("clean with erasures", erased=max(t, 1), erased_right=max(t, 1))
+    add("garbage with erasures", erased=t, word=rng.integers(0, 256, n, dtype=np.uint8))
+    add("t errors, again", errors=t)
+    return (np.stack([r[1] for r in rows]), np.stack([r[2] for r in rows]), np.stack([r[3] for r in rows]), [r[0] for r in rows])
+
+
+_CASES = {}
+
+
+def case(n, k):
+    """the rows of a code with both references, computed once and shared by every test; nobody changes them"""
+    if (n, k) not in _CASES:
+        words, flags, sent, names = patterns(n, k)
+        out_e, info_e = rs_decode_ref(words, n - k, flags)
+        out_0, info_0 = rs_decode_ref(words, n - k, None)
+        for a in (words, flags, sent, out_e, info_e, out_0, info_0):
+            a.setflags(write=False)
+        _CASES[(n, k)] = dict(words=words, flags=flags, sent=sent, names=names, erased=(out_e, info_e), plain=(out_0, info_0))
+    return _CASES[(n, k)]
+
+
+def encoder_rows(n, k, counts=(1, 5, 70)):
+    """the data blocks the encoder's GPU test sends, per row count"""
+    rng = np.random.default_rng(n * 300 + k)
+    sets = []
+    for R in counts:
+        data = rng.integers(0, 256, (R, k), dtype=np.uint8)
+        data[0] = 0xFF
+        data[R // 2] = 0
+        sets.append((R, data))
+    return sets
+
+
 @pytest.mark.parametrize("n,k", RS_CODES)
 def test_every_encoded_row_is_systematic_and_has_zero_syndromes(n, k):
     rng = np.random.default_rng(n * 256 + k)

@@ -2,15 +2,16 @@
 test_rs_cpu.py (REED-SOLOMON of include/qpsk_hip.h): every code and error pattern in one call per code, so that neighbouring waves leave by
 different exits; the call shapes (row counts, pitches with poison between the rows, in place, either output alone, guards); the encoder;
 the erasure identity; the error contract; and the link of the CPU test on the device, the deframer's bytes decoded where they lie.  There
-is no tolerance anywhere."""
+is no tolerance anywhere.  Section 7 decodes the rare paths and the seams of the kernel's lane chunks, the rows of rs_rows.py."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from test_deframe_coded_cpu import dibits_to_costas
+from rs_rows import directed_codes, directed_rows, edge_codes, edge_rows
 from test_punct_cpu import NAMED
-from test_rs_cpu import LINK, RS_CODES, link_result, rs_decode_ref, rs_encode_ref
+from test_rs_cpu import LINK, RS_CODES, case, encoder_rows, link_result, rs_decode_ref, rs_encode_ref
 from test_viterbi_gpu import GUARD, modem, ptr
 
 pytestmark = pytest.mark.gpu
@@ -20,68 +21,6 @@ POISON, OUT_FILL, INFO_FILL = 0xA5, 0x55, 0x55555555
 
 
 # ------------------------------------------------------------------------------------------ the rows of one code, and their references
-def patterns(n, k):
-    """-> (words (R, n), flags (R, n), sent (R, n), names): codewords damaged in every way the issue lists, in an order that puts rows
-    with different exits next to each other"""
-    nroots, t = n - k, (n - k) // 2
-    rng = np.random.default_rng(1000 * n + k)
-    rows = []
-
-    def add(name, errors=0, erased=0, erased_right=0, at=None, word=None):
-        """a fresh codeword with `erased` flagged positions, of which `erased_right` keep their byte, and `errors` unflagged wrong bytes
-        (at the places `at` when given)"""
-        sent = rs_encode_ref(rng.integers(0, 256, (1, k), dtype=np.uint8), nroots)[0]
-        w, fl = sent.copy(), np.zeros(n, np.uint8)
-        if word is not None:
-            sent = w = np.asarray(word, np.uint8)
-        erased, errors = min(erased, n), min(errors, n - min(erased, n))
-        order = rng.permutation(n) if at is None else np.concatenate([at, np.setdiff1d(rng.permutation(n), at, assume_unique=True)])
-        err_at, era_at = order[:errors], order[errors:errors + erased]
-        fl[era_at] = 1
-        hit = np.concatenate([err_at, era_at[erased_right:]]).astype(np.int64)
-        w = w.copy()
-        w[hit] ^= rng.integers(1, 256, len(hit), dtype=np.uint8)
-        rows.append((name, w, fl, sent))
-
-    add("clean")
-    add("1 error", errors=1)
-    add("t errors", errors=t)
-    add("t + 1 errors", errors=t + 1)
-    add("clean, again")
-    add("error at j = 0", errors=1, at=np.array([0]))
-    add("f = nroots + 1", erased=nroots + 1)
-    add("error at j = n - 1", errors=1, at=np.array([n - 1]))
-    add("all zero", word=np.zeros(n, np.uint8))
-    add("error in the parity", errors=1, at=np.array([k + (nroots - 1) // 2]))
-    add("garbage", word=rng.integers(0, 256, n, dtype=np.uint8))
-    add("errors at both ends and in the parity", errors=min(3, max(t, 1)), at=np.array([0, n - 1, n - 2][:min(3, max(t, 1))]))
-    add("all 0xFF", word=np.full(n, 0xFF, np.uint8))
-    add("f = nroots, e = 0", erased=nroots)
-    e = max(1, t // 2)
-    add("2 e + f = nroots", errors=e, erased=max(nroots - 2 * e, 0))
-    add("2 e + f = nroots + 1", errors=e, erased=max(nroots + 1 - 2 * e, 0))
-    add("erased bytes that are right", erased=nroots, erased_right=(nroots + 1) // 2)
-    add("clean with erasures", erased=max(t, 1), erased_right=max(t, 1))
-    add("garbage with erasures", erased=t, word=rng.integers(0, 256, n, dtype=np.uint8))
-    add("t errors, again", errors=t)
-    return (np.stack([r[1] for r in rows]), np.stack([r[2] for r in rows]), np.stack([r[3] for r in rows]), [r[0] for r in rows])
-
-
-_CASES = {}
-
-
-def case(n, k):
-    """the rows of a code with both references, computed once and shared by every test; nobody changes them"""
-    if (n, k) not in _CASES:
-        words, flags, sent, names = patterns(n, k)
-        out_e, info_e = rs_decode_ref(words, n - k, flags)
-        out_0, info_0 = rs_decode_ref(words, n - k, None)
-        for a in (words, flags, sent, out_e, info_e, out_0, info_0):
-            a.setflags(write=False)
-        _CASES[(n, k)] = dict(words=words, flags=flags, sent=sent, names=names, erased=(out_e, info_e), plain=(out_0, info_0))
-    return _CASES[(n, k)]
-
-
 def tile(a, R):
     return np.ascontiguousarray(np.resize(a, (R,) + a.shape[1:]))
 
@@ -202,11 +141,7 @@ def encode(m, data, nroots, data_pitch=0, out_pitch=0):
 @pytest.mark.parametrize("n,k", RS_CODES)
 def test_encoder_equals_the_restatement_for_every_row_count_and_pitch(n, k):
     m = modem()
-    rng = np.random.default_rng(n * 300 + k)
-    for R in (1, 5, 70):
-        data = rng.integers(0, 256, (R, k), dtype=np.uint8)
-        data[0] = 0xFF
-        data[R // 2] = 0
+    for R, data in encoder_rows(n, k):
         want = rs_encode_ref(data, n - k)
         for dp, op in ((0, 0), (k + 3, 0), (0, n + 2), (k + 1, n + 5)):
             assert np.array_equal(encode(m, data, n - k, dp, op), want), (R, dp, op)
@@ -215,10 +150,9 @@ def test_encoder_equals_the_restatement_for_every_row_count_and_pitch(n, k):
 
 
 # ------------------------------------------------------------------------------------------ 4. encode, erase, decode
-@pytest.mark.parametrize("n,k", RS_CODES)
-def test_the_encoder_s_rows_come_back_from_random_erasures_of_up_to_nroots_positions(n, k):
+def encode_erase_decode(m, n, k):
+    """the encoder's rows with random erasures of up to nroots places each come back, with the counts the damage says"""
     import torch
-    m = modem()
     nroots, R = n - k, 33
     rng = np.random.default_rng(n + 7 * k)
     data = torch.from_numpy(rng.integers(0, 256, (R, k), dtype=np.uint8)).cuda()
@@ -235,6 +169,12 @@ def test_the_encoder_s_rows_come_back_from_random_erasures_of_up_to_nroots_posit
     out, info = out.cpu().numpy(), info.cpu().numpy()
     assert np.array_equal(out, sent)
     assert np.array_equal(info[:, 0], (hit != sent).sum(axis=1)) and np.array_equal(info[:, 1], flags.sum(axis=1)) and not info[:, 2].any()
+
+
+@pytest.mark.parametrize("n,k", RS_CODES)
+def test_the_encoder_s_rows_come_back_from_random_erasures_of_up_to_nroots_positions(n, k):
+    m = modem()
+    encode_erase_decode(m, n, k)
     m.sync()
     m.close()
 
@@ -374,4 +314,52 @@ def test_the_cpu_link_on_the_device_with_the_deframer_s_bytes_decoded_where_they
     m.sync()
     after = d["bytes"].cpu().numpy()[:, 0]
     assert np.array_equal(after[:, :n], want_out) and np.array_equal(after[:, n:], before[:, 0, n:])
+    m.close()
+
+
+# ------------------------------------------------------------------------------------------ 7. the rare paths and the chunk seams
+@pytest.mark.parametrize("n,k", directed_codes())
+def test_the_directed_rows_of_a_code_in_one_call_bit_for_bit(n, k):
+    """rows picked with the scalar port's trace for what a random draw does not reach (rs_rows.directed_rows): zero discrepancies inside
+    Berlekamp-Massey, lengths that jump, repeated roots, roots among the missing bytes, words that fail the last check alone,
+    miscorrections; decoded and failing rows in turn, so that the waves of a workgroup leave by different exits"""
+    c = directed_rows(n, k)
+    ok = c["erased"][1][:, 0] >= 0
+    assert sum(bool(a) != bool(b) for a, b in zip(ok[:-1], ok[1:])) >= 8
+    m = modem()
+    got = decode(m, c["words"], n - k, c["flags"])
+    assert got["kernel"] == "rs_decode_kernel"
+    assert_rows(got, c["erased"], c["names"], "erasures")
+    assert_rows(decode(m, c["words"], n - k, None), c["plain"], c["names"], "d_erase NULL")
+    m.sync()
+    m.close()
+
+
+PITCHED_EDGE = (129, 121)
+assert PITCHED_EDGE in edge_codes()
+
+
+@pytest.mark.parametrize("n,k", edge_codes())
+def test_the_edge_codes_decode_and_encode_bit_for_bit(n, k):
+    """n on both sides of the 64-lane chunks' seams, errors and erasures on the seams (rs_rows.edge_rows), nroots 33 and 63"""
+    c = edge_rows(n, k)
+    m = modem()
+    assert_rows(decode(m, c["words"], n - k, c["flags"]), c["erased"], c["names"], "erasures")
+    assert_rows(decode(m, c["words"], n - k, None), c["plain"], c["names"], "d_erase NULL")
+    if (n, k) == PITCHED_EDGE:
+        for what, kw in (("pitched input", dict(in_pitch=n + 2)), ("in place", dict(inplace=True)), ("in place, pitched", dict(inplace=True, in_pitch=n + 3))):
+            assert_rows(decode(m, c["words"], n - k, c["flags"], **kw), c["erased"], c["names"], what)
+    (R, data), = encoder_rows(n, k, (5,))
+    want = rs_encode_ref(data, n - k)
+    for dp, op in ((0, 0), (k + 3, 0), (0, n + 2), (k + 1, n + 5)):
+        assert np.array_equal(encode(m, data, n - k, dp, op), want), (dp, op)
+    m.sync()
+    m.close()
+
+
+@pytest.mark.parametrize("n,k", edge_codes())
+def test_the_edge_codes_rows_come_back_from_random_erasures(n, k):
+    m = modem()
+    encode_erase_decode(m, n, k)
+    m.sync()
     m.close()
