@@ -20,20 +20,20 @@ int qpsk_soft_batch(qpsk_ctx *c, const float *d_costas, long long row_pitch, int
     if (skip < 0 || skip >= nsym) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: skip = %d outside 0..%d", skip, nsym - 1);
     if (mode != QPSK_SOFT_UNIT && mode != QPSK_SOFT_LLR) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: unknown mode %d", mode);
     if (!(scale > 0.0f && scale <= 3.402823466e+38f)) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: scale = %g is not finite and > 0", (double)scale);
-    if (row_pitch == 0) row_pitch = nsym;
-    if (row_pitch < nsym) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: row_pitch = %lld (0, or >= nsym %d)", row_pitch, nsym);
+    size_t pitch = 0;
+    if (!pitch_ok(row_pitch, nsym, LLONG_MAX, &pitch)) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: row_pitch = %lld (0, or >= nsym %d)", row_pitch, nsym);
     if ((uintptr_t)d_costas % 8) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: d_costas is not 8-byte aligned");
     if (d_soft) {
         if (nout < 0 || first < 0 || (long long)first + nout > nsym)
             return fail(QPSK_ERR_ARG, "qpsk_soft_batch: first %d, nout %d do not fit a row of %d", first, nout, nsym);
         if ((uintptr_t)d_soft % 2) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: d_soft is not 2-byte aligned");
-        const uintptr_t o0 = (uintptr_t)d_soft, o1 = o0 + 2 * (size_t)nrows * (size_t)nout;
-        const uintptr_t i0 = (uintptr_t)d_costas, i1 = i0 + 8 * ((size_t)(nrows - 1) * (size_t)row_pitch + (size_t)nsym);
-        if (o0 < i1 && i0 < o1) return fail(QPSK_ERR_ARG, "qpsk_soft_batch: d_soft overlaps d_costas");
+        /* nout = 0 makes d_soft empty; an empty d_soft that points past the input's first byte and not past its last has always been refused */
+        const Span in = {d_costas, 8 * rows_extent(nrows, pitch, nsym), "d_costas"}, out = {d_soft, 2 * (size_t)nrows * (size_t)nout, "d_soft"};
+        if (overlap(out, in) || (nout == 0 && (const void *)d_soft != d_costas && overlap(Span{d_soft, 1, "d_soft"}, in)))
+            return fail(QPSK_ERR_ARG, "qpsk_soft_batch: d_soft overlaps d_costas");
     }
     static_assert(QPSK_SOFT_UNIT == SOFT_MODE_UNIT && QPSK_SOFT_LLR == SOFT_MODE_LLR, "the kernels take the header's mode values");
     if (bind(c)) return QPSK_ERR_HIP;
-    const size_t pitch = (size_t)row_pitch;
     const bool need_sums = d_quality || d_sums || !d_gain_in;
     if (!d_soft) {
         KERNEL_TRY(launch_soft_sums(d_costas, pitch, nrows, nsym, skip, mode, scale, nullptr, d_quality, d_sums, c->status.d_status, c->stream));
@@ -204,8 +204,8 @@ static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long
 #endif
     if (flags & ~known) return fail(QPSK_ERR_ARG, "%s: unknown flags 0x%x", who, flags);
     const long long nrow = coded_ndibits(l, nsteps);      /* the dibits of a row */
-    if (row_pitch == 0) row_pitch = nrow;
-    if (row_pitch < nrow) return fail(QPSK_ERR_ARG, "%s: row_pitch = %lld (0, or >= %s %lld)", who, row_pitch, pattern ? "ntx" : "nsteps", nrow);
+    size_t pitch = 0;
+    if (!pitch_ok(row_pitch, nrow, LLONG_MAX, &pitch)) return fail(QPSK_ERR_ARG, "%s: row_pitch = %lld (0, or >= %s %lld)", who, row_pitch, pattern ? "ntx" : "nsteps", nrow);
     if ((uintptr_t)d_soft % 2) return fail(QPSK_ERR_ARG, "%s: d_soft is not 2-byte aligned", who);
     if ((uintptr_t)d_info % 4) return fail(QPSK_ERR_ARG, "%s: d_info is not 4-byte aligned", who);
     if (int rc = layout_add_stride(who, nsteps, stride, &l)) return rc;
@@ -214,7 +214,7 @@ static int viterbi_impl(qpsk_ctx *c, const char *who, const int8_t *d_soft, long
     const ViterbiRoute route = viterbi_route(c, (size_t)nrows, nsteps);
     /* one launch of rows [r0, r0 + n) */
     const auto launch = [&](size_t r0, int n, unsigned long long *scratch) {
-        return launch_viterbi(d_soft + 2 * r0 * (size_t)row_pitch, (size_t)row_pitch, n, nsteps, l, d_flip, flags, scratch, route.lds,
+        return launch_viterbi(d_soft + 2 * r0 * pitch, pitch, n, nsteps, l, d_flip, flags, scratch, route.lds,
                               d_bits ? d_bits + r0 * (((size_t)nsteps + 7) / 8) : nullptr, d_info ? d_info + 4 * r0 : nullptr, c->stream);
     };
     if (route.lds) {      /* nothing to chunk for: one launch */
@@ -260,16 +260,6 @@ int qpsk_rs_generator(int nroots, uint8_t *h_g)
     return QPSK_OK;
 }
 
-/* a pitch argument: 0 = tight, otherwise at least the row and small enough for nrows rows to stay inside 63 bits */
-static bool rs_pitch(long long pitch, int row, int nrows, size_t *out)
-{
-    if (pitch != 0 && (pitch < row || pitch > (LLONG_MAX >> 1) / nrows)) return false;
-    *out = pitch ? (size_t)pitch : (size_t)row;
-    return true;
-}
-
-static bool rs_overlap(uintptr_t a0, uintptr_t a1, uintptr_t b0, uintptr_t b1) { return a0 < b1 && b0 < a1; }
-
 int qpsk_rs_encode_batch(qpsk_ctx *c, const uint8_t *d_data, long long data_pitch, int nrows, int k, int nroots, uint8_t *d_out,
                          long long out_pitch)
 {
@@ -279,12 +269,11 @@ int qpsk_rs_encode_batch(qpsk_ctx *c, const uint8_t *d_data, long long data_pitc
                     nrows, k, nroots, RS_MAX_ROOTS);
     const int n = k + nroots;
     size_t ip = 0, op = 0;
-    if (!rs_pitch(data_pitch, k, nrows, &ip) || !rs_pitch(out_pitch, n, nrows, &op))
+    if (!pitch_ok(data_pitch, k, rs_pitch_limit(nrows), &ip) || !pitch_ok(out_pitch, n, rs_pitch_limit(nrows), &op))
         return fail(QPSK_ERR_ARG, "qpsk_rs_encode_batch: data_pitch = %lld (0 or >= k = %d), out_pitch = %lld (0 or >= n = %d)", data_pitch, k,
                     out_pitch, n);
-    const uintptr_t i0 = (uintptr_t)d_data, i1 = i0 + (size_t)(nrows - 1) * ip + (size_t)k;
-    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)(nrows - 1) * op + (size_t)n;
-    if (rs_overlap(i0, i1, o0, o1)) return fail(QPSK_ERR_ARG, "qpsk_rs_encode_batch: d_out overlaps d_data");
+    if (overlap(Span{d_data, rows_extent(nrows, ip, k), "d_data"}, Span{d_out, rows_extent(nrows, op, n), "d_out"}))      /* both given, neither empty */
+        return fail(QPSK_ERR_ARG, "qpsk_rs_encode_batch: d_out overlaps d_data");
     if (bind(c)) return QPSK_ERR_HIP;
     KERNEL_TRY(launch_rs_encode(d_data, ip, nrows, k, nroots, d_out, op, c->stream));
     c->last_kernel = "rs_encode_kernel";
@@ -300,18 +289,16 @@ int qpsk_rs_decode_batch(qpsk_ctx *c, const uint8_t *d_in, long long in_pitch, i
         return fail(QPSK_ERR_ARG, "qpsk_rs_decode_batch: nrows = %d, n = %d, nroots = %d (nrows >= 1, 1 <= nroots <= %d, nroots < n <= 255)", nrows,
                     n, nroots, RS_MAX_ROOTS);
     size_t ip = 0, op = 0;
-    if (!rs_pitch(in_pitch, n, nrows, &ip) || !rs_pitch(out_pitch, n, nrows, &op))
+    if (!pitch_ok(in_pitch, n, rs_pitch_limit(nrows), &ip) || !pitch_ok(out_pitch, n, rs_pitch_limit(nrows), &op))
         return fail(QPSK_ERR_ARG, "qpsk_rs_decode_batch: in_pitch = %lld, out_pitch = %lld (each 0 or >= n = %d)", in_pitch, out_pitch, n);
-    const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (size_t)(nrows - 1) * ip + (size_t)n;
-    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)(nrows - 1) * op + (size_t)n;
-    const uintptr_t e0 = (uintptr_t)d_erase, e1 = e0 + (size_t)nrows * (size_t)n;
-    const uintptr_t f0 = (uintptr_t)d_info, f1 = f0 + 16 * (size_t)nrows;
+    /* d_erase, d_out and d_info may each be absent, and an absent range overlaps nothing; none is empty */
+    const Span in = {d_in, rows_extent(nrows, ip, n), "d_in"}, out = {d_out, rows_extent(nrows, op, n), "d_out"};
+    const Span erase = {d_erase, (size_t)nrows * (size_t)n, "d_erase"}, info = {d_info, 16 * (size_t)nrows, "d_info"};
     /* in place: exactly the input rows, each wave reads its whole row before it writes it */
-    if (d_out && !(d_out == d_in && op == ip) && rs_overlap(i0, i1, o0, o1))
+    if (!(d_out == d_in && op == ip) && overlap(in, out))
         return fail(QPSK_ERR_ARG, "qpsk_rs_decode_batch: d_out overlaps d_in (allowed: d_out == d_in with the same pitch)");
-    if (d_out && d_erase && rs_overlap(e0, e1, o0, o1)) return fail(QPSK_ERR_ARG, "qpsk_rs_decode_batch: d_out overlaps d_erase");
-    if (d_info && (((uintptr_t)d_info & 3) || rs_overlap(f0, f1, i0, i1) || (d_out && rs_overlap(f0, f1, o0, o1)) ||
-                   (d_erase && rs_overlap(f0, f1, e0, e1))))
+    if (overlap(erase, out)) return fail(QPSK_ERR_ARG, "qpsk_rs_decode_batch: d_out overlaps d_erase");
+    if (((uintptr_t)d_info & 3) || overlap(info, in) || overlap(info, out) || overlap(info, erase))
         return fail(QPSK_ERR_ARG, "qpsk_rs_decode_batch: d_info is not 4-byte aligned, or overlaps d_in, d_out or d_erase");
     if (bind(c)) return QPSK_ERR_HIP;
     KERNEL_TRY(launch_rs_decode(d_in, ip, nrows, n, nroots, d_erase, d_out, op, d_info, c->stream));

@@ -9,38 +9,6 @@ using namespace qpsk;
 
 namespace {
 
-struct Span {
-    const void *p;
-    size_t bytes;
-    const char *name;
-};
-
-bool overlap(const Span &a, const Span &b)
-{
-    const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
-    return a.p && b.p && a.bytes && b.bytes && x < y + b.bytes && y < x + a.bytes;
-}
-
-/* the first pair of spans that share a byte, or 0 */
-int first_overlap(const char *who, const Span *s, size_t count)
-{
-    for (size_t i = 0; i < count; i++)
-        for (size_t j = i + 1; j < count; j++)
-            if (overlap(s[i], s[j])) return fail(QPSK_ERR_ARG, "%s: %s overlaps %s", who, s[j].name, s[i].name);
-    return QPSK_OK;
-}
-
-/* a pitch argument: 0 = tight, otherwise at least the row, and small enough for `rows` rows to stay inside 62 bits */
-bool pitch_ok(long long pitch, int row, long long rows, size_t *out)
-{
-    if (pitch != 0 && (pitch < row || pitch > (LLONG_MAX >> 1) / rows)) return false;
-    *out = pitch ? (size_t)pitch : (size_t)row;
-    return true;
-}
-
-/* [rows][pitch] of which `row` bytes count: from the first byte to the last one used */
-size_t extent(long long rows, size_t pitch, int row) { return (size_t)(rows - 1) * pitch + (size_t)row; }
-
 int code_ok(const char *who, int ngroups, int k, int nroots, int len, int skip)
 {
     if (ngroups < 1) return fail(QPSK_ERR_ARG, "%s: ngroups = %d", who, ngroups);
@@ -58,7 +26,7 @@ int qpsk_rs_cross_encode_batch(qpsk_ctx *c, uint8_t *d_group, long long pitch, i
     if (!c || !d_group) return fail(QPSK_ERR_ARG, "%s: null context or d_group", who);
     if (int rc = code_ok(who, ngroups, k, nroots, len, skip)) return rc;
     size_t gp = 0;
-    if (!pitch_ok(pitch, len, (long long)ngroups * (k + nroots), &gp)) return fail(QPSK_ERR_ARG, "%s: pitch = %lld (0, or >= len = %d)", who, pitch, len);
+    if (!pitch_ok(pitch, len, rs_pitch_limit((long long)ngroups * (k + nroots)), &gp)) return fail(QPSK_ERR_ARG, "%s: pitch = %lld (0, or >= len = %d)", who, pitch, len);
     if (bind(c)) return QPSK_ERR_HIP;
     KERNEL_TRY(launch_rs_cross_encode(d_group, gp, ngroups, k, nroots, len, skip, c->stream));
     c->last_kernel = "rs_cross_encode_kernel";
@@ -74,10 +42,10 @@ int qpsk_rs_cross_decode_batch(qpsk_ctx *c, const uint8_t *d_group, long long pi
     if (int rc = code_ok(who, ngroups, n - nroots, nroots, len, skip)) return rc;
     const long long rows = (long long)ngroups * n;
     size_t gp = 0, op = 0;
-    if (!pitch_ok(pitch, len, rows, &gp) || !pitch_ok(out_pitch, len, rows, &op))
+    if (!pitch_ok(pitch, len, rs_pitch_limit(rows), &gp) || !pitch_ok(out_pitch, len, rs_pitch_limit(rows), &op))
         return fail(QPSK_ERR_ARG, "%s: pitch = %lld, out_pitch = %lld (each 0, or >= len = %d)", who, pitch, out_pitch, len);
     if ((uintptr_t)d_info & 3) return fail(QPSK_ERR_ARG, "%s: d_info is not 4-byte aligned", who);
-    const Span in = {d_group, extent(rows, gp, len), "d_group"}, out = {d_out, extent(rows, op, len), "d_out"};
+    const Span in = {d_group, rows_extent(rows, gp, len), "d_group"}, out = {d_out, rows_extent(rows, op, len), "d_out"};
     /* in place: exactly the input's packets; a lane reads its column before it writes it, and columns do not meet */
     if (d_out && !(d_out == d_group && op == gp) && overlap(in, out))
         return fail(QPSK_ERR_ARG, "%s: d_out overlaps d_group (allowed: d_out == d_group with the same pitch)", who);
@@ -104,12 +72,12 @@ int qpsk_rs_cross_place_batch(qpsk_ctx *c, const uint8_t *d_bytes, long long byt
         return fail(QPSK_ERR_ARG, "%s: n = %d, ngroups = %d (1 <= n <= 255, ngroups >= 1, ngroups n <= 256: a sequence number is one byte)", who, n, ngroups);
     const long long window = (long long)ngroups * n, slots = (long long)nstreams * max_packets;
     size_t bp = 0, gp = 0;
-    if (!pitch_ok(byte_pitch, len, slots, &bp) || !pitch_ok(pitch, len, (long long)nstreams * window, &gp))
+    if (!pitch_ok(byte_pitch, len, rs_pitch_limit(slots), &bp) || !pitch_ok(pitch, len, rs_pitch_limit((long long)nstreams * window), &gp))
         return fail(QPSK_ERR_ARG, "%s: byte_pitch = %lld, pitch = %lld (each 0, or >= len = %d)", who, byte_pitch, pitch, len);
     if (((uintptr_t)d_count | (uintptr_t)d_base) & 3) return fail(QPSK_ERR_ARG, "%s: d_count or d_base is not 4-byte aligned", who);
     /* no output may share a byte with an input or with the other output */
-    const Span s[] = {{d_group, extent((long long)nstreams * window, gp, len), "d_group"}, {d_have, (size_t)nstreams * (size_t)window, "d_have"}};
-    const Span ins[] = {{d_bytes, extent(slots, bp, len), "d_bytes"}, {d_count, 4 * (size_t)nstreams, "d_count"}, {d_crc_ok, (size_t)slots, "d_crc_ok"},
+    const Span s[] = {{d_group, rows_extent(nstreams * window, gp, len), "d_group"}, {d_have, (size_t)nstreams * (size_t)window, "d_have"}};
+    const Span ins[] = {{d_bytes, rows_extent(slots, bp, len), "d_bytes"}, {d_count, 4 * (size_t)nstreams, "d_count"}, {d_crc_ok, (size_t)slots, "d_crc_ok"},
                         {d_base, 4 * (size_t)nstreams, "d_base"}};
     if (overlap(s[0], s[1])) return fail(QPSK_ERR_ARG, "%s: d_have overlaps d_group", who);
     for (const Span &o : s)

@@ -117,6 +117,22 @@ int qpsk::use_context_gains(qpsk_ctx *c)
     return QPSK_OK;
 }
 
+/* the new state of a reset that replaces a group's (api_ctx.h) */
+int qpsk::replace_state(qpsk_ctx *c, const char *who, const char *noun, int count, size_t stride, uint8_t **state)
+{
+    void *p = nullptr;
+    if (stride > SIZE_MAX / (size_t)count || hipMalloc(&p, stride * (size_t)count) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(QPSK_ERR_ALLOC, "%s: %d %s of %zu bytes of state", who, count, noun, stride);
+    }
+    if (hipStreamSynchronize(c->stream) != hipSuccess) {
+        hipFree(p);
+        return fail(QPSK_ERR_HIP, "%s: hipStreamSynchronize failed", who);
+    }
+    *state = (uint8_t *)p;
+    return QPSK_OK;
+}
+
 const char *qpsk_last_error(void) { return g_err; }
 const char *qpsk_version(void) { return "qpsk_hip 0.3 (gfx950)"; }
 

@@ -1,6 +1,7 @@
 /*
- * api_ctx.h -- what the units of the C ABI layer share: the context, its groups of state, error reporting and the few helpers
- * that cross a unit boundary.  Internal: included by api_*.cpp only, never installed.
+ * api_ctx.h -- what the units of the C ABI layer share: the context, its groups of state, error reporting, the checks of buffer
+ * arguments (Span, overlap, rows_extent, first_overlap, pitch_ok) and the few helpers that cross a unit boundary.  Internal: included
+ * by api_*.cpp only, never installed.
  *
  *   api_ctx.cpp      contexts, tuning, the status word, setters and getters, device memory
  *   api_rx.cpp       the receive batch calls, their routing and the stage calls
@@ -94,6 +95,45 @@ struct Tuning {
 };
 
 static inline int tuned(int v, int dflt) { return v >= 0 ? v : dflt; }
+
+/* ---- buffer arguments: what the entry points ask of the byte ranges they are handed.  The one place with interval arithmetic on pointers */
+
+/* a byte range of a call under its argument's name; p = NULL is an optional buffer that is absent */
+struct Span {
+    const void *p;
+    size_t bytes;
+    const char *name;
+};
+
+/* do the two share a byte?  An absent or an empty range shares none */
+static inline bool overlap(const Span &a, const Span &b)
+{
+    const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
+    return a.p && b.p && a.bytes && b.bytes && x < y + b.bytes && y < x + a.bytes;
+}
+
+/* [rows][pitch] of which row_bytes count: from the first row's first byte to the last row's last; what lies behind that is not the buffer's */
+static inline size_t rows_extent(long long rows, size_t pitch, long long row_bytes) { return (size_t)(rows - 1) * pitch + (size_t)row_bytes; }
+
+/* no two of s[0 .. count) may share a byte: the refusal for the first pair that does, the later one named first, or QPSK_OK */
+static inline int first_overlap(const char *who, const Span *s, size_t count)
+{
+    for (size_t i = 0; i < count; i++)
+        for (size_t j = i + 1; j < count; j++)
+            if (overlap(s[i], s[j])) return fail(QPSK_ERR_ARG, "%s: %s overlaps %s", who, s[j].name, s[i].name);
+    return QPSK_OK;
+}
+
+/* the Reed-Solomon calls' limit for pitch_ok: the largest pitch with which `rows` rows stay inside 62 bits */
+static inline long long rs_pitch_limit(long long rows) { return (LLONG_MAX >> 1) / rows; }
+
+/* a pitch argument: 0 = tight, otherwise at least the row and at most `limit` (the caller's, from its row count; LLONG_MAX where it has its
+ * own refusal for that).  *out = the pitch in force, also behind `false`, for the caller's message */
+static inline bool pitch_ok(long long pitch, long long row, long long limit, size_t *out)
+{
+    *out = (size_t)(pitch ? pitch : row);
+    return pitch == 0 || (pitch >= row && pitch <= limit);
+}
 
 /* ---- the context's groups of state, one per owner.  Plain structs: each frees and clears what it holds in release() */
 
@@ -281,6 +321,11 @@ QPSK_UNIT_LOCAL int check_status(qpsk_ctx *c);
 QPSK_UNIT_LOCAL int bind(const qpsk_ctx *c);
 /* make d_gains[0] the context's own (alpha, beta) again after a bandwidth sweep replaced it */
 QPSK_UNIT_LOCAL int use_context_gains(qpsk_ctx *c);
+/* for a reset that replaces per-stream device state (who: the entry point, noun: what `count` counts, "streams" or "links"): *state = count
+ * x stride new bytes, allocated FIRST, so that a failure leaves the context and the state it has as they were, and handed over behind a
+ * synchronisation of the context's stream, because pushes of the old state may still run.  The caller then release()s the old group,
+ * assigns the new one and launches its init kernel */
+QPSK_UNIT_LOCAL int replace_state(qpsk_ctx *c, const char *who, const char *noun, int count, size_t stride, uint8_t **state);
 
 /* ---- api_rx.cpp, for the streams' kernels apart */
 QPSK_UNIT_LOCAL int fir_full_rate(qpsk_ctx *c, const float *x, const float *memory, float *y, int nframes, int length, size_t in_pitch = 0);

@@ -49,13 +49,6 @@ int qpsk_dispersal_sequence(int len, int group, int flags, uint8_t *out)
     return group * len - 1;
 }
 
-/* do [p, p + np) and [q, q + nq) share a byte?  A NULL or empty range shares none */
-static bool dispersal_overlap(const void *p, size_t np, const void *q, size_t nq)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return p && q && np && nq && a < b + nq && b < a + np;
-}
-
 int qpsk_dispersal_batch(qpsk_ctx *c, const uint8_t *d_in, long long in_pitch, int nrows, int len, int group, int flags, const uint8_t *d_flags,
                          int first, uint8_t *d_out, long long out_pitch)
 {
@@ -64,20 +57,18 @@ int qpsk_dispersal_batch(qpsk_ctx *c, const uint8_t *d_in, long long in_pitch, i
     if (!d_in || !d_out) return fail(QPSK_ERR_ARG, "%s: null d_in or d_out", who);
     if (int rc = dispersal_geometry(who, len, group, flags)) return rc;
     if (nrows < 1) return fail(QPSK_ERR_ARG, "%s: nrows = %d", who, nrows);
-    if (in_pitch == 0) in_pitch = len;
-    if (out_pitch == 0) out_pitch = len;
-    if (in_pitch < len) return fail(QPSK_ERR_ARG, "%s: in_pitch = %lld (0, or >= len = %d)", who, in_pitch, len);
-    if (out_pitch < len) return fail(QPSK_ERR_ARG, "%s: out_pitch = %lld (0, or >= len = %d)", who, out_pitch, len);
+    size_t ip = 0, op = 0;      /* the pitches in force; what is too large for the address space is refused below, in its own words */
+    if (!pitch_ok(in_pitch, len, LLONG_MAX, &ip)) return fail(QPSK_ERR_ARG, "%s: in_pitch = %lld (0, or >= len = %d)", who, in_pitch, len);
+    if (!pitch_ok(out_pitch, len, LLONG_MAX, &op)) return fail(QPSK_ERR_ARG, "%s: out_pitch = %lld (0, or >= len = %d)", who, out_pitch, len);
     if (d_flags ? first != 0 : (first < 0 || first >= group))
         return fail(QPSK_ERR_ARG, d_flags ? "%s: first = %d with d_flags (the rows' indices are d_flags', first must be 0)" : "%s: first = %d outside 0..group - 1", who, first);
-    if ((size_t)in_pitch > SIZE_MAX / 2 / (size_t)nrows || (size_t)out_pitch > SIZE_MAX / 2 / (size_t)nrows)
-        return fail(QPSK_ERR_ARG, "%s: the buffers leave the address space", who);
-    /* a buffer is what lies between its first row's first byte and its last row's last: in place is allowed, any other shared byte is not */
-    const size_t in_bytes = (size_t)(nrows - 1) * (size_t)in_pitch + (size_t)len, out_bytes = (size_t)(nrows - 1) * (size_t)out_pitch + (size_t)len;
-    if (!(d_out == d_in && out_pitch == in_pitch) && dispersal_overlap(d_out, out_bytes, d_in, in_bytes))
+    if (ip > SIZE_MAX / 2 / (size_t)nrows || op > SIZE_MAX / 2 / (size_t)nrows) return fail(QPSK_ERR_ARG, "%s: the buffers leave the address space", who);
+    /* in place is allowed, any other shared byte is not */
+    const Span in = {d_in, rows_extent(nrows, ip, len), "d_in"}, out = {d_out, rows_extent(nrows, op, len), "d_out"}, fl = {d_flags, (size_t)nrows, "d_flags"};
+    if (!(d_out == d_in && op == ip) && overlap(out, in))
         return fail(QPSK_ERR_ARG, "%s: d_out overlaps d_in (in place is d_out == d_in with equal pitches)", who);
-    if (dispersal_overlap(d_flags, (size_t)nrows, d_in, in_bytes)) return fail(QPSK_ERR_ARG, "%s: d_flags overlaps d_in", who);
-    if (dispersal_overlap(d_flags, (size_t)nrows, d_out, out_bytes)) return fail(QPSK_ERR_ARG, "%s: d_flags overlaps d_out", who);
+    if (overlap(fl, in)) return fail(QPSK_ERR_ARG, "%s: d_flags overlaps d_in", who);
+    if (overlap(fl, out)) return fail(QPSK_ERR_ARG, "%s: d_flags overlaps d_out", who);
     if (!c) return fail(QPSK_ERR_ARG, "%s: null context", who);
     if (bind(c)) return QPSK_ERR_HIP;
     Dispersal &d = c->dispersal;
@@ -103,7 +94,7 @@ int qpsk_dispersal_batch(qpsk_ctx *c, const uint8_t *d_in, long long in_pitch, i
         d.group = group;
         d.flags = flags;
     }
-    KERNEL_TRY(launch_dispersal(d_in, (size_t)in_pitch, nrows, len, group, d.table, d_flags, first, d_out, (size_t)out_pitch, c->stream));
+    KERNEL_TRY(launch_dispersal(d_in, ip, nrows, len, group, d.table, d_flags, first, d_out, op, c->stream));
     c->last_kernel = "dispersal_kernel";
     return QPSK_OK;
 }

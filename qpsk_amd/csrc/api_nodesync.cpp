@@ -61,16 +61,7 @@ int qpsk_nodesync_reset(qpsk_ctx *c, int nlinks, int nrot, int nshift, int span,
     n.thr_num = thr_num;
     n.thr_den = thr_den;
     n.drop = drop;
-    /* the new state first: a failed allocation leaves the context, and a node sync it has, as they were */
-    if (NODESYNC_STRIDE > SIZE_MAX / (size_t)nlinks || hipMalloc(&n.state, NODESYNC_STRIDE * (size_t)nlinks) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(QPSK_ERR_ALLOC, "%s: %d links of %zu bytes of state", who, nlinks, NODESYNC_STRIDE);
-    }
-    /* pushes of the old node sync may still run */
-    if (hipStreamSynchronize(c->stream) != hipSuccess) {
-        hipFree(n.state);
-        return fail(QPSK_ERR_HIP, "%s: hipStreamSynchronize failed", who);
-    }
+    if (int rc = replace_state(c, who, "links", nlinks, NODESYNC_STRIDE, &n.state)) return rc;      /* a failure leaves the node sync the context has */
     c->nodesync.release();
     c->nodesync = n;
     KERNEL_TRY(launch_nodesync_init(nodesync_args(c->nodesync), nlinks, nullptr, false, c->stream));
@@ -91,13 +82,6 @@ int qpsk_nodesync_set(qpsk_ctx *c, const int32_t *d_cand)
     return QPSK_OK;
 }
 
-/* do [p, p + np) and [q, q + nq) share a byte? */
-static bool nodesync_overlap(const void *p, size_t np, const void *q, size_t nq)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + nq && b < a + np;
-}
-
 int qpsk_nodesync_push(qpsk_ctx *c, const int8_t *d_soft_in, long long in_pitch, int ntx, const int32_t *d_vinfo, int8_t *d_soft_out,
                        long long out_pitch, int32_t *d_info)
 {
@@ -107,24 +91,25 @@ int qpsk_nodesync_push(qpsk_ctx *c, const int8_t *d_soft_in, long long in_pitch,
     if (!n.state) return fail(QPSK_ERR_STATE, "%s: no qpsk_nodesync_reset yet", who);
     if (ntx < 1 || ntx < n.nshift - 1 || ntx > NODESYNC_MAX_NTX)
         return fail(QPSK_ERR_ARG, "%s: ntx = %d outside max(1, nshift - 1 = %d)..%d", who, ntx, n.nshift - 1, NODESYNC_MAX_NTX);
-    if (in_pitch == 0) in_pitch = ntx;
-    if (out_pitch == 0) out_pitch = ntx;
-    if (in_pitch < ntx || out_pitch < ntx) return fail(QPSK_ERR_ARG, "%s: in_pitch = %lld, out_pitch = %lld (0, or >= ntx %d)", who, in_pitch, out_pitch, ntx);
+    size_t ip = 0, op = 0;      /* the pitches in force, which the message shows: ntx for a 0 */
+    const bool in_ok = pitch_ok(in_pitch, ntx, LLONG_MAX, &ip), out_ok = pitch_ok(out_pitch, ntx, LLONG_MAX, &op);
+    if (!in_ok || !out_ok)
+        return fail(QPSK_ERR_ARG, "%s: in_pitch = %lld, out_pitch = %lld (0, or >= ntx %d)", who, (long long)ip, (long long)op, ntx);
     if ((uintptr_t)d_soft_in % 2 || (uintptr_t)d_soft_out % 2) return fail(QPSK_ERR_ARG, "%s: d_soft_in or d_soft_out is not 2-byte aligned", who);
     if ((uintptr_t)d_vinfo % 4 || (uintptr_t)d_info % 4) return fail(QPSK_ERR_ARG, "%s: d_vinfo or d_info is not 4-byte aligned", who);
     const size_t L = (size_t)n.nlinks;
-    if ((size_t)in_pitch > SIZE_MAX / 4 / L || (size_t)out_pitch > SIZE_MAX / 4 / L) return fail(QPSK_ERR_ARG, "%s: the buffers leave the address space", who);
-    /* the bytes the rows span, without what lies behind the last one */
-    const size_t in_bytes = 2 * ((L - 1) * (size_t)in_pitch + (size_t)ntx), out_bytes = 2 * ((L - 1) * (size_t)out_pitch + (size_t)ntx);
-    if (nodesync_overlap(d_soft_in, in_bytes, d_soft_out, out_bytes)) return fail(QPSK_ERR_ARG, "%s: d_soft_out overlaps d_soft_in", who);
+    if (ip > SIZE_MAX / 4 / L || op > SIZE_MAX / 4 / L) return fail(QPSK_ERR_ARG, "%s: the buffers leave the address space", who);
+    /* both pointers are given and ntx >= 1: neither range is absent or empty */
+    const Span in = {d_soft_in, 2 * rows_extent(n.nlinks, ip, ntx), "d_soft_in"}, out = {d_soft_out, 2 * rows_extent(n.nlinks, op, ntx), "d_soft_out"};
+    if (overlap(in, out)) return fail(QPSK_ERR_ARG, "%s: d_soft_out overlaps d_soft_in", who);
     if (bind(c)) return QPSK_ERR_HIP;
     NodeSyncArgs a = nodesync_args(n);
     a.soft_in = d_soft_in;
-    a.in_pitch = (size_t)in_pitch;
+    a.in_pitch = ip;
     a.ntx = ntx;
     a.vinfo = d_vinfo;
     a.soft_out = d_soft_out;
-    a.out_pitch = (size_t)out_pitch;
+    a.out_pitch = op;
     a.info = d_info;
     KERNEL_TRY(launch_nodesync_push(a, n.nlinks, c->stream));
     n.have = (int)std::min<long long>((long long)n.have + ntx, n.nshift - 1);

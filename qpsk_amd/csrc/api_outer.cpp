@@ -64,16 +64,7 @@ static int outer_reset(const char *who, qpsk_ctx *c, int nstreams, int n, int br
     o.flags = flags;
     o.group = group;
     o.stride = outer_state_stride(n, branches, lock);
-    /* the new state first: a failed allocation leaves the context, and a link it has, as they were */
-    if (o.stride > SIZE_MAX / (size_t)nstreams || hipMalloc(&o.state, o.stride * (size_t)nstreams) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(QPSK_ERR_ALLOC, "%s: %d streams of %zu bytes of state", who, nstreams, o.stride);
-    }
-    /* pushes of the old link may still run */
-    if (hipStreamSynchronize(c->stream) != hipSuccess) {
-        hipFree(o.state);
-        return fail(QPSK_ERR_HIP, "%s: hipStreamSynchronize failed", who);
-    }
+    if (int rc = replace_state(c, who, "streams", nstreams, o.stride, &o.state)) return rc;      /* a failure leaves the link the context has */
     c->outer.release();
     c->outer = o;
     KERNEL_TRY(launch_outer_init(outer_args(c->outer), nstreams, c->stream));
@@ -101,13 +92,6 @@ int qpsk_outer_max_words(qpsk_ctx *c, int nbits)
     return o.lock + (nbits + 8 * o.n - 1) / (8 * o.n);
 }
 
-/* do [p, p + np) and [q, q + nq) share a byte?  A NULL or empty range shares none */
-static bool outer_overlap(const void *p, size_t np, const void *q, size_t nq)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return p && q && np && nq && a < b + nq && b < a + np;
-}
-
 int qpsk_outer_push(qpsk_ctx *c, const uint8_t *d_bits, long long bits_pitch, int nbits, int max_words, int32_t *d_count, uint8_t *d_words,
                     long long word_pitch, long long *d_pos, uint8_t *d_flags, int32_t *d_info)
 {
@@ -117,35 +101,28 @@ int qpsk_outer_push(qpsk_ctx *c, const uint8_t *d_bits, long long bits_pitch, in
     if (!o.state) return fail(QPSK_ERR_STATE, "%s: no qpsk_outer_reset yet", who);
     if (nbits < 1 || nbits > OUTER_MAX_BITS) return fail(QPSK_ERR_ARG, "%s: nbits = %d outside 1..%d", who, nbits, OUTER_MAX_BITS);
     const long long need = (nbits + 7) / 8;
-    if (bits_pitch == 0) bits_pitch = need;
-    if (bits_pitch < need) return fail(QPSK_ERR_ARG, "%s: bits_pitch = %lld (0, or >= %lld bytes for the %d bits of this call)", who, bits_pitch, need, nbits);
+    size_t bp = 0, wp = 0;      /* the pitches in force; what is too large for the address space is refused below, in its own words */
+    if (!pitch_ok(bits_pitch, need, LLONG_MAX, &bp)) return fail(QPSK_ERR_ARG, "%s: bits_pitch = %lld (0, or >= %lld bytes for the %d bits of this call)", who, bits_pitch, need, nbits);
     if (max_words < 0) return fail(QPSK_ERR_ARG, "%s: max_words = %d", who, max_words);
-    if (word_pitch == 0) word_pitch = o.n;
-    if (word_pitch < o.n) return fail(QPSK_ERR_ARG, "%s: word_pitch = %lld (0, or >= n = %d)", who, word_pitch, o.n);
+    if (!pitch_ok(word_pitch, o.n, LLONG_MAX, &wp)) return fail(QPSK_ERR_ARG, "%s: word_pitch = %lld (0, or >= n = %d)", who, word_pitch, o.n);
     if ((uintptr_t)d_count % 4 || (uintptr_t)d_info % 4) return fail(QPSK_ERR_ARG, "%s: d_count or d_info is not 4-byte aligned", who);
     if ((uintptr_t)d_pos % 8) return fail(QPSK_ERR_ARG, "%s: d_pos is not 8-byte aligned", who);
     if (o.total > LLONG_MAX - nbits) return fail(QPSK_ERR_ARG, "%s: the position would leave 64 bits", who);
     const size_t S = (size_t)o.nstreams, slots = S * (size_t)max_words;
-    if ((size_t)word_pitch > SIZE_MAX / 2 / (slots ? slots : 1) || (size_t)bits_pitch > SIZE_MAX / 2 / S) return fail(QPSK_ERR_ARG, "%s: the buffers leave the address space", who);
-    /* no output may share a byte with the input or with another output */
-    const struct {
-        const void *p;
-        size_t bytes;
-        const char *name;
-    } bufs[] = {{d_bits, S * (size_t)bits_pitch, "d_bits"},   {d_count, S * 4, "d_count"}, {d_words, slots * (size_t)word_pitch, "d_words"},
-                {d_pos, slots * 8, "d_pos"},                  {d_flags, slots, "d_flags"}, {d_info, S * 16, "d_info"}};
-    for (size_t i = 0; i < 6; i++)
-        for (size_t j = i + 1; j < 6; j++)
-            if (outer_overlap(bufs[i].p, bufs[i].bytes, bufs[j].p, bufs[j].bytes)) return fail(QPSK_ERR_ARG, "%s: %s overlaps %s", who, bufs[j].name, bufs[i].name);
+    if (wp > SIZE_MAX / 2 / (slots ? slots : 1) || bp > SIZE_MAX / 2 / S) return fail(QPSK_ERR_ARG, "%s: the buffers leave the address space", who);
+    /* no output may share a byte with the input or with another output; here a buffer is whole pitches, the last row's padding included */
+    const Span bufs[] = {{d_bits, S * bp, "d_bits"},   {d_count, S * 4, "d_count"}, {d_words, slots * wp, "d_words"},
+                         {d_pos, slots * 8, "d_pos"},  {d_flags, slots, "d_flags"}, {d_info, S * 16, "d_info"}};
+    if (int rc = first_overlap(who, bufs, 6)) return rc;
     if (bind(c)) return QPSK_ERR_HIP;
     OuterArgs a = outer_args(o);
     a.bits = d_bits;
-    a.bits_pitch = (size_t)bits_pitch;
+    a.bits_pitch = bp;
     a.nbits = nbits;
     a.max_words = max_words;
     a.count = d_count;
     a.words = d_words;
-    a.word_pitch = (size_t)word_pitch;
+    a.word_pitch = wp;
     a.pos = d_pos;
     a.wflags = d_flags;
     a.info = d_info;
@@ -179,11 +156,10 @@ int qpsk_outer_interleave_batch(qpsk_ctx *c, const uint8_t *d_words, int nrows, 
     if (int rc = outer_geometry(who, n, branches)) return rc;
     if (nrows < 1 || nwords < 1 || nwords > (1 << 20)) return fail(QPSK_ERR_ARG, "%s: nrows = %d, nwords = %d (1..2^20)", who, nrows, nwords);
     const size_t words = (size_t)nrows * (size_t)nwords * (size_t)n, hist = (size_t)nrows * (size_t)(branches - 1) * (size_t)n;
-    if (outer_overlap(d_out, words, d_words, words) || outer_overlap(d_out, words, d_hist_in, hist))
-        return fail(QPSK_ERR_ARG, "%s: d_out overlaps an input", who);
-    if (outer_overlap(d_hist_out, hist, d_words, words) || outer_overlap(d_hist_out, hist, d_hist_in, hist))
-        return fail(QPSK_ERR_ARG, "%s: d_hist_out overlaps an input", who);
-    if (outer_overlap(d_hist_out, hist, d_out, words)) return fail(QPSK_ERR_ARG, "%s: d_hist_out overlaps d_out", who);
+    const Span in = {d_words, words, "d_words"}, hin = {d_hist_in, hist, "d_hist_in"}, out = {d_out, words, "d_out"}, hout = {d_hist_out, hist, "d_hist_out"};
+    if (overlap(out, in) || overlap(out, hin)) return fail(QPSK_ERR_ARG, "%s: d_out overlaps an input", who);
+    if (overlap(hout, in) || overlap(hout, hin)) return fail(QPSK_ERR_ARG, "%s: d_hist_out overlaps an input", who);
+    if (overlap(hout, out)) return fail(QPSK_ERR_ARG, "%s: d_hist_out overlaps d_out", who);
     if (!c) return fail(QPSK_ERR_ARG, "%s: null context", who);
     if (bind(c)) return QPSK_ERR_HIP;
     KERNEL_TRY(launch_outer_interleave(d_words, nrows, nwords, n, branches, d_hist_in, d_hist_out, d_out, c->stream));

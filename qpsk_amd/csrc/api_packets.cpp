@@ -175,22 +175,19 @@ int qpsk_deframer_reset_coded_ilv(qpsk_ctx *c, int nstreams, const uint8_t *h_sy
 }
 
 /* what both pushes do behind their own argument checks (who = the entry point's name): the state checks, no output (the caller's
- * list; NULL entries are skipped) may overlap the input of sym_bytes a symbol, the device, and the hunt's arguments from the context */
-struct DeframeOutput { const void *p; size_t bytes; const char *name; };
+ * list; absent ones overlap nothing) may overlap the input of sym_bytes a symbol, the device, and the hunt's arguments from the context */
 static int deframer_push_begin(qpsk_ctx *c, const char *who, bool coded, const void *in, size_t sym_bytes, int nsym,
-                               std::initializer_list<DeframeOutput> outs, DeframeHuntArgs &a)
+                               std::initializer_list<Span> outs, DeframeHuntArgs &a)
 {
     if (!c->df.state) return fail(QPSK_ERR_STATE, "%s: no %s yet", who, coded ? "qpsk_deframer_reset_coded" : "qpsk_deframer_reset");
     if (c->df.coded != coded)
         return fail(QPSK_ERR_STATE, "%s: the deframer was reset in %s mode (%s)", who, coded ? "uncoded" : "coded",
                     coded ? "qpsk_deframer_push" : "qpsk_deframer_push_coded");
     if (!c->df.ready) return fail(QPSK_ERR_STATE, "%s: the deframer's state is undefined after a failed push; reset it", who);
-    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (size_t)c->df.nstreams * (size_t)nsym * sym_bytes;
-    for (const auto &o : outs) {
-        if (!o.p) continue;
-        const uintptr_t o0 = (uintptr_t)o.p, o1 = o0 + o.bytes;
-        if (o0 < i1 && i0 < o1) return fail(QPSK_ERR_ARG, "%s: %s overlaps the input", who, o.name);
-    }
+    /* no range is empty: the input is given and nsym >= 1, and behind a reset nstreams, max_packets and nbytes are all >= 1 */
+    const Span input = {in, (size_t)c->df.nstreams * (size_t)nsym * sym_bytes, "the input"};
+    for (const Span &o : outs)
+        if (overlap(o, input)) return fail(QPSK_ERR_ARG, "%s: %s overlaps the input", who, o.name);
     if (bind(c)) return QPSK_ERR_HIP;
     a.nstreams = c->df.nstreams;
     a.nsym = nsym;
@@ -383,22 +380,20 @@ static int frame_impl(qpsk_ctx *c, const char *who, const uint8_t *d_payload, lo
     if (int rc = frame_body(who, nbytes, coding, Pattern{period, keep0, keep1}, &l, &nbody)) return rc;
     if (nrows < 1 || per_row < 1 || per_row > FRAME_MAX_PER_ROW || (long long)nrows * per_row > INT_MAX)
         return fail(QPSK_ERR_ARG, "%s: nrows = %d, per_row = %d (1..%d, nrows * per_row < 2^31)", who, nrows, per_row, FRAME_MAX_PER_ROW);
-    if (payload_pitch != 0 && payload_pitch < nbytes)
-        return fail(QPSK_ERR_ARG, "%s: payload_pitch = %lld below nbytes = %d", who, payload_pitch, nbytes);
+    size_t pitch = 0;
+    if (!pitch_ok(payload_pitch, nbytes, LLONG_MAX, &pitch)) return fail(QPSK_ERR_ARG, "%s: payload_pitch = %lld below nbytes = %d", who, payload_pitch, nbytes);
     if (lead < 0 || gap < 0) return fail(QPSK_ERR_ARG, "%s: lead = %d, gap = %d", who, lead, gap);
     const long long need = (long long)lead + (long long)per_row * (nsync + nbody) + (long long)(per_row - 1) * gap;
     if (row_len < 1 || row_len > FRAME_MAX_ROW || need > row_len)
         return fail(QPSK_ERR_ARG, "%s: lead %d + %d packets of %d dibits + gaps of %d = %lld do not fit row_len = %d (up to %d)", who, lead,
                     per_row, nsync + nbody, gap, need, row_len, FRAME_MAX_ROW);
-    const size_t npk = (size_t)nrows * (size_t)per_row, pitch = payload_pitch ? (size_t)payload_pitch : (size_t)nbytes;
-    const uintptr_t i0 = (uintptr_t)d_payload, i1 = i0 + (npk - 1) * pitch + (size_t)nbytes;
-    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)nrows * (size_t)row_len;
-    if (o0 < i1 && i0 < o1) return fail(QPSK_ERR_ARG, "%s: d_out overlaps d_payload", who);
-    if (d_crc) {
-        const uintptr_t r0 = (uintptr_t)d_crc, r1 = r0 + 2 * npk;
-        if (((uintptr_t)d_crc & 1) || (r0 < i1 && i0 < r1) || (r0 < o1 && o0 < r1))
-            return fail(QPSK_ERR_ARG, "%s: d_crc is not 2-byte aligned, or overlaps d_payload or d_out", who);
-    }
+    /* d_payload and d_out are given and no range is empty (nrows, per_row, nbytes, row_len >= 1); d_crc may be absent */
+    const size_t npk = (size_t)nrows * (size_t)per_row;
+    const Span in = {d_payload, rows_extent((long long)npk, pitch, nbytes), "d_payload"}, out = {d_out, (size_t)nrows * (size_t)row_len, "d_out"};
+    const Span crc = {d_crc, 2 * npk, "d_crc"};
+    if (overlap(out, in)) return fail(QPSK_ERR_ARG, "%s: d_out overlaps d_payload", who);
+    if (((uintptr_t)d_crc & 1) || overlap(crc, in) || overlap(crc, out))
+        return fail(QPSK_ERR_ARG, "%s: d_crc is not 2-byte aligned, or overlaps d_payload or d_out", who);
     /* the stride: the uncoded format has none; 1 is no interleaving at all and, here alone, takes the kernel of the layer below, frame_kernel<coded> */
     if (stride && coding == QPSK_FRAME_UNCODED && *stride != 1) return fail(QPSK_ERR_ARG, "%s: stride = %d with QPSK_FRAME_UNCODED (1 only)", who, *stride);
     if (stride && coding == QPSK_FRAME_CODED) {

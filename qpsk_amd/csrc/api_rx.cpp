@@ -582,11 +582,9 @@ int qpsk_sync_batch(qpsk_ctx *c, const uint8_t *d_data, int nframes, int nsym, c
     if (!d_out && !d_lag && !d_rot && !d_score) return fail(QPSK_ERR_ARG, "qpsk_sync_batch: every output is NULL");
     for (int i = 0; i < nsync; i++)
         if (h_sync[i] > 3) return fail(QPSK_ERR_ARG, "qpsk_sync_batch: sync[%d] = %d is not a dibit", i, (int)h_sync[i]);
-    if (d_out && nout > 0) {
-        const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)nframes * (size_t)nout;
-        const uintptr_t d0 = (uintptr_t)d_data, d1 = d0 + (size_t)nframes * (size_t)nsym;
-        if (o0 < d1 && d0 < o1) return fail(QPSK_ERR_ARG, "qpsk_sync_batch: d_out overlaps d_data");
-    }
+    /* an absent d_out, or an empty one (nout = 0), overlaps nothing */
+    if (overlap(Span{d_out, (size_t)nframes * (size_t)nout, "d_out"}, Span{d_data, (size_t)nframes * (size_t)nsym, "d_data"}))
+        return fail(QPSK_ERR_ARG, "qpsk_sync_batch: d_out overlaps d_data");
     if (bind(c)) return QPSK_ERR_HIP;
     KERNEL_TRY(launch_sync_search(d_data, nframes, nsym, h_sync, nsync, lag_min, lag_max, nout, nout > 0 ? d_out : nullptr, d_lag, d_rot,
                                   d_score, c->stream));

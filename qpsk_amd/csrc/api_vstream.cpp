@@ -64,16 +64,7 @@ int qpsk_viterbi_stream_reset(qpsk_ctx *c, int nstreams, int depth, int window, 
     v.punct = l.punct;
     v.punctured = !(period == 1 && keep0 == 1u && keep1 == 1u);
     v.stride = vstream_state_stride((depth + window) / 64);
-    /* the new state first: a failed allocation leaves the context, and a decoder it has, as they were */
-    if (v.stride > SIZE_MAX / (size_t)nstreams || hipMalloc(&v.state, v.stride * (size_t)nstreams) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(QPSK_ERR_ALLOC, "%s: %d streams of %zu bytes of state", who, nstreams, v.stride);
-    }
-    /* pushes of the old decoder may still run */
-    if (hipStreamSynchronize(c->stream) != hipSuccess) {
-        hipFree(v.state);
-        return fail(QPSK_ERR_HIP, "%s: hipStreamSynchronize failed", who);
-    }
+    if (int rc = replace_state(c, who, "streams", nstreams, v.stride, &v.state)) return rc;      /* a failure leaves the decoder the context has */
     c->vs.release();
     c->vs = v;
     KERNEL_TRY(launch_vstream_init(vstream_args(c->vs), nstreams, c->stream));
@@ -96,7 +87,7 @@ static int vstream_outputs(const char *who, long long nbits, const uint8_t *d_bi
     if (!d_bits && !d_info) return fail(QPSK_ERR_ARG, "%s: every output is NULL", who);
     if ((uintptr_t)d_info % 4) return fail(QPSK_ERR_ARG, "%s: d_info is not 4-byte aligned", who);
     const long long need = (nbits + 7) / 8;
-    if (*bits_pitch == 0) *bits_pitch = need;
+    if (*bits_pitch == 0) *bits_pitch = need;      /* (not pitch_ok: without d_bits any pitch passes) */
     if (d_bits && *bits_pitch < need) return fail(QPSK_ERR_ARG, "%s: bits_pitch = %lld (0, or >= %lld bytes for the %lld bits of this call)", who, *bits_pitch, need, nbits);
     return QPSK_OK;
 }
@@ -110,8 +101,8 @@ int qpsk_viterbi_stream_push(qpsk_ctx *c, const int8_t *d_soft, long long row_pi
     if (!v.state) return fail(QPSK_ERR_STATE, "%s: no qpsk_viterbi_stream_reset yet", who);
     const int n = vstream_steps(v, ntx);
     if (!n) return fail(QPSK_ERR_ARG, "%s: ntx = %d is not whole periods of %d sent bits, or not 1..%d steps", who, ntx, v.punct.K, VITERBI_MAX_STEPS);
-    if (row_pitch == 0) row_pitch = ntx;
-    if (row_pitch < ntx) return fail(QPSK_ERR_ARG, "%s: row_pitch = %lld (0, or >= ntx %d)", who, row_pitch, ntx);
+    size_t pitch = 0;
+    if (!pitch_ok(row_pitch, ntx, LLONG_MAX, &pitch)) return fail(QPSK_ERR_ARG, "%s: row_pitch = %lld (0, or >= ntx %d)", who, row_pitch, ntx);
     if ((uintptr_t)d_soft % 2) return fail(QPSK_ERR_ARG, "%s: d_soft is not 2-byte aligned", who);
     if (v.total > LLONG_MAX - n) return fail(QPSK_ERR_ARG, "%s: the position would leave 64 bits", who);
     const long long nbits = vstream_emits(v, n);
@@ -119,7 +110,7 @@ int qpsk_viterbi_stream_push(qpsk_ctx *c, const int8_t *d_soft, long long row_pi
     if (bind(c)) return QPSK_ERR_HIP;
     VStreamArgs a = vstream_args(v);
     a.soft = d_soft;
-    a.pitch = (size_t)row_pitch;
+    a.pitch = pitch;
     a.n = n;
     a.pc = (int)(v.total % 64);
     a.slot = (int)((v.total - v.advanced) / 64 % a.nring);
@@ -192,10 +183,8 @@ int qpsk_conv_encode_stream_batch(qpsk_ctx *c, const uint8_t *d_bits, int nrows,
     const long long nsent = coded_nsent(l, nbits);
     if (nbits % period || nsent < 2 || (nsent & 1))
         return fail(QPSK_ERR_ARG, "%s: nbits = %d is not whole periods of %d steps that send whole dibits (%lld sent bits)", who, nbits, period, nsent);
-    if (d_state_in && d_state_out) {
-        const uintptr_t i0 = (uintptr_t)d_state_in, o0 = (uintptr_t)d_state_out;
-        if (i0 < o0 + (size_t)nrows && o0 < i0 + (size_t)nrows) return fail(QPSK_ERR_ARG, "%s: d_state_out overlaps d_state_in", who);
-    }
+    if (overlap(Span{d_state_in, (size_t)nrows, "d_state_in"}, Span{d_state_out, (size_t)nrows, "d_state_out"}))      /* nrows >= 1; either may be absent */
+        return fail(QPSK_ERR_ARG, "%s: d_state_out overlaps d_state_in", who);
     if (bind(c)) return QPSK_ERR_HIP;
     KERNEL_TRY(launch_conv_encode_stream(d_bits, nrows, nbits, l.punct, d_state_in, d_state_out, d_dibits, c->stream));
     c->last_kernel = "conv_encode_stream_kernel";

@@ -28,6 +28,7 @@
 #include "costas_asm.h"      /* lds_addr() */
 #include "fir_full8s_asm.h"
 #include "kernels.h"
+#include "wave_sync.h"
 
 namespace qpsk {
 
@@ -40,12 +41,6 @@ constexpr int WAVES_PER_SIMD = 4;
 __device__ __host__ constexpr int slot_of(int p) { return p + PADS * (p / R); }
 static_assert(slot_of(TILE + HIST - 1) < WSLOTS && slot_of(R * 63) + slot_of(NTAPS + R) + 2 <= WSLOTS, "window geometry");
 static_assert(FIR_FULL8S_ASM_END_VGPR <= 104, "four waves per SIMD: 128 VGPRs");
-
-__device__ __forceinline__ void wave_sync()      /* one wave, in-order LDS: only the compiler needs telling */
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
 } // namespace firs
 
 __global__ void __launch_bounds__(64 * firs::WAVES) __attribute__((amdgpu_waves_per_eu(firs::WAVES_PER_SIMD, firs::WAVES_PER_SIMD)))

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "wave_sync.h"
 
 namespace qpsk {
 
@@ -34,12 +35,6 @@ namespace {
 constexpr int NS_WAVES = 4;
 constexpr int NS_HDR = 32;
 static_assert(NS_HDR + 2 * (NODESYNC_MAX_SHIFT - 1) <= (int)NODESYNC_STRIDE && NODESYNC_STRIDE % 4 == 0, "a link's header and history fit its state");
-
-__device__ __forceinline__ void wave_sync()      /* one wave, in-order LDS: only the compiler needs telling */
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
 
 /* four int8 at once, (a0, b0, a1, b1) = two dibits: -128 -> -127, then turn_r.  No carry crosses a byte: the low seven bits of a byte
  * plus 1 reach bit 7 at most */

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "wave_sync.h"
 
 namespace qpsk {
 
@@ -41,12 +42,6 @@ constexpr int OUTER_HDR = 32;
 __host__ __device__ constexpr int outer_ring_bytes(int n, int branches, int lock) { return ((branches > lock ? branches : lock) * n + 8 + 15) & ~15; }
 /* a wave's slice of the LDS: the ring, a chunk, the byte a phase spills into, and what a two-byte read may touch behind the last bit */
 __host__ __device__ constexpr int outer_slice_bytes(int n, int branches, int lock) { return outer_ring_bytes(n, branches, lock) + OUTER_CHUNK + 16; }
-
-__device__ __forceinline__ void wave_sync()      /* one wave, in-order LDS: only the compiler needs telling */
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
 
 /* V(u) over the window */
 template <bool MSB>

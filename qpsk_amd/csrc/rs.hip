@@ -1,11 +1,11 @@
 /*
  * rs.hip -- qpsk_rs_generator, qpsk_rs_encode_batch, qpsk_rs_decode_batch (include/qpsk_hip.h, REED-SOLOMON): the byte-oriented outer code
- * behind the K = 7 inner code.  GF(256) modulo 0x11D, alpha = 2, generator roots alpha^0 .. alpha^(nroots - 1).  The definition is restated
+ * behind the K = 7 inner code.  GF(256) as gf256.h builds it, alpha = 2, generator roots alpha^0 .. alpha^(nroots - 1).  The definition is restated
  * in numpy by tests/test_rs_cpu.py (rs_encode_ref, rs_decode_ref -- Euclid and a linear solve, not the algorithm below -- pinned to a
  * codebook decoder).  Integers only: no tolerance anywhere.
  *
  * ONE WAVE PER CODEWORD, RS_WAVES codewords per workgroup; this is why nroots <= 64.  The workgroup copies the field's exp / log tables
- * (768 bytes, built at compile time) into LDS and meets ONE barrier, before any wave can leave; behind it a wave works on its own LDS slice
+ * (gf256.h: 768 bytes, built at compile time) into LDS and meets ONE barrier, before any wave can leave; behind it a wave works on its own LDS slice
  * only, in order, and takes whichever exit its row needs (clean, corrected, failed) without waiting for its neighbours.
  *
  * rs_decode_kernel, per wave:
@@ -35,35 +35,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gf256.h"
 #include "kernels.h"
+#include "wave_sync.h"
 
 namespace qpsk {
 
 namespace {
 
 constexpr int RS_WAVES = 4;
-
-struct GfTables {
-    uint8_t exp[512];      /* alpha^i for i < 510 (the period twice: log a + log b needs no reduction) */
-    uint8_t log[256];      /* log[0] is never used as a logarithm */
-};
-
-constexpr GfTables gf_make()
-{
-    GfTables t{};
-    unsigned x = 1;
-    for (int i = 0; i < 255; i++) {
-        t.exp[i] = (uint8_t)x;
-        t.exp[i + 255] = (uint8_t)x;
-        t.log[x] = (uint8_t)i;
-        x <<= 1;
-        if (x & 0x100u) x ^= 0x11Du;
-    }
-    return t;
-}
-
-constexpr GfTables H_GF = gf_make();
-__constant__ GfTables c_gf = gf_make();
 
 struct RsSlice {
     uint8_t row[256];      /* the word, right-aligned in 4 q bytes */
@@ -73,36 +53,9 @@ struct RsSlice {
 };
 
 struct RsLds {
-    GfTables gf;
+    GfTables gf;           /* first: tests/rs_port.py models the offsets */
     RsSlice w[RS_WAVES];
 };
-
-__device__ __forceinline__ void wave_sync()      /* one wave, in-order LDS: only the compiler needs telling */
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ void load_tables(RsLds &L)
-{
-    static_assert(sizeof(GfTables) == 768, "192 dwords");
-    const unsigned *src = reinterpret_cast<const unsigned *>(&c_gf);
-    unsigned *dst = reinterpret_cast<unsigned *>(&L.gf);
-    for (unsigned i = threadIdx.x; i < 192u; i += 64u * RS_WAVES) dst[i] = src[i];
-}
-
-__device__ __forceinline__ unsigned gmul(const GfTables &g, unsigned a, unsigned b)
-{
-    const unsigned v = g.exp[(unsigned)g.log[a] + (unsigned)g.log[b]];
-    return (a && b) ? v : 0u;
-}
-
-/* a alpha^l, l < 255 */
-__device__ __forceinline__ unsigned gmul_log(const GfTables &g, unsigned a, unsigned l)
-{
-    const unsigned v = g.exp[(unsigned)g.log[a] + l];
-    return a ? v : 0u;
-}
 
 __device__ __forceinline__ unsigned wave_xor(unsigned v)
 {
@@ -149,7 +102,7 @@ rs_decode_kernel(RsDecodeArgs a)
     unsigned rb[4] = {0, 0, 0, 0};
     bool fl[4] = {false, false, false, false};
 
-    load_tables(L);
+    gf_load(L.gf, threadIdx.x, 64u * RS_WAVES);
     if (live) {
         const uint8_t *src = a.in + (size_t)urow * a.in_pitch;
         const uint8_t *er = a.erase ? a.erase + (size_t)urow * (size_t)n : nullptr;
@@ -322,7 +275,7 @@ rs_encode_kernel(RsEncodeArgs a)
     RsSlice &w = L.w[wave];
     const GfTables &g = L.gf;
 
-    load_tables(L);
+    gf_load(L.gf, threadIdx.x, 64u * RS_WAVES);
     if (live) {
         const uint8_t *src = a.data + (size_t)urow * a.data_pitch;
         uint8_t *dst = a.out + (size_t)urow * a.out_pitch;

@@ -39,7 +39,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gf256.h"
 #include "kernels.h"
+#include "wave_sync.h"
 
 namespace qpsk {
 
@@ -47,39 +49,10 @@ namespace {
 
 constexpr int RSX_WAVES = 4;
 
-/* the field, a second time (rs.hip keeps its own: its kernels stay as they are) */
-struct GfTables {
-    uint8_t exp[512];
-    uint8_t log[256];
-};
-
-constexpr GfTables gf_make()
-{
-    GfTables t{};
-    unsigned x = 1;
-    for (int i = 0; i < 255; i++) {
-        t.exp[i] = (uint8_t)x;
-        t.exp[i + 255] = (uint8_t)x;
-        t.log[x] = (uint8_t)i;
-        x <<= 1;
-        if (x & 0x100u) x ^= 0x11Du;
-    }
-    return t;
-}
-
-constexpr GfTables H_GF = gf_make();
-__constant__ GfTables c_xgf = gf_make();
-
 /* G[word][b]: byte c of the dword = g's coefficient for slot 4 word + c, times alpha^b */
 struct CrossGen {
     uint32_t g[16][8];
 };
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
 
 template <int NW>
 __device__ __forceinline__ void shift_byte(uint32_t (&R)[NW])
@@ -211,8 +184,8 @@ rs_cross_decode_kernel(CrossDecodeArgs a)
     const uint8_t *have = a.have + g * (size_t)n;
 
     {
-        static_assert(sizeof(GfTables) == 768, "192 dwords");
-        const unsigned *s = reinterpret_cast<const unsigned *>(&c_xgf);
+        /* gf_load()'s loop, written out: through the call the compiler schedules this kernel's prologue in another order */
+        const unsigned *s = reinterpret_cast<const unsigned *>(&c_gf);
         unsigned *d = reinterpret_cast<unsigned *>(&L.gf);
         for (int i = tid; i < 192; i += nthreads) d[i] = s[i];
         for (int p = tid; p < 260; p += nthreads) L.hv[p] = (p < n && have[p] != 0) ? 1 : 0;

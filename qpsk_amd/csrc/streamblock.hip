@@ -29,6 +29,7 @@
 #include "fir_full8_asm.h"
 #include "carrier.h"
 #include "kernels.h"
+#include "wave_sync.h"
 
 namespace qpsk {
 
@@ -54,12 +55,6 @@ __device__ __host__ constexpr int slot_of(int p) { return p + PADS * (p / R); }
 __device__ __host__ constexpr int tiles_of(int L) { return (L + TILE - 1) / TILE; }
 __device__ __host__ constexpr int xs_slots(int L) { return tiles_of(L) * TILE + 128; }      /* positions 0..125 history, 126.. samples, zero padded */
 __device__ __host__ constexpr int ds_slots(int N) { return ((N + 15) / 16) * 16 + 4; }       /* the stream fetches a pair past its last group */
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
 } // namespace sblk
 
 template <bool INLINE>

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "qpsk_device.h"
+#include "wave_sync.h"
 
 namespace qpsk {
 namespace tfft {
@@ -35,13 +36,7 @@ __device__ __forceinline__ cd half_butterfly(cd e, cd o, double wr, double wi, d
     return r;
 }
 
-/* LDS is shared by the lanes of ONE wave here and a wave's LDS instructions execute in order: this only keeps the
- * compiler from moving them across */
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
+using qpsk::wave_sync;      /* wave_sync.h: LDS is shared by the lanes of ONE wave here */
 
 /* samples N0 - HIST .. N0 + NFFT - 1 = 2 .. 639 of a frame as pairs: pair i (samples 2i, 2i+1), i = 1 .. 319, lane l takes
  * 1 + l + 64 j.  aligned: the frame starts on a 16-byte boundary */

@@ -357,6 +357,105 @@ def test_every_bad_argument_is_refused_with_nothing_written_and_the_context_stay
     m.close()
 
 
+def test_decode_buffers_that_touch_are_accepted_and_one_shared_byte_is_refused():
+    """2 groups of (6, 4), len 70, skip 2 (two column tiles, one partial) inside one allocation: 12 packets span 840 bytes tight and
+    11 * 80 + 70 = 950 at pitch 80 -- the padding behind the last packet is not the buffer.  d_have is 12 bytes, d_info 32, d_colfail 136.
+    Every pair the call compares, with the later range on the byte behind the earlier one's last (accepted, every output the reference's) and
+    on that last byte (refused, with the present text); d_info is 4-byte aligned, so it is its neighbour that moves"""
+    import torch
+    G, n, nroots, ln, skip = 2, 6, 2, 70, 2
+    c = case(n, n - nroots, G, ln, skip, first=1)
+    m = modem()
+    L, h = m.L, m.h
+    arena = torch.zeros(4096, dtype=torch.uint8, device="cuda")
+    at = lambda off: None if off is None else C.c_void_p(arena.data_ptr() + off)      # noqa: E731
+
+    def dec(i=1000, ip=0, o=2000, op=0, hv=3000, f=3100, cf=3200):
+        host = np.zeros(4096, np.uint8)
+        p = ip or ln
+        for r in range(G * n):
+            host[i + r * p:i + r * p + ln] = c["groups"].reshape(G * n, ln)[r]
+        host[hv:hv + G * n] = c["have"].reshape(-1)
+        arena.copy_(torch.from_numpy(host))
+        rc = L.qpsk_rs_cross_decode_batch(h, at(i), ip, G, n, nroots, ln, skip, at(hv), at(o), op, at(f), at(cf))
+        torch.cuda.synchronize()
+        return rc
+
+    accepted = (dict(o=1840), dict(o=160), dict(ip=80, o=1950), dict(op=80, o=50), dict(hv=988), dict(hv=1840), dict(hv=1988), dict(hv=2840),
+                dict(f=968), dict(f=1840), dict(f=1968), dict(f=2840), dict(cf=864), dict(cf=1840), dict(cf=1864), dict(cf=2840),
+                dict(hv=3088), dict(hv=3132), dict(hv=3188), dict(hv=3336), dict(f=3168), dict(f=3336), dict(o=1000), dict(ip=80, op=80, o=1000),
+                dict(o=None), dict(f=None), dict(cf=None), dict(f=None, cf=None))
+    for kw in accepted:
+        assert dec(**kw) == 0, (kw, L.qpsk_last_error())
+        host = arena.cpu().numpy()
+        o, op, f, cf = kw.get("o", 2000), kw.get("op", 0) or ln, kw.get("f", 3100), kw.get("cf", 3200)
+        if o is not None:
+            assert np.array_equal(np.stack([host[o + r * op:o + r * op + ln] for r in range(G * n)]).reshape(G, n, ln), c["ref"][0]), kw
+        if f is not None:
+            assert np.array_equal(host[f:f + 16 * G].view(np.int32).reshape(G, 4), c["ref"][1]), kw
+        if cf is not None:
+            assert np.array_equal(host[cf:cf + G * (ln - skip)].reshape(G, ln - skip), c["ref"][2]), kw
+    io, side = b"d_out overlaps d_group (allowed", b" overlaps d_group or d_out"
+    refused = ((dict(o=1839), io), (dict(o=161), io), (dict(ip=80, o=1949), io), (dict(op=80, o=51), io), (dict(o=1000, op=80), io),
+               (dict(hv=989), b"d_have" + side), (dict(hv=1839), b"d_have" + side), (dict(hv=1989), b"d_have" + side), (dict(hv=2839), b"d_have" + side),
+               (dict(i=999, f=968), b"d_info" + side), (dict(i=1001, f=1840), b"d_info" + side), (dict(o=1999, f=1968), b"d_info" + side),
+               (dict(o=2001, f=2840), b"d_info" + side), (dict(cf=865), b"d_colfail" + side), (dict(cf=1839), b"d_colfail" + side),
+               (dict(cf=1865), b"d_colfail" + side), (dict(cf=2839), b"d_colfail" + side), (dict(hv=3089), b"d_info overlaps d_have"),
+               (dict(hv=3131), b"d_info overlaps d_have"), (dict(hv=3189), b"d_colfail overlaps d_have"), (dict(hv=3335), b"d_colfail overlaps d_have"),
+               (dict(cf=3131), b"d_colfail overlaps d_info"), (dict(cf=2965, hv=3500), b"d_colfail overlaps d_info"))
+    for kw, text in refused:
+        assert dec(**kw) == QPSK_ERR_ARG and b"qpsk_rs_cross_decode_batch: " + text in L.qpsk_last_error(), (kw, L.qpsk_last_error())
+    m.sync()
+    m.close()
+
+
+def test_place_buffers_that_touch_are_accepted_and_one_shared_byte_is_refused():
+    """2 streams of 3 slots of 6 bytes at byte_pitch 8 (5 * 8 + 6 = 46 bytes) into windows of 2 groups of 3 at pitch 8 (11 * 8 + 6 = 94
+    bytes), all inside one allocation: each output in front of and behind each input and the other output, touching (accepted, groups and
+    d_have the reference's) and one byte further in (refused, with the present text).  d_base is given only where it is the input in question"""
+    import torch
+    rng = np.random.default_rng(8)
+    S, M, ln, n, ng, P = 2, 3, 6, 3, 2, 8
+    byts = rng.integers(0, 256, (S, M, P), dtype=np.uint8)
+    byts[0, :, 0], byts[1, :, 0] = (0, 4, 5), (11, 12, 19)
+    byts[:, :, ln:] = 0      # the padding: an output may begin in the last row's, and the call never clears
+    count, crc_ok, base = np.array([3, 3], np.int32), np.array([[1, 1, 1], [1, 0, 1]], np.uint8), np.array([0, 10 + 256], np.int32)
+    wants = {False: cross_place_ref(byts, count, crc_ok, n, ng, None, length=ln), True: cross_place_ref(byts, count, crc_ok, n, ng, base, length=ln)}
+    assert wants[False][1].tolist() == [[1, 0, 0, 0, 1, 1], [0] * 6] and wants[True][1].tolist() == [[1, 0, 0, 0, 1, 1], [0, 1, 0, 0, 0, 0]]
+    m = modem()
+    L, h = m.L, m.h
+    arena = torch.zeros(4096, dtype=torch.uint8, device="cuda")
+    at = lambda off: None if off is None else C.c_void_p(arena.data_ptr() + off)      # noqa: E731
+    ins = dict(d_bytes=(1000, 46), d_count=(1200, 8), d_crc_ok=(1500, 6), d_base=(1800, 8))
+    outs = dict(d_group=(2400, 94), d_have=(2600, 12))
+
+    def place(grp=2400, hv=2600, with_base=False):
+        host = np.zeros(4096, np.uint8)
+        host[1000:1048] = byts.reshape(-1)
+        host[1200:1208], host[1500:1506], host[1800:1808] = count.view(np.uint8), crc_ok.reshape(-1), base.view(np.uint8)
+        arena.copy_(torch.from_numpy(host))
+        rc = L.qpsk_rs_cross_place_batch(h, at(1000), P, at(1200), at(1500), S, M, ln, n, ng, at(1800) if with_base else None, at(grp), P, at(hv))
+        torch.cuda.synchronize()
+        if rc == 0:
+            host = arena.cpu().numpy()
+            groups = np.stack([host[grp + r * P:grp + r * P + ln] for r in range(S * ng * n)]).reshape(S, ng, n, ln)
+            assert np.array_equal(groups, wants[with_base][0]) and np.array_equal(host[hv:hv + S * ng * n].reshape(S, ng * n), wants[with_base][1])
+        return rc
+
+    assert place() == 0 and place(with_base=True) == 0, L.qpsk_last_error()
+    pairs = [(o, i, i == "d_base") for o in outs for i in ins] + [("d_have", "d_group", False)]
+    for o, i, with_base in pairs:
+        (start, size), mine = {**ins, **outs}[i], outs[o][1]
+        for off, accepted in ((start - mine, True), (start + size, True), (start - mine + 1, False), (start + size - 1, False)):
+            rc = place(with_base=with_base, **{"grp" if o == "d_group" else "hv": off})
+            if accepted:
+                assert rc == 0, (o, i, off, L.qpsk_last_error())
+            else:
+                assert rc == QPSK_ERR_ARG and ("qpsk_rs_cross_place_batch: %s overlaps %s" % (o, i)).encode() in L.qpsk_last_error(), (o, i, off, L.qpsk_last_error())
+    m.sync()
+    m.close()
+
+
 # ------------------------------------------------------------------------------------------ 7. the link of the CPU test, on the device
 def test_the_cpu_link_on_the_device_with_library_calls_only():
     """Modem.rs_cross_encode -> Modem.frame -> the CPU test's lost rows and inverted runs -> costas_frame[] rows -> Modem.deframe_coded ->

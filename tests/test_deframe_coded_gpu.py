@@ -355,6 +355,43 @@ def test_errors_state_and_rereset():
     m.close()
 
 
+def test_outputs_that_touch_the_input_are_accepted_and_the_least_shared_bytes_are_refused():
+    """2 streams, 100 symbols of costas_frame[] a push (1600 bytes), 4 slots of 2 + 2 bytes; all seven outputs are given"""
+    import torch
+    from test_deframe_gpu import boundary_pushes
+    rng = np.random.default_rng(22)
+    S, M, nsym, nbytes, total = 2, 4, 100, 2, 1500
+    sync = rng.integers(0, 4, 16, dtype=np.uint8)
+    z = planted_costas(rng, S, total + nsym, sync, nbytes, max_err=1, noise=0.1, gap=150, burst=8)      # a push more than is made: what the last refused calls are handed
+    gain = np.full(S, 60.0, np.float32)
+    d_gain = torch.from_numpy(gain).cuda()
+    sizes = dict(d_count=S * 4, d_bytes=S * M * (nbytes + 2), d_pos=S * M * 8, d_rot=S * M * 4, d_score=S * M * 4, d_crc_ok=S * M, d_info=S * M * 16)
+    steps = dict(d_count=4, d_bytes=1, d_pos=8, d_rot=4, d_score=4, d_crc_ok=1, d_info=4)
+    shapes = dict(pos=(np.int64, (S, M)), rot=(np.int32, (S, M)), score=(np.int32, (S, M)), bytes=(np.uint8, (S, M, nbytes + 2)),
+                  crc_ok=(np.uint8, (S, M)), info=(np.int32, (S, M, 4)))
+    m = modem()
+    m.deframer_reset_coded(S, sync, nbytes, 15, max_packets=M)
+    got = [[] for _ in range(S)]
+
+    def parse(host, where, k):
+        cut = lambda name, dtype, shape: host[where[name]:where[name] + sizes[name]].view(dtype).reshape(shape)      # noqa: E731
+        cnt = cut("d_count", np.int32, (S,))
+        h = {key: cut("d_" + key, *shapes[key]) for key in KEYS}
+        assert (cnt <= M).all()
+        for s in range(S):
+            got[s] += [rec(k, {key: h[key][s, j] for key in KEYS}) for j in range(cnt[s])]
+
+    call = lambda d_in, n, p: m.L.qpsk_deframer_push_coded(m.h, d_in, n, C.c_void_p(d_gain.data_ptr()), p["d_count"], p["d_bytes"], p["d_pos"],  # noqa: E731
+                                                           p["d_rot"], p["d_score"], p["d_crc_ok"], p["d_info"])
+    put = lambda k: np.ascontiguousarray(z[:, k * nsym:(k + 1) * nsym]).view(np.uint8).reshape(-1)      # noqa: E731
+    pushes = boundary_pushes(m, call, S, M, nsym, S * nsym * 8, put, sizes, steps, parse, "qpsk_deframer_push_coded")
+    assert pushes == 15 == total // nsym
+    rows = rows_of(z[:, :total], [nsym] * pushes)
+    assert got == want_all(rows, np.tile(gain, (pushes, 1)), sync, 15, nbytes) and all(got)
+    m.sync()
+    m.close()
+
+
 def nan_case(where):
     """one stream pair: stream 0 carries a packet, stream 1 none (abandoned); a NaN is put `where` -> the synchronisation's verdict"""
     import qpsk_amd

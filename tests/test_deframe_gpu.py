@@ -242,6 +242,61 @@ def test_errors_and_rereset():
     m.close()
 
 
+def boundary_pushes(m, call, S, M, nsym, in_bytes, put_input, sizes, steps, parse, who):
+    """what the overlap tests of both pushes share: the input of in_bytes bytes at byte 1024 of one allocation, every output at a home of its
+    own; then each output in turn ends where the input begins and begins where it ends (accepted; parse(host, where, push index) compares
+    the push), and lies one step of its alignment further in (refused: "<who>: <output> overlaps the input").  -> the pushes made"""
+    import torch
+    arena = torch.zeros(8192, dtype=torch.uint8, device="cuda")
+    home = {name: 256 * ((1024 + in_bytes + 255) // 256 + 1 + i) for i, name in enumerate(sizes)}      # behind the input, apart from each other
+    pushes = 0
+    for name in [None] + list(sizes):
+        for shift, accepted in ((0, True),) if name is None else ((-sizes[name], True), (in_bytes, True), (-sizes[name] + steps[name], False), (in_bytes - steps[name], False)):
+            where = dict(home) if name is None else {**home, name: 1024 + shift}
+            host = np.zeros(8192, np.uint8)
+            host[1024:1024 + in_bytes] = put_input(pushes)
+            arena.copy_(torch.from_numpy(host))
+            rc = call(C.c_void_p(arena.data_ptr() + 1024), nsym, {k: C.c_void_p(arena.data_ptr() + v) for k, v in where.items()})
+            torch.cuda.synchronize()
+            if not accepted:
+                assert rc == QPSK_ERR_ARG and ("%s: %s overlaps the input" % (who, name)).encode() in m.L.qpsk_last_error(), (name, shift, rc, m.L.qpsk_last_error())
+                continue
+            assert rc == 0, (name, shift, m.L.qpsk_last_error())
+            parse(arena.cpu().numpy(), where, pushes)
+            pushes += 1
+    return pushes
+
+
+def test_outputs_that_touch_the_input_are_accepted_and_the_least_shared_bytes_are_refused():
+    """2 streams, 100 dibits a push on the data input (200 bytes), 4 slots of 4 + 2 bytes; every optional output is given"""
+    rng = np.random.default_rng(21)
+    S, M, nsym, nbytes, total = 2, 4, 100, 4, 1300
+    sync = rng.integers(0, 4, 16, dtype=np.uint8)
+    D = planted_streams(rng, S, total + nsym, sync, nbytes, max_err=1)      # a push more than is made: what the last refused calls are handed
+    sizes = dict(d_count=S * 4, d_bytes=S * M * (nbytes + 2), d_pos=S * M * 8, d_rot=S * M * 4, d_score=S * M * 4, d_crc_ok=S * M)
+    steps = dict(d_count=4, d_bytes=1, d_pos=8, d_rot=4, d_score=4, d_crc_ok=1)
+    m = modem()
+    m.deframer_reset(S, sync, nbytes, 15, max_packets=M)
+    got = [[] for _ in range(S)]
+
+    def parse(host, where, k):
+        cut = lambda name, dtype, shape: host[where[name]:where[name] + sizes[name]].view(dtype).reshape(shape)      # noqa: E731
+        cnt, by, pos = cut("d_count", np.int32, (S,)), cut("d_bytes", np.uint8, (S, M, nbytes + 2)), cut("d_pos", np.int64, (S, M))
+        rot, sc, ok = cut("d_rot", np.int32, (S, M)), cut("d_score", np.int32, (S, M)), cut("d_crc_ok", np.uint8, (S, M))
+        assert (cnt <= M).all()
+        for s in range(S):
+            for j in range(cnt[s]):
+                got[s].append((k, int(pos[s, j]), int(rot[s, j]), int(sc[s, j]), by[s, j].tobytes(), bool(ok[s, j])))
+
+    call = lambda d_in, n, p: m.L.qpsk_deframer_push(m.h, None, d_in, n, p["d_count"], p["d_bytes"], p["d_pos"], p["d_rot"], p["d_score"], p["d_crc_ok"])  # noqa: E731
+    pushes = boundary_pushes(m, call, S, M, nsym, S * nsym, lambda k: D[:, k * nsym:(k + 1) * nsym].reshape(-1), sizes, steps, parse, "qpsk_deframer_push")
+    assert pushes == 13 == total // nsym
+    for s in range(S):
+        assert got[s] == want_of(D[s, :total], [nsym] * pushes, sync, 15, nbytes) and got[s], s
+    m.sync()
+    m.close()
+
+
 def test_deframer_and_receive_streams_do_not_disturb_each_other():
     fs, rs, L, S = 9600.0, 2400.0, 512, 40
     rng = np.random.default_rng(14)

@@ -375,6 +375,16 @@ def test_every_argument_error_of_the_new_calls_is_decided_before_a_device_is_tou
     for k in (dict(o=at(buf)), dict(o=at(buf), ip=204, op=204), dict(o=at(buf, 752)), dict(f=at(buf, 752)), dict(f=at(fl)), dict(first=7),
               dict(len=2, group=1), dict(len=255, group=16, nrows=1), dict(ip=204, op=207), dict(flags=DISPERSAL_MSB_FIRST)):
         refused(disp(**k), b"null context")                   # in place, abutting buffers and the corners of the ranges
+    # the boundary of every overlap test, a byte on either side: 3 rows of 188 at pitch 204 end at byte 2 * 204 + 188 = 596, padding apart
+    pad = dict(nrows=3, ip=204, op=204)
+    for k, text in ((dict(pad, o=at(buf, 595)), b"d_out overlaps d_in"), (dict(pad, i=at(buf, 595), o=at(buf)), b"d_out overlaps d_in"),
+                    (dict(pad, f=at(buf, 595)), b"d_flags overlaps d_in"), (dict(pad, i=at(buf, 2), f=at(buf)), b"d_flags overlaps d_in"),
+                    (dict(pad, f=at(out, 595)), b"d_flags overlaps d_out"), (dict(pad, o=at(out, 2), f=at(out)), b"d_flags overlaps d_out"),
+                    (dict(i=at(buf, 751), o=at(buf)), b"d_out overlaps d_in"), (dict(o=at(buf), ip=204), b"d_out overlaps d_in")):
+        refused(disp(**k), text)                              # one shared byte, the last of one range on the first of the other
+    for k in (dict(pad, o=at(buf, 596)), dict(pad, i=at(buf, 596), o=at(buf)), dict(pad, f=at(buf, 596)), dict(pad, i=at(buf, 3), f=at(buf)),
+              dict(pad, f=at(out, 596)), dict(pad, o=at(out, 3), f=at(out)), dict(i=at(buf, 752), o=at(buf)), dict(pad, o=at(buf))):
+        refused(disp(**k), b"null context")                   # touching: the padding behind the last row is not the buffer; in place at pitch 204
     for (n, G, flags), text in (((1, 8, 0), b"len = 1 outside"), ((256, 8, 0), b"len = 256"), ((188, 0, 0), b"group = 0"), ((188, 17, 0), b"group = 17"),
                                 ((188, 8, 2), b"unknown flags 0x2")):
         refused(L.qpsk_dispersal_sequence(n, G, flags, out), text)

@@ -165,6 +165,42 @@ def test_dispersal_through_the_modem_is_an_involution_takes_strided_rows_and_ref
     m.close()
 
 
+def test_dispersal_buffers_that_touch_are_accepted_and_descramble_as_ever():
+    """3 rows of 188 at pitch 204 inside one allocation: a buffer is 2 * 204 + 188 = 596 bytes, the 16 bytes of padding behind its last row
+    are not part of it.  d_out and the 3 bytes of d_flags in front of and behind the input and each other, touching: accepted, and every
+    row is the reference's.  One byte further in the call is refused (test_dvb_cpu.py has the rows; two of them once more on a context)"""
+    import torch
+    rng = np.random.default_rng(204)
+    R, n, P, G = 3, 188, 204, 8
+    x = rng.integers(0, 256, (R, n), dtype=np.uint8)
+    idx = np.array([7, 0, 3])
+    m = modem()
+    arena = torch.zeros(4096, dtype=torch.uint8, device="cuda")
+    at = lambda off: None if off is None else C.c_void_p(arena.data_ptr() + off)      # noqa: E731
+
+    def run(i=1000, o=2000, f=None):
+        host = np.full(4096, 0x55, np.uint8)
+        for r in range(R):
+            host[i + r * P:i + r * P + n] = x[r]
+        if f is not None:
+            host[f:f + R] = (idx << 4) | 5
+        arena.copy_(torch.from_numpy(host))
+        rc = m.L.qpsk_dispersal_batch(m.h, at(i), P, R, n, G, 0, at(f), 0, at(o), P)
+        torch.cuda.synchronize()
+        if rc == 0:
+            got = arena.cpu().numpy()
+            want = dispersal_ref(x, G, np.arange(R) % G if f is None else idx, False)
+            assert np.array_equal(np.stack([got[o + r * P:o + r * P + n] for r in range(R)]), want), (i, o, f)
+        return rc
+    for kw in (dict(o=1596), dict(o=404), dict(f=1596), dict(f=997), dict(f=2596), dict(f=1997), dict(o=1000), dict(o=1000, f=1596)):
+        assert run(**kw) == 0, (kw, m.L.qpsk_last_error())
+    for kw, text in ((dict(o=1595), b"d_out overlaps d_in"), (dict(o=405), b"d_out overlaps d_in"), (dict(f=1595), b"d_flags overlaps d_in"),
+                     (dict(f=998), b"d_flags overlaps d_in"), (dict(f=2595), b"d_flags overlaps d_out"), (dict(f=1998), b"d_flags overlaps d_out")):
+        assert run(**kw) == -2 and b"qpsk_dispersal_batch: " + text in m.L.qpsk_last_error(), (kw, m.L.qpsk_last_error())
+    m.sync()
+    m.close()
+
+
 # ------------------------------------------------------------------------------------------ 4. the link at DVB-S's own parameters
 def test_the_dvb_link_with_the_library_s_calls():
     """test_dvb_cpu's link: dispersal -> rs_encode (204, 188) -> outer_interleave (12) -> conv_encode_stream at rate 3/4 -> the half turn and

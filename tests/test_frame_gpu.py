@@ -290,6 +290,30 @@ def test_bad_arguments_are_refused_and_leave_the_output_alone(m):
     payloads = src.cpu().numpy()[:30].reshape(6, 5)
     assert np.array_equal(out.cpu().numpy()[:600].reshape(2, 300), frame_ref(payloads, sync[:16], False, None, 3, 3, 2, 300)[0])
     assert (out.cpu().numpy()[600:] == GUARD).all()
+    # all three buffers inside `out`: 6 payloads of 5 bytes at pitch 8 span 5 * 8 + 5 = 45 bytes (the padding behind the last one is not the
+    # buffer), d_out 600, d_crc 12.  Touching on either side is accepted and frames as ever; one byte shared (d_crc is 2-byte aligned: two) is not
+    want, want_crc = frame_ref(payloads, sync[:16], False, None, 3, 3, 2, 300)
+    crc_text = b"d_crc is not 2-byte aligned, or overlaps d_payload or d_out"
+    for kw, text in ((dict(out=q + 1045), None), (dict(out=q + 400), None), (dict(out=q + 1044), b"d_out overlaps d_payload"),
+                     (dict(out=q + 401), b"d_out overlaps d_payload"), (dict(crc=q + 988), None), (dict(crc=q + 990), crc_text),
+                     (dict(payload=q + 1001, crc=q + 1046), None), (dict(payload=q + 1001, crc=q + 1044), crc_text), (dict(crc=q + 1988), None),
+                     (dict(crc=q + 1990), crc_text), (dict(crc=q + 2600), None), (dict(crc=q + 2598), crc_text), (dict(crc=0), None)):
+        a = dict(dict(payload=q + 1000, pitch=8, out=q + 2000, crc=q + 3000, coding=UNCODED), **kw)
+        host = np.full(4096, GUARD, np.uint8)
+        at = a["payload"] - q
+        for i in range(6):
+            host[at + 8 * i:at + 8 * i + 5] = payloads[i]
+        out.copy_(torch.from_numpy(host))
+        rc = call(**a)
+        if text:
+            assert rc == QPSK_ERR_ARG and b"qpsk_frame_batch: " + text in m.L.qpsk_last_error(), (kw, rc, m.L.qpsk_last_error())
+            continue
+        assert rc == 0, (kw, m.L.qpsk_last_error())
+        m.sync()
+        host = out.cpu().numpy()
+        assert np.array_equal(host[a["out"] - q:a["out"] - q + 600].reshape(2, 300), want), kw
+        assert not a["crc"] or np.array_equal(host[a["crc"] - q:a["crc"] - q + 12].view(np.uint16), want_crc), kw
+        assert all(np.array_equal(host[at + 8 * i:at + 8 * i + 5], payloads[i]) for i in range(6)), kw
 
 
 def test_a_framer_call_disturbs_neither_a_deframer_nor_the_receive_streams_nor_the_scrambler(m):

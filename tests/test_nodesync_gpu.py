@@ -271,3 +271,44 @@ def test_refusals_launch_nothing_and_leave_the_state_as_it_was():
     assert got["info"][:, 1].tolist() == [2, 0, 1]                # -1 = 2^32 - 1 = 0 mod 3, 7 = 1 mod 3
     m.sync()
     m.close()
+
+
+# ------------------------------------------------------------------------------------------ 11. the boundary of the overlap test
+def test_buffers_that_touch_are_accepted_and_a_shared_dibit_is_refused():
+    """2 links of 64 dibits inside one allocation.  The rows of a buffer span 2 ((S - 1) pitch + ntx) bytes: 256 when tight, 272 at pitch 72,
+    and the 16 bytes of padding behind the last row are not the buffer.  Both pointers are 2-byte aligned, so the least two ranges can share
+    is one dibit.  An accepted call's output is the reference's; a refused one leaves the links where they were."""
+    import torch
+    rng = np.random.default_rng(11)
+    S, ntx, pitch = 2, 64, 72
+    soft = random_soft(rng, S, ntx)
+    m = modem()
+    L = m.L
+    kw = dict(nrot=4, nshift=8)
+    m.nodesync_reset(S, **kw)
+    m.nodesync_set(cand_tensor([5, 14]))
+    ref = nodesync_ref(S, **kw)
+    ref.set([5, 14])
+    arena = torch.zeros(2048, dtype=torch.uint8, device="cuda")
+    at = lambda off: C.c_void_p(arena.data_ptr() + off)
+    cases = (      # the input at, its pitch, the output at, its pitch, accepted
+        (512, 0, 768, 0, True), (512, 0, 256, 0, True), (512, 0, 766, 0, False), (512, 0, 258, 0, False),
+        (512, pitch, 784, 0, True), (512, pitch, 782, 0, False), (512, 0, 240, pitch, True), (512, 0, 242, pitch, False))
+    for k, (i0, ip, o0, op, accepted) in enumerate(cases):
+        rows = np.zeros((S, ip or ntx, 2), np.int8)
+        rows[:, :ntx] = soft
+        arena[i0:i0 + rows.size] = torch.from_numpy(rows.view(np.uint8).reshape(-1)).cuda()
+        info = torch.full((S * 8,), POISON, dtype=torch.int32, device="cuda") if k else None      # the first call: no d_info, and never a d_vinfo
+        rc = L.qpsk_nodesync_push(m.h, at(i0), ip, ntx, None, at(o0), op, ptr(info))
+        if not accepted:
+            assert rc == QPSK_ERR_ARG and b"d_soft_out overlaps d_soft_in" in L.qpsk_last_error(), (k, rc, L.qpsk_last_error())
+            continue
+        assert rc == 0, (k, L.qpsk_last_error())
+        torch.cuda.synchronize()
+        h = arena.cpu().numpy()
+        got = dict(soft=np.stack([h[o0 + 2 * s * (op or ntx):][:2 * ntx] for s in range(S)]).reshape(S, ntx, 2).view(np.int8))
+        if info is not None:
+            got["info"] = info.cpu().numpy().reshape(S, 8)
+        same(got, ref.push(soft), cases[k])
+    m.sync()
+    m.close()

@@ -518,6 +518,15 @@ def test_every_argument_error_decided_before_a_device_is_touched(qpsk_lib):
                     (dict(hout=at(buf, 40)), b"d_hist_out overlaps an input"), (dict(hout=at(out, 59)), b"d_hist_out overlaps d_out")):
         refused(il(**k), text)
     refused(il(o=at(buf, 60)), b"null context")               # abutting, not overlapping
+    # the boundary of every pair, a byte on either side: the words are 2 * 5 * 6 = 60 bytes, a history 2 * 2 * 6 = 24
+    for k, text in ((dict(words=at(buf, 59), o=at(buf)), b"d_out overlaps an input"), (dict(hin=at(out, 23), o=at(out, 46)), b"d_out overlaps an input"),
+                    (dict(hout=at(buf, 59)), b"d_hist_out overlaps an input"), (dict(words=at(buf, 23), hout=at(buf)), b"d_hist_out overlaps an input"),
+                    (dict(hin=at(buf, 123), hout=at(buf, 100)), b"d_hist_out overlaps an input"), (dict(o=at(out, 23), hout=at(out)), b"d_hist_out overlaps d_out")):
+        refused(il(**k), text)                                # one shared byte
+    for k in (dict(words=at(buf, 60), o=at(buf)), dict(hin=at(out, 60)), dict(hin=at(out, 22), o=at(out, 46)), dict(hout=at(buf, 60)),
+              dict(words=at(buf, 24), hout=at(buf)), dict(hin=at(buf, 100), hout=at(buf, 124)), dict(hin=at(buf, 124), hout=at(buf, 100)),
+              dict(hout=at(out, 60)), dict(o=at(out, 24), hout=at(out)), dict(hin=at(buf, 100)), dict(hout=at(buf, 100))):
+        refused(il(**k), b"null context")                     # touching on either side; one history without the other
 
 
 # ------------------------------------------------------------------- 2. the interleaver is Forney's

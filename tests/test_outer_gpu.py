@@ -313,6 +313,63 @@ def test_refused_calls_launch_nothing_and_leave_the_state_untouched():
     m.close()
 
 
+def test_push_buffers_that_touch_are_accepted_and_the_least_shared_bytes_are_refused():
+    """2 streams, n = 4, 64 bits a push, four slots, all six buffers inside one allocation.  Every pair of them, one of the two moved so
+    that it ends where the other begins and begins where the other ends (accepted, and the push is the restatement's), then one step of
+    its alignment further in (refused: "<the later argument> overlaps <the earlier>"); the link goes on behind the refusals"""
+    import torch
+    from test_outer_cpu import LEADS, streams_of
+    S, n, nbits, mw = 2, 4, 64, 4
+    bits = streams_of(np.random.default_rng(64), n, 2, 70, ("clean", "delete"), leads=LEADS[:2])[0]
+    assert bits.shape[0] == S and bits.shape[1] >= 31 * nbits
+    m = modem()
+    m.outer_reset(S, n, 2, 0x47, 2, 2)
+    ref = outer_ref(S, n, 2, 0x47, 2, 2)
+    assert m.outer_max_words(nbits) == mw
+    names = ("d_bits", "d_count", "d_words", "d_pos", "d_flags", "d_info")
+    size = dict(d_bits=S * 8, d_count=S * 4, d_words=S * mw * n, d_pos=S * mw * 8, d_flags=S * mw, d_info=S * 16)
+    align = dict(d_bits=1, d_count=4, d_words=1, d_pos=8, d_flags=1, d_info=4)
+    home = {name: 256 * (i + 1) for i, name in enumerate(names)}
+    arena = torch.zeros(2048, dtype=torch.uint8, device="cuda")
+    pushes = 0
+
+    def push_at(where):
+        nonlocal pushes
+        chunk = bits[:, pushes * nbits:(pushes + 1) * nbits]
+        host = np.full(2048, 0x55, np.uint8)
+        host[where["d_bits"]:where["d_bits"] + S * 8] = pack_bits(chunk).reshape(-1)
+        arena.copy_(torch.from_numpy(host))
+        p = {k: C.c_void_p(arena.data_ptr() + v) for k, v in where.items()}
+        rc = m.L.qpsk_outer_push(m.h, p["d_bits"], 0, nbits, mw, p["d_count"], p["d_words"], 0, p["d_pos"], p["d_flags"], p["d_info"])
+        torch.cuda.synchronize()
+        if rc:
+            return rc
+        pushes += 1
+        host = arena.cpu().numpy()
+        cut = lambda name, dtype, shape: host[where[name]:where[name] + size[name]].view(dtype).reshape(shape)      # noqa: E731
+        count = cut("d_count", np.int32, (S,))
+        kept = np.minimum(count, mw)
+        got = dict(count=count, max_words=mw, info=cut("d_info", np.int32, (S, 4)), words=[cut("d_words", np.uint8, (S, mw, n))[i, :kept[i]] for i in range(S)],
+                   pos=[cut("d_pos", np.int64, (S, mw))[i, :kept[i]] for i in range(S)], flags=[cut("d_flags", np.uint8, (S, mw))[i, :kept[i]] for i in range(S)])
+        same(got, ref.push(chunk), where)
+        return 0
+
+    assert push_at(home) == 0
+    for j, later in enumerate(names):
+        for earlier in names[:j]:
+            mover, fixed = (later, earlier) if align[later] <= align[earlier] else (earlier, later)
+            lo, hi, step = home[fixed] - size[mover], home[fixed] + size[fixed], align[mover]
+            for off, accepted in ((lo, True), (hi, True), (lo + step, False), (hi - step, False)):
+                rc = push_at({**home, mover: off})
+                if accepted:
+                    assert rc == 0, (later, earlier, off, m.L.qpsk_last_error())
+                else:
+                    assert rc == QPSK_ERR_ARG and ("qpsk_outer_push: %s overlaps %s" % (later, earlier)).encode() in m.L.qpsk_last_error(), (later, earlier, off)
+    assert pushes == 31
+    m.sync()
+    m.close()
+
+
 def test_a_reset_over_an_armed_link_replaces_it():
     bits, other = replaced_link_inputs()
     S, N = bits.shape

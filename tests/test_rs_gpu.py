@@ -273,6 +273,77 @@ def test_every_bad_argument_is_refused_with_nothing_written_and_the_context_stay
     m.close()
 
 
+def test_buffers_that_touch_are_accepted_and_one_shared_byte_is_refused():
+    """3 rows of (15, 11) inside one allocation, tight (45 bytes) or at pitch 20 (2 * 20 + 15 = 55 bytes: the padding behind the last row is
+    not the buffer).  Every pair of ranges the two calls compare, with the later one beginning at the byte behind the earlier one's last
+    (accepted, and the call's results are the reference's) and on that last byte (refused, with the present text)"""
+    import torch
+    rng = np.random.default_rng(15)
+    R, n, nroots, pitch = 3, 15, 4, 20
+    k = n - nroots
+    sent = rs_encode_ref(rng.integers(0, 256, (R, k), dtype=np.uint8), nroots)
+    words, flags = sent.copy(), np.zeros((R, n), np.uint8)
+    words[1, 2] ^= 0x40
+    words[1, 9] ^= 0x01
+    words[2, 0] ^= 0xFF
+    words[2, 7] ^= 0x10
+    flags[2, 0] = flags[2, 7] = 1
+    wants = {True: rs_decode_ref(words, nroots, flags), False: rs_decode_ref(words, nroots, None)}
+    assert all(np.array_equal(w[0], sent) for w in wants.values()) and wants[True][1][1:, 0].all()
+    m = modem()
+    L, h = m.L, m.h
+    arena = torch.zeros(1024, dtype=torch.uint8, device="cuda")
+    at = lambda off: None if off is None else C.c_void_p(arena.data_ptr() + off)      # noqa: E731
+
+    def put(off, rows, p):
+        for r in range(R):
+            arena[off + r * p:off + r * p + rows.shape[1]] = torch.from_numpy(rows[r].copy()).cuda()
+
+    def get(off, w, p):
+        host = arena.cpu().numpy()
+        return np.stack([host[off + r * p:off + r * p + w] for r in range(R)])
+
+    def dec(i=400, ip=0, e=None, o=800, op=0, f=900):
+        arena.zero_()
+        put(i, words, ip or n)
+        if e is not None:
+            put(e, flags, n)
+        rc = L.qpsk_rs_decode_batch(h, at(i), ip, R, n, nroots, at(e), at(o), op, at(f))
+        torch.cuda.synchronize()
+        return rc
+
+    accepted = (dict(o=445, f=352), dict(i=403, o=358, f=448), dict(ip=20, o=455), dict(ip=20, o=345, op=20), dict(o=500, e=545), dict(o=500, e=455),
+                dict(e=603, f=648), dict(e=600, f=552), dict(o=603, f=648), dict(o=600, f=552), dict(o=400), dict(ip=20, o=400, op=20),
+                dict(o=None), dict(f=None), dict(e=200, f=None))
+    for kw in accepted:
+        assert dec(**kw) == 0, (kw, L.qpsk_last_error())
+        want_out, want_info = wants[kw.get("e") is not None]
+        if kw.get("o", 800) is not None:
+            assert np.array_equal(get(kw.get("o", 800), n, kw.get("op", 0) or n), want_out), kw
+        if kw.get("f", 900) is not None:
+            assert np.array_equal(get(kw.get("f", 900), 16, 16).view(np.int32), want_info), kw
+    io, oe, info = b"d_out overlaps d_in", b"d_out overlaps d_erase", b"d_info is not 4-byte aligned, or overlaps d_in, d_out or d_erase"
+    refused = ((dict(o=444), io), (dict(i=403, o=359), io), (dict(ip=20, o=454), io), (dict(ip=20, o=346, op=20), io), (dict(o=400, op=20), io),
+               (dict(o=500, e=544), oe), (dict(o=500, e=456), oe), (dict(e=604, f=648), info), (dict(e=599, f=552), info),
+               (dict(o=604, f=648), info), (dict(o=599, f=552), info), (dict(i=404, f=448), info), (dict(i=399, f=352), info))
+    for kw, text in refused:
+        assert dec(**kw) == QPSK_ERR_ARG and b"qpsk_rs_decode_batch: " + text in L.qpsk_last_error(), (kw, L.qpsk_last_error())
+
+    def enc(i=400, ip=0, o=800, op=0):
+        arena.zero_()
+        put(i, sent[:, :k], ip or k)
+        rc = L.qpsk_rs_encode_batch(h, at(i), ip, R, k, nroots, at(o), op)
+        torch.cuda.synchronize()
+        return rc
+    for kw in (dict(o=433), dict(i=445, o=400), dict(ip=20, o=451), dict(i=455, o=400, op=20)):      # the data are 33 bytes, or 2 * 20 + 11 = 51
+        assert enc(**kw) == 0, (kw, L.qpsk_last_error())
+        assert np.array_equal(get(kw["o"], n, kw.get("op", 0) or n), sent), kw
+    for kw in (dict(o=432), dict(i=444, o=400), dict(ip=20, o=450), dict(i=454, o=400, op=20)):
+        assert enc(**kw) == QPSK_ERR_ARG and b"qpsk_rs_encode_batch: d_out overlaps d_data" in L.qpsk_last_error(), (kw, L.qpsk_last_error())
+    m.sync()
+    m.close()
+
+
 # ------------------------------------------------------------------------------------------ 6. the link of the CPU test, on the device
 def test_the_cpu_link_on_the_device_with_the_deframer_s_bytes_decoded_where_they_lie():
     """Modem.rs_encode -> Modem.frame -> the CPU test's inverted run -> Modem.deframe_coded, then qpsk_rs_decode_batch straight on the

@@ -260,6 +260,22 @@ def test_sync_argument_errors():
                  (p(buf), 100, sw, 8, 0, 10, 10, C.c_void_p(buf.data_ptr() + 399), p(lag))]:
         assert call(*args) == QPSK_ERR_ARG, args
     assert call(p(data), 100, sw, 8, 0, 82, 10, p(buf), p(lag)) == 0      # lag_max + nsync + nout == nsym
+    assert call(p(data), 100, sw, 8, 0, 10, 0, C.c_void_p(data.data_ptr() + 50), p(lag)) == 0      # nout = 0: d_out is not looked at
+    # the 400 bytes of data and the 40 of d_out inside one allocation: touching on either side (accepted, the reference's output), one byte shared
+    rows, word, _, _ = planted(4, 100, 8, np.random.default_rng(5), 0, 10)
+    want = sync_ref(rows, word, 0, 10, 10)
+    arena, d_word = torch.zeros(1024, dtype=torch.uint8, device="cuda"), (C.c_uint8 * 8)(*word.tolist())
+    for off, accepted in ((500, True), (60, True), (499, False), (61, False)):
+        arena.zero_()
+        arena[100:500] = torch.from_numpy(rows.reshape(-1)).cuda()
+        rc = call(C.c_void_p(arena.data_ptr() + 100), 100, d_word, 8, 0, 10, 10, C.c_void_p(arena.data_ptr() + off), p(lag))
+        if not accepted:
+            assert rc == QPSK_ERR_ARG and b"qpsk_sync_batch: d_out overlaps d_data" in m.L.qpsk_last_error(), (off, rc)
+            continue
+        assert rc == 0, (off, m.L.qpsk_last_error())
+        m.sync()
+        assert bits_equal(arena[off:off + 40].cpu().numpy().reshape(4, 10), want["out"]) and bits_equal(lag.cpu().numpy(), want["lag"])
+        assert np.array_equal(arena[100:500].cpu().numpy(), rows.reshape(-1))
     m.sync()
     m.close()
 

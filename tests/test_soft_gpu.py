@@ -296,6 +296,33 @@ def test_argument_errors_launch_nothing():
     m.close()
 
 
+def test_a_soft_output_that_touches_the_input_is_accepted_and_a_shared_pair_is_refused():
+    """2 rows of 16 symbols at pitch 20 inside one allocation: the input spans 8 (20 + 16) = 288 bytes -- the 32 bytes of padding behind the
+    last row are not the buffer -- and d_soft 64.  d_soft is 2-byte aligned, so the least the two can share is one int8 pair.  An empty
+    d_soft (nout = 0) that points inside the input is refused as it always was; on either end of it, it is accepted"""
+    import torch
+    m = modem()
+    R, N, P = 2, 16, 20
+    z = random_rows(R, N, 77)
+    want = soft_ref(z, first=0, nout=N)
+    arena = torch.zeros(1024, dtype=torch.uint8, device="cuda")
+    at = lambda off: C.c_void_p(arena.data_ptr() + off)      # noqa: E731
+    rows = np.zeros((R, P, 2), np.float32)
+    rows[:, :N] = z
+    for off, nout, accepted in ((544, N, True), (192, N, True), (542, N, False), (194, N, False), (256, 0, True), (544, 0, True), (300, 0, False)):
+        arena.zero_()
+        arena[256:256 + rows.nbytes] = torch.from_numpy(rows.view(np.uint8).reshape(-1)).cuda()
+        rc = raw(m, at(256), P, R, N, 0, 0, 64.0, None, None, None, 0, nout, at(off), None, None)
+        if not accepted:
+            assert rc == QPSK_ERR_ARG and b"qpsk_soft_batch: d_soft overlaps d_costas" in m.L.qpsk_last_error(), (off, nout, rc)
+            continue
+        assert rc == 0, (off, nout, m.L.qpsk_last_error())
+        m.sync()
+        if nout:
+            assert np.array_equal(arena[off:off + 2 * R * N].cpu().numpy().view(np.int8).reshape(R, N, 2), want["soft"]), off
+    m.close()
+
+
 @pytest.mark.parametrize("N", [600, ONE_PASS_MAX + 600])
 def test_bad_device_lag_gives_zeros_for_that_row_only(N):
     import qpsk_amd

@@ -363,5 +363,20 @@ def test_loopback_through_the_stream_encoder_in_three_chunks(name):
     assert m.L.qpsk_conv_encode_stream_batch(m.h, ptr(b), S, 10, 7, 0x51, 0x2F, None, None, ptr(o)) == QPSK_ERR_ARG
     assert m.L.qpsk_conv_encode_stream_batch(m.h, ptr(b), S, 2, 2, 0x1, 0x3, None, None, ptr(o)) == QPSK_ERR_ARG
     assert m.L.qpsk_conv_encode_stream_batch(m.h, ptr(b), S, 8, 1, 1, 1, ptr(st), ptr(st), ptr(o)) == QPSK_ERR_ARG
+    # the two states inside one allocation: S bytes each, touching on either side (accepted, the row encoded as ever), one byte shared (refused)
+    part, before = pack_bits(data[:, :chunk]), np.array([5, 63, 0, 17], np.uint8)
+    want_dibits, want_state = conv_encode_stream_ref(part, chunk, pattern, before)
+    d_part, both = torch.from_numpy(part).cuda(), torch.zeros(2 * S, dtype=torch.uint8, device="cuda")
+    for i0, o0, accepted in ((0, S, True), (S, 0, True), (0, S - 1, False), (S - 1, 0, False)):
+        both.zero_()
+        both[i0:i0 + S] = torch.from_numpy(before).cuda()
+        rc = m.L.qpsk_conv_encode_stream_batch(m.h, ptr(d_part), S, chunk, *pattern, C.c_void_p(both.data_ptr() + i0), C.c_void_p(both.data_ptr() + o0), ptr(o))
+        if not accepted:
+            assert rc == QPSK_ERR_ARG and b"d_state_out overlaps d_state_in" in m.L.qpsk_last_error(), (i0, o0, rc)
+            continue
+        assert rc == 0, (i0, o0, m.L.qpsk_last_error())
+        m.sync()
+        assert np.array_equal(o.reshape(-1)[:want_dibits.size].cpu().numpy().reshape(want_dibits.shape), want_dibits)
+        assert np.array_equal(both[o0:o0 + S].cpu().numpy(), want_state) and np.array_equal(both[i0:i0 + S].cpu().numpy(), before)
     m.sync()
     m.close()
