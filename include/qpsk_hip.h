@@ -882,6 +882,51 @@ int qpsk_dispersal_batch(qpsk_ctx *ctx, const uint8_t *d_in, long long in_pitch,
 int qpsk_dispersal_sequence(int len, int group, int flags, uint8_t *out);
 
 /* -------------------------------------------------------------------------
+ * CHANNELISER: a critically sampled polyphase analysis filter bank, the stage in front of qpsk_streams_rx_cplx -- one wideband complex
+ * capture that carries M carriers side by side comes out as M channel rows, each at 1 / M of the wideband rate, laid out as that call takes
+ * them.  State (the filter's history) is carried from push to push.  The library's own definition, every operation in fp32 and in a stated
+ * order (the reference has no channeliser; parity unpinned), restated in numpy by tests/test_channel_cpu.py (channel_ref)
+ * and compared with the kernel bit for bit.  There is no tolerance anywhere.
+ *
+ * M   channels, a power of two, 2 <= M <= 4096.   P   taps per branch, 1 <= P <= 32.
+ * h[0 .. M P)   the caller's real prototype low-pass, finite floats (the library designs no filter).
+ * s   the history followed by the pushed samples; the history is (P - 1) M samples, all zero after a reset.  block(b) = s[b M .. b M + M).
+ *   Output time m of a push is the block that holds the push's samples [m M, m M + M); block(m - q) is the block q blocks before it.
+ * BRANCH SUMS, p = 0 .. M - 1, real and imaginary part separately, fp32, no contraction:
+ *       u_m[p] = sum_{q = 0}^{P - 1} h[q M + p] block(m - q)[M - 1 - p]
+ *   acc = fl(h[p] x_0), then acc = acc + fl(h[q M + p] x_q) for q = 1 .. P - 1 in that order.
+ * TRANSFORM, fp32: the butterfly network of the library's radix-2 transform with the inverse sign.  v = u_m in bit-reversed order
+ *   (v[bitrev(p)] = u_m[p]); then stages s = 1 .. log2 M, half = 2^(s - 1): for every lo whose bit s - 1 is clear, k = lo mod half,
+ *   hi = lo + half, e = v[lo], o = v[hi], w = tw[k (M >> s)]:
+ *       z = (w.re o.re - w.im o.im, w.re o.im + w.im o.re),   v[lo] = e + z,   v[hi] = e - z
+ *   tw[j] = ((float)cos(TAU j / M), (float)sin(TAU j / M)), j < M / 2, computed in double with libm on the host, TAU = 2 * 3.14159265358979323846
+ *   (qpsk_channel_twiddles writes the table: it is part of the definition).  No scaling.
+ *       y_k[m] = v[k] is channel k: the band centred at +k / M cycles per wideband sample (k > M / 2: at k / M - 1), with the gain
+ *       sum h at its centre, up to a fixed rotation per channel that the Costas loop absorbs.
+ *   The kernel keeps two stages in registers per pass; it performs exactly these operations on these operands.
+ * OUTPUT.  d_out[i][m] = y_{chan[i]}[m], rows out_pitch complex samples apart (0 = tight, T), the unit of frame_pitch.
+ * NaN, Inf.  A non-finite sample propagates as IEEE arithmetic says (0 * Inf = NaN included, -0.0 as the operations give it); the call
+ *   raises no status -- the stream call behind it has the fence.
+ * HISTORY.  After a push the history is the last (P - 1) M samples of s: a push of T < P - 1 blocks shifts the old history.
+ *
+ *   qpsk_channel_twiddles  host only, no context: tw[M / 2][2] into h_tw.  QPSK_ERR_ARG for an M outside M's rule or a NULL h_tw
+ *   qpsk_channel_reset     (M, P, h_proto [M P]); h_chan [nsel] host channel numbers in [0, M), any order, repeats allowed,
+ *                1 <= nsel <= 65536; NULL = all M channels in order (nsel is then not looked at).  Copies both, zeroes the history,
+ *                replaces a channeliser the context has (behind a synchronisation of the context's stream); a refused reset leaves it
+ *   qpsk_channel_push      d_x [T M][2] -> d_out [nsel] rows of [T][2].  T >= 1, T M <= 2^30; out_pitch 0 or >= T; d_out must not
+ *                overlap d_x.  QPSK_ERR_STATE before a reset
+ * QPSK_ERR_ARG at the call for a bad argument -- a non-finite tap among them -- nothing launched.  A push is stream-ordered on the
+ * context's stream and touches neither the receive streams, the deframers, the histogram mode's guess, the Viterbi scratch, the outer link
+ * nor the node sync.  qpsk_ctx_last_kernel() names channel_push_kernel (channel_history_kernel, the launch behind it, moves the history
+ * into the second of two buffers, so that no launch reads what it writes).
+ * Not built: the synthesis (transmit) bank; oversampled banks; M that is no power of two; PCM or int16 wideband input; qpsk_multi; routing
+ * inside bench.py.  Usage: INTEGRATION.md 2.0.
+ * ------------------------------------------------------------------------- */
+int qpsk_channel_twiddles(int M, float *h_tw);
+int qpsk_channel_reset(qpsk_ctx *ctx, int M, int P, const float *h_proto, const int32_t *h_chan, int nsel);
+int qpsk_channel_push(qpsk_ctx *ctx, const float *d_x, int T, float *d_out, long long out_pitch);
+
+/* -------------------------------------------------------------------------
  * NODE SYNC: what stands between qpsk_soft_batch and VITERBI STREAM on a continuously coded link -- the quarter turn the Costas loop may
  * have locked on and the phase of the puncturing pattern are unknown, and a loop that slips changes both mid-stream.  Per link a CANDIDATE
  * (quarter turn r, delay h in dibits) is applied to the soft rows, and a MONITOR judges it by the error count the stream decoder reported for

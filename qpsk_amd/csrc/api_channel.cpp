@@ -1,0 +1,127 @@
+/*
+ * api_channel.cpp -- the polyphase channeliser in the C ABI (CHANNELISER in include/qpsk_hip.h; kernels: channel.hip): the stage in front of
+ * qpsk_streams_rx_cplx, one wideband capture into the rows that call takes.  Owns qpsk_ctx::channel and nothing else.
+ */
+#include "api_ctx.h"
+
+using namespace qpsk;
+
+/* no channeliser (qpsk_ctx_destroy): behind a synchronisation of the context's stream */
+void Channeliser::release()
+{
+    hipFree(state);
+    *this = Channeliser();
+}
+
+static int channel_log2(int M)
+{
+    if (M < 2 || M > CHANNEL_MAX_M || (M & (M - 1))) return -1;
+    int l = 0;
+    while ((1 << l) < M) l++;
+    return l;
+}
+
+/* tw[j] = ((float)cos(TAU j / M), (float)sin(TAU j / M)), j < M / 2: fft_lds.h's table rounded to fp32 */
+static void channel_twiddles(int M, float *tw)
+{
+    const double tau = 2.0 * 3.14159265358979323846;
+    for (int j = 0; j < M / 2; j++) {
+        tw[2 * j] = (float)cos(tau * (double)j / (double)M);
+        tw[2 * j + 1] = (float)sin(tau * (double)j / (double)M);
+    }
+}
+
+int qpsk_channel_twiddles(int M, float *h_tw)
+{
+    static const char *const who = "qpsk_channel_twiddles";
+    if (channel_log2(M) < 0) return fail(QPSK_ERR_ARG, "%s: M = %d is no power of two in 2..%d", who, M, CHANNEL_MAX_M);
+    if (!h_tw) return fail(QPSK_ERR_ARG, "%s: null h_tw", who);
+    channel_twiddles(M, h_tw);
+    return QPSK_OK;
+}
+
+int qpsk_channel_reset(qpsk_ctx *c, int M, int P, const float *h_proto, const int32_t *h_chan, int nsel)
+{
+    static const char *const who = "qpsk_channel_reset";
+    /* what the arguments alone decide comes first: it needs neither a context nor a device */
+    if (channel_log2(M) < 0) return fail(QPSK_ERR_ARG, "%s: M = %d is no power of two in 2..%d", who, M, CHANNEL_MAX_M);
+    if (P < 1 || P > CHANNEL_MAX_P) return fail(QPSK_ERR_ARG, "%s: P = %d outside 1..%d", who, P, CHANNEL_MAX_P);
+    if (!h_proto) return fail(QPSK_ERR_ARG, "%s: null h_proto", who);
+    for (int r = 0; r < M * P; r++)
+        if (!isfinite(h_proto[r])) return fail(QPSK_ERR_ARG, "%s: h_proto[%d] is not finite", who, r);
+    if (!h_chan) nsel = M;
+    if (nsel < 1 || nsel > CHANNEL_MAX_SEL) return fail(QPSK_ERR_ARG, "%s: nsel = %d outside 1..%d", who, nsel, CHANNEL_MAX_SEL);
+    std::vector<int32_t> chan((size_t)nsel);
+    for (int i = 0; i < nsel; i++) {
+        chan[i] = h_chan ? h_chan[i] : i;
+        if (chan[i] < 0 || chan[i] >= M) return fail(QPSK_ERR_ARG, "%s: h_chan[%d] = %d outside 0..M - 1 = %d", who, i, (int)chan[i], M - 1);
+    }
+    if (!c) return fail(QPSK_ERR_ARG, "%s: null context", who);
+    if (bind(c)) return QPSK_ERR_HIP;
+    /* one allocation: proto [P M] floats, tw [M / 2][2], the two histories [(P - 1) M][2] each, chan [nsel].  Allocated FIRST, so that a
+     * failure leaves the channeliser the context has as it was */
+    const size_t nproto = (size_t)M * P, nhist = (size_t)M * (P - 1);
+    const size_t floats = nproto + (size_t)M + 4 * nhist;
+    uint8_t *state = nullptr;
+    if (hipMalloc((void **)&state, floats * sizeof(float) + (size_t)nsel * sizeof(int32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(QPSK_ERR_ALLOC, "%s: hipMalloc of the state (M = %d, P = %d, nsel = %d)", who, M, P, nsel);
+    }
+    std::vector<float> head(nproto + (size_t)M);
+    memcpy(head.data(), h_proto, nproto * sizeof(float));
+    channel_twiddles(M, head.data() + nproto);
+    float *f = reinterpret_cast<float *>(state);
+    hipError_t e = hipStreamSynchronize(c->stream);      /* pushes on the old state may still run */
+    if (e == hipSuccess) e = hipMemcpy(f, head.data(), head.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && nhist) e = hipMemset(f + head.size(), 0, 4 * nhist * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(f + floats, chan.data(), chan.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(state);
+        return fail(QPSK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    Channeliser &ch = c->channel;
+    ch.release();
+    ch.state = state;
+    ch.M = M;
+    ch.P = P;
+    ch.nsel = nsel;
+    ch.proto = f;
+    ch.tw = f + nproto;
+    ch.hist[0] = nhist ? f + head.size() : nullptr;
+    ch.hist[1] = nhist ? f + head.size() + 2 * nhist : nullptr;
+    ch.chan = reinterpret_cast<int32_t *>(f + floats);
+    ch.cur = 0;
+    ch.ready = true;
+    return QPSK_OK;
+}
+
+int qpsk_channel_push(qpsk_ctx *c, const float *d_x, int T, float *d_out, long long out_pitch)
+{
+    static const char *const who = "qpsk_channel_push";
+    if (!d_x || !d_out) return fail(QPSK_ERR_ARG, "%s: null d_x or d_out", who);
+    if (T < 1) return fail(QPSK_ERR_ARG, "%s: T = %d", who, T);
+    size_t op = 0;
+    if (!pitch_ok(out_pitch, T, LLONG_MAX >> 4, &op)) return fail(QPSK_ERR_ARG, "%s: out_pitch = %lld (0, or >= T = %d)", who, out_pitch, T);
+    if (!c) return fail(QPSK_ERR_ARG, "%s: null context", who);
+    Channeliser &ch = c->channel;
+    if (!ch.ready) return fail(QPSK_ERR_STATE, "%s: no channeliser (qpsk_channel_reset first; a failed push ends it)", who);
+    if ((long long)T * ch.M > CHANNEL_MAX_SAMPLES)
+        return fail(QPSK_ERR_ARG, "%s: T M = %lld samples in one push, more than %lld", who, (long long)T * ch.M, CHANNEL_MAX_SAMPLES);
+    if (op > SIZE_MAX / 16 / (size_t)ch.nsel) return fail(QPSK_ERR_ARG, "%s: the output leaves the address space", who);
+    const size_t xn = (size_t)T * ch.M, cplx = 2 * sizeof(float);
+    const Span in = {d_x, xn * cplx, "d_x"}, out = {d_out, rows_extent(ch.nsel, op * cplx, (long long)T * (long long)cplx), "d_out"};
+    if (overlap(out, in)) return fail(QPSK_ERR_ARG, "%s: d_out overlaps d_x", who);
+    if (bind(c)) return QPSK_ERR_HIP;
+    const float2 *x = reinterpret_cast<const float2 *>(d_x);
+    const float2 *hist = reinterpret_cast<const float2 *>(ch.hist[ch.cur]);
+    ch.ready = false;      /* until both launches are in the queue */
+    KERNEL_TRY(launch_channel_push(x, T, ch.M, ch.P, ch.proto, reinterpret_cast<const float2 *>(ch.tw), hist, ch.chan, ch.nsel,
+                                   reinterpret_cast<float2 *>(d_out), op, c->stream));
+    c->last_kernel = "channel_push_kernel";
+    if (ch.P > 1) {
+        KERNEL_TRY(launch_channel_history(hist, x, (size_t)ch.M * (ch.P - 1), xn, reinterpret_cast<float2 *>(ch.hist[ch.cur ^ 1]), c->stream));
+        ch.cur ^= 1;
+    }
+    ch.ready = true;
+    return QPSK_OK;
+}

@@ -202,6 +202,7 @@ int qpsk_ctx_create(qpsk_ctx **out, int device, const qpsk_params *p, void *stre
     KERNEL_TRY(prepare_stream_block());
     KERNEL_TRY(prepare_stream_scan());
     KERNEL_TRY(prepare_carrier_est());
+    KERNEL_TRY(prepare_channel());
     qpsk_ctx *c = new qpsk_ctx();
     c->device = device;
     for (const auto &k : TUNING_KEYS) {   /* the only place the environment is read */
@@ -276,6 +277,7 @@ void qpsk_ctx_destroy(qpsk_ctx *c)
     c->outer.release();
     c->nodesync.release();
     c->dispersal.release();
+    c->channel.release();
     delete c;
 }
 

@@ -13,6 +13,7 @@
  *   api_dispersal.cpp DVB's energy dispersal behind the Reed-Solomon decoder
  *   api_nodesync.cpp the node sync in front of it: the candidate transform and the monitor on the decoder's error count
  *   api_cross.cpp    the packet erasure code: Reed-Solomon across the packets of a group, and the place call in front of it
+ *   api_channel.cpp  the polyphase channeliser in front of the streams: one wideband capture into stream rows
  *
  * OWNERSHIP: each nested group of qpsk_ctx below names the one unit that reads and writes it; the members outside a group
  * (configuration, scratch buffers) are every unit's.  DESIGN.md, "The host layer", lists the few places that reach across.
@@ -268,6 +269,19 @@ struct QPSK_UNIT_LOCAL Dispersal {
     void release();               /* leaves the group value-initialised: no table.  Behind a synchronisation of the context's stream */
 };
 
+/* api_channel.cpp.  The polyphase channeliser (qpsk_channel_*): one allocation (`state`) that holds the prototype, the transform's table, the
+ * selection and TWO histories of (P - 1) M samples -- a push reads hist[cur] and leaves the next history in the other, so no launch reads what
+ * it writes */
+struct QPSK_UNIT_LOCAL Channeliser {
+    uint8_t *state = nullptr;
+    int M = 0, P = 0, nsel = 0;
+    float *proto = nullptr, *tw = nullptr, *hist[2] = {nullptr, nullptr};      /* into state; hist: NULL at P = 1 */
+    int32_t *chan = nullptr;
+    int cur = 0;
+    bool ready = false;           /* a reset has completed and no push has failed since */
+    void release();               /* leaves the group value-initialised: no channeliser.  Behind a synchronisation of the context's stream */
+};
+
 } // namespace qpsk
 
 struct qpsk_ctx {
@@ -308,6 +322,7 @@ struct qpsk_ctx {
     qpsk::OuterLink outer;
     qpsk::NodeSync nodesync;
     qpsk::Dispersal dispersal;
+    qpsk::Channeliser channel;
 };
 
 namespace qpsk {

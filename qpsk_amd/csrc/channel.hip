@@ -1,0 +1,241 @@
+/*
+ * channel.hip -- the polyphase channeliser (CHANNELISER in include/qpsk_hip.h, restated in numpy by tests/test_channel_cpu.py): one wideband
+ * complex stream in, M channel rows out, as qpsk_streams_rx_cplx takes them.  s = the history ((P - 1) M samples) followed by the push.
+ *
+ * channel_push_kernel<PT, NT>: a workgroup of NT threads takes a tile of TB consecutive output times (TB = channel_tile(M), kernels.h) and
+ * runs three phases over one LDS image of TB rows of M complex values:
+ *   1. branch sums.  The NT threads are G = NT / min(M, NT) groups of min(M, NT) lanes; a group takes R = TB / G consecutive times, a lane
+ *      the branches p = lane, lane + NT, ...  Lanes adjacent in p read adjacent samples (reversed), and adjacent taps.  PT = P > 0: the
+ *      lane keeps the P taps and the last P - 1 samples of its branch in registers and loads one new sample per time (a run re-reads
+ *      (R + P - 1) / R of its input); PT = 0, any P: every product loads its tap and its sample, nothing is kept.  u_m[p] goes to
+ *      row m, element bitrev(p).
+ *   2. the transform: fft_lds.h's butterflies, inverse sign, fp32.  Two stages per pass over the LDS: a thread holds the four values
+ *      i0 + {0, 1, 2, 3} half of stages s and s + 1 and performs the four butterflies of the definition on them, the operands and
+ *      the order of every operation as there; an odd log2 M runs stage 1 alone first.
+ *   3. the transposed store: TB consecutive times of a selected channel are 8 TB contiguous bytes of its row.
+ * Element e of a row lies at e + (e >> 5), rows M + (M >> 5) + 1 elements apart: the strided accesses of the early stages and of the store's
+ * column reads spread over the banks.  Times at or beyond T are computed on the push's last block and not stored; no address outside the
+ * buffers is formed for them.
+ *
+ * channel_history_kernel: the last (P - 1) M samples of s into the OTHER history buffer (the host swaps the two), so that no launch reads
+ * what it writes, and a push shorter than the history shifts it.
+ */
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kernels.h"
+
+namespace qpsk {
+
+namespace {
+
+struct ChannelArgs {
+    const float2 *x;          /* [T M] */
+    const float2 *hist;       /* [(P - 1) M]: the blocks -(P - 1) .. -1 */
+    const float *proto;       /* [P M] */
+    const float2 *tw;         /* [M / 2] */
+    const int32_t *chan;      /* [nsel] */
+    float2 *out;              /* [nsel] rows, pitch elements apart */
+    size_t pitch;
+    int T, M, log2m, P, nsel;
+    int tb, run, lanes;       /* the tile, R, min(M, NT) */
+};
+
+__device__ __forceinline__ int phys(int e) { return e + (e >> 5); }
+
+/* block bb of the push (negative: of the history), branch p.  No branch, so that a lane's loads go out together: a block at or beyond T
+ * (an output time that is never stored) reads the push's last block instead */
+__device__ __forceinline__ float2 sample(const ChannelArgs &a, long long bb, int p)
+{
+    bb = bb < a.T ? bb : (long long)a.T - 1;
+    const float2 *block = bb >= 0 ? a.x + (size_t)bb * a.M : a.hist + (size_t)(bb + a.P - 1) * a.M;
+    return block[a.M - 1 - p];
+}
+
+__device__ __forceinline__ void butterfly(const float2 w, const float2 e, const float2 o, float2 &lo, float2 &hi)
+{
+    const float zr = w.x * o.x - w.y * o.y;
+    const float zi = w.x * o.y + w.y * o.x;
+    lo = make_float2(e.x + zr, e.y + zi);
+    hi = make_float2(e.x - zr, e.y - zi);
+}
+
+template <int PT, int NT>
+__global__ void __launch_bounds__(NT) channel_push_kernel(ChannelArgs a)
+{
+    extern __shared__ float2 channel_lds[];
+    float2 *v = channel_lds;
+    const int tid = threadIdx.x, M = a.M, log2m = a.log2m;
+    const int row_pitch = M + (M >> 5) + 1;
+    const long long m0 = (long long)blockIdx.x * a.tb;
+    constexpr int RUN_UNROLL = NT == 256 ? 8 : 4;      /* new samples a lane has in flight: a run is 32 times at most at 256 threads, 16 at 1024 */
+
+    /* ---- 1. branch sums */
+    {
+        const int lane = tid & (a.lanes - 1), grp = tid / a.lanes;
+        const int r0 = grp * a.run;
+        for (int p = lane; p < M; p += NT) {
+            const int at = phys((int)(__brev((unsigned)p) >> (32 - log2m)));
+            if constexpr (PT > 0) {
+                float h[PT];
+                float2 w[PT > 1 ? PT - 1 : 1];      /* w[j] = block(m - 1 - j) */
+#pragma unroll
+                for (int q = 0; q < PT; q++) h[q] = a.proto[(size_t)q * M + p];
+#pragma unroll
+                for (int j = 0; j < PT - 1; j++) w[j] = sample(a, m0 + r0 - 1 - j, p);
+#pragma unroll RUN_UNROLL
+                for (int r = r0; r < r0 + a.run; r++) {
+                    const float2 x0 = sample(a, m0 + r, p);
+                    float accr = h[0] * x0.x, acci = h[0] * x0.y;
+#pragma unroll
+                    for (int q = 1; q < PT; q++) {
+                        accr = accr + h[q] * w[q - 1].x;
+                        acci = acci + h[q] * w[q - 1].y;
+                    }
+                    v[r * row_pitch + at] = make_float2(accr, acci);
+#pragma unroll
+                    for (int j = PT - 2; j > 0; j--) w[j] = w[j - 1];
+                    if (PT > 1) w[0] = x0;
+                }
+            } else {
+                for (int r = r0; r < r0 + a.run; r++) {
+                    const float2 x0 = sample(a, m0 + r, p);
+                    const float h0 = a.proto[p];
+                    float accr = h0 * x0.x, acci = h0 * x0.y;
+#pragma unroll 4
+                    for (int q = 1; q < a.P; q++) {
+                        const float2 xq = sample(a, m0 + r - q, p);
+                        const float hq = a.proto[(size_t)q * M + p];
+                        accr = accr + hq * xq.x;
+                        acci = acci + hq * xq.y;
+                    }
+                    v[r * row_pitch + at] = make_float2(accr, acci);
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    /* ---- 2. the transform of every row */
+    int s = 1;
+    if (log2m & 1) {      /* stage 1 alone: half = 1, k = 0 */
+        const float2 w = a.tw[0];
+        const int per_row = M >> 1;
+        for (int item = tid; item < a.tb * per_row; item += NT) {
+            float2 *row = v + (item >> (log2m - 1)) * row_pitch;
+            const int lo = phys(2 * (item & (per_row - 1))), hi = phys(2 * (item & (per_row - 1)) + 1);
+            float2 c0, c1;
+            butterfly(w, row[lo], row[hi], c0, c1);
+            row[lo] = c0;
+            row[hi] = c1;
+        }
+        __syncthreads();
+        s = 2;
+    }
+    for (; s < log2m; s += 2) {      /* stages s and s + 1 */
+        const int half = 1 << (s - 1), per_row = M >> 2;
+        for (int item = tid; item < a.tb * per_row; item += NT) {
+            float2 *row = v + (item >> (log2m - 2)) * row_pitch;
+            const int j = item & (per_row - 1);
+            const int k = j & (half - 1);
+            const int i0 = ((j >> (s - 1)) << (s + 1)) + k;
+            const int e0 = phys(i0), e1 = phys(i0 + half), e2 = phys(i0 + 2 * half), e3 = phys(i0 + 3 * half);
+            const float2 w1 = a.tw[k * (M >> s)];
+            const float2 w2a = a.tw[k * (M >> (s + 1))], w2b = a.tw[(k + half) * (M >> (s + 1))];
+            float2 b0, b1, b2, b3, c0, c1, c2, c3;
+            butterfly(w1, row[e0], row[e1], b0, b1);
+            butterfly(w1, row[e2], row[e3], b2, b3);
+            butterfly(w2a, b0, b2, c0, c2);
+            butterfly(w2b, b1, b3, c1, c3);
+            row[e0] = c0;
+            row[e1] = c1;
+            row[e2] = c2;
+            row[e3] = c3;
+        }
+        __syncthreads();
+    }
+
+    /* ---- 3. the transposed store */
+    {
+        const int log2tb = __ffs(a.tb) - 1;
+        const long long left = (long long)a.T - m0;
+        const int rows = left < a.tb ? (int)left : a.tb;
+        const long long items = (long long)a.nsel << log2tb;
+        for (long long item = tid; item < items; item += NT) {
+            const int r = (int)(item & (a.tb - 1));
+            const long long i = item >> log2tb;
+            if (r < rows) a.out[(size_t)i * a.pitch + (size_t)(m0 + r)] = v[r * row_pitch + phys(a.chan[i])];
+        }
+    }
+}
+
+/* next [n] = the last n = (P - 1) M samples of (hist [n], x [xn]) */
+__global__ void __launch_bounds__(256) channel_history_kernel(const float2 *__restrict__ hist, const float2 *__restrict__ x, size_t n, size_t xn,
+                                                              float2 *__restrict__ next)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const size_t at = i + xn;      /* in s */
+        next[i] = at < n ? hist[at] : x[at - n];
+    }
+}
+
+size_t channel_lds_bytes(int M, int tb) { return (size_t)(M + (M >> 5) + 1) * (size_t)tb * sizeof(float2); }
+
+template <int PT, int NT>
+void launch_push(const ChannelArgs &a, unsigned blocks, hipStream_t s)
+{
+    hipLaunchKernelGGL((channel_push_kernel<PT, NT>), dim3(blocks), dim3(NT), channel_lds_bytes(a.M, a.tb), s, a);
+}
+
+template <int PT, int NT>
+hipError_t prepare_push()
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(channel_push_kernel<PT, NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)channel_lds_bytes(CHANNEL_MAX_M, channel_tile(CHANNEL_MAX_M)));
+}
+
+} // namespace
+
+int prepare_channel()
+{
+    hipError_t e = prepare_push<0, 256>();
+    if (e == hipSuccess) e = prepare_push<8, 256>();
+    if (e == hipSuccess) e = prepare_push<16, 256>();
+    if (e == hipSuccess) e = prepare_push<0, 1024>();
+    if (e == hipSuccess) e = prepare_push<8, 1024>();
+    return (int)e;
+}
+
+int launch_channel_push(const float2 *x, int T, int M, int P, const float *proto, const float2 *tw, const float2 *hist, const int32_t *chan, int nsel,
+                        float2 *out, size_t pitch, hipStream_t s)
+{
+    if (!x || !proto || !tw || !chan || !out || T < 1 || M < 2 || M > CHANNEL_MAX_M || (M & (M - 1)) || P < 1 || P > CHANNEL_MAX_P ||
+        (P > 1 && !hist) || nsel < 1 || pitch < (size_t)T || (long long)T * M > CHANNEL_MAX_SAMPLES)
+        return (int)hipErrorInvalidValue;
+    int log2m = 0;
+    while ((1 << log2m) < M) log2m++;
+    const int tb = channel_tile(M), nt = channel_threads(M);
+    const int lanes = M < nt ? M : nt, run = tb / (nt / lanes);
+    if (run < 1 || channel_lds_bytes(M, tb) > (size_t)MAX_LDS_BYTES) return (int)hipErrorInvalidValue;
+    const ChannelArgs a = {x, hist, proto, tw, chan, out, pitch, T, M, log2m, P, nsel, tb, run, lanes};
+    const unsigned blocks = (unsigned)(((long long)T + tb - 1) / tb);
+    if (nt == 256) {
+        if (P == 8) launch_push<8, 256>(a, blocks, s);
+        else if (P == 16) launch_push<16, 256>(a, blocks, s);
+        else launch_push<0, 256>(a, blocks, s);
+    } else {
+        if (P == 8) launch_push<8, 1024>(a, blocks, s);      /* P = 16 would spill under the 128 registers of 1024 threads */
+        else launch_push<0, 1024>(a, blocks, s);
+    }
+    return (int)hipGetLastError();
+}
+
+int launch_channel_history(const float2 *hist, const float2 *x, size_t n, size_t xn, float2 *next, hipStream_t s)
+{
+    if (!hist || !x || !next || n < 1 || xn < 1) return (int)hipErrorInvalidValue;
+    const size_t want = (n + 255) / 256;
+    hipLaunchKernelGGL(channel_history_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, hist, x, n, xn, next);
+    return (int)hipGetLastError();
+}
+
+} // namespace qpsk

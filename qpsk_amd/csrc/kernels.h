@@ -558,8 +558,21 @@ int launch_rs_cross_decode(const uint8_t *in, size_t pitch, int ngroups, int n, 
                            uint8_t *out, size_t out_pitch, int32_t *info, uint8_t *colfail, hipStream_t s);
 int launch_rs_cross_place(const uint8_t *bytes, size_t byte_pitch, const int32_t *count, const uint8_t *crc_ok, int nstreams, int max_packets,
                           int len, int n, int ngroups, const int32_t *base, uint8_t *group, size_t pitch, uint8_t *have, hipStream_t s);
+/* channel.hip: the polyphase channeliser (the definition: include/qpsk_hip.h, CHANNELISER).  A workgroup of channel_threads(M) threads takes
+ * channel_tile(M) consecutive output times: 16384 complex values of LDS image from M = 1024 on (one workgroup of 1024 threads per compute
+ * unit), 8192 below (256 threads), at most 128 times.  x [T M]; proto [P M]; tw [M / 2]; hist [(P - 1) M] (NULL at P = 1); chan [nsel], every
+ * entry in [0, M): the caller has checked them, and every overlap; out rows pitch >= T elements apart */
+constexpr int CHANNEL_MAX_M = 4096, CHANNEL_MAX_P = 32, CHANNEL_MAX_SEL = 1 << 16;
+constexpr long long CHANNEL_MAX_SAMPLES = 1ll << 30;      /* T M of one push */
+constexpr int channel_threads(int M) { return M >= 1024 ? 1024 : 256; }
+constexpr int channel_tile(int M) { return M >= 1024 ? 16384 / M : M >= 64 ? 8192 / M : 128; }
+int prepare_channel();
+int launch_channel_push(const float2 *x, int T, int M, int P, const float *proto, const float2 *tw, const float2 *hist, const int32_t *chan, int nsel,
+                        float2 *out, size_t pitch, hipStream_t s);
+/* channel_history_kernel: next [n] = the last n samples of hist [n] followed by x [xn]; next is neither of them */
+int launch_channel_history(const float2 *hist, const float2 *x, size_t n, size_t xn, float2 *next, hipStream_t s);
 /* txchain.hip */
-int tx_history_symbols(void);         /* symbols of state per transmitter (uint8 each, 4 = none yet) */
+int tx_history_symbols(void);        /* symbols of state per transmitter (uint8 each, 4 = none yet) */
 int launch_tx_shape(const uint8_t *sym, uint8_t *hist, const float *taps, float *sig, int nstreams, int nsym,
                     int cycles, hipStream_t s);   /* shaped baseband of nsym symbols per transmitter; updates hist */
 int launch_tx_upmix(const float *sig, int16_t *pcm, float *state, int nstreams, int length, hipStream_t s);

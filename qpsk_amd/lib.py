@@ -72,6 +72,7 @@ API_SYMBOLS = [
     "qpsk_outer_reset", "qpsk_outer_max_words", "qpsk_outer_push", "qpsk_outer_interleave_batch", "qpsk_test_outer_advance",
     "qpsk_nodesync_reset", "qpsk_nodesync_shifts", "qpsk_nodesync_push", "qpsk_nodesync_set",
     "qpsk_outer_reset_group", "qpsk_dispersal_batch", "qpsk_dispersal_sequence",
+    "qpsk_channel_twiddles", "qpsk_channel_reset", "qpsk_channel_push",
 ]
 # the named puncturing patterns of include/qpsk_hip.h (QPSK_PUNCT_*): rate -> (period, keep0, keep1), bit r of a mask = step r of the period
 PUNCTURE = {"1/2": (1, 0x1, 0x1), "2/3": (2, 0x1, 0x3), "3/4": (3, 0x5, 0x3), "5/6": (5, 0x15, 0x0B), "7/8": (7, 0x51, 0x2F)}
@@ -197,6 +198,9 @@ def load():
     L.qpsk_outer_reset_group.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32]
     L.qpsk_dispersal_batch.argtypes = [vp, vp, C.c_longlong, i32, i32, i32, i32, vp, i32, vp, C.c_longlong]
     L.qpsk_dispersal_sequence.argtypes = [i32, i32, i32, vp]
+    L.qpsk_channel_twiddles.argtypes = [i32, vp]
+    L.qpsk_channel_reset.argtypes = [vp, i32, i32, vp, vp, i32]
+    L.qpsk_channel_push.argtypes = [vp, vp, i32, vp, C.c_longlong]
     L.qpsk_outer_max_words.argtypes = [vp, i32]
     L.qpsk_outer_push.argtypes = [vp, vp, C.c_longlong, i32, i32, vp, vp, C.c_longlong, vp, vp, vp]
     L.qpsk_outer_interleave_batch.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
@@ -287,6 +291,28 @@ def dispersal_sequence(len=188, group=8, msb_first=False):      # noqa: A002 (th
     return out[:rc].tobytes()
 
 
+def channel_twiddles(M):
+    """qpsk_channel_twiddles: the (M / 2, 2) float32 table (cos, sin)(TAU j / M) of the channeliser's transform (CHANNELISER in
+    include/qpsk_hip.h), part of its definition.  Host only, needs no GPU"""
+    L = load()
+    tw = np.zeros((max(int(M) // 2, 1), 2), np.float32)
+    rc = L.qpsk_channel_twiddles(int(M), tw.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise QpskError("libqpsk_hip error %d: %s" % (rc, L.qpsk_last_error().decode()))
+    return tw
+
+
+def channel_prototype(M, P, beta=8.0):
+    """A prototype for Modem.channel_reset(): the M P taps of a Kaiser-windowed sinc with its cut-off at half the channel spacing
+    (1 / (2 M) cycles per wideband sample), symmetric, unit gain at DC, float32.  A numpy convenience: the library designs no filter, and
+    any finite taps do"""
+    n = int(M) * int(P)
+    t = (np.arange(n) - (n - 1) / 2.0) / float(M)
+    h = np.sinc(t) * np.kaiser(n, float(beta))
+    h = 0.5 * (h + h[::-1])
+    return (h / h.sum()).astype(np.float32)
+
+
 def nodesync_shifts(puncture):
     """qpsk_nodesync_shifts: the delays (in dibits) a node sync has to try for a pattern, a key of PUNCTURE or a (period, keep0, keep1)
     tuple: nodesync_reset()'s nshift.  Host only, needs no GPU"""
@@ -335,6 +361,7 @@ class Modem:
         self._vs_streams = 0      # streams of the streaming Viterbi decoder (viterbi_stream_reset)
         self._outer = None        # (streams, n) of the outer link (outer_reset)
         self._ns_links = 0        # links of the node sync (nodesync_reset)
+        self._channel = None      # (M, nsel) of the channeliser (channel_reset)
 
     def _check(self, rc):
         if rc != 0:
@@ -980,6 +1007,37 @@ class Modem:
         self._check(self.L.qpsk_streams_rx_pcm(self.h, _ptr(x), _ptr(o["sym"]), _ptr(o["freq"]), _ptr(o["phase"]),
                                                _ptr(o["costas"]), _ptr(o["index"])))
         return o
+
+    # ---- the polyphase channeliser in front of the streams (CHANNELISER in include/qpsk_hip.h)
+    def channel_reset(self, M, P, proto, chan=None):
+        """qpsk_channel_reset: M channels (a power of two, 2..4096), P taps per branch (1..32), proto the M P real taps (e.g.
+        channel_prototype(M, P)); chan: the channel numbers of the output rows, any order, repeats allowed; None = all M in order.
+        Zeroes the history"""
+        h = np.ascontiguousarray(np.asarray(proto, dtype=np.float32).reshape(-1))
+        if h.size != int(M) * int(P):
+            raise ValueError("channel_reset() proto must hold M * P = %d taps" % (int(M) * int(P)))
+        ch = None if chan is None else np.ascontiguousarray(np.asarray(chan, dtype=np.int32).reshape(-1))
+        self._check(self.L.qpsk_channel_reset(self.h, int(M), int(P), h.ctypes.data_as(C.c_void_p),
+                                              None if ch is None else ch.ctypes.data_as(C.c_void_p), 0 if ch is None else len(ch)))
+        self._channel = (int(M), int(M) if ch is None else len(ch))
+
+    def channel(self, x, pitch=0):
+        """qpsk_channel_push: x (T * M, 2) float32, the next T * M wideband samples -> (nsel, T, 2) float32, row i = channel chan[i]:
+        the blocks streams_rx_cplx() takes.  pitch: the complex samples between the OUTPUT's rows (0 = tight); the result is then a view
+        of a (nsel, pitch, 2) buffer whose other samples are not written"""
+        t = self.torch
+        if self._channel is None:
+            raise QpskError("channel() before channel_reset()")
+        M, nsel = self._channel
+        x = self._dev(x, t.float32)
+        if x.dim() != 2 or x.shape[1] != 2 or x.shape[0] < M or x.shape[0] % M:
+            raise ValueError("channel() input must be (T * %d, 2) float32" % M)
+        T = x.shape[0] // M
+        rows = int(pitch) if pitch else T
+        buf = self.empty((nsel, rows, 2), t.float32)
+        self._check(self.L.qpsk_channel_push(self.h, _ptr(x), T, _ptr(buf), int(pitch)))
+        self._channel_keep = (x,)      # the input stays alive until the stream has run the call
+        return buf[:, :T]
 
     # ---- packets from continuous streams (qpsk_deframer_*)
     def deframer_reset(self, nstreams, sync, nbytes, min_score, max_packets=8):
