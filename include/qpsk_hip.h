@@ -919,12 +919,58 @@ int qpsk_dispersal_sequence(int len, int group, int flags, uint8_t *out);
  * context's stream and touches neither the receive streams, the deframers, the histogram mode's guess, the Viterbi scratch, the outer link
  * nor the node sync.  qpsk_ctx_last_kernel() names channel_push_kernel (channel_history_kernel, the launch behind it, moves the history
  * into the second of two buffers, so that no launch reads what it writes).
- * Not built: the synthesis (transmit) bank; oversampled banks; M that is no power of two; PCM or int16 wideband input; qpsk_multi; routing
- * inside bench.py.  Usage: INTEGRATION.md 2.0.
+ * Not built: oversampled banks; M that is no power of two; PCM or int16 wideband input; qpsk_multi; routing inside bench.py.  The
+ * transmit twin is SYNTHESIS BANK below.  Usage: INTEGRATION.md 2.0.
  * ------------------------------------------------------------------------- */
 int qpsk_channel_twiddles(int M, float *h_tw);
 int qpsk_channel_reset(qpsk_ctx *ctx, int M, int P, const float *h_proto, const int32_t *h_chan, int nsel);
 int qpsk_channel_push(qpsk_ctx *ctx, const float *d_x, int T, float *d_out, long long out_pitch);
+
+/* -------------------------------------------------------------------------
+ * SYNTHESIS BANK: the channeliser's transmit twin, a critically sampled polyphase synthesis filter bank -- nsel channel rows, each at 1 / M
+ * of the wideband rate (the shaped baseband qpsk_tx_symbols hands out, for one), come out as ONE wideband complex capture with row i in
+ * channel chan[i]: what CHANNELISER takes.  State (the last transformed vectors) is carried from push to push.  The library's own definition,
+ * every operation in fp32 and in a stated order (the reference has no filter bank; parity unpinned), restated in numpy by
+ * tests/test_synth_cpu.py (synth_ref) and compared with the kernels bit for bit.  There is no tolerance anywhere.
+ *
+ * M   channels, a power of two, 2 <= M <= 4096.   P   taps per branch, 1 <= P <= 32.
+ * g[0 .. M P)   the caller's real prototype low-pass, finite floats.  The library applies no scaling: the interpolation gain M is the
+ *   caller's (M h for a prototype h of unit gain is exact in fp32, M being a power of two).
+ * c_i[m], i < nsel, m < T   the input rows; row i feeds channel chan[i].  The channel numbers are DISTINCT (a repeat is QPSK_ERR_ARG), so
+ *   nsel <= M; a channel nobody names is +0.0.
+ * TRANSFORM, fp32: CHANNELISER's butterfly network and its table (qpsk_channel_twiddles), the same inverse sign, the same operands, the
+ *   same order.  For every time m: v[bitrev(chan[i])] = c_i[m], +0.0 elsewhere; then the stages s = 1 .. log2 M exactly as written under
+ *   CHANNELISER; V_m[r] = v[r], r = 0 .. M - 1.
+ * BRANCH FILTER, r = 0 .. M - 1, real and imaginary part separately, fp32, no contraction:
+ *       x[m M + r] = sum_{q = 0}^{P - 1} g[q M + r] V_{m - q}[r]
+ *   acc = fl(g[r] V_m[r]), then acc = acc + fl(g[q M + r] V_{m - q}[r]) for q = 1 .. P - 1 in that order.
+ * HISTORY.  The last P - 1 transformed vectors V, (P - 1) M complex values, all zero after a reset; a push of T < P - 1 times shifts it.
+ * NaN, Inf.  A non-finite sample propagates as IEEE arithmetic says (0 * Inf = NaN included, -0.0 as the operations give it); no status
+ *   is raised.
+ * WITH THE ANALYSIS BANK BEHIND IT (prototype h there, g here, both of M P taps, exact arithmetic): channel k of CHANNELISER on x is
+ *       y_k[m'] = e^{j TAU k (M - 1) / M} sum_m c_k[m] (h * g)[(m' - m) M + M - 1]       (h * g: the convolution of the two prototypes)
+ *   plus what the other channels leak through the two stop bands.  For symmetric prototypes (h * g) peaks at M P - 1, so the row comes back
+ *   delayed by exactly P - 1 channel samples and turned by a fixed -k / M of a circle per channel, which the Costas loop and the deframer's
+ *   rotation search absorb.
+ *
+ *   qpsk_synth_reset   (M, P, h_proto [M P] = g); h_chan [nsel] host channel numbers in [0, M), any order, DISTINCT, 1 <= nsel <= M; NULL =
+ *                all M channels in order (nsel is then not looked at).  Copies both, zeroes the history, replaces a bank the context has
+ *                (behind a synchronisation of the context's stream); a refused reset leaves it
+ *   qpsk_synth_push    d_in [nsel] rows of [T][2], in_pitch complex samples apart (0 = tight, T) -> d_x [T M][2].  T >= 1, T M <= 2^27 (the
+ *                scratch of transformed vectors between the bank's two launches is then 1 GiB); in_pitch 0 or >= T; d_x must not overlap
+ *                the rows.  QPSK_ERR_STATE before a reset.  The scratch is the context's, sized by the largest push so far: a push that
+ *                needs a larger one waits for the context's stream once and reallocates (QPSK_ERR_ALLOC leaves bank and history as they
+ *                were); any other push is three launches and no synchronisation
+ * QPSK_ERR_ARG at the call for a bad argument -- a non-finite tap and a channel named twice among them -- decided before the context is
+ * looked at, nothing launched.  A push is stream-ordered on the context's stream.  The bank is state of its own: its calls touch neither
+ * the channeliser, the receive streams, the deframers, the histogram mode's guess, the Viterbi scratch, the outer link nor the node sync,
+ * and none of those calls touches the bank.  qpsk_ctx_last_kernel() names synth_filter_kernel (synth_transform_kernel runs in front of
+ * it, channel_history_kernel behind it, into the second of two buffers, so that no launch reads what it writes).
+ * Not built: a fused single-launch bank for small M; oversampled banks; M that is no power of two; real or int16 output; qpsk_multi; routing
+ * inside bench.py.  Usage: INTEGRATION.md 2.0.
+ * ------------------------------------------------------------------------- */
+int qpsk_synth_reset(qpsk_ctx *ctx, int M, int P, const float *h_proto, const int32_t *h_chan, int nsel); /* h_chan NULL = all M in order */
+int qpsk_synth_push(qpsk_ctx *ctx, const float *d_in, long long in_pitch, int T, float *d_x);
 
 /* -------------------------------------------------------------------------
  * NODE SYNC: what stands between qpsk_soft_batch and VITERBI STREAM on a continuously coded link -- the quarter turn the Costas loop may

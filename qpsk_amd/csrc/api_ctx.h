@@ -13,7 +13,8 @@
  *   api_dispersal.cpp DVB's energy dispersal behind the Reed-Solomon decoder
  *   api_nodesync.cpp the node sync in front of it: the candidate transform and the monitor on the decoder's error count
  *   api_cross.cpp    the packet erasure code: Reed-Solomon across the packets of a group, and the place call in front of it
- *   api_channel.cpp  the polyphase channeliser in front of the streams: one wideband capture into stream rows
+ *   api_channel.cpp  the polyphase channeliser in front of the streams: one wideband capture into stream rows; the synthesis bank, its
+ *                    transmit twin
  *
  * OWNERSHIP: each nested group of qpsk_ctx below names the one unit that reads and writes it; the members outside a group
  * (configuration, scratch buffers) are every unit's.  DESIGN.md, "The host layer", lists the few places that reach across.
@@ -282,6 +283,15 @@ struct QPSK_UNIT_LOCAL Channeliser {
     void release();               /* leaves the group value-initialised: no channeliser.  Behind a synchronisation of the context's stream */
 };
 
+/* api_channel.cpp.  The polyphase synthesis bank (qpsk_synth_*): the channeliser's state under the transmit bank's meaning -- the histories
+ * are the last P - 1 TRANSFORMED vectors, (P - 1) M values, and the selection holds distinct channels -- and the scratch of V rows between
+ * the bank's two launches, sized by the largest push so far.  Separate from qpsk_ctx::channel: both banks are live in one context */
+struct QPSK_UNIT_LOCAL Synthesiser {
+    Channeliser bank;
+    DevBuf scratch;               /* V [T][M][2] floats of the running push */
+    void release();               /* leaves the group value-initialised: no bank, no scratch.  Behind a synchronisation of the context's stream */
+};
+
 } // namespace qpsk
 
 struct qpsk_ctx {
@@ -323,6 +333,7 @@ struct qpsk_ctx {
     qpsk::NodeSync nodesync;
     qpsk::Dispersal dispersal;
     qpsk::Channeliser channel;
+    qpsk::Synthesiser synth;
 };
 
 namespace qpsk {

@@ -9,9 +9,9 @@
  *      lane keeps the P taps and the last P - 1 samples of its branch in registers and loads one new sample per time (a run re-reads
  *      (R + P - 1) / R of its input); PT = 0, any P: every product loads its tap and its sample, nothing is kept.  u_m[p] goes to
  *      row m, element bitrev(p).
- *   2. the transform: fft_lds.h's butterflies, inverse sign, fp32.  Two stages per pass over the LDS: a thread holds the four values
- *      i0 + {0, 1, 2, 3} half of stages s and s + 1 and performs the four butterflies of the definition on them, the operands and
- *      the order of every operation as there; an odd log2 M runs stage 1 alone first.
+ *   2. the transform (channel_fft.h, shared with synth.hip): fft_lds.h's butterflies, inverse sign, fp32.  Two stages per pass over the
+ *      LDS: a thread holds the four values i0 + {0, 1, 2, 3} half of stages s and s + 1 and performs the four butterflies of the
+ *      definition on them, the operands and the order of every operation as there; an odd log2 M runs stage 1 alone first.
  *   3. the transposed store: TB consecutive times of a selected channel are 8 TB contiguous bytes of its row.
  * Element e of a row lies at e + (e >> 5), rows M + (M >> 5) + 1 elements apart: the strided accesses of the early stages and of the store's
  * column reads spread over the banks.  Times at or beyond T are computed on the push's last block and not stored; no address outside the
@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "channel_fft.h"
 #include "kernels.h"
 
 namespace qpsk {
@@ -41,8 +42,6 @@ struct ChannelArgs {
     int tb, run, lanes;       /* the tile, R, min(M, NT) */
 };
 
-__device__ __forceinline__ int phys(int e) { return e + (e >> 5); }
-
 /* block bb of the push (negative: of the history), branch p.  No branch, so that a lane's loads go out together: a block at or beyond T
  * (an output time that is never stored) reads the push's last block instead */
 __device__ __forceinline__ float2 sample(const ChannelArgs &a, long long bb, int p)
@@ -50,14 +49,6 @@ __device__ __forceinline__ float2 sample(const ChannelArgs &a, long long bb, int
     bb = bb < a.T ? bb : (long long)a.T - 1;
     const float2 *block = bb >= 0 ? a.x + (size_t)bb * a.M : a.hist + (size_t)(bb + a.P - 1) * a.M;
     return block[a.M - 1 - p];
-}
-
-__device__ __forceinline__ void butterfly(const float2 w, const float2 e, const float2 o, float2 &lo, float2 &hi)
-{
-    const float zr = w.x * o.x - w.y * o.y;
-    const float zi = w.x * o.y + w.y * o.x;
-    lo = make_float2(e.x + zr, e.y + zi);
-    hi = make_float2(e.x - zr, e.y - zi);
 }
 
 template <int PT, int NT>
@@ -75,7 +66,7 @@ __global__ void __launch_bounds__(NT) channel_push_kernel(ChannelArgs a)
         const int lane = tid & (a.lanes - 1), grp = tid / a.lanes;
         const int r0 = grp * a.run;
         for (int p = lane; p < M; p += NT) {
-            const int at = phys((int)(__brev((unsigned)p) >> (32 - log2m)));
+            const int at = channel_phys((int)(__brev((unsigned)p) >> (32 - log2m)));
             if constexpr (PT > 0) {
                 float h[PT];
                 float2 w[PT > 1 ? PT - 1 : 1];      /* w[j] = block(m - 1 - j) */
@@ -116,44 +107,8 @@ __global__ void __launch_bounds__(NT) channel_push_kernel(ChannelArgs a)
     }
     __syncthreads();
 
-    /* ---- 2. the transform of every row */
-    int s = 1;
-    if (log2m & 1) {      /* stage 1 alone: half = 1, k = 0 */
-        const float2 w = a.tw[0];
-        const int per_row = M >> 1;
-        for (int item = tid; item < a.tb * per_row; item += NT) {
-            float2 *row = v + (item >> (log2m - 1)) * row_pitch;
-            const int lo = phys(2 * (item & (per_row - 1))), hi = phys(2 * (item & (per_row - 1)) + 1);
-            float2 c0, c1;
-            butterfly(w, row[lo], row[hi], c0, c1);
-            row[lo] = c0;
-            row[hi] = c1;
-        }
-        __syncthreads();
-        s = 2;
-    }
-    for (; s < log2m; s += 2) {      /* stages s and s + 1 */
-        const int half = 1 << (s - 1), per_row = M >> 2;
-        for (int item = tid; item < a.tb * per_row; item += NT) {
-            float2 *row = v + (item >> (log2m - 2)) * row_pitch;
-            const int j = item & (per_row - 1);
-            const int k = j & (half - 1);
-            const int i0 = ((j >> (s - 1)) << (s + 1)) + k;
-            const int e0 = phys(i0), e1 = phys(i0 + half), e2 = phys(i0 + 2 * half), e3 = phys(i0 + 3 * half);
-            const float2 w1 = a.tw[k * (M >> s)];
-            const float2 w2a = a.tw[k * (M >> (s + 1))], w2b = a.tw[(k + half) * (M >> (s + 1))];
-            float2 b0, b1, b2, b3, c0, c1, c2, c3;
-            butterfly(w1, row[e0], row[e1], b0, b1);
-            butterfly(w1, row[e2], row[e3], b2, b3);
-            butterfly(w2a, b0, b2, c0, c2);
-            butterfly(w2b, b1, b3, c1, c3);
-            row[e0] = c0;
-            row[e1] = c1;
-            row[e2] = c2;
-            row[e3] = c3;
-        }
-        __syncthreads();
-    }
+    /* ---- 2. the transform of every row (channel_fft.h) */
+    channel_transform_rows<NT>(v, a.tw, tid, M, log2m, a.tb, row_pitch);
 
     /* ---- 3. the transposed store */
     {
@@ -164,7 +119,7 @@ __global__ void __launch_bounds__(NT) channel_push_kernel(ChannelArgs a)
         for (long long item = tid; item < items; item += NT) {
             const int r = (int)(item & (a.tb - 1));
             const long long i = item >> log2tb;
-            if (r < rows) a.out[(size_t)i * a.pitch + (size_t)(m0 + r)] = v[r * row_pitch + phys(a.chan[i])];
+            if (r < rows) a.out[(size_t)i * a.pitch + (size_t)(m0 + r)] = v[r * row_pitch + channel_phys(a.chan[i])];
         }
     }
 }
@@ -178,8 +133,6 @@ __global__ void __launch_bounds__(256) channel_history_kernel(const float2 *__re
         next[i] = at < n ? hist[at] : x[at - n];
     }
 }
-
-size_t channel_lds_bytes(int M, int tb) { return (size_t)(M + (M >> 5) + 1) * (size_t)tb * sizeof(float2); }
 
 template <int PT, int NT>
 void launch_push(const ChannelArgs &a, unsigned blocks, hipStream_t s)

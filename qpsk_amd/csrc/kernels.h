@@ -566,11 +566,23 @@ constexpr int CHANNEL_MAX_M = 4096, CHANNEL_MAX_P = 32, CHANNEL_MAX_SEL = 1 << 1
 constexpr long long CHANNEL_MAX_SAMPLES = 1ll << 30;      /* T M of one push */
 constexpr int channel_threads(int M) { return M >= 1024 ? 1024 : 256; }
 constexpr int channel_tile(int M) { return M >= 1024 ? 16384 / M : M >= 64 ? 8192 / M : 128; }
+/* the LDS image of tb rows: element e of a row at e + (e >> 5), rows M + (M >> 5) + 1 elements apart (channel_fft.h) */
+constexpr size_t channel_lds_bytes(int M, int tb) { return (size_t)(M + (M >> 5) + 1) * (size_t)tb * sizeof(float2); }
 int prepare_channel();
 int launch_channel_push(const float2 *x, int T, int M, int P, const float *proto, const float2 *tw, const float2 *hist, const int32_t *chan, int nsel,
                         float2 *out, size_t pitch, hipStream_t s);
 /* channel_history_kernel: next [n] = the last n samples of hist [n] followed by x [xn]; next is neither of them */
 int launch_channel_history(const float2 *hist, const float2 *x, size_t n, size_t xn, float2 *next, hipStream_t s);
+/* synth.hip: the polyphase synthesis bank (the definition: include/qpsk_hip.h, SYNTHESIS BANK), two launches through the scratch V [T][M] of
+ * transformed vectors.  synth_transform_kernel has the channeliser's geometry (channel_tile, channel_threads): in [nsel] rows pitch >= T
+ * elements apart; chan [nsel], DISTINCT entries in [0, M): the caller has checked them, and every overlap.  synth_filter_kernel: a lane
+ * takes SYNTH_RUN consecutive times of one branch; hist [P - 1][M] (NULL at P = 1) = the vectors before the push; x [T M].  The history
+ * moves on with launch_channel_history(hist, V, (P - 1) M, T M, next) */
+constexpr long long SYNTH_MAX_SAMPLES = 1ll << 27;      /* T M of one push: a scratch of 1 GiB */
+constexpr int SYNTH_RUN = 16;
+int prepare_synth();
+int launch_synth_transform(const float2 *in, size_t pitch, int T, int M, const float2 *tw, const int32_t *chan, int nsel, float2 *V, hipStream_t s);
+int launch_synth_filter(const float2 *V, const float2 *hist, int T, int M, int P, const float *proto, float2 *x, hipStream_t s);
 /* txchain.hip */
 int tx_history_symbols(void);        /* symbols of state per transmitter (uint8 each, 4 = none yet) */
 int launch_tx_shape(const uint8_t *sym, uint8_t *hist, const float *taps, float *sig, int nstreams, int nsym,

@@ -72,7 +72,7 @@ API_SYMBOLS = [
     "qpsk_outer_reset", "qpsk_outer_max_words", "qpsk_outer_push", "qpsk_outer_interleave_batch", "qpsk_test_outer_advance",
     "qpsk_nodesync_reset", "qpsk_nodesync_shifts", "qpsk_nodesync_push", "qpsk_nodesync_set",
     "qpsk_outer_reset_group", "qpsk_dispersal_batch", "qpsk_dispersal_sequence",
-    "qpsk_channel_twiddles", "qpsk_channel_reset", "qpsk_channel_push",
+    "qpsk_channel_twiddles", "qpsk_channel_reset", "qpsk_channel_push", "qpsk_synth_reset", "qpsk_synth_push",
 ]
 # the named puncturing patterns of include/qpsk_hip.h (QPSK_PUNCT_*): rate -> (period, keep0, keep1), bit r of a mask = step r of the period
 PUNCTURE = {"1/2": (1, 0x1, 0x1), "2/3": (2, 0x1, 0x3), "3/4": (3, 0x5, 0x3), "5/6": (5, 0x15, 0x0B), "7/8": (7, 0x51, 0x2F)}
@@ -201,6 +201,8 @@ def load():
     L.qpsk_channel_twiddles.argtypes = [i32, vp]
     L.qpsk_channel_reset.argtypes = [vp, i32, i32, vp, vp, i32]
     L.qpsk_channel_push.argtypes = [vp, vp, i32, vp, C.c_longlong]
+    L.qpsk_synth_reset.argtypes = [vp, i32, i32, vp, vp, i32]
+    L.qpsk_synth_push.argtypes = [vp, vp, C.c_longlong, i32, vp]
     L.qpsk_outer_max_words.argtypes = [vp, i32]
     L.qpsk_outer_push.argtypes = [vp, vp, C.c_longlong, i32, i32, vp, vp, C.c_longlong, vp, vp, vp]
     L.qpsk_outer_interleave_batch.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
@@ -302,15 +304,16 @@ def channel_twiddles(M):
     return tw
 
 
-def channel_prototype(M, P, beta=8.0):
+def channel_prototype(M, P, beta=8.0, gain=1.0):
     """A prototype for Modem.channel_reset(): the M P taps of a Kaiser-windowed sinc with its cut-off at half the channel spacing
     (1 / (2 M) cycles per wideband sample), symmetric, unit gain at DC, float32.  A numpy convenience: the library designs no filter, and
-    any finite taps do"""
+    any finite taps do.  gain multiplies the float32 taps: Modem.synth_reset() wants the interpolation gain M, and gain=M is exact in
+    float32, M being a power of two -- the synthesis prototype is then M times the analysis one tap for tap"""
     n = int(M) * int(P)
     t = (np.arange(n) - (n - 1) / 2.0) / float(M)
     h = np.sinc(t) * np.kaiser(n, float(beta))
     h = 0.5 * (h + h[::-1])
-    return (h / h.sum()).astype(np.float32)
+    return np.float32(gain) * (h / h.sum()).astype(np.float32)
 
 
 def nodesync_shifts(puncture):
@@ -362,6 +365,7 @@ class Modem:
         self._outer = None        # (streams, n) of the outer link (outer_reset)
         self._ns_links = 0        # links of the node sync (nodesync_reset)
         self._channel = None      # (M, nsel) of the channeliser (channel_reset)
+        self._synth = None        # (M, nsel) of the synthesis bank (synth_reset)
 
     def _check(self, rc):
         if rc != 0:
@@ -1038,6 +1042,41 @@ class Modem:
         self._check(self.L.qpsk_channel_push(self.h, _ptr(x), T, _ptr(buf), int(pitch)))
         self._channel_keep = (x,)      # the input stays alive until the stream has run the call
         return buf[:, :T]
+
+    # ---- the synthesis bank, the channeliser's transmit twin (SYNTHESIS BANK in include/qpsk_hip.h)
+    def synth_reset(self, M, P, proto, chan=None):
+        """qpsk_synth_reset: M channels (a power of two, 2..4096), P taps per branch (1..32), proto the M P real taps with the
+        interpolation gain in them (e.g. channel_prototype(M, P, gain=M)); chan: the channels the input rows go to, any order, no
+        repeats; None = all M in order.  Zeroes the history"""
+        h = np.ascontiguousarray(np.asarray(proto, dtype=np.float32).reshape(-1))
+        if h.size != int(M) * int(P):
+            raise ValueError("synth_reset() proto must hold M * P = %d taps" % (int(M) * int(P)))
+        ch = None if chan is None else np.ascontiguousarray(np.asarray(chan, dtype=np.int32).reshape(-1))
+        self._check(self.L.qpsk_synth_reset(self.h, int(M), int(P), h.ctypes.data_as(C.c_void_p),
+                                            None if ch is None else ch.ctypes.data_as(C.c_void_p), 0 if ch is None else len(ch)))
+        self._synth = (int(M), int(M) if ch is None else len(ch))
+
+    def synth(self, rows, pitch=0):
+        """qpsk_synth_push: rows (nsel, T, 2) float32, the next T samples of every selected channel (row i goes to channel chan[i]) ->
+        (T * M, 2) float32, the next T * M wideband samples: what channel() takes.  pitch: the complex samples between the INPUT's rows
+        (0 = tight); rows is then a view (nsel, T, 2) of a (nsel, pitch, 2) float32 buffer on the device, read where it lies"""
+        t = self.torch
+        if self._synth is None:
+            raise QpskError("synth() before synth_reset()")
+        M, nsel = self._synth
+        if pitch:
+            c = rows
+            if not isinstance(c, t.Tensor) or c.device != self.dev or c.dtype != t.float32 or c.dim() != 3 or c.stride() != (2 * int(pitch), 2, 1):
+                raise ValueError("synth() with a pitch takes a float32 device view whose rows lie 2 * pitch floats apart")
+        else:
+            c = self._dev(rows, t.float32)
+        if c.dim() != 3 or c.shape[0] != nsel or c.shape[1] < 1 or c.shape[2] != 2:
+            raise ValueError("synth() input must be (%d, T, 2) float32" % nsel)
+        T = c.shape[1]
+        x = self.empty((T * M, 2), t.float32)
+        self._check(self.L.qpsk_synth_push(self.h, _ptr(c), int(pitch), T, _ptr(x)))
+        self._synth_keep = (c,)      # the input stays alive until the stream has run the call
+        return x
 
     # ---- packets from continuous streams (qpsk_deframer_*)
     def deframer_reset(self, nstreams, sync, nbytes, min_score, max_packets=8):
