@@ -973,6 +973,55 @@ int qpsk_synth_reset(qpsk_ctx *ctx, int M, int P, const float *h_proto, const in
 int qpsk_synth_push(qpsk_ctx *ctx, const float *d_in, long long in_pitch, int T, float *d_x);
 
 /* -------------------------------------------------------------------------
+ * RESAMPLER: a batched polyphase rational resampler, the stage between a capture's rate and the modem's -- both banks above are critically
+ * sampled, so their rows run at exactly 1 / M of the capture rate, and the modem behind them at exactly FS = CYCLES RS; a front end that was
+ * not made for this modem delivers FS D / L.  nstreams rows go in at one rate and come out at L / D of it, laid out as qpsk_streams_rx_cplx
+ * (or, on the transmit side, qpsk_synth_push) takes them.  State is carried from push to push.  Input and output lengths differ per push,
+ * so the interface is driven from the OUTPUT: the caller names the outputs it wants, qpsk_resample_need says how many inputs they consume.
+ * The library's own definition, every operation in fp32 and in a stated order (the reference has no resampler; parity unpinned, DESIGN.md
+ * 4.4.20), restated in numpy by tests/test_resample_cpu.py (resample_ref) and compared with the kernel bit for bit.  There is no tolerance
+ * anywhere.
+ *
+ * L   interpolation factor, 1 <= L <= 512.   D   decimation factor, 1 <= D <= 4096; gcd(L, D) need not be 1.
+ * P   taps per branch, 1 <= P <= 32.   h[0 .. L P)   the caller's real prototype, finite floats.  The library designs no filter and applies
+ *   no scaling: the interpolation gain L is the caller's.
+ * nstreams rows, 1 <= nstreams <= 65536; all share L, D, P, h and the position, so the rows stay aligned.
+ * s   per stream, every complex sample pushed since the reset, preceded by zeros.
+ * OUTPUT n, counted from the reset: t = n D, i = t div L, b = t mod L,
+ *       y[n] = sum_{q = 0}^{P - 1} h[q L + b] s[i - q]
+ *   real and imaginary part separately, fp32, no contraction: acc = fl(h[b] s[i]), then acc = acc + fl(h[q L + b] s[i - q]) for
+ *   q = 1 .. P - 1 in that order.  This is v = h * (s zero-stuffed by L), y[n] = v[n D].
+ * POSITION.  After the outputs [0, n0) a stream has consumed c0 = (the input index of output n0 - 1) + 1 inputs.  The whole carried position
+ *   is the one integer r = n0 D - c0 L: 0 after a reset, in [D - L, D) after every push; no counter grows.  A push of N outputs uses t = r + n D, n < N,
+ *   relative to its first new input (floor division: i = t div L >= -1), consumes K = (r + (N - 1) D) div L + 1 inputs -- K may be 0 when
+ *   L > D and N is small -- and leaves r += N D - K L.
+ * HISTORY.  The last P consumed samples per stream (not P - 1: with L > D an output may use no new input at all, i = -1), all zero after a
+ *   reset.  A push with K < P shifts it, a push with K = 0 leaves it.
+ * NaN, Inf.  A non-finite sample propagates as IEEE arithmetic says (0 * Inf = NaN included, -0.0 as the operations give it); the call
+ *   raises no status -- the stream call behind it has the fence.
+ *
+ *   qpsk_resample_reset  (nstreams, L, D, P, h_proto [L P]).  Copies the taps, zeroes the history and r, replaces a resampler the context
+ *                has (behind a synchronisation of the context's stream); a refused reset leaves it
+ *   qpsk_resample_need   host only: the K the NEXT push of nout outputs consumes; < 0 on error (QPSK_ERR_STATE before a reset)
+ *   qpsk_resample_push   d_in [nstreams] rows of [nin][2], in_pitch complex samples apart (0 = tight, nin) -> d_out [nstreams] rows of
+ *                [nout][2], out_pitch apart (0 = tight, nout: with nout = frame_size exactly the block qpsk_streams_rx_cplx takes; with
+ *                in_pitch = qpsk_channel_push's out_pitch the channeliser's rows are read where they lie).  1 <= nout <= 2^24 and
+ *                nout D + L < 2^31; nin must equal qpsk_resample_need(ctx, nout), and nin = 0 is legal (d_in may then be NULL); a pitch is 0
+ *                or at least its row; d_out must not overlap d_in.  QPSK_ERR_STATE before a reset
+ * QPSK_ERR_ARG at the call for a bad argument -- a non-finite tap and an nin other than the need among them -- nothing launched, state
+ * untouched; what the arguments alone decide is decided before the context is looked at.  A push is stream-ordered on the context's stream
+ * with no host synchronisation.  The resampler is state of its own: its calls touch neither the two banks, the receive streams, the
+ * transmitters, the deframers, the Viterbi scratch, the outer link nor the node sync, and none of those calls touches it.
+ * qpsk_ctx_last_kernel() names resample_push_kernel (resample_history_kernel, the launch behind it when K > 0, moves the history into the
+ * second of two buffers, so that no launch reads what it writes).
+ * Not built: per-stream ratios; a ratio that changes while running (clock-drift tracking); irrational ratios and Farrow structures; real or
+ * int16 rows; qpsk_multi; routing inside bench.py.  Usage: INTEGRATION.md 2.0.
+ * ------------------------------------------------------------------------- */
+int qpsk_resample_reset(qpsk_ctx *ctx, int nstreams, int L, int D, int P, const float *h_proto);
+int qpsk_resample_need(qpsk_ctx *ctx, int nout);   /* host only: the K the NEXT push of nout outputs consumes; < 0 on error */
+int qpsk_resample_push(qpsk_ctx *ctx, const float *d_in, long long in_pitch, int nin, int nout, float *d_out, long long out_pitch);
+
+/* -------------------------------------------------------------------------
  * NODE SYNC: what stands between qpsk_soft_batch and VITERBI STREAM on a continuously coded link -- the quarter turn the Costas loop may
  * have locked on and the phase of the puncturing pattern are unknown, and a loop that slips changes both mid-stream.  Per link a CANDIDATE
  * (quarter turn r, delay h in dibits) is applied to the soft rows, and a MONITOR judges it by the error count the stream decoder reported for

@@ -8,4 +8,5 @@ device pointers of torch tensors (PyTorch is used for device memory and streams,
 There is no CPU fallback: without the built library, or without a GPU, everything raises.
 """
 from .lib import (QpskError, Modem, MultiJob, Params, PUNCTURE, TIMING_FIXED, TIMING_FFT, TIMING_HIST, build, lib_path, load,  # noqa: F401
-                  TAU, channel_prototype, channel_twiddles, dispersal_sequence, frame_len, ilv_stride, nodesync_shifts, rs_generator, version)
+                  TAU, channel_prototype, channel_twiddles, dispersal_sequence, frame_len, ilv_stride, nodesync_shifts, resample_prototype,
+                  rs_generator, version)

@@ -204,6 +204,7 @@ int qpsk_ctx_create(qpsk_ctx **out, int device, const qpsk_params *p, void *stre
     KERNEL_TRY(prepare_carrier_est());
     KERNEL_TRY(prepare_channel());
     KERNEL_TRY(prepare_synth());
+    KERNEL_TRY(prepare_resample());
     qpsk_ctx *c = new qpsk_ctx();
     c->device = device;
     for (const auto &k : TUNING_KEYS) {   /* the only place the environment is read */
@@ -280,6 +281,7 @@ void qpsk_ctx_destroy(qpsk_ctx *c)
     c->dispersal.release();
     c->channel.release();
     c->synth.release();
+    c->resample.release();
     delete c;
 }
 

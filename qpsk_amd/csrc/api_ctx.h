@@ -15,6 +15,7 @@
  *   api_cross.cpp    the packet erasure code: Reed-Solomon across the packets of a group, and the place call in front of it
  *   api_channel.cpp  the polyphase channeliser in front of the streams: one wideband capture into stream rows; the synthesis bank, its
  *                    transmit twin
+ *   api_resample.cpp the batched rational resampler between the capture's rate and the modem's
  *
  * OWNERSHIP: each nested group of qpsk_ctx below names the one unit that reads and writes it; the members outside a group
  * (configuration, scratch buffers) are every unit's.  DESIGN.md, "The host layer", lists the few places that reach across.
@@ -292,6 +293,19 @@ struct QPSK_UNIT_LOCAL Synthesiser {
     void release();               /* leaves the group value-initialised: no bank, no scratch.  Behind a synchronisation of the context's stream */
 };
 
+/* api_resample.cpp.  The batched rational resampler (qpsk_resample_*): one allocation (`state`) that holds the L P taps and TWO histories of
+ * the last P consumed samples per stream -- a push reads hist[cur] and leaves the next history in the other, so no launch reads what it
+ * writes.  The position r = n0 D - c0 L (0 after a reset, then in [D - L, D)) is the same for every stream and is the host's */
+struct QPSK_UNIT_LOCAL Resampler {
+    uint8_t *state = nullptr;
+    int nstreams = 0, L = 0, D = 0, P = 0;
+    int r = 0;
+    float *proto = nullptr, *hist[2] = {nullptr, nullptr};      /* into state */
+    int cur = 0;
+    bool ready = false;           /* a reset has completed and no push has failed since */
+    void release();               /* leaves the group value-initialised: no resampler.  Behind a synchronisation of the context's stream */
+};
+
 } // namespace qpsk
 
 struct qpsk_ctx {
@@ -334,6 +348,7 @@ struct qpsk_ctx {
     qpsk::Dispersal dispersal;
     qpsk::Channeliser channel;
     qpsk::Synthesiser synth;
+    qpsk::Resampler resample;
 };
 
 namespace qpsk {

@@ -583,6 +583,26 @@ constexpr int SYNTH_RUN = 16;
 int prepare_synth();
 int launch_synth_transform(const float2 *in, size_t pitch, int T, int M, const float2 *tw, const int32_t *chan, int nsel, float2 *V, hipStream_t s);
 int launch_synth_filter(const float2 *V, const float2 *hist, int T, int M, int P, const float *proto, float2 *x, hipStream_t s);
+/* resample.hip: the batched polyphase rational resampler (the definition: include/qpsk_hip.h, RESAMPLER).  A workgroup of RESAMPLE_TILE
+ * threads takes one stream and RESAMPLE_TILE consecutive outputs; the L P taps lie in LDS (64 KiB at most).  A tile's input window is at
+ * most resample_window(L, D, P) samples; where that is no more than RESAMPLE_WIN_MAX (32 KiB behind the taps) it is staged in LDS, otherwise
+ * every lane loads its own samples.  in [nstreams] rows of nin, in_pitch elements apart (may be NULL at nin = 0); hist [nstreams][P]; r the
+ * carried position, 0 or in [D - L, D); nin must be the K the position gives for nout: the launcher refuses any other.  The caller has checked
+ * the extents and every overlap */
+constexpr int RESAMPLE_MAX_L = 512, RESAMPLE_MAX_D = 4096, RESAMPLE_MAX_P = 32, RESAMPLE_MAX_STREAMS = 1 << 16, RESAMPLE_MAX_OUT = 1 << 24;
+constexpr int RESAMPLE_TILE = 256, RESAMPLE_WIN_MAX = 4096;
+constexpr long long resample_window(int L, int D, int P) { return (long long)(RESAMPLE_TILE - 1) * D / L + 1 + P; }
+constexpr bool resample_staged(int L, int D, int P) { return resample_window(L, D, P) <= RESAMPLE_WIN_MAX; }
+/* the taps, padded to a whole float2, then the window where it is staged */
+constexpr size_t resample_lds_bytes(int L, int D, int P, bool staged)
+{
+    return (size_t)((L * P + 1) & ~1) * sizeof(float) + (staged ? (size_t)resample_window(L, D, P) * sizeof(float2) : 0);
+}
+int prepare_resample();
+int launch_resample_push(const float2 *in, size_t in_pitch, int nin, const float2 *hist, const float *proto, int nstreams, int L, int D, int P, int r,
+                         int nout, float2 *out, size_t out_pitch, hipStream_t s);
+/* resample_history_kernel: next [nstreams][P] = per stream the last P of hist [P] followed by in [K], K >= 1; next is neither of them */
+int launch_resample_history(const float2 *hist, const float2 *in, size_t in_pitch, int K, int nstreams, int P, float2 *next, hipStream_t s);
 /* txchain.hip */
 int tx_history_symbols(void);        /* symbols of state per transmitter (uint8 each, 4 = none yet) */
 int launch_tx_shape(const uint8_t *sym, uint8_t *hist, const float *taps, float *sig, int nstreams, int nsym,

@@ -73,6 +73,7 @@ API_SYMBOLS = [
     "qpsk_nodesync_reset", "qpsk_nodesync_shifts", "qpsk_nodesync_push", "qpsk_nodesync_set",
     "qpsk_outer_reset_group", "qpsk_dispersal_batch", "qpsk_dispersal_sequence",
     "qpsk_channel_twiddles", "qpsk_channel_reset", "qpsk_channel_push", "qpsk_synth_reset", "qpsk_synth_push",
+    "qpsk_resample_reset", "qpsk_resample_need", "qpsk_resample_push",
 ]
 # the named puncturing patterns of include/qpsk_hip.h (QPSK_PUNCT_*): rate -> (period, keep0, keep1), bit r of a mask = step r of the period
 PUNCTURE = {"1/2": (1, 0x1, 0x1), "2/3": (2, 0x1, 0x3), "3/4": (3, 0x5, 0x3), "5/6": (5, 0x15, 0x0B), "7/8": (7, 0x51, 0x2F)}
@@ -203,6 +204,9 @@ def load():
     L.qpsk_channel_push.argtypes = [vp, vp, i32, vp, C.c_longlong]
     L.qpsk_synth_reset.argtypes = [vp, i32, i32, vp, vp, i32]
     L.qpsk_synth_push.argtypes = [vp, vp, C.c_longlong, i32, vp]
+    L.qpsk_resample_reset.argtypes = [vp, i32, i32, i32, i32, vp]
+    L.qpsk_resample_need.argtypes = [vp, i32]
+    L.qpsk_resample_push.argtypes = [vp, vp, C.c_longlong, i32, i32, vp, C.c_longlong]
     L.qpsk_outer_max_words.argtypes = [vp, i32]
     L.qpsk_outer_push.argtypes = [vp, vp, C.c_longlong, i32, i32, vp, vp, C.c_longlong, vp, vp, vp]
     L.qpsk_outer_interleave_batch.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
@@ -316,6 +320,20 @@ def channel_prototype(M, P, beta=8.0, gain=1.0):
     return np.float32(gain) * (h / h.sum()).astype(np.float32)
 
 
+def resample_prototype(L, D, P, beta=10.0, gain=None):
+    """A prototype for Modem.resample_reset(): the L P taps of a Kaiser-windowed sinc with its cut-off at 1 / (2 max(L, D)) cycles per
+    interpolated sample -- half the LOWER of the two rates, so neither the images of the interpolation nor the aliases of the decimation
+    pass -- symmetric, float32, every tap rounded once, their sum equal to gain (default: the interpolation gain L).  A numpy convenience:
+    the library designs no filter, and any finite taps do.  The transition band is the window's main lobe: the stop band begins
+    sqrt(1 + (beta / pi)^2) / (L P) cycles per interpolated sample beyond the cut-off (the Kaiser window's first null; 3.34 / (L P) at
+    beta = 10), the pass band ends as far below it, and the stop band lies about beta / 0.1102 + 8.7 dB down (Kaiser's rule: 99 dB)"""
+    n = int(L) * int(P)
+    t = (np.arange(n) - (n - 1) / 2.0) / float(max(int(L), int(D)))
+    h = np.sinc(t) * np.kaiser(n, float(beta))
+    h = 0.5 * (h + h[::-1])
+    return (h * (float(L if gain is None else gain) / h.sum())).astype(np.float32)
+
+
 def nodesync_shifts(puncture):
     """qpsk_nodesync_shifts: the delays (in dibits) a node sync has to try for a pattern, a key of PUNCTURE or a (period, keep0, keep1)
     tuple: nodesync_reset()'s nshift.  Host only, needs no GPU"""
@@ -366,6 +384,7 @@ class Modem:
         self._ns_links = 0        # links of the node sync (nodesync_reset)
         self._channel = None      # (M, nsel) of the channeliser (channel_reset)
         self._synth = None        # (M, nsel) of the synthesis bank (synth_reset)
+        self._resample = 0        # streams of the resampler (resample_reset)
 
     def _check(self, rc):
         if rc != 0:
@@ -1077,6 +1096,50 @@ class Modem:
         self._check(self.L.qpsk_synth_push(self.h, _ptr(c), int(pitch), T, _ptr(x)))
         self._synth_keep = (c,)      # the input stays alive until the stream has run the call
         return x
+
+    # ---- the rational resampler between the capture's rate and the modem's (RESAMPLER in include/qpsk_hip.h)
+    def resample_reset(self, nstreams, L, D, P, proto):
+        """qpsk_resample_reset: nstreams rows (1..65536) resampled by L / D (L 1..512, D 1..4096), P taps per branch (1..32), proto the
+        L P real taps with the interpolation gain in them (e.g. resample_prototype(L, D, P)).  Zeroes the history and the position"""
+        h = np.ascontiguousarray(np.asarray(proto, dtype=np.float32).reshape(-1))
+        if h.size != int(L) * int(P):
+            raise ValueError("resample_reset() proto must hold L * P = %d taps" % (int(L) * int(P)))
+        self._check(self.L.qpsk_resample_reset(self.h, int(nstreams), int(L), int(D), int(P), h.ctypes.data_as(C.c_void_p)))
+        self._resample = int(nstreams)
+
+    def resample_need(self, nout):
+        """qpsk_resample_need: the input samples per stream the NEXT resample() of nout outputs consumes (0 is possible when L > D)"""
+        rc = self.L.qpsk_resample_need(self.h, int(nout))
+        if rc < 0:
+            self._check(rc)
+        return rc
+
+    def resample(self, rows, nout, pitch=0, out_pitch=0):
+        """qpsk_resample_push: rows (nstreams, nin, 2) float32, the next nin samples of every stream, nin = resample_need(nout) (ValueError
+        otherwise) -> (nstreams, nout, 2) float32, the next nout outputs.  pitch: the complex samples between the INPUT's rows (0 = tight);
+        rows is then a view (nstreams, nin, 2) of a (nstreams, pitch, 2) float32 buffer on the device, read where it lies (what channel()
+        returns with its pitch).  out_pitch: the same for the OUTPUT's rows; the result is then a view of a (nstreams, out_pitch, 2) buffer
+        whose other samples are not written"""
+        t = self.torch
+        if not self._resample:
+            raise QpskError("resample() before resample_reset()")
+        S = self._resample
+        if pitch:
+            c = rows
+            if not isinstance(c, t.Tensor) or c.device != self.dev or c.dtype != t.float32 or c.dim() != 3 or \
+                    (c.shape[1] > 0 and (c.stride()[1:] != (2, 1) or (c.shape[0] > 1 and c.stride(0) != 2 * int(pitch)))):
+                raise ValueError("resample() with a pitch takes a float32 device view whose rows lie 2 * pitch floats apart")
+        else:
+            c = self._dev(rows, t.float32)
+        if c.dim() != 3 or c.shape[0] != S or c.shape[2] != 2:
+            raise ValueError("resample() input must be (%d, nin, 2) float32" % S)
+        need = self.resample_need(nout)
+        if c.shape[1] != need:
+            raise ValueError("resample() of %d outputs consumes %d samples per stream now, not %d" % (int(nout), need, c.shape[1]))
+        buf = self.empty((S, int(out_pitch) if out_pitch else int(nout), 2), t.float32)
+        self._check(self.L.qpsk_resample_push(self.h, _ptr(c) if need else None, int(pitch), need, int(nout), _ptr(buf), int(out_pitch)))
+        self._resample_keep = (c,)      # the input stays alive until the stream has run the call
+        return buf[:, :int(nout)]
 
     # ---- packets from continuous streams (qpsk_deframer_*)
     def deframer_reset(self, nstreams, sync, nbytes, min_score, max_packets=8):
