@@ -917,7 +917,7 @@ int qpsk_dispersal_sequence(int len, int group, int flags, uint8_t *out);
  *                overlap d_x.  QPSK_ERR_STATE before a reset
  * QPSK_ERR_ARG at the call for a bad argument -- a non-finite tap among them -- nothing launched.  A push is stream-ordered on the
  * context's stream and touches neither the receive streams, the deframers, the histogram mode's guess, the Viterbi scratch, the outer link
- * nor the node sync.  qpsk_ctx_last_kernel() names channel_push_kernel (channel_history_kernel, the launch behind it, moves the history
+ * nor the node sync.  qpsk_ctx_last_kernel() names channel_push_kernel (polyphase_history_kernel, the launch behind it, moves the history
  * into the second of two buffers, so that no launch reads what it writes).
  * Not built: oversampled banks; M that is no power of two; PCM or int16 wideband input; qpsk_multi; routing inside bench.py.  The
  * transmit twin is SYNTHESIS BANK below.  Usage: INTEGRATION.md 2.0.
@@ -965,7 +965,7 @@ int qpsk_channel_push(qpsk_ctx *ctx, const float *d_x, int T, float *d_out, long
  * looked at, nothing launched.  A push is stream-ordered on the context's stream.  The bank is state of its own: its calls touch neither
  * the channeliser, the receive streams, the deframers, the histogram mode's guess, the Viterbi scratch, the outer link nor the node sync,
  * and none of those calls touches the bank.  qpsk_ctx_last_kernel() names synth_filter_kernel (synth_transform_kernel runs in front of
- * it, channel_history_kernel behind it, into the second of two buffers, so that no launch reads what it writes).
+ * it, polyphase_history_kernel behind it, into the second of two buffers, so that no launch reads what it writes).
  * Not built: a fused single-launch bank for small M; oversampled banks; M that is no power of two; real or int16 output; qpsk_multi; routing
  * inside bench.py.  Usage: INTEGRATION.md 2.0.
  * ------------------------------------------------------------------------- */
@@ -1012,7 +1012,7 @@ int qpsk_synth_push(qpsk_ctx *ctx, const float *d_in, long long in_pitch, int T,
  * untouched; what the arguments alone decide is decided before the context is looked at.  A push is stream-ordered on the context's stream
  * with no host synchronisation.  The resampler is state of its own: its calls touch neither the two banks, the receive streams, the
  * transmitters, the deframers, the Viterbi scratch, the outer link nor the node sync, and none of those calls touches it.
- * qpsk_ctx_last_kernel() names resample_push_kernel (resample_history_kernel, the launch behind it when K > 0, moves the history into the
+ * qpsk_ctx_last_kernel() names resample_push_kernel (polyphase_history_kernel, the launch behind it when K > 0, moves the history into the
  * second of two buffers, so that no launch reads what it writes).
  * Not built: per-stream ratios; a ratio that changes while running (clock-drift tracking); irrational ratios and Farrow structures; real or
  * int16 rows; qpsk_multi; routing inside bench.py.  Usage: INTEGRATION.md 2.0.

@@ -8,21 +8,6 @@
 
 using namespace qpsk;
 
-/* no channeliser (qpsk_ctx_destroy): behind a synchronisation of the context's stream */
-void Channeliser::release()
-{
-    hipFree(state);
-    *this = Channeliser();
-}
-
-static int channel_log2(int M)
-{
-    if (M < 2 || M > CHANNEL_MAX_M || (M & (M - 1))) return -1;
-    int l = 0;
-    while ((1 << l) < M) l++;
-    return l;
-}
-
 /* tw[j] = ((float)cos(TAU j / M), (float)sin(TAU j / M)), j < M / 2: fft_lds.h's table rounded to fp32 */
 static void channel_twiddles(int M, float *tw)
 {
@@ -51,8 +36,7 @@ static int bank_reset(qpsk_ctx *c, Channeliser *bank, const char *who, int M, in
     if (channel_log2(M) < 0) return fail(QPSK_ERR_ARG, "%s: M = %d is no power of two in 2..%d", who, M, CHANNEL_MAX_M);
     if (P < 1 || P > CHANNEL_MAX_P) return fail(QPSK_ERR_ARG, "%s: P = %d outside 1..%d", who, P, CHANNEL_MAX_P);
     if (!h_proto) return fail(QPSK_ERR_ARG, "%s: null h_proto", who);
-    for (int r = 0; r < M * P; r++)
-        if (!isfinite(h_proto[r])) return fail(QPSK_ERR_ARG, "%s: h_proto[%d] is not finite", who, r);
+    if (int rc = taps_finite(who, h_proto, (size_t)M * P)) return rc;
     if (!h_chan) nsel = M;
     const int max_sel = distinct ? M : CHANNEL_MAX_SEL;
     if (nsel < 1 || nsel > max_sel) return fail(QPSK_ERR_ARG, "%s: nsel = %d outside 1..%d", who, nsel, max_sel);
@@ -66,42 +50,22 @@ static int bank_reset(qpsk_ctx *c, Channeliser *bank, const char *who, int M, in
             named[(size_t)chan[i]] = true;
         }
     }
-    if (!c) return fail(QPSK_ERR_ARG, "%s: null context", who);
-    if (bind(c)) return QPSK_ERR_HIP;
-    /* one allocation: proto [P M] floats, tw [M / 2][2], the two histories [(P - 1) M][2] each, chan [nsel].  Allocated FIRST, so that a
-     * failure leaves the bank the context has as it was */
-    const size_t nproto = (size_t)M * P, nhist = (size_t)M * (P - 1);
-    const size_t floats = nproto + (size_t)M + 4 * nhist;
-    uint8_t *state = nullptr;
-    if (hipMalloc((void **)&state, floats * sizeof(float) + (size_t)nsel * sizeof(int32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(QPSK_ERR_ALLOC, "%s: hipMalloc of the state (M = %d, P = %d, nsel = %d)", who, M, P, nsel);
-    }
+    /* the state: proto [P M] floats and tw [M / 2][2], the two histories [(P - 1) M][2] each, chan [nsel] */
+    const size_t nproto = (size_t)M * P, nhist = (size_t)M * (P - 1) * 2;
     std::vector<float> head(nproto + (size_t)M);
     memcpy(head.data(), h_proto, nproto * sizeof(float));
     channel_twiddles(M, head.data() + nproto);
-    float *f = reinterpret_cast<float *>(state);
-    hipError_t e = hipStreamSynchronize(c->stream);      /* pushes on the old state may still run */
-    if (e == hipSuccess) e = hipMemcpy(f, head.data(), head.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess && nhist) e = hipMemset(f + head.size(), 0, 4 * nhist * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(f + floats, chan.data(), chan.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        hipFree(state);
-        return fail(QPSK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    }
-    Channeliser &ch = *bank;
-    ch.release();
-    ch.state = state;
-    ch.M = M;
-    ch.P = P;
-    ch.nsel = nsel;
-    ch.proto = f;
-    ch.tw = f + nproto;
-    ch.hist[0] = nhist ? f + head.size() : nullptr;
-    ch.hist[1] = nhist ? f + head.size() + 2 * nhist : nullptr;
-    ch.chan = reinterpret_cast<int32_t *>(f + floats);
-    ch.cur = 0;
-    ch.ready = true;
+    char sizes[64];
+    snprintf(sizes, sizeof sizes, "M = %d, P = %d, nsel = %d", M, P, nsel);
+    Channeliser fresh;
+    if (int rc = polyphase_reset(c, &fresh, who, sizes, head.data(), head.size(), nhist, chan.data(), chan.size() * sizeof(int32_t))) return rc;
+    fresh.M = M;
+    fresh.P = P;
+    fresh.nsel = nsel;
+    fresh.tw = fresh.proto + nproto;
+    fresh.chan = reinterpret_cast<int32_t *>(fresh.proto + head.size() + 2 * nhist);
+    bank->release();
+    *bank = fresh;
     return QPSK_OK;
 }
 
@@ -114,13 +78,6 @@ int qpsk_channel_reset(qpsk_ctx *c, int M, int P, const float *h_proto, const in
 int qpsk_synth_reset(qpsk_ctx *c, int M, int P, const float *h_proto, const int32_t *h_chan, int nsel)
 {
     return bank_reset(c, c ? &c->synth.bank : nullptr, "qpsk_synth_reset", M, P, h_proto, h_chan, nsel, true);
-}
-
-/* no synthesis bank (qpsk_ctx_destroy): behind a synchronisation of the context's stream */
-void Synthesiser::release()
-{
-    bank.release();
-    scratch.release();
 }
 
 int qpsk_synth_push(qpsk_ctx *c, const float *d_in, long long in_pitch, int T, float *d_x)
@@ -143,18 +100,11 @@ int qpsk_synth_push(qpsk_ctx *c, const float *d_in, long long in_pitch, int T, f
     /* a scratch that has to grow waits for the stream once (ensure); a growth that fails leaves the bank and its history as they were */
     if (int rc = ensure(c, c->synth.scratch, xn * cplx)) return rc;
     float2 *V = reinterpret_cast<float2 *>(c->synth.scratch.p);
-    const float2 *hist = reinterpret_cast<const float2 *>(b.hist[b.cur]);
-    b.ready = false;      /* until every launch is in the queue */
+    const float2 *hist = b.begin_push();
     KERNEL_TRY(launch_synth_transform(reinterpret_cast<const float2 *>(d_in), ip, T, b.M, reinterpret_cast<const float2 *>(b.tw), b.chan, b.nsel, V,
                                       c->stream));
     KERNEL_TRY(launch_synth_filter(V, hist, T, b.M, b.P, b.proto, reinterpret_cast<float2 *>(d_x), c->stream));
-    c->last_kernel = "synth_filter_kernel";
-    if (b.P > 1) {
-        KERNEL_TRY(launch_channel_history(hist, V, (size_t)b.M * (b.P - 1), xn, reinterpret_cast<float2 *>(b.hist[b.cur ^ 1]), c->stream));
-        b.cur ^= 1;
-    }
-    b.ready = true;
-    return QPSK_OK;
+    return polyphase_end_push(c, b, "synth_filter_kernel", V, xn, xn, 1, (size_t)b.M * (b.P - 1));
 }
 
 int qpsk_channel_push(qpsk_ctx *c, const float *d_x, int T, float *d_out, long long out_pitch)
@@ -175,15 +125,7 @@ int qpsk_channel_push(qpsk_ctx *c, const float *d_x, int T, float *d_out, long l
     if (overlap(out, in)) return fail(QPSK_ERR_ARG, "%s: d_out overlaps d_x", who);
     if (bind(c)) return QPSK_ERR_HIP;
     const float2 *x = reinterpret_cast<const float2 *>(d_x);
-    const float2 *hist = reinterpret_cast<const float2 *>(ch.hist[ch.cur]);
-    ch.ready = false;      /* until both launches are in the queue */
-    KERNEL_TRY(launch_channel_push(x, T, ch.M, ch.P, ch.proto, reinterpret_cast<const float2 *>(ch.tw), hist, ch.chan, ch.nsel,
+    KERNEL_TRY(launch_channel_push(x, T, ch.M, ch.P, ch.proto, reinterpret_cast<const float2 *>(ch.tw), ch.begin_push(), ch.chan, ch.nsel,
                                    reinterpret_cast<float2 *>(d_out), op, c->stream));
-    c->last_kernel = "channel_push_kernel";
-    if (ch.P > 1) {
-        KERNEL_TRY(launch_channel_history(hist, x, (size_t)ch.M * (ch.P - 1), xn, reinterpret_cast<float2 *>(ch.hist[ch.cur ^ 1]), c->stream));
-        ch.cur ^= 1;
-    }
-    ch.ready = true;
-    return QPSK_OK;
+    return polyphase_end_push(c, ch, "channel_push_kernel", x, xn, xn, 1, (size_t)ch.M * (ch.P - 1));
 }

@@ -133,6 +133,50 @@ int qpsk::replace_state(qpsk_ctx *c, const char *who, const char *noun, int coun
     return QPSK_OK;
 }
 
+/* the two steps of a polyphase stage's reset and the end of its push (api_ctx.h) */
+int qpsk::taps_finite(const char *who, const float *h_proto, size_t n)
+{
+    for (size_t i = 0; i < n; i++)
+        if (!isfinite(h_proto[i])) return fail(QPSK_ERR_ARG, "%s: h_proto[%d] is not finite", who, (int)i);
+    return QPSK_OK;
+}
+
+int qpsk::polyphase_reset(qpsk_ctx *c, PolyphaseState *fresh, const char *who, const char *sizes, const float *h_head, size_t nhead, size_t nhist,
+                          const void *h_tail, size_t ntail)
+{
+    if (!c) return fail(QPSK_ERR_ARG, "%s: null context", who);
+    if (bind(c)) return QPSK_ERR_HIP;
+    const size_t hist_at = (nhead + 1) & ~(size_t)1, floats = hist_at + 2 * nhist;
+    float *f = nullptr;
+    if (hipMalloc((void **)&f, floats * sizeof(float) + ntail) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(QPSK_ERR_ALLOC, "%s: hipMalloc of the state (%s)", who, sizes);
+    }
+    hipError_t e = hipStreamSynchronize(c->stream);      /* pushes on the old state may still run */
+    if (e == hipSuccess) e = hipMemcpy(f, h_head, nhead * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && nhist) e = hipMemset(f + hist_at, 0, 2 * nhist * sizeof(float));
+    if (e == hipSuccess && ntail) e = hipMemcpy(f + floats, h_tail, ntail, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(f);
+        return fail(QPSK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    fresh->state = reinterpret_cast<uint8_t *>(f);
+    fresh->proto = f;
+    fresh->hist[0] = nhist ? f + hist_at : nullptr;
+    fresh->hist[1] = nhist ? f + hist_at + nhist : nullptr;
+    fresh->ready = true;
+    return QPSK_OK;
+}
+
+int qpsk::polyphase_end_push(qpsk_ctx *c, PolyphaseState &st, const char *kernel, const float2 *in, size_t in_pitch, size_t K, int rows, size_t n)
+{
+    c->last_kernel = kernel;
+    const float2 *hist = reinterpret_cast<const float2 *>(st.hist[st.cur]);
+    if (K > 0 && n > 0) KERNEL_TRY(launch_polyphase_history(hist, in, in_pitch, K, rows, n, st.flip(), c->stream));
+    st.ready = true;
+    return QPSK_OK;
+}
+
 const char *qpsk_last_error(void) { return g_err; }
 const char *qpsk_version(void) { return "qpsk_hip 0.3 (gfx950)"; }
 

@@ -271,17 +271,27 @@ struct QPSK_UNIT_LOCAL Dispersal {
     void release();               /* leaves the group value-initialised: no table.  Behind a synchronisation of the context's stream */
 };
 
-/* api_channel.cpp.  The polyphase channeliser (qpsk_channel_*): one allocation (`state`) that holds the prototype, the transform's table, the
- * selection and TWO histories of (P - 1) M samples -- a push reads hist[cur] and leaves the next history in the other, so no launch reads what
- * it writes */
-struct QPSK_UNIT_LOCAL Channeliser {
+/* What the three polyphase stages' groups share: one allocation (`state`) that begins with the taps and holds TWO histories -- a push reads
+ * hist[cur] and leaves the next history in the other, so no launch reads what it writes.  polyphase_reset fills one; a push is
+ * begin_push(), the stage's launches, polyphase_end_push (below) */
+struct QPSK_UNIT_LOCAL PolyphaseState {
     uint8_t *state = nullptr;
-    int M = 0, P = 0, nsel = 0;
-    float *proto = nullptr, *tw = nullptr, *hist[2] = {nullptr, nullptr};      /* into state; hist: NULL at P = 1 */
-    int32_t *chan = nullptr;
+    float *proto = nullptr, *hist[2] = {nullptr, nullptr};      /* into state; hist: NULL where the stage has none */
     int cur = 0;
     bool ready = false;           /* a reset has completed and no push has failed since */
-    void release();               /* leaves the group value-initialised: no channeliser.  Behind a synchronisation of the context's stream */
+    /* a push begins: the history its launches read.  Not ready until polyphase_end_push: a push that fails between the two ends the stage */
+    const float2 *begin_push() { ready = false; return reinterpret_cast<const float2 *>(hist[cur]); }
+    float2 *flip() { return reinterpret_cast<float2 *>(hist[cur ^= 1]); }      /* the other history, from now on the current one */
+    void release() { hipFree(state); *this = PolyphaseState(); }               /* behind a synchronisation of the context's stream */
+};
+
+/* api_channel.cpp.  The polyphase channeliser (qpsk_channel_*): behind the prototype the state holds the transform's table and the
+ * selection; the histories are (P - 1) M samples, none at P = 1 */
+struct QPSK_UNIT_LOCAL Channeliser : PolyphaseState {
+    int M = 0, P = 0, nsel = 0;
+    float *tw = nullptr;          /* into state */
+    int32_t *chan = nullptr;
+    void release() { PolyphaseState::release(); *this = Channeliser(); }      /* leaves the group value-initialised: no channeliser */
 };
 
 /* api_channel.cpp.  The polyphase synthesis bank (qpsk_synth_*): the channeliser's state under the transmit bank's meaning -- the histories
@@ -290,20 +300,15 @@ struct QPSK_UNIT_LOCAL Channeliser {
 struct QPSK_UNIT_LOCAL Synthesiser {
     Channeliser bank;
     DevBuf scratch;               /* V [T][M][2] floats of the running push */
-    void release();               /* leaves the group value-initialised: no bank, no scratch.  Behind a synchronisation of the context's stream */
+    void release() { bank.release(); scratch.release(); }      /* no bank, no scratch.  Behind a synchronisation of the context's stream */
 };
 
-/* api_resample.cpp.  The batched rational resampler (qpsk_resample_*): one allocation (`state`) that holds the L P taps and TWO histories of
- * the last P consumed samples per stream -- a push reads hist[cur] and leaves the next history in the other, so no launch reads what it
- * writes.  The position r = n0 D - c0 L (0 after a reset, then in [D - L, D)) is the same for every stream and is the host's */
-struct QPSK_UNIT_LOCAL Resampler {
-    uint8_t *state = nullptr;
+/* api_resample.cpp.  The batched rational resampler (qpsk_resample_*): the L P taps and histories of the last P consumed samples per
+ * stream.  The position r = n0 D - c0 L (0 after a reset, then in [D - L, D)) is the same for every stream and is the host's */
+struct QPSK_UNIT_LOCAL Resampler : PolyphaseState {
     int nstreams = 0, L = 0, D = 0, P = 0;
     int r = 0;
-    float *proto = nullptr, *hist[2] = {nullptr, nullptr};      /* into state */
-    int cur = 0;
-    bool ready = false;           /* a reset has completed and no push has failed since */
-    void release();               /* leaves the group value-initialised: no resampler.  Behind a synchronisation of the context's stream */
+    void release() { PolyphaseState::release(); *this = Resampler(); }      /* leaves the group value-initialised: no resampler */
 };
 
 } // namespace qpsk
@@ -367,6 +372,20 @@ QPSK_UNIT_LOCAL int use_context_gains(qpsk_ctx *c);
  * synchronisation of the context's stream, because pushes of the old state may still run.  The caller then release()s the old group,
  * assigns the new one and launches its init kernel */
 QPSK_UNIT_LOCAL int replace_state(qpsk_ctx *c, const char *who, const char *noun, int count, size_t stride, uint8_t **state);
+/* for a reset of a polyphase stage (who: the entry point): are the n taps finite ... */
+QPSK_UNIT_LOCAL int taps_finite(const char *who, const float *h_proto, size_t n);
+/* ... and, behind the stage's own checks of its arguments, the new state in *fresh, a group of the caller's own that holds nothing yet:
+ * nhead floats of h_head (the taps first), rounded up to a whole complex value, two zeroed histories of nhist floats each, ntail bytes of
+ * h_tail; sizes: the stage's own, for the allocation's refusal.  Refuses a NULL context; allocates FIRST, so that a failure leaves the
+ * stage the context has as it was; uploads behind a synchronisation of the context's stream, because pushes on the old state may still
+ * run.  The caller then sets its own members in *fresh, release()s the context's group and assigns the new one */
+QPSK_UNIT_LOCAL int polyphase_reset(qpsk_ctx *c, PolyphaseState *fresh, const char *who, const char *sizes, const float *h_head, size_t nhead,
+                                    size_t nhist, const void *h_tail, size_t ntail);
+/* behind a push's launches on st.begin_push() (`kernel`: the name qpsk_ctx_last_kernel reports): unless K = 0 or the stage has no history
+ * (n = 0), polyphase_history_kernel leaves the last n of every row's (history, in [K]) in the other history, which becomes the current
+ * one; the stage is ready again */
+QPSK_UNIT_LOCAL int polyphase_end_push(qpsk_ctx *c, PolyphaseState &st, const char *kernel, const float2 *in, size_t in_pitch, size_t K, int rows,
+                                       size_t n);
 
 /* ---- api_rx.cpp, for the streams' kernels apart */
 QPSK_UNIT_LOCAL int fir_full_rate(qpsk_ctx *c, const float *x, const float *memory, float *y, int nframes, int length, size_t in_pitch = 0);

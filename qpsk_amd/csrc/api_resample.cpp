@@ -6,13 +6,6 @@
 
 using namespace qpsk;
 
-/* no resampler (qpsk_ctx_destroy): behind a synchronisation of the context's stream */
-void Resampler::release()
-{
-    hipFree(state);
-    *this = Resampler();
-}
-
 /* floor(a / b), b > 0 */
 static long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
@@ -46,39 +39,18 @@ int qpsk_resample_reset(qpsk_ctx *c, int nstreams, int L, int D, int P, const fl
     if (D < 1 || D > RESAMPLE_MAX_D) return fail(QPSK_ERR_ARG, "%s: D = %d outside 1..%d", who, D, RESAMPLE_MAX_D);
     if (P < 1 || P > RESAMPLE_MAX_P) return fail(QPSK_ERR_ARG, "%s: P = %d outside 1..%d", who, P, RESAMPLE_MAX_P);
     if (!h_proto) return fail(QPSK_ERR_ARG, "%s: null h_proto", who);
-    for (int i = 0; i < L * P; i++)
-        if (!isfinite(h_proto[i])) return fail(QPSK_ERR_ARG, "%s: h_proto[%d] is not finite", who, i);
-    if (!c) return fail(QPSK_ERR_ARG, "%s: null context", who);
-    if (bind(c)) return QPSK_ERR_HIP;
-    /* one allocation: proto [L P] floats (padded to a whole complex sample), the two histories [nstreams][P][2] each.  Allocated FIRST, so
-     * that a failure leaves the resampler the context has as it was */
-    const size_t nproto = ((size_t)L * P + 1) & ~(size_t)1, nhist = (size_t)nstreams * P * 2;
-    uint8_t *state = nullptr;
-    if (hipMalloc((void **)&state, (nproto + 2 * nhist) * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(QPSK_ERR_ALLOC, "%s: hipMalloc of the state (nstreams = %d, L = %d, P = %d)", who, nstreams, L, P);
-    }
-    float *f = reinterpret_cast<float *>(state);
-    hipError_t e = hipStreamSynchronize(c->stream);      /* pushes on the old state may still run */
-    if (e == hipSuccess) e = hipMemcpy(f, h_proto, (size_t)L * P * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(f + nproto, 0, 2 * nhist * sizeof(float));
-    if (e != hipSuccess) {
-        hipFree(state);
-        return fail(QPSK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    }
-    Resampler &rs = c->resample;
-    rs.release();
-    rs.state = state;
-    rs.nstreams = nstreams;
-    rs.L = L;
-    rs.D = D;
-    rs.P = P;
-    rs.r = 0;
-    rs.proto = f;
-    rs.hist[0] = f + nproto;
-    rs.hist[1] = f + nproto + nhist;
-    rs.cur = 0;
-    rs.ready = true;
+    if (int rc = taps_finite(who, h_proto, (size_t)L * P)) return rc;
+    /* the state: proto [L P] floats, the two histories [nstreams][P][2] each */
+    char sizes[64];
+    snprintf(sizes, sizeof sizes, "nstreams = %d, L = %d, P = %d", nstreams, L, P);
+    Resampler fresh;
+    if (int rc = polyphase_reset(c, &fresh, who, sizes, h_proto, (size_t)L * P, (size_t)nstreams * P * 2, nullptr, 0)) return rc;
+    fresh.nstreams = nstreams;
+    fresh.L = L;
+    fresh.D = D;
+    fresh.P = P;
+    c->resample.release();
+    c->resample = fresh;
     return QPSK_OK;
 }
 
@@ -119,16 +91,8 @@ int qpsk_resample_push(qpsk_ctx *c, const float *d_in, long long in_pitch, int n
     if (overlap(out, in)) return fail(QPSK_ERR_ARG, "%s: d_out overlaps d_in", who);
     if (bind(c)) return QPSK_ERR_HIP;
     const float2 *x = reinterpret_cast<const float2 *>(nin ? d_in : nullptr);
-    const float2 *hist = reinterpret_cast<const float2 *>(rs.hist[rs.cur]);
-    rs.ready = false;      /* until every launch is in the queue */
-    KERNEL_TRY(launch_resample_push(x, ip, nin, hist, rs.proto, rs.nstreams, rs.L, rs.D, rs.P, rs.r, nout, reinterpret_cast<float2 *>(d_out), op,
-                                    c->stream));
-    c->last_kernel = "resample_push_kernel";
-    if (nin > 0) {      /* K = 0 leaves the history */
-        KERNEL_TRY(launch_resample_history(hist, x, ip, nin, rs.nstreams, rs.P, reinterpret_cast<float2 *>(rs.hist[rs.cur ^ 1]), c->stream));
-        rs.cur ^= 1;
-    }
+    KERNEL_TRY(launch_resample_push(x, ip, nin, rs.begin_push(), rs.proto, rs.nstreams, rs.L, rs.D, rs.P, rs.r, nout,
+                                    reinterpret_cast<float2 *>(d_out), op, c->stream));
     rs.r += (int)((long long)nout * rs.D - K * rs.L);
-    rs.ready = true;
-    return QPSK_OK;
+    return polyphase_end_push(c, rs, "resample_push_kernel", x, ip, (size_t)nin, rs.nstreams, (size_t)rs.P);      /* K = 0 leaves the history */
 }

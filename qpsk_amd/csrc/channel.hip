@@ -5,26 +5,22 @@
  * channel_push_kernel<PT, NT>: a workgroup of NT threads takes a tile of TB consecutive output times (TB = channel_tile(M), kernels.h) and
  * runs three phases over one LDS image of TB rows of M complex values:
  *   1. branch sums.  The NT threads are G = NT / min(M, NT) groups of min(M, NT) lanes; a group takes R = TB / G consecutive times, a lane
- *      the branches p = lane, lane + NT, ...  Lanes adjacent in p read adjacent samples (reversed), and adjacent taps.  PT = P > 0: the
- *      lane keeps the P taps and the last P - 1 samples of its branch in registers and loads one new sample per time (a run re-reads
- *      (R + P - 1) / R of its input); PT = 0, any P: every product loads its tap and its sample, nothing is kept.  u_m[p] goes to
- *      row m, element bitrev(p).
+ *      the branches p = lane, lane + NT, ...  Lanes adjacent in p read adjacent samples (reversed), and adjacent taps.  A branch's run of R
+ *      times is polyphase.h's (PT = P > 0: taps and window in registers; PT = 0: any P).  u_m[p] goes to row m, element bitrev(p).
  *   2. the transform (channel_fft.h, shared with synth.hip): fft_lds.h's butterflies, inverse sign, fp32.  Two stages per pass over the
  *      LDS: a thread holds the four values i0 + {0, 1, 2, 3} half of stages s and s + 1 and performs the four butterflies of the
  *      definition on them, the operands and the order of every operation as there; an odd log2 M runs stage 1 alone first.
  *   3. the transposed store: TB consecutive times of a selected channel are 8 TB contiguous bytes of its row.
  * Element e of a row lies at e + (e >> 5), rows M + (M >> 5) + 1 elements apart: the strided accesses of the early stages and of the store's
  * column reads spread over the banks.  Times at or beyond T are computed on the push's last block and not stored; no address outside the
- * buffers is formed for them.
- *
- * channel_history_kernel: the last (P - 1) M samples of s into the OTHER history buffer (the host swaps the two), so that no launch reads
- * what it writes, and a push shorter than the history shifts it.
+ * buffers is formed for them.  Behind the push, polyphase_history_kernel (polyphase.hip) moves the history on.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "channel_fft.h"
 #include "kernels.h"
+#include "polyphase.h"
 
 namespace qpsk {
 
@@ -42,15 +38,6 @@ struct ChannelArgs {
     int tb, run, lanes;       /* the tile, R, min(M, NT) */
 };
 
-/* block bb of the push (negative: of the history), branch p.  No branch, so that a lane's loads go out together: a block at or beyond T
- * (an output time that is never stored) reads the push's last block instead */
-__device__ __forceinline__ float2 sample(const ChannelArgs &a, long long bb, int p)
-{
-    bb = bb < a.T ? bb : (long long)a.T - 1;
-    const float2 *block = bb >= 0 ? a.x + (size_t)bb * a.M : a.hist + (size_t)(bb + a.P - 1) * a.M;
-    return block[a.M - 1 - p];
-}
-
 template <int PT, int NT>
 __global__ void __launch_bounds__(NT) channel_push_kernel(ChannelArgs a)
 {
@@ -67,42 +54,9 @@ __global__ void __launch_bounds__(NT) channel_push_kernel(ChannelArgs a)
         const int r0 = grp * a.run;
         for (int p = lane; p < M; p += NT) {
             const int at = channel_phys((int)(__brev((unsigned)p) >> (32 - log2m)));
-            if constexpr (PT > 0) {
-                float h[PT];
-                float2 w[PT > 1 ? PT - 1 : 1];      /* w[j] = block(m - 1 - j) */
-#pragma unroll
-                for (int q = 0; q < PT; q++) h[q] = a.proto[(size_t)q * M + p];
-#pragma unroll
-                for (int j = 0; j < PT - 1; j++) w[j] = sample(a, m0 + r0 - 1 - j, p);
-#pragma unroll RUN_UNROLL
-                for (int r = r0; r < r0 + a.run; r++) {
-                    const float2 x0 = sample(a, m0 + r, p);
-                    float accr = h[0] * x0.x, acci = h[0] * x0.y;
-#pragma unroll
-                    for (int q = 1; q < PT; q++) {
-                        accr = accr + h[q] * w[q - 1].x;
-                        acci = acci + h[q] * w[q - 1].y;
-                    }
-                    v[r * row_pitch + at] = make_float2(accr, acci);
-#pragma unroll
-                    for (int j = PT - 2; j > 0; j--) w[j] = w[j - 1];
-                    if (PT > 1) w[0] = x0;
-                }
-            } else {
-                for (int r = r0; r < r0 + a.run; r++) {
-                    const float2 x0 = sample(a, m0 + r, p);
-                    const float h0 = a.proto[p];
-                    float accr = h0 * x0.x, acci = h0 * x0.y;
-#pragma unroll 4
-                    for (int q = 1; q < a.P; q++) {
-                        const float2 xq = sample(a, m0 + r - q, p);
-                        const float hq = a.proto[(size_t)q * M + p];
-                        accr = accr + hq * xq.x;
-                        acci = acci + hq * xq.y;
-                    }
-                    v[r * row_pitch + at] = make_float2(accr, acci);
-                }
-            }
+            polyphase_branch_run<PT, RUN_UNROLL>(
+                a.proto, p, M, a.P, r0, a.run, [&](long long r) { return polyphase_at(a.x, a.hist, m0 + r, a.T, a.P, M, M - 1 - p); },
+                [&](int r, float2 u) { v[r * row_pitch + at] = u; });
         }
     }
     __syncthreads();
@@ -121,16 +75,6 @@ __global__ void __launch_bounds__(NT) channel_push_kernel(ChannelArgs a)
             const long long i = item >> log2tb;
             if (r < rows) a.out[(size_t)i * a.pitch + (size_t)(m0 + r)] = v[r * row_pitch + channel_phys(a.chan[i])];
         }
-    }
-}
-
-/* next [n] = the last n = (P - 1) M samples of (hist [n], x [xn]) */
-__global__ void __launch_bounds__(256) channel_history_kernel(const float2 *__restrict__ hist, const float2 *__restrict__ x, size_t n, size_t xn,
-                                                              float2 *__restrict__ next)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const size_t at = i + xn;      /* in s */
-        next[i] = at < n ? hist[at] : x[at - n];
     }
 }
 
@@ -162,11 +106,10 @@ int prepare_channel()
 int launch_channel_push(const float2 *x, int T, int M, int P, const float *proto, const float2 *tw, const float2 *hist, const int32_t *chan, int nsel,
                         float2 *out, size_t pitch, hipStream_t s)
 {
-    if (!x || !proto || !tw || !chan || !out || T < 1 || M < 2 || M > CHANNEL_MAX_M || (M & (M - 1)) || P < 1 || P > CHANNEL_MAX_P ||
-        (P > 1 && !hist) || nsel < 1 || pitch < (size_t)T || (long long)T * M > CHANNEL_MAX_SAMPLES)
+    const int log2m = channel_log2(M);
+    if (!x || !proto || !tw || !chan || !out || T < 1 || log2m < 0 || P < 1 || P > CHANNEL_MAX_P || (P > 1 && !hist) || nsel < 1 ||
+        pitch < (size_t)T || (long long)T * M > CHANNEL_MAX_SAMPLES)
         return (int)hipErrorInvalidValue;
-    int log2m = 0;
-    while ((1 << log2m) < M) log2m++;
     const int tb = channel_tile(M), nt = channel_threads(M);
     const int lanes = M < nt ? M : nt, run = tb / (nt / lanes);
     if (run < 1 || channel_lds_bytes(M, tb) > (size_t)MAX_LDS_BYTES) return (int)hipErrorInvalidValue;
@@ -180,14 +123,6 @@ int launch_channel_push(const float2 *x, int T, int M, int P, const float *proto
         if (P == 8) launch_push<8, 1024>(a, blocks, s);      /* P = 16 would spill under the 128 registers of 1024 threads */
         else launch_push<0, 1024>(a, blocks, s);
     }
-    return (int)hipGetLastError();
-}
-
-int launch_channel_history(const float2 *hist, const float2 *x, size_t n, size_t xn, float2 *next, hipStream_t s)
-{
-    if (!hist || !x || !next || n < 1 || xn < 1) return (int)hipErrorInvalidValue;
-    const size_t want = (n + 255) / 256;
-    hipLaunchKernelGGL(channel_history_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, hist, x, n, xn, next);
     return (int)hipGetLastError();
 }
 

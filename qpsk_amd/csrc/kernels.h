@@ -564,6 +564,14 @@ int launch_rs_cross_place(const uint8_t *bytes, size_t byte_pitch, const int32_t
  * entry in [0, M): the caller has checked them, and every overlap; out rows pitch >= T elements apart */
 constexpr int CHANNEL_MAX_M = 4096, CHANNEL_MAX_P = 32, CHANNEL_MAX_SEL = 1 << 16;
 constexpr long long CHANNEL_MAX_SAMPLES = 1ll << 30;      /* T M of one push */
+/* log2 M of a power of two in 2..CHANNEL_MAX_M, -1 for any other M: both banks' test of M, on the host and in the launchers */
+constexpr int channel_log2(int M)
+{
+    if (M < 2 || M > CHANNEL_MAX_M || (M & (M - 1))) return -1;
+    int l = 1;
+    while ((1 << l) < M) l++;
+    return l;
+}
 constexpr int channel_threads(int M) { return M >= 1024 ? 1024 : 256; }
 constexpr int channel_tile(int M) { return M >= 1024 ? 16384 / M : M >= 64 ? 8192 / M : 128; }
 /* the LDS image of tb rows: element e of a row at e + (e >> 5), rows M + (M >> 5) + 1 elements apart (channel_fft.h) */
@@ -571,13 +579,15 @@ constexpr size_t channel_lds_bytes(int M, int tb) { return (size_t)(M + (M >> 5)
 int prepare_channel();
 int launch_channel_push(const float2 *x, int T, int M, int P, const float *proto, const float2 *tw, const float2 *hist, const int32_t *chan, int nsel,
                         float2 *out, size_t pitch, hipStream_t s);
-/* channel_history_kernel: next [n] = the last n samples of hist [n] followed by x [xn]; next is neither of them */
-int launch_channel_history(const float2 *hist, const float2 *x, size_t n, size_t xn, float2 *next, hipStream_t s);
+/* polyphase.hip: the history of all three polyphase stages moves on.  polyphase_history_kernel: next [rows][n] = per row the last n values
+ * of hist [n] followed by in [K], the rows of `in` in_pitch >= K >= 1 elements apart; next is neither of them.  K < n shifts the history.
+ * The banks' is one row: n = (P - 1) M, K = T M */
+int launch_polyphase_history(const float2 *hist, const float2 *in, size_t in_pitch, size_t K, int rows, size_t n, float2 *next, hipStream_t s);
 /* synth.hip: the polyphase synthesis bank (the definition: include/qpsk_hip.h, SYNTHESIS BANK), two launches through the scratch V [T][M] of
  * transformed vectors.  synth_transform_kernel has the channeliser's geometry (channel_tile, channel_threads): in [nsel] rows pitch >= T
  * elements apart; chan [nsel], DISTINCT entries in [0, M): the caller has checked them, and every overlap.  synth_filter_kernel: a lane
  * takes SYNTH_RUN consecutive times of one branch; hist [P - 1][M] (NULL at P = 1) = the vectors before the push; x [T M].  The history
- * moves on with launch_channel_history(hist, V, (P - 1) M, T M, next) */
+ * moves on with launch_polyphase_history(hist, V, T M, T M, 1, (P - 1) M, next) */
 constexpr long long SYNTH_MAX_SAMPLES = 1ll << 27;      /* T M of one push: a scratch of 1 GiB */
 constexpr int SYNTH_RUN = 16;
 int prepare_synth();
@@ -588,7 +598,7 @@ int launch_synth_filter(const float2 *V, const float2 *hist, int T, int M, int P
  * most resample_window(L, D, P) samples; where that is no more than RESAMPLE_WIN_MAX (32 KiB behind the taps) it is staged in LDS, otherwise
  * every lane loads its own samples.  in [nstreams] rows of nin, in_pitch elements apart (may be NULL at nin = 0); hist [nstreams][P]; r the
  * carried position, 0 or in [D - L, D); nin must be the K the position gives for nout: the launcher refuses any other.  The caller has checked
- * the extents and every overlap */
+ * the extents and every overlap.  The history moves on with launch_polyphase_history(hist, in, in_pitch, nin, nstreams, P, next) where nin > 0 */
 constexpr int RESAMPLE_MAX_L = 512, RESAMPLE_MAX_D = 4096, RESAMPLE_MAX_P = 32, RESAMPLE_MAX_STREAMS = 1 << 16, RESAMPLE_MAX_OUT = 1 << 24;
 constexpr int RESAMPLE_TILE = 256, RESAMPLE_WIN_MAX = 4096;
 constexpr long long resample_window(int L, int D, int P) { return (long long)(RESAMPLE_TILE - 1) * D / L + 1 + P; }
@@ -601,8 +611,6 @@ constexpr size_t resample_lds_bytes(int L, int D, int P, bool staged)
 int prepare_resample();
 int launch_resample_push(const float2 *in, size_t in_pitch, int nin, const float2 *hist, const float *proto, int nstreams, int L, int D, int P, int r,
                          int nout, float2 *out, size_t out_pitch, hipStream_t s);
-/* resample_history_kernel: next [nstreams][P] = per stream the last P of hist [P] followed by in [K], K >= 1; next is neither of them */
-int launch_resample_history(const float2 *hist, const float2 *in, size_t in_pitch, int K, int nstreams, int P, float2 *next, hipStream_t s);
 /* txchain.hip */
 int tx_history_symbols(void);        /* symbols of state per transmitter (uint8 each, 4 = none yet) */
 int launch_tx_shape(const uint8_t *sym, uint8_t *hist, const float *taps, float *sig, int nstreams, int nsym,

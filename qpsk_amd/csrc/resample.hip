@@ -15,8 +15,8 @@
  * No address outside the buffers is formed: i <= K - 1 = nin - 1 for the push's last output (the host has refused any other nin), i - q >= -P,
  * and lanes beyond nout do nothing after the barrier.
  *
- * resample_history_kernel: the last P of (history, push) per stream into the OTHER history buffer (the host swaps the two), so that no
- * launch reads what it writes, and a push of K < P samples shifts the history.  A push with K = 0 launches none and swaps nothing.
+ * Behind the push, polyphase_history_kernel (polyphase.hip) moves the history on, n = P per stream; a push with K = 0 launches none and
+ * swaps nothing.  The tap loop is not polyphase.h's: an output has its own branch b and no neighbour in time to share a window with.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -105,17 +105,6 @@ __global__ void __launch_bounds__(RESAMPLE_TILE) resample_push_kernel(ResampleAr
     a.out[stream * a.out_pitch + (size_t)(n0 + tid)] = make_float2(accr, acci);
 }
 
-/* next [nstreams][P] = per stream the last P of (hist [P], in [K]) */
-__global__ void __launch_bounds__(256) resample_history_kernel(const float2 *__restrict__ hist, const float2 *__restrict__ in, size_t in_pitch, int K,
-                                                               int P, size_t items, float2 *__restrict__ next)
-{
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < items; e += (size_t)gridDim.x * 256) {
-        const size_t stream = e / (unsigned)P;
-        const long long at = (long long)(e - stream * (unsigned)P) + K;      /* in (hist, in) */
-        next[e] = at < P ? hist[stream * (unsigned)P + (size_t)at] : in[stream * in_pitch + (size_t)(at - P)];
-    }
-}
-
 template <int PT, bool STAGED>
 void launch_push(const ResampleArgs &a, unsigned blocks, size_t lds, hipStream_t s)
 {
@@ -169,14 +158,6 @@ int launch_resample_push(const float2 *in, size_t in_pitch, int nin, const float
         else if (P == 16) launch_push<16, false>(a, blocks, lds, s);
         else launch_push<0, false>(a, blocks, lds, s);
     }
-    return (int)hipGetLastError();
-}
-
-int launch_resample_history(const float2 *hist, const float2 *in, size_t in_pitch, int K, int nstreams, int P, float2 *next, hipStream_t s)
-{
-    if (!hist || !in || !next || K < 1 || in_pitch < (size_t)K || nstreams < 1 || P < 1 || P > RESAMPLE_MAX_P) return (int)hipErrorInvalidValue;
-    const size_t items = (size_t)nstreams * P, want = (items + 255) / 256;
-    hipLaunchKernelGGL(resample_history_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, hist, in, in_pitch, K, P, items, next);
     return (int)hipGetLastError();
 }
 

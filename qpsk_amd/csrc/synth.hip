@@ -1,7 +1,7 @@
 /*
  * synth.hip -- the polyphase synthesis bank (SYNTHESIS BANK in include/qpsk_hip.h, restated in numpy by tests/test_synth_cpu.py), the
  * channeliser's transmit twin: nsel channel rows in, one wideband complex stream out.  Two launches through a scratch buffer V [T][M] of
- * transformed vectors; channel_history_kernel (channel.hip) behind them keeps the last P - 1 of those.
+ * transformed vectors; polyphase_history_kernel (polyphase.hip) behind them keeps the last P - 1 of those.
  *
  * synth_transform_kernel<NT>: channel_push_kernel's geometry (channel_tile(M) times per workgroup of channel_threads(M) threads) and its LDS
  * image of TB rows of M complex values, element e at e + (e >> 5):
@@ -13,16 +13,15 @@
  *   3. the rows go out in natural order: the tile is TB M contiguous values of V, lanes adjacent in r.
  *
  * synth_filter_kernel<PT>: a lane owns branch r for a run of SYNTH_RUN consecutive times; lanes adjacent in r, so the loads of V and of the
- * taps and the stores of x coalesce.  PT = P > 0: the lane keeps its P taps and the last P - 1 values of its branch in registers and loads
- * one new value per time (a run re-reads (SYNTH_RUN + P - 1) / SYNTH_RUN of V), the run unrolled so that several loads are in flight;
- * PT = 0, any P: every product loads its tap and its value.  Rows before the push come from the history, rows from 0 on from V, selected
- * without a branch.
+ * taps and the stores of x coalesce.  The run is polyphase.h's (PT = P > 0: taps and window in registers, 8 loads in flight; PT = 0: any
+ * P); rows before the push come from the history, rows from 0 on from V, selected without a branch.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "channel_fft.h"
 #include "kernels.h"
+#include "polyphase.h"
 
 namespace qpsk {
 
@@ -85,15 +84,6 @@ struct SynthFilterArgs {
     long long items;          /* runs x M */
 };
 
-/* V of time m (negative: of the history), branch r.  No branch, so that a lane's loads go out together: a time at or beyond T (whose
- * output is never stored) reads the push's last vector instead */
-__device__ __forceinline__ float2 vector_at(const SynthFilterArgs &a, long long m, int r)
-{
-    m = m < a.T ? m : (long long)a.T - 1;
-    const float2 *row = m >= 0 ? a.V + (size_t)m * a.M : a.hist + (size_t)(m + a.P - 1) * a.M;
-    return row[r];
-}
-
 template <int PT>
 __global__ void __launch_bounds__(256) synth_filter_kernel(SynthFilterArgs a)
 {
@@ -101,44 +91,11 @@ __global__ void __launch_bounds__(256) synth_filter_kernel(SynthFilterArgs a)
     if (gid >= a.items) return;
     const int M = a.M, r = (int)(gid & (M - 1));
     const long long m0 = (gid >> a.log2m) * SYNTH_RUN;
-    if constexpr (PT > 0) {
-        float g[PT];
-        float2 w[PT > 1 ? PT - 1 : 1];      /* w[j] = V of time m - 1 - j */
-#pragma unroll
-        for (int q = 0; q < PT; q++) g[q] = a.proto[(size_t)q * M + r];
-#pragma unroll
-        for (int j = 0; j < PT - 1; j++) w[j] = vector_at(a, m0 - 1 - j, r);
-#pragma unroll 8
-        for (int t = 0; t < SYNTH_RUN; t++) {
-            const long long m = m0 + t;
-            const float2 v0 = vector_at(a, m, r);
-            float accr = g[0] * v0.x, acci = g[0] * v0.y;
-#pragma unroll
-            for (int q = 1; q < PT; q++) {
-                accr = accr + g[q] * w[q - 1].x;
-                acci = acci + g[q] * w[q - 1].y;
-            }
-            if (m < a.T) a.x[(size_t)m * M + r] = make_float2(accr, acci);
-#pragma unroll
-            for (int j = PT - 2; j > 0; j--) w[j] = w[j - 1];
-            if (PT > 1) w[0] = v0;
-        }
-    } else {
-        for (int t = 0; t < SYNTH_RUN; t++) {
-            const long long m = m0 + t;
-            const float2 v0 = vector_at(a, m, r);
-            const float g0 = a.proto[r];
-            float accr = g0 * v0.x, acci = g0 * v0.y;
-#pragma unroll 4
-            for (int q = 1; q < a.P; q++) {
-                const float2 vq = vector_at(a, m - q, r);
-                const float gq = a.proto[(size_t)q * M + r];
-                accr = accr + gq * vq.x;
-                acci = acci + gq * vq.y;
-            }
-            if (m < a.T) a.x[(size_t)m * M + r] = make_float2(accr, acci);
-        }
-    }
+    polyphase_branch_run<PT, 8>(
+        a.proto, r, M, a.P, 0, SYNTH_RUN, [&](long long t) { return polyphase_at(a.V, a.hist, m0 + t, a.T, a.P, M, r); },
+        [&](int t, float2 y) {
+            if (m0 + t < a.T) a.x[(size_t)(m0 + t) * M + r] = y;
+        });
 }
 
 template <int NT>
@@ -159,11 +116,9 @@ int prepare_synth()
 
 int launch_synth_transform(const float2 *in, size_t pitch, int T, int M, const float2 *tw, const int32_t *chan, int nsel, float2 *V, hipStream_t s)
 {
-    if (!in || !tw || !chan || !V || T < 1 || M < 2 || M > CHANNEL_MAX_M || (M & (M - 1)) || nsel < 1 || nsel > M || pitch < (size_t)T ||
-        (long long)T * M > SYNTH_MAX_SAMPLES)
+    const int log2m = channel_log2(M);
+    if (!in || !tw || !chan || !V || T < 1 || log2m < 0 || nsel < 1 || nsel > M || pitch < (size_t)T || (long long)T * M > SYNTH_MAX_SAMPLES)
         return (int)hipErrorInvalidValue;
-    int log2m = 0;
-    while ((1 << log2m) < M) log2m++;
     const int tb = channel_tile(M), nt = channel_threads(M);
     if (channel_lds_bytes(M, tb) > (size_t)MAX_LDS_BYTES) return (int)hipErrorInvalidValue;
     const SynthTransformArgs a = {in, tw, chan, V, pitch, T, M, log2m, nsel, tb};
@@ -175,11 +130,9 @@ int launch_synth_transform(const float2 *in, size_t pitch, int T, int M, const f
 
 int launch_synth_filter(const float2 *V, const float2 *hist, int T, int M, int P, const float *proto, float2 *x, hipStream_t s)
 {
-    if (!V || !proto || !x || T < 1 || M < 2 || M > CHANNEL_MAX_M || (M & (M - 1)) || P < 1 || P > CHANNEL_MAX_P || (P > 1 && !hist) ||
-        (long long)T * M > SYNTH_MAX_SAMPLES)
+    const int log2m = channel_log2(M);
+    if (!V || !proto || !x || T < 1 || log2m < 0 || P < 1 || P > CHANNEL_MAX_P || (P > 1 && !hist) || (long long)T * M > SYNTH_MAX_SAMPLES)
         return (int)hipErrorInvalidValue;
-    int log2m = 0;
-    while ((1 << log2m) < M) log2m++;
     const long long items = (((long long)T + SYNTH_RUN - 1) / SYNTH_RUN) << log2m;
     const SynthFilterArgs a = {V, hist, proto, x, T, M, log2m, P, items};
     const dim3 blocks((unsigned)((items + 255) / 256)), threads(256);

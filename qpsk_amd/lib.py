@@ -308,15 +308,20 @@ def channel_twiddles(M):
     return tw
 
 
+def _kaiser_sinc(n, spacing, beta):
+    """The n float64 taps of a Kaiser-windowed sinc with its nulls `spacing` taps apart (cut-off 1 / (2 spacing) cycles per tap), centred
+    and made symmetric bit for bit; unscaled: the *_prototype functions scale and round"""
+    t = (np.arange(n) - (n - 1) / 2.0) / float(spacing)
+    h = np.sinc(t) * np.kaiser(n, float(beta))
+    return 0.5 * (h + h[::-1])
+
+
 def channel_prototype(M, P, beta=8.0, gain=1.0):
     """A prototype for Modem.channel_reset(): the M P taps of a Kaiser-windowed sinc with its cut-off at half the channel spacing
     (1 / (2 M) cycles per wideband sample), symmetric, unit gain at DC, float32.  A numpy convenience: the library designs no filter, and
     any finite taps do.  gain multiplies the float32 taps: Modem.synth_reset() wants the interpolation gain M, and gain=M is exact in
     float32, M being a power of two -- the synthesis prototype is then M times the analysis one tap for tap"""
-    n = int(M) * int(P)
-    t = (np.arange(n) - (n - 1) / 2.0) / float(M)
-    h = np.sinc(t) * np.kaiser(n, float(beta))
-    h = 0.5 * (h + h[::-1])
+    h = _kaiser_sinc(int(M) * int(P), int(M), beta)
     return np.float32(gain) * (h / h.sum()).astype(np.float32)
 
 
@@ -327,10 +332,7 @@ def resample_prototype(L, D, P, beta=10.0, gain=None):
     the library designs no filter, and any finite taps do.  The transition band is the window's main lobe: the stop band begins
     sqrt(1 + (beta / pi)^2) / (L P) cycles per interpolated sample beyond the cut-off (the Kaiser window's first null; 3.34 / (L P) at
     beta = 10), the pass band ends as far below it, and the stop band lies about beta / 0.1102 + 8.7 dB down (Kaiser's rule: 99 dB)"""
-    n = int(L) * int(P)
-    t = (np.arange(n) - (n - 1) / 2.0) / float(max(int(L), int(D)))
-    h = np.sinc(t) * np.kaiser(n, float(beta))
-    h = 0.5 * (h + h[::-1])
+    h = _kaiser_sinc(int(L) * int(P), max(int(L), int(D)), beta)
     return (h * (float(L if gain is None else gain) / h.sum())).astype(np.float32)
 
 

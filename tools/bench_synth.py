@@ -3,7 +3,7 @@
 rounds interleaved, medians: the method of tools/bench_channel.py.
 
   synth 4096       M = 4096, P = 8, T = 2048, all channels: 64 MiB in, 64 MiB out, synth_transform_kernel<1024> (tile 4) into the scratch
-                   of transformed vectors (64 MiB written, read (16 + 7) / 16 times), synth_filter_kernel<8>, channel_history_kernel
+                   of transformed vectors (64 MiB written, read (16 + 7) / 16 times), synth_filter_kernel<8>, polyphase_history_kernel
   synth 64         M = 64, P = 16, T = 131072: the same bytes, synth_transform_kernel<256> (tile 128), synth_filter_kernel<16>
   synth 4096 x1    synth 4096 with ONE channel selected: 16 KiB in; the transform of 4095 zeros and one value, the whole filter
   push 4096 / 64   THE YARDSTICK of each shape: qpsk_channel_push on the same M, P, T
